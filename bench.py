@@ -15,6 +15,12 @@ ESC.decode (de-quantise -> decoder -> ISTFT).
 than N devices, and `n_gpus` in the JSON line is the size of the communicator, never the flag.
 Inputs are resident in HBM before the timed region.
 Weights are the deterministic name-keyed synthetic ESC-Base weights (no checkpoints exist offline); fp32 throughout.
+
+A plain run sets up, warms up, times the K steps and prints the JSON line; nothing else runs.  `--full` adds everything the line
+carried besides its headline: the per-kernel profile passes and roofline, the single-clip latency, the CPU baseline (oracle), the
+other precision modes, the 288-clip N = 1 point and the training / adversarial-step riders.
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB); the inputs
+and weights are the same from run to run, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -59,6 +65,33 @@ DTYPE_TEXT = {
              "(tests/test_gpu_parity.py::test_layer_accuracy_against_fp64); escx_set_precision(ESCX_PRECISION_F16X2), the library default; the exact three-term form and the "
              "all-fp32-MFMA form ride along in precision_riders)",
 }
+
+
+DUMP_MAX_BYTES = 64 * 2 ** 20
+DUMP_SAMPLE = 4 * 2 ** 20          # elements: a larger array is dumped as this fixed, seeded sample of its flat elements
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array as `dirname/<name>.npy`, float32 when the tensor holds fp32 (or narrower) values, float64 otherwise (integer
+    codes exactly).  An array of more than DUMP_SAMPLE elements is replaced by the elements at fixed sorted indices (seed 0), the same in every run."""
+    os.makedirs(dirname, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        t = t.detach()
+        t = t.float() if t.is_floating_point() and t.dtype != torch.float64 else (t if t.dtype == torch.float64 else t.double())
+        a = t.cpu().numpy()
+        if a.size > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_SAMPLE, replace=False))
+            a = a.reshape(-1)[idx]
+        total += a.nbytes
+        if total > DUMP_MAX_BYTES:
+            raise SystemExit(f"bench.py --dump-outputs: more than {DUMP_MAX_BYTES >> 20} MB of outputs")
+        np.save(os.path.join(dirname, f"{name}.npy"), a)
+
+
+def flat_parameters(module):
+    """All parameters of `module` in name order, as one flat vector (what a training step hands back: the updated weights)."""
+    return torch.cat([p.detach().reshape(-1).float() for _, p in sorted(module.named_parameters(), key=lambda kv: kv[0])])
 
 
 def base_config():
@@ -360,7 +393,31 @@ def run_train(args, rank, world, device, use_dist, emit=True):
     assert torch.isfinite(loss).all()
     if rank != 0:
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"loss": loss, "parameters": flat_parameters(model)})
     lib, hd = model._handle(device, for_training=True)
+    audio_s = CLIPS_PER_GPU * world * args.steps * (TRAIN_SAMPLES / 16000.0)
+    roofline = train_roofline(args, lib, hd, step, elapsed, device) if args.full else None
+    out = {"metric": "audio-seconds/sec trained (forward + mel/STFT/VQ losses + backward + clip + AdamW), ESC-Base 9kbps 3s@16kHz",
+           "value": round(audio_s / elapsed, 2), "unit": "audio-seconds/sec", "n_gpus": (dist.get_world_size() if use_dist else 1), "steps": args.steps, "warmup": args.warmup,
+           "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+           "dtype": "f32" if os.environ.get("ESCX_TRAIN_X3") == "0" else "f32 (linear layers from 96 columns up: fp32 operands as three exact bf16 terms, six cross products, fp32 accumulate)",
+           "data": "synthetic",
+           "config": {"workload": f"ESC-Base training step (scripts/trainer_no_adv.py:95-118, non-adversarial), batch={CLIPS_PER_GPU} clips of {TRAIN_SAMPLES} samples per GPU, "
+                                  "num_streams=6, fp32 (the reference has no AMP); first slice of BASELINE configs[4]",
+                      "global_batch": CLIPS_PER_GPU * world, "clip_samples": TRAIN_SAMPLES, "num_streams": NUM_STREAMS,
+                      "parallelism": f"dp{world}" + (" (flat-gradient all-reduce over RCCL before the clip, esc.distributed.all_reduce_gradients)" if use_dist else ""),
+                      "optimizer": "AdamW (flat, 2 kernels) + clip_grad_norm 0.5", "tape_gb": round(lib.escx_train_tape_bytes(hd) / 2 ** 30, 2),
+                      "steps_per_sec": round(args.steps / elapsed, 3)},
+           "roofline": roofline,
+           "cpu_baseline": None if (not args.full or args.no_cpu_baseline or world > 1) else train_cpu_baseline(cfg, sd, x_cpu)}
+    if not emit:
+        return out
+    print(json.dumps(out))
+
+
+def train_roofline(args, lib, hd, step, elapsed, device):
+    """--full, --mode train: a few profiled steps (events around every launch group) -> the dominant GEMM-class group and the whole step's rate."""
     lib.escx_profile_enable(hd, 1)
     psteps = max(2, min(args.profile_steps, 3))
     for _ in range(psteps):
@@ -384,24 +441,8 @@ def run_train(args, rank, world, device, use_dist, emit=True):
                 "executed_gflop_per_clip": round(sum(r["flops"] for r in recs) / psteps / CLIPS_PER_GPU / 1e9, 2),
                 "note": "kernel = the GEMM-class launch group with the largest share of the step; traffic not collected in train mode; FLOPs are algorithmic fp32 FLOPs "
                         "(a split-operand launch executes six bf16 MFMA products per counted product), fractions are against the fp32 MFMA peak"}
-    audio_s = CLIPS_PER_GPU * world * args.steps * (TRAIN_SAMPLES / 16000.0)
     roofline["whole_step_frac_executed_flops"] = round(roofline["executed_gflop_per_clip"] * 1e9 * CLIPS_PER_GPU * args.steps / elapsed / PEAK_F32_MFMA, 4)
-    out = {"metric": "audio-seconds/sec trained (forward + mel/STFT/VQ losses + backward + clip + AdamW), ESC-Base 9kbps 3s@16kHz",
-           "value": round(audio_s / elapsed, 2), "unit": "audio-seconds/sec", "n_gpus": (dist.get_world_size() if use_dist else 1), "steps": args.steps, "warmup": args.warmup,
-           "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-           "dtype": "f32" if os.environ.get("ESCX_TRAIN_X3") == "0" else "f32 (linear layers from 96 columns up: fp32 operands as three exact bf16 terms, six cross products, fp32 accumulate)",
-           "data": "synthetic",
-           "config": {"workload": f"ESC-Base training step (scripts/trainer_no_adv.py:95-118, non-adversarial), batch={CLIPS_PER_GPU} clips of {TRAIN_SAMPLES} samples per GPU, "
-                                  "num_streams=6, fp32 (the reference has no AMP); first slice of BASELINE configs[4]",
-                      "global_batch": CLIPS_PER_GPU * world, "clip_samples": TRAIN_SAMPLES, "num_streams": NUM_STREAMS,
-                      "parallelism": f"dp{world}" + (" (flat-gradient all-reduce over RCCL before the clip, esc.distributed.all_reduce_gradients)" if use_dist else ""),
-                      "optimizer": "AdamW (flat, 2 kernels) + clip_grad_norm 0.5", "tape_gb": round(lib.escx_train_tape_bytes(hd) / 2 ** 30, 2),
-                      "steps_per_sec": round(args.steps / elapsed, 3)},
-           "roofline": roofline,
-           "cpu_baseline": None if (args.no_cpu_baseline or world > 1) else train_cpu_baseline(cfg, sd, x_cpu)}
-    if not emit:
-        return out
-    print(json.dumps(out))
+    return roofline
 
 
 def run_train_adv(args, rank, world, device, use_dist, emit=True):
@@ -441,33 +482,10 @@ def run_train_adv(args, rank, world, device, use_dist, emit=True):
     assert all(bool(torch.isfinite(v).all()) for v in log.values() if torch.is_tensor(v))
     if rank != 0:
         return
-    # per-kernel pass (diagnostic mode: events + a sync around every discriminator launch group, events around every generator launch): the launch
-    # group with the largest share of the step, its rate against the fp32 MFMA peak, and the ten largest groups
-    from esc import _native
-    lib = _native.load()
-    glib, ghd = model._handle(device, for_training=True)
-    lib.escx_disc_profile_enable(1); glib.escx_profile_enable(ghd, 1)
-    psteps = 2
-    for n in range(psteps):
-        st.step(x, args.warmup + args.steps + n)
-    torch.cuda.synchronize(device)
-    lib.escx_disc_profile_enable(0); glib.escx_profile_enable(ghd, 0)
-    recs = json.loads(lib.escx_disc_profile_report().decode()) + json.loads(glib.escx_profile_report(ghd).decode())
-    recs = [r for r in recs if r["flops"] > 0 and r["ms"] > 0]
-    recs.sort(key=lambda r: -r["ms"])
-    ptot = sum(r["ms"] for r in recs)
-    dom = recs[0]
-    kern_roof = {"kernel": dom["name"], "avg_us": round(dom["ms"] / dom["calls"] * 1e3, 1), "launches_per_step": dom["calls"] // psteps,
-                 "achieved": round(dom["flops"] / dom["ms"] / 1e9, 2), "frac": round(dom["flops"] / dom["ms"] / 1e9 / (PEAK_F32_MFMA / 1e12), 4),
-                 "share_of_profiled_gemm_time": round(dom["ms"] / ptot, 4), "profiled_gemm_ms_per_step": round(ptot / psteps, 2),
-                 "profiled_gemm_tflops": round(sum(r["flops"] for r in recs) / ptot / 1e9, 2),
-                 "top": [{"name": r["name"], "ms_per_step": round(r["ms"] / psteps, 3), "tflops": round(r["flops"] / r["ms"] / 1e9, 1)} for r in recs[:10]]}
-    if prec != "fp32":      # the dominant launches may run on the bf16 MFMA (one product, or six per fp32 product): a fraction of the fp32 peak says nothing about them
-        kern_roof["frac"] = None
-        kern_roof["frac_note"] = "achieved = algorithmic fp32 FLOPs / time; not priced against the fp32 MFMA peak in this precision (see --adv-precision fp32)"
-    if os.environ.get("ESCX_BENCH_BREAKDOWN"):
-        for r in recs:
-            print(f"# {r['name']:60s} calls {r['calls']:4d}  {r['ms'] / psteps:9.3f} ms/step  {r['flops'] / r['ms'] / 1e9:9.1f} TFLOP/s", file=sys.stderr)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {**{f"log_{k}": v for k, v in sorted(log.items()) if torch.is_tensor(v)},
+                                         "generator_parameters": flat_parameters(model), "discriminator_parameters": flat_parameters(disc)})
+    kern_roof = adv_kernel_roofline(args, model, st, x, prec, device) if args.full else None
     n_gen, n_disc = sum(p.numel() for p in model.parameters()), sum(p.numel() for p in disc.parameters())
     # convolution FLOPs of one discriminator pass per clip (2 x MACs), from the feature-map geometry
     lay = disc.fmap_layout(device, TRAIN_SAMPLES)
@@ -500,11 +518,43 @@ def run_train_adv(args, rank, world, device, use_dist, emit=True):
                         "dominant_launch_group": kern_roof,
                         **({} if prec != "bf16" else {"precision_note": "fractions are against the fp32 MFMA peak (157.3 TFLOP/s); the period convolutions 128->512->1024->1024 "
                                                                         "run on the bf16 MFMA (dense peak 2500 TFLOP/s) and can exceed it, see dominant_launch_group.top"})},
-           "cpu_baseline": None if (args.no_cpu_baseline or world > 1) else
+           "cpu_baseline": None if (not args.full or args.no_cpu_baseline or world > 1) else
                            train_adv_cpu_baseline(cfg, sd, {k: v.detach().cpu() for k, v in disc.state_dict().items()}, x.cpu(), st.w)}
     if not emit:
         return out
     print(json.dumps(out))
+
+
+def adv_kernel_roofline(args, model, st, x, prec, device):
+    """--full, --mode train_adv: two profiled steps after the timed ones."""
+    # per-kernel pass (diagnostic mode: events + a sync around every discriminator launch group, events around every generator launch): the launch
+    # group with the largest share of the step, its rate against the fp32 MFMA peak, and the ten largest groups
+    from esc import _native
+    lib = _native.load()
+    glib, ghd = model._handle(device, for_training=True)
+    lib.escx_disc_profile_enable(1); glib.escx_profile_enable(ghd, 1)
+    psteps = 2
+    for n in range(psteps):
+        st.step(x, args.warmup + args.steps + n)
+    torch.cuda.synchronize(device)
+    lib.escx_disc_profile_enable(0); glib.escx_profile_enable(ghd, 0)
+    recs = json.loads(lib.escx_disc_profile_report().decode()) + json.loads(glib.escx_profile_report(ghd).decode())
+    recs = [r for r in recs if r["flops"] > 0 and r["ms"] > 0]
+    recs.sort(key=lambda r: -r["ms"])
+    ptot = sum(r["ms"] for r in recs)
+    dom = recs[0]
+    kern_roof = {"kernel": dom["name"], "avg_us": round(dom["ms"] / dom["calls"] * 1e3, 1), "launches_per_step": dom["calls"] // psteps,
+                 "achieved": round(dom["flops"] / dom["ms"] / 1e9, 2), "frac": round(dom["flops"] / dom["ms"] / 1e9 / (PEAK_F32_MFMA / 1e12), 4),
+                 "share_of_profiled_gemm_time": round(dom["ms"] / ptot, 4), "profiled_gemm_ms_per_step": round(ptot / psteps, 2),
+                 "profiled_gemm_tflops": round(sum(r["flops"] for r in recs) / ptot / 1e9, 2),
+                 "top": [{"name": r["name"], "ms_per_step": round(r["ms"] / psteps, 3), "tflops": round(r["flops"] / r["ms"] / 1e9, 1)} for r in recs[:10]]}
+    if prec != "fp32":      # the dominant launches may run on the bf16 MFMA (one product, or six per fp32 product): a fraction of the fp32 peak says nothing about them
+        kern_roof["frac"] = None
+        kern_roof["frac_note"] = "achieved = algorithmic fp32 FLOPs / time; not priced against the fp32 MFMA peak in this precision (see --adv-precision fp32)"
+    if os.environ.get("ESCX_BENCH_BREAKDOWN"):
+        for r in recs:
+            print(f"# {r['name']:60s} calls {r['calls']:4d}  {r['ms'] / psteps:9.3f} ms/step  {r['flops'] / r['ms'] / 1e9:9.1f} TFLOP/s", file=sys.stderr)
+    return kern_roof
 
 
 def time_codec_steps(model, x, steps, warmup, device):
@@ -561,7 +611,7 @@ def other_workloads(args, device):
     res = {}
     for name, fn, steps, warm in (("train", run_train, 5, 2), ("train_adv", run_train_adv, 4, 2), ("train_adv_fp32mfma", run_train_adv, 4, 2), ("train_adv_bf16", run_train_adv, 4, 2)):
         a = copy.copy(args)
-        a.steps, a.warmup, a.no_cpu_baseline, a.profile_steps = steps, warm, True, 2
+        a.steps, a.warmup, a.no_cpu_baseline, a.profile_steps, a.full, a.dump_outputs = steps, warm, True, 2, True, None
         # train_adv: the default (split operands, fp32-grade); _fp32mfma: the fp32 MFMA everywhere (rounds 2-4); _bf16: the opt-in reduced precision
         a.adv_precision = "bf16" if name.endswith("bf16") else ("fp32" if name.endswith("fp32mfma") else "split")
         mixed = name in ("train_adv", "train_adv_bf16")        # hot kernels on the bf16 MFMA: no meaningful fraction of the fp32 peak
@@ -615,9 +665,16 @@ def main():
                     help="codec mode on one GPU: do not append the short training / adversarial-step blocks (\"other_workloads\") - for rocprofv3 runs")
     ap.add_argument("--skip-isolated", action="store_true",
                     help="omit the isolated-kernel timing pass (used under rocprofv3 so that its per-kernel averages cover two-stream launches only)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run everything else the line can carry: per-kernel profile passes and roofline, single-clip latency, CPU baseline, "
+                         "the other precision modes, the 288-clip N = 1 point and the training riders (the --skip-* / --no-cpu-baseline flags trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB; larger arrays as a fixed seeded sample)")
     args = ap.parse_args()
     if args.steps is None:
         args.steps = {"codec": 200, "train": 20, "train_adv": 6}[args.mode]
+    if args.steps < 1 and not args.dry_run:
+        raise SystemExit("bench.py: --steps must be >= 1")
 
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
@@ -732,11 +789,14 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     assert (allc.shape[0] == (total_clips if use_dist else n_local) or os.environ.get("ESCX_BENCH_SKIP_GATHER")) and torch.isfinite(wave).all()
+    if rank == 0 and args.dump_outputs:
+        # the codes the step hands back (all ranks' clips when they are gathered) and this rank's decoded audio
+        dump_outputs(args.dump_outputs, {"codes": allc, "audio": wave})
 
-    # per-kernel pass: HIP events around every launch, on the stream the kernels run on
-    lib, hd = model._handle(device)
+    # --full: per-kernel pass, HIP events around every launch, on the stream the kernels run on
     roofline = None
-    if rank == 0:
+    if rank == 0 and args.full:
+        lib, hd = model._handle(device)
         lib.escx_profile_enable(hd, 1)
         for _ in range(args.profile_steps):
             c, s = model.encode(x, NUM_STREAMS)
@@ -837,7 +897,7 @@ def main():
                           f"{r['flops'] / max(r['ms'], 1e-9) / 1e9:9.1f} TFLOP/s  {r['bytes'] / max(r['ms'], 1e-9) / 1e6:9.1f} GB/s", file=sys.stderr)
 
     single_gpu = None
-    if rank == 0 and world == 1 and not args.skip_single_clip:
+    if rank == 0 and world == 1 and args.full and not args.skip_single_clip:
         # BASELINE configs[0] workload (one 3 s clip) on the GPU, next to cpu_baseline.single_clip
         x1 = x[:1].contiguous()
         for _ in range(3):
@@ -877,12 +937,12 @@ def main():
             roofline["whole_path_peak_tflops"] = whole_peak / 1e12
             roofline["whole_path_frac_ref_flops"] = round(FLOP_PER_CLIP * clips_per_s / world / whole_peak, 4)
             roofline["whole_path_frac_executed_flops"] = round(roofline["executed_gflop_per_clip"] * 1e9 * clips_per_s / world / whole_peak, 4)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(cfg, sd, x_cpu)
         else:
             out["cpu_baseline"] = None
         out["config"]["precision"] = PRECISION
-        if world == 1 and not use_dist and not args.skip_other_workloads:
+        if args.full and world == 1 and not use_dist and not args.skip_other_workloads:
             headline_codes, _ = model.encode(x, NUM_STREAMS)
             out["precision_riders"] = precision_riders(model, x, args, device, headline_codes)
             out["fp32_mfma_only"] = out["precision_riders"].get("fp32")            # round-5 key, kept for continuity
@@ -890,7 +950,7 @@ def main():
             if not strong:
                 out["strong_scaling_n1"] = strong_scaling_n1_rider(model, args, device)
             del headline_codes
-        if world == 1 and not use_dist and not args.skip_other_workloads:
+        if args.full and world == 1 and not use_dist and not args.skip_other_workloads:
             del model, x, allc, wave
             import gc
             gc.collect(); torch.cuda.empty_cache()

@@ -102,3 +102,30 @@ def test_data_parallel_training_step_touches_rccl():
     assert r.returncode == 0, r.stderr[-3000:]
     d = _json_line(r.stdout)
     assert d["n_gpus"] == 1 and "all-reduce over RCCL" in d["config"]["parallelism"] and d["value"] > 100
+
+
+def test_plain_run_is_lean_and_full_is_an_option():
+    """`--full` carries the extras (profile passes, CPU baseline, riders); `--dump-outputs DIR` exists; `--steps` is the count of timed steps."""
+    r = _run(["--help"])
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout
+    r = _run(["--steps", "0"])
+    assert r.returncode != 0 and "--steps" in r.stderr
+
+
+def test_dump_outputs_writes_fixed_float_arrays(tmp_path):
+    import numpy as np
+    import torch
+    import bench
+    codes = torch.arange(36 * 6 * 3 * 5, dtype=torch.int64).view(36, 6, 3, 5) % 1024
+    audio = torch.linspace(-1, 1, 36 * 480).view(36, 480)
+    big = torch.arange(bench.DUMP_SAMPLE + 1000, dtype=torch.float32)
+    for d in (tmp_path / "a", tmp_path / "b"):
+        bench.dump_outputs(str(d), {"codes": codes, "audio": audio, "big": big, "half": audio.bfloat16()})
+    a = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("codes", "audio", "big", "half")}
+    assert a["codes"].dtype == np.float64 and np.array_equal(a["codes"], codes.numpy())
+    assert a["audio"].dtype == np.float32 and np.array_equal(a["audio"], audio.numpy())
+    assert a["half"].dtype == np.float32 and a["half"].shape == (36, 480)
+    assert a["big"].shape == (bench.DUMP_SAMPLE,) and np.all(np.diff(a["big"]) > 0)          # sorted sample of the flat elements
+    assert np.array_equal(a["big"], np.load(tmp_path / "b" / "big.npy"))                       # the same sample in every run
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "c"), {f"x{i}": big for i in range(5)})             # 5 x 16 MB > 64 MB

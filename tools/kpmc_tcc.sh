@@ -3,7 +3,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}; NAME=$1; shift
 O=$R/gpurun_out/kpmc_tcc_$NAME; rm -rf $O; mkdir -p $O
 cd /tmp; export TMPDIR=/tmp
-PC="python $R/bench.py --steps 2 --warmup 1 --profile-steps 1 --no-cpu-baseline --skip-isolated --skip-single-clip --skip-other-workloads"
+PC="python $R/bench.py --full --steps 2 --warmup 1 --profile-steps 1 --no-cpu-baseline --skip-isolated --skip-single-clip --skip-other-workloads"
 env ESCX_STREAMS=1 "$@" timeout 600 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum -f csv -d $O/p1 -o p -- $PC > $O/log1.txt 2>&1
 env ESCX_STREAMS=1 "$@" timeout 600 rocprofv3 --pmc FETCH_SIZE -f csv -d $O/p2 -o p -- $PC > $O/log2.txt 2>&1
 python $R/tools/pmc_agg.py $O --json $O/agg.json --top 0 > /dev/null

@@ -8,4 +8,4 @@ timeout 2400 python -m pytest tests -x -q -m gpu --durations=8 > $O/pytest_gpu.t
 s=$SECONDS
 timeout 600 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1; tail -3 $O/smoke.txt; echo "smoke wall $((SECONDS - s)) s"
 s=$SECONDS
-timeout 900 python bench.py --steps 20 --warmup 5 2>$O/bench.err | tail -1 > $O/bench.json; cut -c1-240 $O/bench.json; echo; echo "bench wall $((SECONDS - s)) s"
+timeout 900 python bench.py --full --steps 20 --warmup 5 2>$O/bench.err | tail -1 > $O/bench.json; cut -c1-240 $O/bench.json; echo; echo "bench wall $((SECONDS - s)) s"

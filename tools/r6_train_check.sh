@@ -16,10 +16,10 @@ for arm in default bwd_off all_off; do
   unset ESCX_TRAIN_MLP_X3 ESCX_TRAIN_MLPBWD_X2
   if [ $arm = bwd_off ]; then export ESCX_TRAIN_MLPBWD_X2=0; fi
   if [ $arm = all_off ]; then export ESCX_TRAIN_MLPBWD_X2=0 ESCX_TRAIN_MLP_X3=0; fi
-  timeout 600 python bench.py --mode train --steps 10 --warmup 3 --no-cpu-baseline 2>$O/train_$arm.err | tail -1 > $O/train_$arm.json
+  timeout 600 python bench.py --full --mode train --steps 10 --warmup 3 --no-cpu-baseline 2>$O/train_$arm.err | tail -1 > $O/train_$arm.json
   python -c "
 import json; d=json.loads(open('$O/train_$arm.json').read()); print('$arm', d['ms_per_step'], d['value'])" | tee -a $O/train_ab.txt
 done
 done
 unset ESCX_TRAIN_MLP_X3 ESCX_TRAIN_MLPBWD_X2
-ESCX_BENCH_BREAKDOWN=1 timeout 600 python bench.py --mode train --steps 6 --warmup 2 --no-cpu-baseline 2>&1 | grep "^# [BT].mlp" | awk '!seen[$0]++' | tee $O/train_mlp_breakdown.txt
+ESCX_BENCH_BREAKDOWN=1 timeout 600 python bench.py --full --mode train --steps 6 --warmup 2 --no-cpu-baseline 2>&1 | grep "^# [BT].mlp" | awk '!seen[$0]++' | tee $O/train_mlp_breakdown.txt

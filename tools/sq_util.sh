@@ -2,7 +2,7 @@
 # datapath utilisation per kernel (SQ_INSTS_MFMA / SQ_INSTS_VALU / GRBM_GUI_ACTIVE), single stream, written to gpurun_out/sq_util.txt
 #   SQ_BENCH_ARGS="--mode train ..." SQ_OUT=sq_util_train.txt tools/sq_util.sh     -> the same table for the training step's kernels
 R=${GRAFT_REPO_ROOT:-/root/repo}; O=$R/gpurun_out/squ; rm -rf $O; mkdir -p $O; cd /tmp; export TMPDIR=/tmp
-PC="python $R/bench.py ${SQ_BENCH_ARGS:---steps 2 --warmup 1 --profile-steps 1 --no-cpu-baseline --skip-isolated --skip-single-clip --skip-other-workloads}"
+PC="python $R/bench.py --full ${SQ_BENCH_ARGS:---steps 2 --warmup 1 --profile-steps 1 --no-cpu-baseline --skip-isolated --skip-single-clip --skip-other-workloads}"
 OUT=${SQ_OUT:-sq_util.txt}
 i=0
 for set in "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVES" "SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_INSTS_SALU"; do
