@@ -11,26 +11,34 @@
 #include <map>
 #include <mutex>
 #include <tuple>
+#include <utility>
+#include <vector>
 
 #include "escx_internal.h"
 #include "launchers.h"
 
 using namespace escx;
 
+// Batch layout of a whole-path call: k parts of `per` clips (part i = clips [i * per, min((i + 1) * per, B))), each walked in passes of at most
+// `pass` clips (escx_params.cpp pass_clips: the workspace sets are sized for one pass).
+static void part_layout(escx_handle_s* h, int B, int T, int* k, int* per, int* pass) {
+    *k = std::min(n_parts(h, B), h->n_sets);
+    *pass = std::max(1, std::min(pass_clips(h, B, T), h->sets[0].shp.B));
+    *per = *k <= 1 ? B : (B + *k - 1) / *k;
+}
+
 // Whole-path calls: run `part(first_clip, n_clips, stream)` once, or as two halves on two streams joined by events.
 // Clips are independent end to end, so the halves never exchange data; overlapping them lets one half's kernels fill
 // the CUs the other half's tail workgroups leave idle (a 36-clip layer launches only ~1.3-2.6 workgroups per CU).
 template <class F>
 static int run_halves(escx_handle_s* h, int B, int T, hipStream_t st, F part) {
-    const int k = std::min(n_parts(h, B), h->n_sets);
-    // a part walks its clips in passes of at most `pass` clips (escx_params.cpp pass_clips: the workspace sets are sized for one pass)
-    const int pass = std::max(1, std::min(pass_clips(h, B, T), h->sets[0].shp.B));
+    int k, per, pass;
+    part_layout(h, B, T, &k, &per, &pass);
     auto run_part = [&](int b0, int nb, hipStream_t si) -> int {
         for (int off = 0; off < nb; off += pass) { const int r = part(b0 + off, std::min(pass, nb - off), si); if (r) return r; }
         return 0;
     };
     if (k <= 1) { use_set(h, 0); return run_part(0, B, st); }
-    const int per = (B + k - 1) / k;
     // Event timing stays valid under concurrency (each kernel is bracketed on its own stream); ESCX_PROF_SERIAL=1 puts the
     // parts back to back on the caller's stream when isolated per-kernel durations are wanted.
     const bool concurrent = !(h->prof && (h->prof_serial || h->prof_isolated));
@@ -698,6 +706,263 @@ extern "C" int escx_forward_feat(escx_handle h, const float* feat, int B, int T,
 }
 
 // ------------------------------------------------------------------------------------------------
+// Mixed-stream batches: escx_encode_streams / escx_decode_streams / escx_forward_streams (include/escx.h).  Clip b carries its own stream
+// count S_b.  A clip's codes and audio do not depend on the batch it runs in, streams are a prefix of the S = max_streams codes, and
+// untransmitted streams pass through (csrvq.py:174-177), so every clip gets exactly what a uniform call at its S_b returns.
+// The clips are laid into WORKSPACE ORDER so that every pass of every part (run_halves) holds its clips sorted by descending S: stream j
+// (and the decoder block that feeds stream j + 1) then runs on a PREFIX of the pass - the same fused kernels on a smaller batch.
+// ------------------------------------------------------------------------------------------------
+namespace {
+struct MixPlan {
+    int B = 0, Smax = 0;
+    std::vector<int32_t> ints;       // [ws2b | b2ws | S in workspace order | S in caller order], uploaded as one block
+    const int32_t* S_ws() const { return ints.data() + 2 * B; }
+};
+}  // namespace
+
+static int check_streams(escx_handle_s* h, int B, const int32_t* streams, int* Smax) {
+    if (!streams) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null streams pointer");
+    if (B < 1) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "batch=%d: the per-clip stream counts need at least one clip", B);
+    int m = 0;
+    for (int b = 0; b < B; ++b) {
+        if (streams[b] < 1 || streams[b] > h->cfg.max_streams)
+            ESCX_FAIL(ESCX_ERR_INVALID_ARG, "streams[%d]=%d outside [1, %d]", b, streams[b], h->cfg.max_streams);
+        m = std::max(m, (int)streams[b]);
+    }
+    *Smax = m;
+    return 0;
+}
+
+// Sort the clips by S (descending, stable) and deal them round-robin over the passes of all parts, in the order run_halves enqueues them:
+// each pass receives non-increasing S, and the parts (streams) get the same mix of stream counts.
+static void plan_streams(escx_handle_s* h, int B, int T, const int32_t* streams, int Smax, MixPlan* p) {
+    int k, per, pass;
+    part_layout(h, B, T, &k, &per, &pass);
+    std::vector<std::pair<int, int>> groups;           // (first workspace position, clips) of every pass
+    for (int off = 0; off < per; off += pass)
+        for (int i = 0; i < std::max(k, 1); ++i) {
+            const int b0 = i * per, nb = std::min(per, B - b0);
+            if (nb <= off) continue;
+            groups.push_back({b0 + off, std::min(pass, nb - off)});
+        }
+    std::vector<int> order(B);
+    for (int b = 0; b < B; ++b) order[b] = b;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return streams[a] > streams[b]; });
+    p->B = B; p->Smax = Smax;
+    p->ints.assign((size_t)4 * B, 0);
+    int32_t *ws2b = p->ints.data(), *b2ws = ws2b + B, *Sws = ws2b + 2 * B, *Sb = ws2b + 3 * B;
+    int next = 0;
+    for (int r = 0; next < B; ++r)
+        for (const auto& g : groups)
+            if (r < g.second && next < B) ws2b[g.first + r] = order[next++];
+    for (int w = 0; w < B; ++w) { b2ws[ws2b[w]] = w; Sws[w] = streams[ws2b[w]]; }
+    for (int b = 0; b < B; ++b) Sb[b] = streams[b];
+}
+
+// Bump allocation in the handle's grow-only staging buffer (mix_buf); growing synchronises the device once (earlier calls may still read it).
+namespace {
+struct MixBufs {
+    size_t used = 0;
+    std::vector<std::pair<void**, size_t>> want;
+    template <class T> void add(T** p, size_t n) { want.push_back({reinterpret_cast<void**>(p), n * sizeof(T)}); }
+};
+}  // namespace
+static int mix_alloc(escx_handle_s* h, MixBufs& m) {
+    size_t total = 0;
+    for (auto& w : m.want) total += (w.second + 255) / 256 * 256;
+    if (total > h->mix_cap) {
+        ESCX_HIP(hipDeviceSynchronize());
+        if (h->mix_buf) { (void)hipFree(h->mix_buf); h->mix_buf = nullptr; h->mix_cap = 0; }
+        ESCX_HIP(hipMalloc(&h->mix_buf, total));
+        h->mix_cap = total;
+    }
+    char* base = static_cast<char*>(h->mix_buf);
+    for (auto& w : m.want) { *w.first = w.second ? base : nullptr; base += (w.second + 255) / 256 * 256; }
+    return 0;
+}
+
+static int upload_plan(escx_handle_s* h, const MixPlan& p, int32_t* dev, hipStream_t st) {
+    ESCX_HIP(hipMemcpyAsync(dev, p.ints.data(), p.ints.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    return 0;
+}
+
+static int clips_over(const int* S, int B, int j) { int c = 0; while (c < B && S[c] > j) ++c; return c; }     // S non-increasing
+
+// csrvq.py:131-158 on a pass whose clips carry S[0] >= S[1] >= ... streams: stream j runs on the clips with S > j; the refinement after it
+// and the decoder block that feeds stream j + 1 only on those with S > j + 1 (run_csvq_encode is the uniform form).
+static int run_csvq_encode_streams(escx_handle_s* h, const Shapes& s, const int* S, long long* codes, long long bstride, hipStream_t st) {
+    const int n = h->n;
+    const long long sstride = (long long)h->cfg.group_size * s.Tq;
+    int rc, H = s.encH[n - 1], Hn;
+    float* dec = h->decA; float* other = h->decB;
+    int nref = clips_over(S, s.B, 1);                                     // clips that go on to stream 1
+    if ((rc = run_pvq_quantize(h, h->quants[0], h->enc_hs[n - 1], nullptr, s.B, s.W, codes, bstride, nullptr, nref ? dec : nullptr, st))) return rc;
+    for (int i = 0; nref > 0; ++i) {
+        const int nq = nref;                                              // clips that carry stream i + 1
+        nref = clips_over(S, nq, i + 2);                                  // ... and stream i + 2: they need the refinement and block i
+        if ((rc = run_pvq_quantize(h, h->quants[i + 1], h->enc_hs[n - 1 - i], dec, nq, s.W, codes + (i + 1) * sstride, bstride, nullptr, nref ? dec : nullptr, st))) return rc;
+        if (!nref) break;
+        if ((rc = run_layer(h, h->layers[n + i], dec, other, nref, H, s.W, &Hn, st))) return rc;
+        std::swap(dec, other); H = Hn;
+    }
+    return 0;
+}
+
+// csrvq.py:160-183 + codecs.py:83-94 on a pass sorted by descending S: stream i + 1 is de-quantised and added in place on the clips that carry
+// it; the others keep `dec` (the reference's pass-through).  Every decoder block runs on the whole pass.
+static int run_csvq_decode_streams(escx_handle_s* h, const long long* codes, long long bstride, int B, const int* S, int Hb, int W, float* rspec, hipStream_t st) {
+    const int n = h->n;
+    const long long sstride = (long long)h->cfg.group_size * (W / h->cfg.overlap);
+    int rc, H = Hb, Hn;
+    float* dec = h->decA; float* other = h->decB;
+    if ((rc = run_pvq_decode(h, h->quants[0], codes, bstride, nullptr, B, W, dec, st))) return rc;
+    for (int i = 0; i + 1 < n; ++i) {
+        const int nq = clips_over(S, B, i + 1);
+        if (nq && (rc = run_pvq_decode(h, h->quants[i + 1], codes + (i + 1) * sstride, bstride, dec, nq, W, dec, st))) return rc;
+        if ((rc = run_layer(h, h->layers[n + i], dec, other, B, H, W, &Hn, st))) return rc;
+        std::swap(dec, other); H = Hn;
+    }
+    if ((rc = run_layer(h, h->layers[2 * n - 1], dec, other, B, H, W, &Hn, st))) return rc;
+    return run_deembed(h, other, B, W, rspec, st);
+}
+
+extern "C" int escx_encode_streams(escx_handle h, const float* wave, int B, int L, const int32_t* streams, int64_t* codes, int* fh, int* fw,
+                                   void* stream) {
+    int rc = check_ready(h); if (rc) return rc;
+    if (!wave || !codes) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null pointer");
+    int Smax = 0; if ((rc = check_streams(h, B, streams, &Smax))) return rc;
+    if (L <= h->n_fft / 2) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "n_samples=%d too short for reflect padding of %d", L, h->n_fft / 2);
+    Shapes s; if ((rc = ensure_ws(h, B, frames_of(h, L), &s))) return rc;
+    MixPlan p; plan_streams(h, B, s.T, streams, Smax, &p);
+    const int GT = h->cfg.group_size * s.Tq;
+    const long long cstride = (long long)Smax * GT;
+    int32_t* maps; float* wave_ws; long long* codes_ws;
+    MixBufs mb; mb.add(&maps, p.ints.size()); mb.add(&wave_ws, (size_t)B * L); mb.add(&codes_ws, (size_t)B * cstride);
+    if ((rc = mix_alloc(h, mb))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if ((rc = ensure_pvq_tables(h, st))) return rc;
+    if ((rc = upload_plan(h, p, maps, st))) return rc;
+    PROF("mix_gather", 0, 2.0 * B * L * 4, rows_permute(wave, wave_ws, maps, B, L, st));
+    rc = run_halves(h, B, s.T, st, [&](int b0, int nb, hipStream_t sti) -> int {
+        Shapes sp = s; sp.B = nb; int r;
+        if ((r = run_stft(h, wave_ws + (size_t)b0 * L, nb, L, sp.T, h->spec, sti))) return r;
+        if ((r = run_encoder(h, sp, sti))) return r;
+        return run_csvq_encode_streams(h, sp, p.S_ws() + b0, codes_ws + b0 * cstride, cstride, sti);
+    });
+    if (rc) return rc;
+    PROF("mix_scatter", 0, 2.0 * B * cstride * 8, codes_permute(codes_ws, cstride, (long long*)codes, maps + B, maps + 3 * B, B, Smax, GT, st));
+    if ((rc = launch_ok("encode_streams"))) return rc;
+    if (fh) *fh = s.encH[h->n - 1];
+    if (fw) *fw = s.W;
+    return ESCX_OK;
+}
+
+extern "C" int escx_decode_streams(escx_handle h, const int64_t* codes, int B, int Smax_in, const int32_t* streams, int fh, int fw, float* wave_out,
+                                   float* recon_feat, void* stream) {
+    int rc = check_infer_ready(h); if (rc) return rc;
+    if (!codes || !wave_out) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null pointer");
+    const escx_config& c = h->cfg;
+    int Smax = 0; if ((rc = check_streams(h, B, streams, &Smax))) return rc;
+    if (Smax_in < Smax || Smax_in > c.max_streams) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "codes.size(1)=%d: must lie in [max(streams)=%d, %d]", Smax_in, Smax, c.max_streams);
+    if (fw < 1 || fw % c.overlap) ESCX_FAIL(ESCX_ERR_ASSERT, "Time dimension must be multiple of overlap");
+    Shapes s; if ((rc = ensure_ws(h, B, frames_for_width(h, fw), &s))) return rc;
+    if (s.W != fw || s.encH[h->n - 1] != fh) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "feat_shape (%d,%d) does not match the model (%d,%d)", fh, fw, s.encH[h->n - 1], s.W);
+    MixPlan p; plan_streams(h, B, s.T, streams, Smax, &p);
+    const int T2 = c.patch_t * fw, out_len = c.hop_length * (T2 - 1), GT = c.group_size * (fw / c.overlap);
+    const long long in_stride = (long long)Smax_in * GT, cstride = (long long)Smax * GT, frow = (long long)T2 * c.in_dim * h->F;
+    int32_t* maps; long long* codes_ws; float *wave_ws, *recon_ws = nullptr;
+    MixBufs mb; mb.add(&maps, p.ints.size()); mb.add(&codes_ws, (size_t)B * cstride); mb.add(&wave_ws, (size_t)B * out_len);
+    if (recon_feat) mb.add(&recon_ws, (size_t)B * frow);
+    if ((rc = mix_alloc(h, mb))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if ((rc = ensure_pvq_tables(h, st))) return rc;
+    if ((rc = upload_plan(h, p, maps, st))) return rc;
+    // workspace-order codes: only slots below S_b are read from the caller's tensor (the rest is filled with -1 and never read either)
+    PROF("mix_gather", 0, 2.0 * B * cstride * 8, codes_permute((const long long*)codes, in_stride, codes_ws, maps, maps + 2 * B, B, Smax, GT, st));
+    rc = run_halves(h, B, s.T, st, [&](int b0, int nb, hipStream_t sti) -> int {
+        int r;
+        if ((r = run_csvq_decode_streams(h, codes_ws + b0 * cstride, cstride, nb, p.S_ws() + b0, fh, fw, h->rspec, sti))) return r;
+        if ((r = run_istft(h, h->rspec, nb, T2, wave_ws + (size_t)b0 * out_len, sti))) return r;
+        if (recon_ws) spec_unpad(h, h->rspec, recon_ws + (size_t)b0 * frow, (long long)nb * T2, sti);
+        return launch_ok("decode_streams");
+    });
+    if (rc) return rc;
+    PROF("mix_scatter", 0, 2.0 * B * out_len * 4, rows_permute(wave_ws, wave_out, maps + B, B, out_len, st));
+    if (recon_feat) PROF("mix_scatter", 0, 2.0 * B * frow * 4, rows_permute(recon_ws, recon_feat, maps + B, B, frow, st));
+    return launch_ok("decode_streams");
+}
+
+// codecs.py:30-66 in eval mode with per-clip stream counts; forward_impl is the uniform form.  Exactly one of `wave` / `feat` is given.
+extern "C" int escx_forward_streams(escx_handle h, const float* wave, const float* feat, int B, int LT, const int32_t* streams, int64_t* codes,
+                                    float* wave_out, float* raw_feat, float* recon_feat, float* cm_loss, void* stream) {
+    int rc = check_infer_ready(h); if (rc) return rc;
+    if ((!wave == !feat) || !codes || !wave_out) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null pointer (exactly one of wave / feat, codes and wave_out are required)");
+    const escx_config& c = h->cfg;
+    int Smax = 0; if ((rc = check_streams(h, B, streams, &Smax))) return rc;
+    const int L = wave ? LT : 0;
+    int T = wave ? 0 : LT;
+    if (wave && L <= h->n_fft / 2) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "n_samples=%d too short for reflect padding of %d", L, h->n_fft / 2);
+    if (!wave && T < c.patch_t) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "n_frames=%d shorter than one patch", T);
+    if (wave) T = frames_of(h, L);
+    Shapes s; if ((rc = ensure_ws(h, B, T, &s))) return rc;
+    if (s.W % c.overlap) ESCX_FAIL(ESCX_ERR_ASSERT, "Time dimension must be multiple of overlap");
+    MixPlan p; plan_streams(h, B, s.T, streams, Smax, &p);
+    const int n = h->n, G = c.group_size, GT = G * s.Tq;
+    const long long cstride = (long long)Smax * GT, sstride = GT;
+    const int T2 = c.patch_t * s.W, out_len = c.hop_length * (T2 - 1);
+    const long long in_row = wave ? (long long)L : (long long)s.T * c.in_dim * h->F, raw_row = (long long)s.T * c.in_dim * h->F, rec_row = (long long)T2 * c.in_dim * h->F;
+    int32_t* maps; float *in_ws, *wave_ws, *raw_ws = nullptr, *recon_ws = nullptr, *loss_ws = nullptr; long long* codes_ws;
+    MixBufs mb; mb.add(&maps, p.ints.size()); mb.add(&in_ws, (size_t)B * in_row); mb.add(&codes_ws, (size_t)B * cstride); mb.add(&wave_ws, (size_t)B * out_len);
+    if (raw_feat) mb.add(&raw_ws, (size_t)B * raw_row);
+    if (recon_feat) mb.add(&recon_ws, (size_t)B * rec_row);
+    if (cm_loss) mb.add(&loss_ws, (size_t)B);
+    if ((rc = mix_alloc(h, mb))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if ((rc = ensure_pvq_tables(h, st))) return rc;
+    if ((rc = upload_plan(h, p, maps, st))) return rc;
+    PROF("mix_gather", 0, 2.0 * B * in_row * 4, rows_permute(wave ? wave : feat, in_ws, maps, B, in_row, st));
+    const int32_t* Sdev = maps + 2 * B;
+    rc = run_halves(h, B, s.T, st, [&](int b0, int nb, hipStream_t st) -> int {
+        Shapes sp = s; sp.B = nb; int r;
+        const int* S = p.S_ws() + b0;
+        long long* cd = codes_ws + b0 * cstride;
+        if (wave) { if ((r = run_stft(h, in_ws + (size_t)b0 * L, nb, L, sp.T, h->spec, st))) return r; }
+        else spec_pad(h, in_ws + (size_t)b0 * in_row, h->spec, (long long)nb * sp.T, st);
+        if (raw_ws) spec_unpad(h, h->spec, raw_ws + (size_t)b0 * raw_row, (long long)nb * sp.T, st);
+        if ((r = run_encoder(h, sp, st))) return r;
+        // per-vector commitment terms of stream slot j go to loss_terms[j][G][clips of slot j * Tq]; reduced per clip over its own slots
+        const size_t lslot = (size_t)G * nb * sp.Tq;
+        float* loss = cm_loss ? h->loss_terms : nullptr;
+        int slot_clips[8] = {nb};
+        int H = sp.encH[n - 1], Hn;
+        float* dec = h->decA; float* other = h->decB;
+        if ((r = run_pvq_quantize(h, h->quants[0], h->enc_hs[n - 1], nullptr, nb, sp.W, cd, cstride, loss, dec, st))) return r;
+        for (int i = 0; i + 1 < n; ++i) {
+            const int nq = clips_over(S, nb, i + 1);                  // clips that carry stream i + 1; the others pass through
+            if (nq) {
+                if ((r = run_pvq_quantize(h, h->quants[i + 1], h->enc_hs[n - 1 - i], dec, nq, sp.W, cd + (i + 1) * sstride, cstride, loss ? loss + (size_t)(i + 1) * lslot : nullptr, dec, st))) return r;
+                slot_clips[i + 1] = nq;
+            }
+            if ((r = run_layer(h, h->layers[n + i], dec, other, nb, H, sp.W, &Hn, st))) return r;
+            std::swap(dec, other); H = Hn;
+        }
+        if ((r = run_layer(h, h->layers[2 * n - 1], dec, other, nb, H, sp.W, &Hn, st))) return r;
+        if ((r = run_deembed(h, other, nb, sp.W, h->rspec, st))) return r;
+        if ((r = run_istft(h, h->rspec, nb, T2, wave_ws + (size_t)b0 * out_len, st))) return r;
+        if (recon_ws) spec_unpad(h, h->rspec, recon_ws + (size_t)b0 * rec_row, (long long)nb * T2, st);
+        if (cm_loss) PROF("loss_reduce_streams", 0, (double)nb * Smax * GT * 4, loss_reduce_streams(loss, (long long)lslot, Sdev + b0, n, slot_clips, G, sp.Tq, nb, loss_ws + b0, st));
+        return launch_ok("forward_streams");
+    });
+    if (rc) return rc;
+    PROF("mix_scatter", 0, 2.0 * B * cstride * 8, codes_permute(codes_ws, cstride, (long long*)codes, maps + B, maps + 3 * B, B, Smax, GT, st));
+    PROF("mix_scatter", 0, 2.0 * B * out_len * 4, rows_permute(wave_ws, wave_out, maps + B, B, out_len, st));
+    if (raw_feat) PROF("mix_scatter", 0, 2.0 * B * raw_row * 4, rows_permute(raw_ws, raw_feat, maps + B, B, raw_row, st));
+    if (recon_feat) PROF("mix_scatter", 0, 2.0 * B * rec_row * 4, rows_permute(recon_ws, recon_feat, maps + B, B, rec_row, st));
+    if (cm_loss) PROF("mix_scatter", 0, 8.0 * B, rows_permute(loss_ws, cm_loss, maps + B, B, 1, st));
+    return launch_ok("forward_streams");
+}
+
+// ------------------------------------------------------------------------------------------------
 // stage-level entry points (reference layouts in and out)
 // ------------------------------------------------------------------------------------------------
 extern "C" int escx_spec_transform(escx_handle h, const float* wave, int B, int L, float* spec, void* stream) {
@@ -827,6 +1092,36 @@ extern "C" int escx_codes_unpack10(const uint8_t* in, int64_t* codes, int64_t n,
     if (!codes || !in || n < 0) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "bad argument");
     codes_unpack10(in, (long long*)codes, n, (hipStream_t)stream);
     return launch_ok("codes_unpack10");
+}
+// Ragged 10-bit packing of a mixed-stream batch: clip b's first streams[b] * gt codes of (batch, smax, gt), compacted in clip order.
+static int ragged_offsets(int B, int Smax, int64_t gt, const int32_t* streams, hipStream_t st, const long long** off_dev, long long* n) {
+    if (!streams || B < 1 || Smax < 1 || gt < 1) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "bad argument");
+    std::vector<long long> off((size_t)B + 1, 0);
+    for (int b = 0; b < B; ++b) {
+        if (streams[b] < 1 || streams[b] > Smax) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "streams[%d]=%d outside [1, %d]", b, streams[b], Smax);
+        off[b + 1] = off[b] + (long long)streams[b] * gt;
+    }
+    long long* d = reinterpret_cast<long long*>(stream_scratch(st, 2, 2 * off.size()));
+    if (!d) ESCX_FAIL(ESCX_ERR_HIP, "scratch allocation failed");
+    ESCX_HIP(hipMemcpyAsync(d, off.data(), off.size() * sizeof(long long), hipMemcpyHostToDevice, st));
+    *off_dev = d; *n = off[B];
+    return 0;
+}
+extern "C" int escx_codes_pack10_streams(const int64_t* codes, int B, int Smax, int64_t gt, const int32_t* streams, uint8_t* out, void* stream) {
+    if (!codes || !out) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    const long long* off; long long n; int rc;
+    if ((rc = ragged_offsets(B, Smax, gt, streams, st, &off, &n))) return rc;
+    codes_pack10_streams((const long long*)codes, out, off, B, (long long)Smax * gt, n, st);
+    return launch_ok("codes_pack10_streams");
+}
+extern "C" int escx_codes_unpack10_streams(const uint8_t* in, int B, int Smax, int64_t gt, const int32_t* streams, int64_t* codes, void* stream) {
+    if (!codes || !in) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    const long long* off; long long n; int rc;
+    if ((rc = ragged_offsets(B, Smax, gt, streams, st, &off, &n))) return rc;
+    codes_unpack10_streams(in, (long long*)codes, off, B, (long long)Smax * gt, st);
+    return launch_ok("codes_unpack10_streams");
 }
 extern "C" int escx_codes_narrow(const int64_t* codes, int16_t* out, int64_t n, void* stream) {
     codes_narrow((const long long*)codes, (short*)out, n, (hipStream_t)stream);

@@ -186,6 +186,7 @@ struct escx_handle_s : escx::WsFields {      // the inherited fields are the CUR
     hipEvent_t ev_fork = nullptr, ev_join[MAX_PARTS] = {nullptr, nullptr, nullptr, nullptr};
 
     void* coll_buf = nullptr; size_t coll_cap = 0;   // int16 staging of escx_allgather_codes (send | recv)
+    void* mix_buf = nullptr; size_t mix_cap = 0;     // mixed-stream calls (escx_*_streams): clip maps and the workspace-order copies of inputs / outputs (grow-only)
 
     // index maps (device), keyed by (H, W, shift) ; shift = -1 -> merge map
     std::map<std::tuple<int, int, int>, int*> maps;

@@ -190,6 +190,7 @@ extern "C" void escx_destroy(escx_handle h) {
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
     for (auto& kv : h->maps) (void)hipFree(kv.second);
     if (h->coll_buf) (void)hipFree(h->coll_buf);
+    if (h->mix_buf) (void)hipFree(h->mix_buf);
     for (Quant& q : h->quants) if (q.tab) (void)hipFree(q.tab);
     for (Layer& L : h->layers) { if (L.sub_x3_buf) (void)hipFree(L.sub_x3_buf); if (L.sub_x3s_buf) (void)hipFree(L.sub_x3s_buf); }
     if (h->dch_x2_buf) (void)hipFree(h->dch_x2_buf);

@@ -589,6 +589,90 @@ __global__ void test_math_kernel(const float* __restrict__ x, float* __restrict_
     if (i >= n) return;
     y[i] = which == 0 ? gelu_bf(x[i]) : (which == 1 ? erf_bf(x[i]) : (which == 2 ? exp_fast(x[i]) : gelu_erf(x[i])));
 }
+// ------------------------------------------------------------------------------------------------
+// Mixed-stream batches (escx_*_streams, escx_api.cpp): every clip carries its own stream count S_b.
+// ------------------------------------------------------------------------------------------------
+// Clip permutation: dst row r = src row map[r], rows of row_len floats (waveforms, spectra, audio, per-clip losses).  vec: row_len % 4 == 0
+// and both bases 16-byte aligned (float4 accesses).
+__global__ __launch_bounds__(256) void rows_permute_kernel(const float* __restrict__ src, float* __restrict__ dst, const int* __restrict__ map, int rows,
+                                                           long long row_len, int vec) {
+    const long long step = (long long)gridDim.x * 256;
+    for (int r = blockIdx.y; r < rows; r += gridDim.y) {
+        const float* s = src + (size_t)map[r] * row_len;
+        float* d = dst + (size_t)r * row_len;
+        if (vec) {
+            for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < row_len / 4; i += step)
+                reinterpret_cast<float4*>(d)[i] = reinterpret_cast<const float4*>(s)[i];
+        } else {
+            for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < row_len; i += step) d[i] = s[i];
+        }
+    }
+}
+// Code rows of (rows, Smax, GT) int64: dst[r][s][:] = src[map[r]][s][:] for s < S[r], -1 for the slots a clip does not carry (source rows are
+// src_stride codes apart; a slot at or past S[r] is never read).
+__global__ void codes_permute_kernel(const long long* __restrict__ src, long long src_stride, long long* __restrict__ dst, const int* __restrict__ map,
+                                     const int* __restrict__ S, int rows, int Smax, int GT) {
+    const long long per = (long long)Smax * GT;
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= rows * per) return;
+    const int r = (int)(idx / per);
+    const long long k = idx - r * per;
+    dst[idx] = k < (long long)S[r] * GT ? src[(size_t)map[r] * src_stride + k] : -1;
+}
+// Per-clip commitment loss of a mixed-stream pass: the slots of loss_reduce_kernel, but clip b sums only its own min(S[b], cap) slots, and stream
+// slot j's terms were written by a launch over the first rows.m[j] / Tq clips (layout [G][m[j]] at terms + j * lslot).  Same summation order as
+// loss_reduce_kernel: a clip's loss is bit for bit the one a uniform call at its S returns.
+struct SlotRows { int m[8]; };         // per stream slot (max_streams <= ESCX_MAX_SCALES = 8)
+__global__ __launch_bounds__(64) void loss_reduce_streams_kernel(const float* __restrict__ terms, long long lslot, const int* __restrict__ S, int cap,
+                                                                 SlotRows rows, int G, int Tq, float* __restrict__ out) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int per = min(S[b], cap) * G * Tq;
+    float acc = 0.f;
+    for (int i = lane; i < per; i += 64) {
+        const int sg = i / Tq, t = i - sg * Tq;
+        const int j = sg / G, g = sg - j * G;
+        acc += terms[(size_t)j * lslot + (size_t)g * rows.m[j] + (size_t)b * Tq + t];
+    }
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) acc += __shfl_xor(acc, o);
+    if (lane == 0) out[b] = acc;
+}
+// Ragged 10-bit wire format: clip b's first S_b * GT codes of a (B, Smax, GT) tensor, compacted in clip order, then packed as codes_pack10_kernel
+// packs a flat array (4 codes -> 5 bytes, little-endian bit order: code i occupies bits [10 i, 10 i + 10) of the payload).  off: B + 1 prefix sums
+// of S_b * GT (off[B] = n).
+__device__ inline int clip_of(const long long* __restrict__ off, int B, long long i) {      // largest b with off[b] <= i
+    int lo = 0, hi = B - 1;
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (off[mid] <= i) lo = mid; else hi = mid - 1; }
+    return lo;
+}
+__global__ void codes_pack10_streams_kernel(const long long* __restrict__ in, unsigned char* __restrict__ out, const long long* __restrict__ off, int B,
+                                            long long clip_stride) {
+    const long long n = off[B];
+    const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q * 4 >= n) return;
+    unsigned long long v = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const long long i = q * 4 + j;
+        if (i >= n) break;
+        const int b = clip_of(off, B, i);
+        v |= (unsigned long long)(in[(size_t)b * clip_stride + (i - off[b])] & 1023) << (10 * j);
+    }
+#pragma unroll
+    for (int j = 0; j < 5; ++j) out[q * 5 + j] = (unsigned char)(v >> (8 * j));
+}
+// Inverse: every element of the padded (B, Smax, GT) output; slots at or past S_b become -1.
+__global__ void codes_unpack10_streams_kernel(const unsigned char* __restrict__ in, long long* __restrict__ out, const long long* __restrict__ off, int B,
+                                              long long clip_stride) {
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= (long long)B * clip_stride) return;
+    const int b = (int)(e / clip_stride);
+    const long long k = e - b * clip_stride;
+    if (k >= off[b + 1] - off[b]) { out[e] = -1; return; }
+    const long long bit = 10 * (off[b] + k);
+    const unsigned v = (unsigned)in[bit >> 3] | ((unsigned)in[(bit >> 3) + 1] << 8);         // bits 10 i .. 10 i + 9 span exactly these two bytes
+    out[e] = (long long)((v >> (bit & 7)) & 1023);
+}
 __global__ void codes_narrow_kernel(const long long* __restrict__ in, short* __restrict__ out, long long n) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = (short)in[i];

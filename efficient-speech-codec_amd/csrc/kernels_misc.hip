@@ -1,4 +1,7 @@
 // Launchers for the non-GEMM kernels.
+#include <algorithm>
+#include <cstdint>
+
 #include "kernels.h"
 #include "fused_pvq.h"
 #include <atomic>
@@ -203,6 +206,29 @@ void test_math(const float* x, float* y, long long n, int which, hipStream_t s) 
 }
 void test_copy_rows(const float* src, float* dst, long long rows, int Cp, hipStream_t s) {
     ESCX_LAUNCH(test_copy_rows_kernel, dim3(4096), dim3(256), 0, s, src, dst, rows, Cp);
+}
+void rows_permute(const float* src, float* dst, const int* map, int rows, long long row_len, hipStream_t s) {
+    const int vec = (row_len % 4 == 0 && (reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) % 16 == 0) ? 1 : 0;
+    const long long per_row = vec ? row_len / 4 : row_len;
+    const unsigned gx = (unsigned)std::max<long long>(1, std::min<long long>((per_row + 255) / 256, 1024));
+    ESCX_LAUNCH(rows_permute_kernel, dim3(gx, (unsigned)std::min(rows, 65535)), dim3(256), 0, s, src, dst, map, rows, row_len, vec);
+}
+void codes_permute(const long long* src, long long src_stride, long long* dst, const int* map, const int* S, int rows, int Smax, int GT, hipStream_t s) {
+    const long long n = (long long)rows * Smax * GT;
+    ESCX_LAUNCH(codes_permute_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src, src_stride, dst, map, S, rows, Smax, GT);
+}
+void loss_reduce_streams(const float* terms, long long lslot, const int* S, int cap, const int* slot_clips, int G, int Tq, int B, float* out, hipStream_t s) {
+    SlotRows r{};
+    for (int j = 0; j < cap && j < 8; ++j) r.m[j] = slot_clips[j] * Tq;
+    ESCX_LAUNCH(loss_reduce_streams_kernel, dim3(B), dim3(64), 0, s, terms, lslot, S, cap, r, G, Tq, out);
+}
+void codes_pack10_streams(const long long* in, unsigned char* out, const long long* off, int B, long long clip_stride, long long n, hipStream_t s) {
+    const long long q = (n + 3) / 4;
+    if (q > 0) ESCX_LAUNCH(codes_pack10_streams_kernel, dim3((unsigned)((q + 255) / 256)), dim3(256), 0, s, in, out, off, B, clip_stride);
+}
+void codes_unpack10_streams(const unsigned char* in, long long* out, const long long* off, int B, long long clip_stride, hipStream_t s) {
+    const long long n = (long long)B * clip_stride;
+    if (n > 0) ESCX_LAUNCH(codes_unpack10_streams_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, in, out, off, B, clip_stride);
 }
 void codes_narrow(const long long* in, short* out, long long n, hipStream_t s) {
     ESCX_LAUNCH(codes_narrow_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, in, out, n);

@@ -134,6 +134,12 @@ void codes_pack10(const long long* in, unsigned char* out, long long n, hipStrea
 void codes_unpack10(const unsigned char* in, long long* out, long long n, hipStream_t s);
 void test_math(const float* x, float* y, long long n, int which, hipStream_t s);
 void test_copy_rows(const float* src, float* dst, long long rows, int Cp, hipStream_t s);
+// mixed-stream batches (kernels.h): clip permutation of float rows / code rows (with the -1 fill), per-clip loss over each clip's own slots, ragged 10-bit packing
+void rows_permute(const float* src, float* dst, const int* map, int rows, long long row_len, hipStream_t s);
+void codes_permute(const long long* src, long long src_stride, long long* dst, const int* map, const int* S, int rows, int Smax, int GT, hipStream_t s);
+void loss_reduce_streams(const float* terms, long long lslot, const int* S, int cap, const int* slot_clips, int G, int Tq, int B, float* out, hipStream_t s);
+void codes_pack10_streams(const long long* in, unsigned char* out, const long long* off, int B, long long clip_stride, long long n, hipStream_t s);
+void codes_unpack10_streams(const unsigned char* in, long long* out, const long long* off, int B, long long clip_stride, hipStream_t s);
 void codes_narrow(const long long* in, short* out, long long n, hipStream_t s);
 void codes_widen(const short* in, long long* out, long long n, hipStream_t s);
 

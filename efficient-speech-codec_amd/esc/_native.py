@@ -45,6 +45,9 @@ SIGNATURES = {
     "escx_decode": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "escx_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "escx_forward_feat": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "escx_encode_streams": (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(c_int32), c_void_p, POINTER(c_int), POINTER(c_int), c_void_p]),
+    "escx_decode_streams": (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(c_int32), c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "escx_forward_streams": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(c_int32), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "escx_num_frames": (c_int, [c_void_p, c_int]),
     "escx_output_samples": (c_int, [c_void_p, c_int]),
     "escx_spec_transform": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
@@ -62,6 +65,8 @@ SIGNATURES = {
     "escx_test_copy_rows": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p]),
     "escx_codes_pack10": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     "escx_codes_unpack10": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
+    "escx_codes_pack10_streams": (c_int, [c_void_p, c_int, c_int, c_int64, POINTER(c_int32), c_void_p, c_void_p]),
+    "escx_codes_unpack10_streams": (c_int, [c_void_p, c_int, c_int, c_int64, POINTER(c_int32), c_void_p, c_void_p]),
     "escx_codes_narrow": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     "escx_codes_widen": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     "escx_flat_param_count": (c_int, [c_void_p]),

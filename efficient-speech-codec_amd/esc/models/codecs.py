@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import ctypes
 import math
+import operator
 from typing import Dict, List, Literal, Optional, Tuple
 
 import torch
@@ -384,13 +385,55 @@ class ESC(nn.Module):
             H = (H + 1) // 2
         return H, T // pt
 
+    @staticmethod
+    def _is_per_clip(num_streams) -> bool:
+        """True for per-clip stream counts (a sequence or a 1-D tensor / array), False for one count for the whole batch."""
+        if isinstance(num_streams, (str, bytes)):
+            return False
+        if isinstance(num_streams, torch.Tensor) or hasattr(num_streams, "ndim"):
+            return int(num_streams.ndim) > 0
+        return isinstance(num_streams, (list, tuple, range))
+
+    def _per_clip_streams(self, num_streams, B: int) -> Optional[List[int]]:
+        """None when `num_streams` is one count for the whole batch; else the per-clip counts (length B, each in [1, max_streams])."""
+        if not self._is_per_clip(num_streams):
+            return None
+        if isinstance(num_streams, torch.Tensor):
+            if num_streams.dim() != 1 or num_streams.dtype.is_floating_point or num_streams.dtype.is_complex or num_streams.dtype == torch.bool:
+                raise ValueError(f"per-clip num_streams must be a 1-D integer tensor (got {num_streams.dtype}, {num_streams.dim()}-D)")
+            vals = num_streams.tolist()
+        else:
+            if int(getattr(num_streams, "ndim", 1)) != 1:
+                raise ValueError("per-clip num_streams must be one-dimensional")
+            vals = list(num_streams)
+        out = []
+        for v in vals:
+            if isinstance(v, bool) or isinstance(v, float):
+                raise ValueError(f"per-clip num_streams must be integers (got {v!r})")
+            try:
+                out.append(operator.index(v))
+            except TypeError:
+                raise ValueError(f"per-clip num_streams must be integers (got {v!r})") from None
+        if len(out) != B:
+            raise ValueError(f"per-clip num_streams has {len(out)} entries for a batch of {B} clips")
+        for b, v in enumerate(out):
+            if not 1 <= v <= self.max_streams:
+                raise ValueError(f"num_streams[{b}]={v} outside [1, {self.max_streams}]")
+        return out
+
     # ---- public API (codecs.py:48-94) ---------------------------------------------------------
     @torch.no_grad()
-    def encode(self, x: torch.Tensor, num_streams: int = 6):
-        """(Bs, L) waveform -> codes (Bs, num_streams, group_size, W/overlap) int64, feat_shape (H, W)."""
+    def encode(self, x: torch.Tensor, num_streams=6):
+        """(Bs, L) waveform -> codes (Bs, num_streams, group_size, W/overlap) int64, feat_shape (H, W).
+        `num_streams` may also be a length-Bs sequence or 1-D integer tensor of per-clip counts (a mixed-bitrate batch): the codes are then
+        (Bs, max(num_streams), group_size, W/overlap) with -1 in the slots past each clip's own count, and clip b's codes equal those of
+        encode(x[b:b+1], num_streams[b])."""
         if x.dim() != 2:
             raise ValueError("x must have shape (Bs, L)")
+        streams = self._per_clip_streams(num_streams, x.shape[0])
         self._need_gpu(x, "x")
+        if streams is not None:
+            return self._encode_streams(x, streams)
         x = x.to(torch.float32).contiguous()
         lib, hd = self._handle(x.device)
         B, L = x.shape
@@ -407,11 +450,37 @@ class ESC(nn.Module):
                                           ctypes.byref(fw), self._stream(x.device)))
         return codes, (fh.value, fw.value)
 
+    def _encode_streams(self, x: torch.Tensor, streams: List[int]):
+        x = x.to(torch.float32).contiguous()
+        B, L = x.shape
+        _, W = self.latent_shape(L)
+        if W % self.cfg["overlap"] != 0:
+            raise AssertionError("Time dimension must be multiple of overlap")       # quantization.py:407
+        codes = torch.empty((B, max(streams, default=0), self.cfg["group_size"], W // self.cfg["overlap"]), dtype=torch.int64, device=x.device)
+        if B == 0:
+            return codes, self.latent_shape(L)
+        lib, hd = self._handle(x.device)
+        fh, fw = ctypes.c_int(), ctypes.c_int()
+        counts = (ctypes.c_int32 * B)(*streams)
+        with torch.cuda.device(x.device):
+            _native.check(lib.escx_encode_streams(hd, x.data_ptr(), B, L, counts, codes.data_ptr(), ctypes.byref(fh), ctypes.byref(fw),
+                                                  self._stream(x.device)))
+        return codes, (fh.value, fw.value)
+
     @torch.no_grad()
-    def decode(self, codes: torch.Tensor, feat_shape=(2, 1000), return_feat: bool = False):
-        """codes (Bs, num_streams, group_size, *) + feat_shape (H, W) -> waveform (Bs, hop*(2W-1))."""
+    def decode(self, codes: torch.Tensor, feat_shape=(2, 1000), return_feat: bool = False, num_streams=None):
+        """codes (Bs, num_streams, group_size, *) + feat_shape (H, W) -> waveform (Bs, hop*(2W-1)).
+        num_streams=None: every clip carries codes.size(1) streams.  A length-Bs sequence / 1-D integer tensor gives each clip its own
+        count (at most codes.size(1)); the slots at or past it are never read."""
         if codes.dim() != 4:
             raise ValueError("codes must have shape (Bs, num_streams, group_size, T)")
+        streams = None
+        if num_streams is not None:
+            if not self._is_per_clip(num_streams):
+                raise ValueError("decode(num_streams=...) takes per-clip counts (a sequence or 1-D tensor); a uniform count is codes.size(1)")
+            streams = self._per_clip_streams(num_streams, codes.shape[0])
+            if streams and max(streams) > codes.shape[1]:
+                raise ValueError(f"num_streams up to {max(streams)} but codes carry {codes.shape[1]} stream slots")
         self._need_gpu(codes, "codes")
         codes = codes.to(torch.int64).contiguous()
         lib, hd = self._handle(codes.device)
@@ -425,8 +494,12 @@ class ESC(nn.Module):
         if B == 0:
             return (out, feat.permute(0, 2, 3, 1)) if return_feat else out
         with torch.cuda.device(codes.device):
-            _native.check(lib.escx_decode(hd, codes.data_ptr(), B, S, H, W, out.data_ptr(),
-                                          feat.data_ptr() if return_feat else None, self._stream(codes.device)))
+            if streams is None:
+                _native.check(lib.escx_decode(hd, codes.data_ptr(), B, S, H, W, out.data_ptr(),
+                                              feat.data_ptr() if return_feat else None, self._stream(codes.device)))
+            else:
+                _native.check(lib.escx_decode_streams(hd, codes.data_ptr(), B, S, (ctypes.c_int32 * B)(*streams), H, W, out.data_ptr(),
+                                                      feat.data_ptr() if return_feat else None, self._stream(codes.device)))
         if return_feat:
             return out, feat.permute(0, 2, 3, 1)
         return out
@@ -435,16 +508,21 @@ class ESC(nn.Module):
         if not self.training and freeze_codebook:
             raise ValueError("``freeze_vq`` must be set False during inference")       # quantization.py:43-44
         if self.training:
+            if self._is_per_clip(num_streams):
+                raise ValueError("per-clip num_streams is an inference feature: the training step draws one num_streams per batch "
+                                 "(scripts/utils.py:11-25)")
             return self._forward_train(x, x_feat, int(num_streams), bool(freeze_codebook))
         if x_feat is not None:
-            return self._forward_from_feat(x, x_feat, int(num_streams))
+            streams = self._per_clip_streams(num_streams, x_feat.shape[0]) if x_feat.dim() == 4 else None
+            return self._forward_from_feat(x, x_feat, int(num_streams) if streams is None else streams)
         if x.dim() != 2:
             raise ValueError("x must have shape (Bs, L)")
+        streams = self._per_clip_streams(num_streams, x.shape[0])
         self._need_gpu(x, "x")
         xin = x.to(torch.float32).contiguous()
         lib, hd = self._handle(xin.device)
         B, L = xin.shape
-        S = int(num_streams)
+        S = int(num_streams) if streams is None else max(streams, default=0)
         _, W = self.latent_shape(L)
         if W % self.cfg["overlap"] != 0:
             raise AssertionError("Time dimension must be multiple of overlap")
@@ -457,16 +535,20 @@ class ESC(nn.Module):
         recon_feat = torch.empty((B, pt * W, self.in_dim, self.in_freq), dtype=torch.float32, device=dev)
         cm = torch.empty((B,), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            if B > 0:                                   # an empty batch returns the (empty) buffers as they are
+            if B > 0 and streams is None:               # an empty batch returns the (empty) buffers as they are
                 _native.check(lib.escx_forward(hd, xin.data_ptr(), B, L, S, codes.data_ptr(), recon.data_ptr(), raw_feat.data_ptr(),
                                                recon_feat.data_ptr(), cm.data_ptr(), self._stream(dev)))
+            elif B > 0:                                 # per-clip counts: codes (B, max S, G, T), -1 past each clip's streams
+                _native.check(lib.escx_forward_streams(hd, xin.data_ptr(), None, B, L, (ctypes.c_int32 * B)(*streams), codes.data_ptr(),
+                                                       recon.data_ptr(), raw_feat.data_ptr(), recon_feat.data_ptr(), cm.data_ptr(), self._stream(dev)))
         return {"cm_loss": cm, "cb_loss": cm.clone(), "raw_audio": x, "recon_audio": recon,
                 "raw_feat": raw_feat.permute(0, 2, 3, 1), "recon_feat": recon_feat.permute(0, 2, 3, 1), "codes": codes}
 
     def _forward_from_feat(self, x, x_feat, S):
         """forward(x, x_feat=...) of the reference (codecs.py:33-34): x_feat is the complex STFT as a real tensor laid out
         (Bs, F, T, 2) - what `rearrange(x_feat, "b h w c -> b c h w")` expects, despite the docstring - and replaces
-        spec_transform(x).  The permutation to the library's frame-major layout is plain data movement."""
+        spec_transform(x).  The permutation to the library's frame-major layout is plain data movement.  S: one count, or a
+        list of per-clip counts."""
         if x_feat.dim() != 4 or x_feat.shape[1] != self.in_freq or x_feat.shape[3] != self.in_dim:
             raise ValueError(f"x_feat must have shape (Bs, {self.in_freq}, T, {self.in_dim})")
         self._need_gpu(x_feat, "x_feat")
@@ -478,13 +560,19 @@ class ESC(nn.Module):
             raise AssertionError("Time dimension must be multiple of overlap")
         dev = feat.device
         lib, hd = self._handle(dev)
-        codes = torch.empty((B, S, self.cfg["group_size"], W // self.cfg["overlap"]), dtype=torch.int64, device=dev)
+        streams = S if isinstance(S, list) else None
+        Smax = max(streams, default=0) if streams is not None else S
+        codes = torch.empty((B, Smax, self.cfg["group_size"], W // self.cfg["overlap"]), dtype=torch.int64, device=dev)
         recon = torch.empty((B, self.hop_length * (pt * W - 1)), dtype=torch.float32, device=dev)
         recon_feat = torch.empty((B, pt * W, self.in_dim, self.in_freq), dtype=torch.float32, device=dev)
         cm = torch.empty((B,), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            _native.check(lib.escx_forward_feat(hd, feat.data_ptr(), B, T, S, codes.data_ptr(), recon.data_ptr(), recon_feat.data_ptr(),
-                                                cm.data_ptr(), self._stream(dev)))
+            if streams is None:
+                _native.check(lib.escx_forward_feat(hd, feat.data_ptr(), B, T, S, codes.data_ptr(), recon.data_ptr(), recon_feat.data_ptr(),
+                                                    cm.data_ptr(), self._stream(dev)))
+            elif B > 0:
+                _native.check(lib.escx_forward_streams(hd, None, feat.data_ptr(), B, T, (ctypes.c_int32 * B)(*streams), codes.data_ptr(),
+                                                       recon.data_ptr(), None, recon_feat.data_ptr(), cm.data_ptr(), self._stream(dev)))
         return {"cm_loss": cm, "cb_loss": cm.clone(), "raw_audio": x, "recon_audio": recon,
                 "raw_feat": x_feat.permute(0, 3, 1, 2), "recon_feat": recon_feat.permute(0, 2, 3, 1), "codes": codes}
 

@@ -129,6 +129,24 @@ int escx_forward(escx_handle h, const float* wave_dev, int batch, int n_samples,
  * (B, T, 2, in_freq) f32 frame-major, i.e. the reference's x_feat (B,F,T,2) permuted (0,2,3,1); the STFT is skipped. */
 int escx_forward_feat(escx_handle h, const float* feat_dev, int batch, int n_frames, int num_streams,
                       int64_t* codes_dev, float* wave_out_dev, float* recon_feat_dev, float* cm_loss_dev, void* stream);
+/* Mixed-bitrate batches: the same three calls with a stream count PER CLIP.  `streams` is a HOST array of `batch` counts, each in [1, max_streams]
+ * (the counts shape the launches).  Clip b's results are bit for bit those of the uniform call at num_streams = streams[b]: the codes of S streams
+ * are the first S of the S = max_streams codes (csrvq.py:131-158) and untransmitted streams pass through the decoder (csrvq.py:160-183, :35-36).
+ * Each stream and each decoder block that feeds a later stream runs only on the clips that need it.  A null `streams`, batch < 1 or a count
+ * outside the range is ESCX_ERR_INVALID_ARG.  The counts are uploaded with every call and the handle's staging buffer grows (synchronously) on first
+ * use of a larger batch: these calls are not meant for graph capture.
+ * ESC.encode (codecs.py:68-81): codes (B, Smax, G, W/overlap) int64, Smax = max(streams); slots [streams[b], Smax) of clip b are -1. */
+int escx_encode_streams(escx_handle h, const float* wave_dev, int batch, int n_samples, const int32_t* streams,
+                        int64_t* codes_dev, int* feat_h, int* feat_w, void* stream);
+/* ESC.decode (codecs.py:83-94): codes (B, smax, G, T) with smax >= max(streams); slots at or past streams[b] are never read.  Codes outside
+ * [0, codebook_size) in the slots below streams[b] are clamped, as in escx_decode. */
+int escx_decode_streams(escx_handle h, const int64_t* codes_dev, int batch, int smax, const int32_t* streams, int feat_h, int feat_w,
+                        float* wave_out_dev, float* recon_feat_dev, void* stream);
+/* ESC.forward in eval mode (codecs.py:30-66, csrvq.py:97-129): exactly one of wave_dev (B, n_samples) / feat_dev (B, n_frames, 2, in_freq)
+ * is given (n_samples_or_frames is the matching length); outputs as escx_forward with codes (B, max(streams), G, T), -1 past each clip's streams;
+ * cm_loss[b] sums only clip b's own streams. */
+int escx_forward_streams(escx_handle h, const float* wave_dev, const float* feat_dev, int batch, int n_samples_or_frames, const int32_t* streams,
+                         int64_t* codes_dev, float* wave_out_dev, float* raw_feat_dev, float* recon_feat_dev, float* cm_loss_dev, void* stream);
 int escx_num_frames(escx_handle h, int n_samples);      /* T = 1 + n_samples / hop                      */
 int escx_output_samples(escx_handle h, int feat_w);     /* hop * (patch_t * W - 1)                      */
 
@@ -178,6 +196,11 @@ int escx_test_fastdiv(int n, int d);
 /* 10-bit wire format (codebook_size 1024): n codes <-> 5*ceil(n/4) bytes; 6 streams x 3 groups x 50 Hz x 10 b = 9 kbps (base.py:70). */
 int escx_codes_pack10(const int64_t* codes_dev, uint8_t* out_dev, int64_t n, void* stream);
 int escx_codes_unpack10(const uint8_t* in_dev, int64_t* codes_dev, int64_t n, void* stream);
+/* Ragged form for mixed-stream batches: codes (batch, smax, gt) with gt = G*T and a HOST array of per-clip counts in [1, smax].  Pack writes
+ * clip b's first streams[b]*gt codes, clips in order, as one 10-bit stream of 5*ceil(n/4) bytes (n = gt * sum(streams)); unpack restores the
+ * padded layout with -1 in the slots at or past streams[b].  One launch each. */
+int escx_codes_pack10_streams(const int64_t* codes_dev, int batch, int smax, int64_t gt, const int32_t* streams, uint8_t* out_dev, void* stream);
+int escx_codes_unpack10_streams(const uint8_t* in_dev, int batch, int smax, int64_t gt, const int32_t* streams, int64_t* codes_dev, void* stream);
 int escx_codes_narrow(const int64_t* codes_dev, int16_t* out_dev, int64_t n, void* stream);
 int escx_codes_widen(const int16_t* in_dev, int64_t* codes_dev, int64_t n, void* stream);
 
