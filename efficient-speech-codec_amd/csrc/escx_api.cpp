@@ -564,6 +564,13 @@ static void spec_pad(escx_handle_s* h, const float* src, float* dst, long long r
 extern "C" int escx_num_frames(escx_handle h, int n_samples) { return h ? 1 + n_samples / h->cfg.hop_length : 0; }
 extern "C" int escx_output_samples(escx_handle h, int feat_w) { return h ? h->cfg.hop_length * (h->cfg.patch_t * feat_w - 1) : 0; }
 
+// rvq+swinT handles (escx_create_rvq): the whole-path entry points below dispatch to these (defined after the mixed-stream section).
+// streams: HOST per-clip counts or nullptr (= S for every clip).
+static int rvq_encode(escx_handle_s* h, const float* wave, int B, int L, const int32_t* streams, int S, int64_t* codes, int* fh, int* fw, void* stream);
+static int rvq_decode(escx_handle_s* h, const int64_t* codes, int B, int S, const int32_t* streams, int fh, int fw, float* wave_out, float* recon_feat, void* stream);
+static int rvq_forward(escx_handle_s* h, const float* wave, const float* feat, int B, int LT, const int32_t* streams, int S, int64_t* codes, float* wave_out,
+                       float* raw_feat, float* recon_feat, float* cm_loss, void* stream);
+
 // csrvq.py:131-158
 static int run_csvq_encode(escx_handle_s* h, const Shapes& s, int S, long long* codes, hipStream_t st) {
     const escx_config& c = h->cfg;
@@ -585,6 +592,7 @@ static int run_csvq_encode(escx_handle_s* h, const Shapes& s, int S, long long* 
 }
 
 extern "C" int escx_encode(escx_handle h, const float* wave, int B, int L, int S, int64_t* codes, int* fh, int* fw, void* stream) {
+    if (h && h->kind == 1) return rvq_encode(h, wave, B, L, nullptr, S, codes, fh, fw, stream);
     int rc = check_ready(h); if (rc) return rc;
     if (!wave || !codes) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null pointer");
     if (S < 1 || S > h->cfg.max_streams) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "num_streams=%d outside [1, %d]", S, h->cfg.max_streams);
@@ -623,6 +631,7 @@ static int run_csvq_decode(escx_handle_s* h, const long long* codes, int B, int 
 
 extern "C" int escx_decode(escx_handle h, const int64_t* codes, int B, int S, int fh, int fw, float* wave_out, float* recon_feat,
                            void* stream) {
+    if (h && h->kind == 1) return rvq_decode(h, codes, B, S, nullptr, fh, fw, wave_out, recon_feat, stream);
     int rc = check_infer_ready(h); if (rc) return rc;
     if (!codes || !wave_out) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null pointer");
     const escx_config& c = h->cfg;
@@ -647,6 +656,7 @@ extern "C" int escx_decode(escx_handle h, const int64_t* codes, int B, int S, in
 // permuted to frame-major) is given; with `feat` the STFT is skipped (codecs.py:33-34).
 static int forward_impl(escx_handle h, const float* wave, const float* feat, int B, int L, int T, int S, int64_t* codes, float* wave_out,
                         float* raw_feat, float* recon_feat, float* cm_loss, void* stream) {
+    if (h && h->kind == 1) return rvq_forward(h, wave, feat, B, wave ? L : T, nullptr, S, codes, wave_out, raw_feat, recon_feat, cm_loss, stream);
     int rc = check_infer_ready(h); if (rc) return rc;
     if ((!wave && !feat) || !codes || !wave_out) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null pointer");
     const escx_config& c = h->cfg;
@@ -828,6 +838,7 @@ static int run_csvq_decode_streams(escx_handle_s* h, const long long* codes, lon
 
 extern "C" int escx_encode_streams(escx_handle h, const float* wave, int B, int L, const int32_t* streams, int64_t* codes, int* fh, int* fw,
                                    void* stream) {
+    if (h && h->kind == 1) return rvq_encode(h, wave, B, L, streams, 0, codes, fh, fw, stream);
     int rc = check_ready(h); if (rc) return rc;
     if (!wave || !codes) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null pointer");
     int Smax = 0; if ((rc = check_streams(h, B, streams, &Smax))) return rc;
@@ -859,6 +870,7 @@ extern "C" int escx_encode_streams(escx_handle h, const float* wave, int B, int 
 
 extern "C" int escx_decode_streams(escx_handle h, const int64_t* codes, int B, int Smax_in, const int32_t* streams, int fh, int fw, float* wave_out,
                                    float* recon_feat, void* stream) {
+    if (h && h->kind == 1) return rvq_decode(h, codes, B, Smax_in, streams, fh, fw, wave_out, recon_feat, stream);
     int rc = check_infer_ready(h); if (rc) return rc;
     if (!codes || !wave_out) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null pointer");
     const escx_config& c = h->cfg;
@@ -895,6 +907,7 @@ extern "C" int escx_decode_streams(escx_handle h, const int64_t* codes, int B, i
 // codecs.py:30-66 in eval mode with per-clip stream counts; forward_impl is the uniform form.  Exactly one of `wave` / `feat` is given.
 extern "C" int escx_forward_streams(escx_handle h, const float* wave, const float* feat, int B, int LT, const int32_t* streams, int64_t* codes,
                                     float* wave_out, float* raw_feat, float* recon_feat, float* cm_loss, void* stream) {
+    if (h && h->kind == 1) return rvq_forward(h, wave, feat, B, LT, streams, 0, codes, wave_out, raw_feat, recon_feat, cm_loss, stream);
     int rc = check_infer_ready(h); if (rc) return rc;
     if ((!wave == !feat) || !codes || !wave_out) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null pointer (exactly one of wave / feat, codes and wave_out are required)");
     const escx_config& c = h->cfg;
@@ -960,6 +973,155 @@ extern "C" int escx_forward_streams(escx_handle h, const float* wave, const floa
     if (recon_feat) PROF("mix_scatter", 0, 2.0 * B * rec_row * 4, rows_permute(recon_ws, recon_feat, maps + B, B, rec_row, st));
     if (cm_loss) PROF("mix_scatter", 0, 8.0 * B, rows_permute(loss_ws, cm_loss, maps + B, B, 1, st));
     return launch_ok("forward_streams");
+}
+
+// ------------------------------------------------------------------------------------------------
+// rvq+swinT (RVQCodecs, codecs.py:96-181): the ESC encoder, ONE product-residual quantiser at the bottleneck (fused_prvq.h: one launch per batch
+// part, per-clip stage counts read on the device) and the plain decoder (base.py:161-203: every decoder block, post_nn, PatchDeEmbed).  Nothing
+// of the decoder depends on the stage count, so a mixed-count batch needs no clip permutation: the per-clip counts go to the quantiser only.
+// ------------------------------------------------------------------------------------------------
+static int run_prvq(escx_handle_s* h, const float* enc, const long long* codes_in, int B, int W, long long* codes, long long bstride, const int* clip_S,
+                    int S, float* loss, long long lslot, float* out, hipStream_t st) {
+    const escx_config& c = h->cfg;
+    const Quant& q = h->quants[0];
+    const int Tq = W / c.overlap, M = B * Tq;
+    const double vec = (double)c.overlap * q.Hq * q.C, G = c.group_size;
+    int rc = -1;
+    PROF(codes_in ? "prvq_decode" : (out ? "prvq_fused" : "prvq_fused_codes"),
+         codes_in ? 2.0 * M * vec * q.d : 2.0 * M * vec * q.d * (out ? 2 : 1) + 2.0 * M * S * G * c.codebook_size * q.d,
+         (double)M * vec * ((codes_in ? 0 : 1) + (out ? 1 : 0)) * 4,
+         rc = prvq_fused(enc, codes_in, B, q.Hq, W, q.Cp, c.overlap, q.wdf, q.Nz, q.Kq, pvq_down_splits(M, q.Kq, q.Cp), pvq_down_bk(q.Cp), q.cbn, q.c2, q.cbraw,
+                         c.group_size, c.codebook_size, q.d, q.dt, q.wup, codes, bstride, clip_S, S, S, loss, lslot, 1.0f / ((float)Tq * q.d * c.group_size),
+                         c.l2norm, out, st));
+    if (rc) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "rvq quantiser: geometry not covered (codebook_dim %d, %d groups)", q.d, c.group_size);
+    return launch_ok("prvq");
+}
+
+// Decoder.forward (base.py:195-203) on the bottleneck map h->decA: blocks, post_nn, PatchDeEmbed -> rspec
+static int run_plain_decoder(escx_handle_s* h, int B, int Hb, int W, float* rspec, hipStream_t st) {
+    const int n = h->n;
+    int rc, H = Hb, Hn;
+    float* dec = h->decA; float* other = h->decB;
+    for (int i = 0; i + 1 < n; ++i) {
+        if ((rc = run_layer(h, h->layers[n + i], dec, other, B, H, W, &Hn, st))) return rc;
+        std::swap(dec, other); H = Hn;
+    }
+    if ((rc = run_layer(h, h->layers[2 * n - 1], dec, other, B, H, W, &Hn, st))) return rc;
+    return run_deembed(h, other, B, W, rspec, st);
+}
+
+// stage counts of an rvq call: per clip (streams != nullptr) in [1, num_rvqs], or one S in [1, num_rvqs]; *Smax = the code slots per clip
+static int rvq_counts(escx_handle_s* h, int B, const int32_t* streams, int S, int* Smax) {
+    if (!streams) {
+        if (S < 1 || S > h->num_rvqs) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "num_streams=%d outside [1, %d] (num_rvqs)", S, h->num_rvqs);
+        *Smax = S;
+        return 0;
+    }
+    if (B < 1) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "batch=%d: the per-clip stream counts need at least one clip", B);
+    int m = 0;
+    for (int b = 0; b < B; ++b) {
+        if (streams[b] < 1 || streams[b] > h->num_rvqs) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "streams[%d]=%d outside [1, %d] (num_rvqs)", b, streams[b], h->num_rvqs);
+        m = std::max(m, (int)streams[b]);
+    }
+    *Smax = m;
+    return 0;
+}
+
+// per-clip counts on the device (the handle's grow-only staging buffer), or nullptr for a uniform call
+static int rvq_upload(escx_handle_s* h, int B, const int32_t* streams, const int** dev, hipStream_t st) {
+    *dev = nullptr;
+    if (!streams) return 0;
+    int32_t* d = nullptr;
+    MixBufs mb; mb.add(&d, (size_t)B);
+    int rc = mix_alloc(h, mb); if (rc) return rc;
+    ESCX_HIP(hipMemcpyAsync(d, streams, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    *dev = d;
+    return 0;
+}
+
+static int rvq_encode(escx_handle_s* h, const float* wave, int B, int L, const int32_t* streams, int S, int64_t* codes, int* fh, int* fw, void* stream) {
+    int rc = check_ready(h); if (rc) return rc;
+    if (!wave || !codes) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null pointer");
+    int Smax = 0; if ((rc = rvq_counts(h, B, streams, S, &Smax))) return rc;
+    if (L <= h->n_fft / 2) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "n_samples=%d too short for reflect padding of %d", L, h->n_fft / 2);
+    Shapes s; if ((rc = ensure_ws(h, B, frames_of(h, L), &s))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const int* Sdev; if ((rc = rvq_upload(h, B, streams, &Sdev, st))) return rc;
+    if ((rc = ensure_pvq_tables(h, st))) return rc;
+    const long long cstride = (long long)Smax * h->cfg.group_size * s.Tq;
+    rc = run_halves(h, B, s.T, st, [&](int b0, int nb, hipStream_t sti) -> int {
+        Shapes sp = s; sp.B = nb; int r;
+        if ((r = run_stft(h, wave + (size_t)b0 * L, nb, L, sp.T, h->spec, sti))) return r;
+        if ((r = run_encoder(h, sp, sti))) return r;
+        return run_prvq(h, h->enc_hs[h->n - 1], nullptr, nb, sp.W, (long long*)codes + b0 * cstride, cstride, Sdev ? Sdev + b0 : nullptr, Smax, nullptr, 0, nullptr, sti);
+    });
+    if (rc) return rc;
+    if (fh) *fh = s.encH[h->n - 1];
+    if (fw) *fw = s.W;
+    return ESCX_OK;
+}
+
+// S = codes.size(1); streams (optional) = per-clip counts, each <= S (slots at or past a clip's count are never read)
+static int rvq_decode(escx_handle_s* h, const int64_t* codes, int B, int S, const int32_t* streams, int fh, int fw, float* wave_out, float* recon_feat, void* stream) {
+    int rc = check_infer_ready(h); if (rc) return rc;
+    if (!codes || !wave_out) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null pointer");
+    const escx_config& c = h->cfg;
+    if (S < 1 || S > h->num_rvqs) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "codes.size(1)=%d outside [1, %d] (num_rvqs)", S, h->num_rvqs);
+    int Smax = 0; if ((rc = rvq_counts(h, B, streams, S, &Smax))) return rc;
+    if (Smax > S) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "codes.size(1)=%d: must be at least max(streams)=%d", S, Smax);
+    if (fw < 1 || fw % c.overlap) ESCX_FAIL(ESCX_ERR_ASSERT, "Time dimension must be multiple of overlap");
+    Shapes s; if ((rc = ensure_ws(h, B, frames_for_width(h, fw), &s))) return rc;
+    if (s.W != fw || s.encH[h->n - 1] != fh) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "feat_shape (%d,%d) does not match the model (%d,%d)", fh, fw, s.encH[h->n - 1], s.W);
+    hipStream_t st = (hipStream_t)stream;
+    const int* Sdev; if ((rc = rvq_upload(h, B, streams, &Sdev, st))) return rc;
+    if ((rc = ensure_pvq_tables(h, st))) return rc;
+    const int T2 = c.patch_t * fw, out_len = c.hop_length * (T2 - 1);
+    const long long cstride = (long long)S * c.group_size * (fw / c.overlap);
+    return run_halves(h, B, s.T, st, [&](int b0, int nb, hipStream_t sti) -> int {
+        int r;
+        if ((r = run_prvq(h, nullptr, (const long long*)codes + b0 * cstride, nb, fw, nullptr, cstride, Sdev ? Sdev + b0 : nullptr, S, nullptr, 0, h->decA, sti))) return r;
+        if ((r = run_plain_decoder(h, nb, fh, fw, h->rspec, sti))) return r;
+        if ((r = run_istft(h, h->rspec, nb, T2, wave_out + (size_t)b0 * out_len, sti))) return r;
+        if (recon_feat) spec_unpad(h, h->rspec, recon_feat + (size_t)b0 * T2 * c.in_dim * h->F, (long long)nb * T2, sti);
+        return launch_ok("rvq_decode");
+    });
+}
+
+// codecs.py:130-146 in eval mode; exactly one of wave (LT = n_samples) / feat (LT = n_frames)
+static int rvq_forward(escx_handle_s* h, const float* wave, const float* feat, int B, int LT, const int32_t* streams, int S, int64_t* codes, float* wave_out,
+                       float* raw_feat, float* recon_feat, float* cm_loss, void* stream) {
+    int rc = check_infer_ready(h); if (rc) return rc;
+    if ((!wave == !feat) || !codes || !wave_out) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null pointer (exactly one of wave / feat, codes and wave_out are required)");
+    const escx_config& c = h->cfg;
+    int Smax = 0; if ((rc = rvq_counts(h, B, streams, S, &Smax))) return rc;
+    const int L = wave ? LT : 0;
+    int T = wave ? 0 : LT;
+    if (wave && L <= h->n_fft / 2) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "n_samples=%d too short for reflect padding of %d", L, h->n_fft / 2);
+    if (!wave && T < c.patch_t) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "n_frames=%d shorter than one patch", T);
+    if (wave) T = frames_of(h, L);
+    Shapes s; if ((rc = ensure_ws(h, B, T, &s))) return rc;
+    if (s.W % c.overlap) ESCX_FAIL(ESCX_ERR_ASSERT, "Time dimension must be multiple of overlap");
+    hipStream_t st = (hipStream_t)stream;
+    const int* Sdev; if ((rc = rvq_upload(h, B, streams, &Sdev, st))) return rc;
+    if ((rc = ensure_pvq_tables(h, st))) return rc;
+    const int G = c.group_size, T2 = c.patch_t * s.W, out_len = c.hop_length * (T2 - 1);
+    const long long cstride = (long long)Smax * G * s.Tq;
+    return run_halves(h, B, s.T, st, [&](int b0, int nb, hipStream_t sti) -> int {
+        Shapes sp = s; sp.B = nb; int r;
+        if (wave) { if ((r = run_stft(h, wave + (size_t)b0 * L, nb, L, sp.T, h->spec, sti))) return r; }
+        else spec_pad(h, feat + (size_t)b0 * sp.T * c.in_dim * h->F, h->spec, (long long)nb * sp.T, sti);
+        if (raw_feat) spec_unpad(h, h->spec, raw_feat + (size_t)b0 * sp.T * c.in_dim * h->F, (long long)nb * sp.T, sti);
+        if ((r = run_encoder(h, sp, sti))) return r;
+        // per-vector commitment terms of stage s go to loss_terms[s][G][nb * Tq] (0 past a clip's own count); reduced per clip in a fixed order
+        const long long lslot = (long long)G * nb * sp.Tq;
+        float* loss = cm_loss ? h->loss_terms : nullptr;
+        if ((r = run_prvq(h, h->enc_hs[h->n - 1], nullptr, nb, sp.W, (long long*)codes + b0 * cstride, cstride, Sdev ? Sdev + b0 : nullptr, Smax, loss, lslot, h->decA, sti))) return r;
+        if ((r = run_plain_decoder(h, nb, sp.encH[h->n - 1], sp.W, h->rspec, sti))) return r;
+        if ((r = run_istft(h, h->rspec, nb, T2, wave_out + (size_t)b0 * out_len, sti))) return r;
+        if (recon_feat) spec_unpad(h, h->rspec, recon_feat + (size_t)b0 * T2 * c.in_dim * h->F, (long long)nb * T2, sti);
+        if (cm_loss) PROF("loss_reduce", 0, (double)lslot * Smax * 4, loss_reduce(loss, Smax, G, nb * sp.Tq, sp.Tq, cm_loss + b0, sti));
+        return launch_ok("rvq_forward");
+    });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1034,6 +1196,7 @@ extern "C" int escx_transformer_layer(escx_handle h, int layer_id, const float* 
 extern "C" int escx_pvq_encode(escx_handle h, int sid, const float* enc, const float* dec, int B, int W, int64_t* codes, int64_t bstride,
                                void* stream) {
     int rc = check_ready(h); if (rc) return rc;
+    if (h->kind != 0) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "escx_pvq_encode: the cross-scale quantisers do not exist on an rvq handle (escx_rvq_encode / escx_rvq_decode)");
     if (sid < 0 || sid >= h->cfg.max_streams) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "stream_id out of range");
     if (W % h->cfg.overlap) ESCX_FAIL(ESCX_ERR_ASSERT, "Time dimension must be multiple of overlap");
     const Quant& q = h->quants[sid];
@@ -1049,6 +1212,7 @@ extern "C" int escx_pvq_encode(escx_handle h, int sid, const float* enc, const f
 extern "C" int escx_pvq_decode(escx_handle h, int sid, const int64_t* codes, int64_t bstride, const float* dec, int B, int W, float* out,
                                void* stream) {
     int rc = check_ready(h); if (rc) return rc;
+    if (h->kind != 0) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "escx_pvq_decode: the cross-scale quantisers do not exist on an rvq handle (escx_rvq_encode / escx_rvq_decode)");
     if (sid < 0 || sid >= h->cfg.max_streams) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "stream_id out of range");
     if (W % h->cfg.overlap) ESCX_FAIL(ESCX_ERR_ASSERT, "Time dimension must be multiple of overlap");
     const Quant& q = h->quants[sid];
@@ -1060,6 +1224,42 @@ extern "C" int escx_pvq_decode(escx_handle h, int sid, const int64_t* codes, int
     if ((rc = run_pvq_decode(h, q, (const long long*)codes, bstride, dec ? h->stageB : nullptr, B, W, h->stageA, st))) return rc;
     unpad_rows(h->stageA, out, rows, q.C, q.Cp, st);
     return launch_ok("pvq_decode");
+}
+
+// ProductResidualVectorQuantize.encode / eval forward on bottleneck tokens in the reference layout (include/escx.h)
+extern "C" int escx_rvq_encode(escx_handle h, const float* tokens, int B, int W, int S, int64_t* codes, float* zq_out, void* stream) {
+    int rc = check_ready(h); if (rc) return rc;
+    if (h->kind != 1) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "escx_rvq_encode needs an rvq handle (escx_create_rvq)");
+    if (!tokens || !codes) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null pointer");
+    if (B < 1 || W < 1) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "batch and W must be positive");
+    if (S < 1 || S > h->num_rvqs) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "num_streams=%d outside [1, %d] (num_rvqs)", S, h->num_rvqs);
+    if (W % h->cfg.overlap) ESCX_FAIL(ESCX_ERR_ASSERT, "Time dimension must be multiple of overlap");
+    const Quant& q = h->quants[0];
+    Shapes s; if ((rc = stage_ws_for_w(h, B, W, &s))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const long long rows = (long long)B * q.Hq * W;
+    pad_rows(tokens, h->stageA, rows, q.C, q.Cp, st);
+    if ((rc = run_prvq(h, h->stageA, nullptr, B, W, (long long*)codes, (long long)S * h->cfg.group_size * (W / h->cfg.overlap), nullptr, S, nullptr, 0,
+                       zq_out ? h->stageB : nullptr, st))) return rc;
+    if (zq_out) unpad_rows(h->stageB, zq_out, rows, q.C, q.Cp, st);
+    return launch_ok("rvq_encode");
+}
+
+// ProductResidualVectorQuantize.decode (include/escx.h)
+extern "C" int escx_rvq_decode(escx_handle h, const int64_t* codes, int B, int S, int W, float* tokens_out, void* stream) {
+    int rc = check_ready(h); if (rc) return rc;
+    if (h->kind != 1) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "escx_rvq_decode needs an rvq handle (escx_create_rvq)");
+    if (!codes || !tokens_out) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null pointer");
+    if (B < 1 || W < 1) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "batch and W must be positive");
+    if (S < 1 || S > h->num_rvqs) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "codes.size(1)=%d outside [1, %d] (num_rvqs)", S, h->num_rvqs);
+    if (W % h->cfg.overlap) ESCX_FAIL(ESCX_ERR_ASSERT, "Time dimension must be multiple of overlap");
+    const Quant& q = h->quants[0];
+    Shapes s; if ((rc = stage_ws_for_w(h, B, W, &s))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if ((rc = run_prvq(h, nullptr, (const long long*)codes, B, W, nullptr, (long long)S * h->cfg.group_size * (W / h->cfg.overlap), nullptr, S, nullptr, 0,
+                       h->stageA, st))) return rc;
+    unpad_rows(h->stageA, tokens_out, (long long)B * q.Hq * W, q.C, q.Cp, st);
+    return launch_ok("rvq_decode");
 }
 
 extern "C" int escx_patch_deembed(escx_handle h, const float* tokens, int B, int W, float* spec, void* stream) {

@@ -75,6 +75,9 @@ struct Quant {                       // one ProductVectorQuantize (quantization.
     // rebuilt after a parameter refresh like the folded de-embedding)
     float *wdf = nullptr, *gq = nullptr, *tab = nullptr;
     bool tab_ok = false;
+    // rvq+swinT (escx_create_rvq): the ONE bottleneck quantiser, keys quantizers.vqs.{g}.*; cbn / c2 / cbraw hold `stages` codebook sets [stage][G][Ksz](dt)
+    bool rvq = false;
+    int stages = 1;
 };
 
 struct Shapes {                      // geometry for one (batch, n_samples)
@@ -119,6 +122,8 @@ int pass_clips(escx_handle_s* h, int B, int T);  // clips one pass of one part h
 
 struct escx_handle_s : escx::WsFields {      // the inherited fields are the CURRENT set (swapped by use_set)
     escx_config cfg;
+    int kind = 0;                    // escx_quantizer_kind: 0 = cross-scale PVQ (ESC), 1 = bottleneck product-residual VQ (RVQCodecs; quants = {one Quant})
+    int num_rvqs = 0;                // kind 1: residual stages per group
     int device = 0;
     int n = 0;                       // n_scales
     int F = 0, Fp = 0, n_fft = 0, left = 0, winP = 0, Kpe = 0, C0 = 0, C0p = 0, Q = 0;

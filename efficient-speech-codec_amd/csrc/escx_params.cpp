@@ -90,7 +90,26 @@ static int build_geometry(escx_handle_s* h) {
     if ((rc = make_layer("decoder.post_nn.", c.h_dims[0], c.swin_heads[0], 0, c.h_dims[0]))) return rc;
 
     const int H0 = c.in_freq / c.patch_f;
-    for (int s = 0; s < c.max_streams; ++s) {                     // base.py:49-69
+    if (h->kind == 1) {                                           // base.py:73-84: one product-residual quantiser at the bottleneck
+        Quant q; q.prefix = "quantizers."; q.rvq = true; q.stages = h->num_rvqs;
+        q.C = c.h_dims[n - 1]; q.Cp = rup(q.C, 16);
+        q.Hq = H0 >> (n - 1);
+        if (q.Hq < 1) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "the bottleneck quantiser has in_freq 0");
+        q.d = c.codebook_dims[0]; q.dt = roundup4(q.d);
+        q.Nz = rup(c.group_size * q.dt, 16); q.Kup = q.Nz;
+        q.Kq = c.overlap * q.Hq * q.Cp;
+        const int D = c.overlap * q.Hq * q.C;
+        for (int g = 0; g < c.group_size; ++g) {
+            const int dg = g + 1 < c.group_size ? D / c.group_size : D - (D / c.group_size) * (c.group_size - 1);     // quantization.py:380-386
+            if (dg == q.d) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "rvq group %d has width %d == codebook_dim: the reference skips the projections there", g, dg);
+            if (dg < 1) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "rvq group %d is empty", g);
+        }
+        if (!prvq_geometry_ok(q.Nz, q.dt, c.group_size, q.Kq, q.Cp, pvq_down_splits(0, q.Kq, q.Cp), pvq_down_bk(q.Cp)))
+            ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "rvq quantiser: codebook_dim %d with %d groups (bottleneck vector %d) is not covered by the fused kernel "
+                                            "(fused_prvq.h: codebook_dim 5..8 with 3 or 4 groups, codebook_dim <= 4 with up to 4 groups)", q.d, c.group_size, D);
+        h->quants.push_back(q);
+    }
+    for (int s = 0; s < c.max_streams && h->kind == 0; ++s) {     // base.py:49-69
         Quant q; q.prefix = "quantizers." + std::to_string(s) + ".";
         q.C = c.h_dims[n - 1 - std::max(s - 1, 0)]; q.Cp = rup(q.C, 16);
         q.Hq = (s == 0) ? H0 >> (c.max_streams - 1) : H0 >> (c.max_streams - s);
@@ -104,7 +123,14 @@ static int build_geometry(escx_handle_s* h) {
 
     // required state_dict keys
     auto& K = h->required;
-    for (int s = 0; s < c.max_streams; ++s)
+    if (h->kind == 1)                                             // quantization.py:152-164, 306-309
+        for (int g = 0; g < c.group_size; ++g) {
+            const std::string p = "quantizers.vqs." + std::to_string(g) + ".";
+            K.push_back(p + "proj_down.weight");
+            K.push_back(p + "proj_up.weight");
+            for (int i = 0; i < h->num_rvqs; ++i) K.push_back(p + "vqs." + std::to_string(i) + ".embedding.weight");
+        }
+    for (int s = 0; s < c.max_streams && h->kind == 0; ++s)
         for (int g = 0; g < c.group_size; ++g) {
             const std::string p = "quantizers." + std::to_string(s) + ".";
             K.push_back(p + "vqs." + std::to_string(g) + ".embedding.weight");
@@ -163,13 +189,13 @@ static int env_defaults(escx_handle_s* h) {
     return 0;
 }
 
-extern "C" int escx_create(const escx_config* cfg, int device, escx_handle* out) {
-    if (!cfg || !out) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null argument");
+static int create_impl(const escx_config* cfg, int kind, int num_rvqs, int device, escx_handle* out) {
     int ndev = 0;
     ESCX_HIP(hipGetDeviceCount(&ndev));
     if (device < 0 || device >= ndev) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "device %d out of range (%d visible)", device, ndev);
     escx_handle_s* h = new escx_handle_s();
     h->cfg = *cfg; h->device = device;
+    h->kind = kind; h->num_rvqs = num_rvqs;
     int erc = env_defaults(h);
     if (erc) { delete h; return erc; }
     int rc = build_geometry(h);
@@ -177,6 +203,24 @@ extern "C" int escx_create(const escx_config* cfg, int device, escx_handle* out)
     *out = h;
     return ESCX_OK;
 }
+
+extern "C" int escx_create(const escx_config* cfg, int device, escx_handle* out) {
+    if (!cfg || !out) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null argument");
+    return create_impl(cfg, 0, 0, device, out);
+}
+
+// RVQCodecs (codecs.py:96-127): the ESC backbone with one product-residual quantiser at the bottleneck; the configuration's codebook_dims are
+// replaced by the one codebook_dim of every stage (slot 0 is what build_geometry reads)
+extern "C" int escx_create_rvq(const escx_rvq_config* cfg, int device, escx_handle* out) {
+    if (!cfg || !out) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null argument");
+    if (cfg->num_rvqs < 1 || cfg->num_rvqs > 16) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "num_rvqs=%d outside [1, 16]", cfg->num_rvqs);
+    if (cfg->codebook_dim < 1 || cfg->codebook_dim > 64) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "codebook_dim=%d outside [1, 64]", cfg->codebook_dim);
+    escx_config c = cfg->base;
+    for (int i = 0; i < ESCX_MAX_SCALES; ++i) c.codebook_dims[i] = cfg->codebook_dim;
+    return create_impl(&c, 1, cfg->num_rvqs, device, out);
+}
+
+extern "C" int escx_quantizer_kind(escx_handle h) { return h ? h->kind : ESCX_ERR_INVALID_ARG; }
 
 extern "C" void escx_destroy(escx_handle h) {
     if (!h) return;
@@ -558,19 +602,22 @@ static int pack_image(escx_handle_s* h, std::vector<float>& image, std::vector<s
     // ---- product quantisers ----
     const int G = c.group_size, Ksz = c.codebook_size;
     for (Quant& q : h->quants) {
-        const int fix = q.Hq * q.C, D = c.overlap * fix;
+        const int fix = q.Hq * q.C, D = c.overlap * fix, NS = q.stages;
         std::vector<int> dims(G, D / G); dims[G - 1] = D - (D / G) * (G - 1);     // quantization.py:380-386
         size_t owd = gslot(&q.wd, (size_t)q.Nz * q.Kq), owu = gslot(&q.wup, (size_t)q.Kq * q.Kup);
         size_t owdT = slot(&q.wdT, (size_t)q.Kq * q.Nz), owuT = slot(&q.wupT, (size_t)q.Kup * q.Kq);
-        size_t ocn = cslot(&q.cbn, (size_t)G * Ksz * q.dt), oc2 = cslot(&q.c2, (size_t)G * Ksz), ocr = gslot(&q.cbraw, (size_t)G * Ksz * q.dt);
+        size_t ocn = cslot(&q.cbn, (size_t)NS * G * Ksz * q.dt), oc2 = cslot(&q.c2, (size_t)NS * G * Ksz), ocr = gslot(&q.cbraw, (size_t)NS * G * Ksz * q.dt);
+        // key names: ESC quantizers.{s}.vqs.{g} / down_projs.{g} / up_projs.{g}; rvq quantizers.vqs.{g}.vqs.{i} / .proj_down / .proj_up (quantization.py:152-164, 306-309)
+        auto emb_key = [&](int g, int i) { return q.rvq ? q.prefix + "vqs." + std::to_string(g) + ".vqs." + std::to_string(i) + ".embedding.weight"
+                                                        : q.prefix + "vqs." + std::to_string(g) + ".embedding.weight"; };
         size_t owf = slot(&q.wdf, (size_t)q.Nz * q.Kq), ogq = cslot(&q.gq, (size_t)q.Kq / 4);
         std::vector<int> grp_of((size_t)q.Kq, -1);                             // group of every element of the framed vector in memory order
         int start = 0;
         for (int g = 0; g < G; ++g) {
             const std::string gs = std::to_string(g);
-            GETP(emb, q.prefix + "vqs." + gs + ".embedding.weight", Ksz, q.d);
-            GETP(dw, q.prefix + "down_projs." + gs + ".weight", q.d, dims[g]);
-            GETP(uw, q.prefix + "up_projs." + gs + ".weight", dims[g], q.d);
+            GETP(emb0, emb_key(g, 0), Ksz, q.d);
+            GETP(dw, q.rvq ? q.prefix + "vqs." + gs + ".proj_down.weight" : q.prefix + "down_projs." + gs + ".weight", q.d, dims[g]);
+            GETP(uw, q.rvq ? q.prefix + "vqs." + gs + ".proj_up.weight" : q.prefix + "up_projs." + gs + ".weight", dims[g], q.d);
             for (int e = 0; e < dims[g]; ++e) {
                 const int flat = start + e;                                     // (o, c, h) order: quantization.py:400-409
                 const int o = flat / fix, r = flat - o * fix, cc = r / q.Hq, hh = r - cc * q.Hq;
@@ -583,19 +630,24 @@ static int pack_image(escx_handle_s* h, std::vector<float>& image, std::vector<s
                     pk.host[owuT + (size_t)(g * q.dt + j) * q.Kq + col] = uw->data[(size_t)e * q.d + j];    // [Kup][Kq]: d z_up = d out . W_up
                 }
             }
-            for (int k = 0; k < Ksz; ++k) {
-                const float* row = emb->data.data() + (size_t)k * q.d;
-                float ss = 0.f;
-                for (int j = 0; j < q.d; ++j) ss += row[j] * row[j];
-                const float den = c.l2norm ? std::max(std::sqrt(ss), 1e-12f) : 1.0f;   // F.normalize (codebook.py:32)
-                float s2 = 0.f;
-                for (int j = 0; j < q.d; ++j) {
-                    const float v = row[j] / den;
-                    pk.host[ocn + ((size_t)g * Ksz + k) * q.dt + j] = v;
-                    pk.host[ocr + ((size_t)g * Ksz + k) * q.dt + j] = row[j];
-                    s2 += v * v;
+            for (int si = 0; si < NS; ++si) {                             // stage si's codebook set (ESC: the one set)
+                const Param* emb = emb0;
+                if (si > 0) { emb = pk.get(emb_key(g, si), {Ksz, q.d}); if (!emb) ESCX_FAIL(ESCX_ERR_STATE, "%s", pk.missing.c_str()); }
+                const size_t cs = (size_t)si * G + g;
+                for (int k = 0; k < Ksz; ++k) {
+                    const float* row = emb->data.data() + (size_t)k * q.d;
+                    float ss = 0.f;
+                    for (int j = 0; j < q.d; ++j) ss += row[j] * row[j];
+                    const float den = c.l2norm ? std::max(std::sqrt(ss), 1e-12f) : 1.0f;   // F.normalize (codebook.py:32)
+                    float s2 = 0.f;
+                    for (int j = 0; j < q.d; ++j) {
+                        const float v = row[j] / den;
+                        pk.host[ocn + (cs * Ksz + k) * q.dt + j] = v;
+                        pk.host[ocr + (cs * Ksz + k) * q.dt + j] = row[j];
+                        s2 += v * v;
+                    }
+                    pk.host[oc2 + cs * Ksz + k] = s2;
                 }
-                pk.host[oc2 + (size_t)g * Ksz + k] = s2;
             }
             start += dims[g];
         }
@@ -617,6 +669,7 @@ static int pack_image(escx_handle_s* h, std::vector<float>& image, std::vector<s
             }
             pk.host[ogq + f4] = (float)g4;
         }
+        if (q.rvq) q.tab_ok = false;        // the up-projection acts on a SUM of rows: no per-code table
     }
     h->train_x3_stale = true;
     h->pvq_tab_stale = true;
@@ -724,7 +777,7 @@ int escx::make_shapes(escx_handle_s* h, int B, int T, Shapes* out) {
     s.encH.push_back(H);
     for (int i = 0; i + 1 < h->n; ++i) { H = (H + 1) / 2; s.encH.push_back(H); }
     // the decoder doubles H per block; residuals need matching shapes (csrvq.py:15-17) and the quantisers a fixed in_freq
-    for (int st = 0; st < c.max_streams; ++st) {
+    for (int st = 0; st < (int)h->quants.size(); ++st) {         // ESC: max_streams quantisers; rvq: the bottleneck one
         const int scale = h->n - 1 - std::max(st - 1, 0);
         if (h->quants[st].Hq != s.encH[scale])
             ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "in_freq/patch (%d) must be divisible by 2^(max_streams-1)", s.H0);
@@ -880,7 +933,7 @@ static int reserve_frames(escx_handle_s* h, int Btotal, int T, int set_clips_min
     auto add = [&](size_t nfl) { total += (nfl * sizeof(float) + 255) / 256 * 256; };
     add(spec); for (int i = 0; i < n; ++i) add(ehs[i]);
     add(work); add(xn); add(qkv); add(ob); add(hid); add(dec); add(dec); add(zp); add(deemb); add(rspec); add(frames);
-    const size_t lterms = (size_t)c.max_streams * c.group_size * B * s.Tq;
+    const size_t lterms = (size_t)std::max(c.max_streams, h->num_rvqs) * c.group_size * B * s.Tq;
     add(stage); add(stage); add(codes); add(B); add(lterms); add(WsFields::N_TICKETS);
 
     ESCX_HIP(hipDeviceSynchronize());

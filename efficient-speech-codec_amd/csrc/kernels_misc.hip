@@ -4,6 +4,7 @@
 
 #include "kernels.h"
 #include "fused_pvq.h"
+#include "fused_prvq.h"
 #include <atomic>
 #include "launchers.h"
 
@@ -235,6 +236,52 @@ void codes_narrow(const long long* in, short* out, long long n, hipStream_t s) {
 }
 void codes_widen(const short* in, long long* out, long long n, hipStream_t s) {
     ESCX_LAUNCH(codes_widen_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, in, out, n);
+}
+
+// ---- the bottleneck product-residual quantiser of rvq+swinT (fused_prvq.h) ----
+
+// slice boundaries of the split-K down-projection (pvq_fused: the engine's split-K slicing, gemm_engine.h launch_tile)
+static bool prvq_slices(int Kq, int splits, int bk, int* k_per_z) {
+    if (bk < 16 || bk % 16 || Kq % bk || splits < 1 || splits > PVQF_WAVES) return false;
+    const int kIters = Kq / bk, per = (kIters + splits - 1) / splits;
+    if ((kIters + per - 1) / per != splits) return false;
+    *k_per_z = per * bk;
+    return true;
+}
+
+bool prvq_geometry_ok(int Np, int dt, int G, int Kq, int Cp, int splits, int bk) {
+    int kz = 0;
+    if (Np % 16 || Kq % 16 || Cp % 16 || dt % 4 || G < 1 || G > PVQF_GMAX || G * dt > Np || !prvq_slices(Kq, splits, bk, &kz)) return false;
+    const int NT = Np / 16, STEPS = dt / 4;
+    return (NT == 2 && STEPS == 2) || (NT == 1 && STEPS == 1);
+}
+
+template <int NT, int STEPS, bool DECODE>
+static void launch_prvq(const PrvqArgs& a, hipStream_t s) {
+    constexpr int lds = DECODE ? 0 : pvqf_lds_floats<NT>() * (int)sizeof(float);
+    static_assert(lds <= 48 * 1024, "the covered geometries stay within the default dynamic LDS limit");
+    auto kern = prvq_fused_kernel<NT, STEPS, DECODE>;
+    ESCX_LAUNCH(kern, dim3((a.M + 15) / 16), dim3(64 * PVQF_WAVES), lds, s, a);
+}
+
+int prvq_fused(const float* enc, const long long* codes_in, int B, int Hq, int Wd, int Cp, int ov, const float* wdf, int Np, int Kq, int splits, int bk,
+               const float* cbn, const float* c2, const float* cbraw, int G, int Ksz, int d, int dt, const float* wup,
+               long long* codes, long long bstride, const int* clip_S, int S, int Smax, float* loss, long long lslot, float loss_scale, int l2norm,
+               float* out, hipStream_t s) {
+    if (!prvq_geometry_ok(Np, dt, G, Kq, Cp, splits, bk) || Ksz < 1 || Smax < 1 || (!codes_in && !codes)) return -1;
+    const int Tq = Wd / ov, M = B * Tq;
+    if (M < 1) return 0;
+    PrvqArgs a{enc, wdf, cbn, c2, cbraw, wup, out, codes, codes_in, bstride, clip_S, S, Smax, loss, lslot, loss_scale,
+               M, Tq, Hq, Wd, Cp, ov, Kq, 0, splits, G, Ksz, d, l2norm};
+    prvq_slices(Kq, splits, bk, &a.k_per_z);
+    const int NT = Np / 16;
+    if (codes_in) {
+        if (!out) return -1;
+        if (NT == 2) launch_prvq<2, 2, true>(a, s); else launch_prvq<1, 1, true>(a, s);
+    } else {
+        if (NT == 2) launch_prvq<2, 2, false>(a, s); else launch_prvq<1, 1, false>(a, s);
+    }
+    return 0;
 }
 
 }  // namespace escx

@@ -114,6 +114,15 @@ int window_attention_any(const float* qkv, const float* bias, float* out, int to
 int pvq_fused(const float* enc, const float* dec, int B, int Hq, int Wd, int Cp, int ov, const float* wdf, int Np, int Kq, int splits, int bk,
               const float* cbn, const float* c2, const float* cbraw, int G, int Ksz, int d, int dt, const float* wup, const float* tab, const float* gq,
               float* out, long long* codes, long long bstride, float* loss, float loss_scale, int l2norm, hipStream_t s);
+// The bottleneck product-residual quantiser of rvq+swinT in ONE launch (fused_prvq.h).  codes_in == nullptr: encode form (down-projection, S_b residual
+// stages, codes with -1 in slots [S_b, Smax), optional per-stage commitment terms loss[s * lslot + g * M + m], optional up-projected sum to `out`);
+// codes_in != nullptr: decode form (gather-sum of the raw rows, up-projection to `out`).  clip_S: per-clip counts on the device (indexed by clip), or
+// nullptr = S for every clip.  -1: geometry not covered (prvq_geometry_ok), nothing launched.
+bool prvq_geometry_ok(int Np, int dt, int G, int Kq, int Cp, int splits, int bk);
+int prvq_fused(const float* enc, const long long* codes_in, int B, int Hq, int Wd, int Cp, int ov, const float* wdf, int Np, int Kq, int splits, int bk,
+               const float* cbn, const float* c2, const float* cbraw, int G, int Ksz, int d, int dt, const float* wup,
+               long long* codes, long long bstride, const int* clip_S, int S, int Smax, float* loss, long long lslot, float loss_scale, int l2norm,
+               float* out, hipStream_t s);
 // out = dec + tab[(h, ov * code_g + o)][c] (g = group of element (o, h, c)): the de-quantise + up-projection + un-frame + add of one stream as a table-row add
 void pvq_tab_add(const long long* codes, long long bstride, const float* tab, const float* gq, int G, int Ksz, int B, int Hq, int Wd, int Cp, int ov,
                  const float* dec, float* out, hipStream_t s);

@@ -578,7 +578,7 @@ int refresh_from_flat(escx_handle_s* h, const float* flat, hipStream_t st) {
     hipLaunchKernelGGL(gather_params_kernel, dim3(blocks_for(n)), dim3(256), 0, st, flat, h->gmap, reinterpret_cast<float*>(h->wts.base), n);
     const escx_config& c = h->cfg;
     for (const Quant& q : h->quants) {
-        const int rows = c.group_size * c.codebook_size;
+        const int rows = q.stages * c.group_size * c.codebook_size;      // every codebook set (rvq: one per stage)
         hipLaunchKernelGGL(codebook_normalize_kernel, dim3(blocks_for(rows)), dim3(256), 0, st, q.cbraw, q.cbn, q.c2, rows, q.d, q.dt, c.l2norm);
     }
     // the folded 7x7 de-embedding (inference path, and the training forward below) from the refreshed convolution weights: fp64 on the device, the
@@ -828,6 +828,7 @@ static int train_forward_entry(escx_handle h, const float* flat_dev, const float
 
 extern "C" int escx_train_forward(escx_handle h, const float* flat_dev, const float* wave, int B, int L, int S, int freeze, int64_t* codes_out,
                                   float* wave_out, float* raw_feat, float* recon_feat, float* cm_loss, float* cb_loss, void* stream) {
+    if (h && h->kind != 0) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "RVQCodecs training is not implemented (escx_create_rvq handles run encode / decode / eval forward only)");
     if (!wave) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null pointer");
     return train_forward_entry(h, flat_dev, wave, nullptr, B, L, S, freeze, codes_out, wave_out, raw_feat, recon_feat, cm_loss, cb_loss, stream);
 }
@@ -836,6 +837,7 @@ extern "C" int escx_train_forward(escx_handle h, const float* flat_dev, const fl
 extern "C" int escx_train_forward_feat(escx_handle h, const float* flat_dev, const float* feat, int B, int n_frames, int S, int freeze, int64_t* codes_out,
                                        float* wave_out, float* recon_feat, float* cm_loss, float* cb_loss, void* stream) {
     if (!h) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null handle");
+    if (h->kind != 0) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "RVQCodecs training is not implemented (escx_create_rvq handles run encode / decode / eval forward only)");
     if (!feat) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null pointer");
     if (n_frames < h->cfg.patch_t) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "n_frames=%d shorter than one patch", n_frames);
     return train_forward_entry(h, flat_dev, nullptr, feat, B, h->cfg.hop_length * (n_frames - 1), S, freeze, codes_out, wave_out, nullptr, recon_feat, cm_loss, cb_loss, stream);
@@ -1163,6 +1165,7 @@ int train_backward_impl(escx_handle_s* h, const float* d_wave, const float* d_re
 extern "C" int escx_train_backward(escx_handle h, const float* d_wave, const float* d_recon_feat, const float* d_cm, const float* d_cb,
                                    float* grad_flat, void* stream) {
     int rc = check_ready(h); if (rc) return rc;
+    if (h->kind != 0) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "RVQCodecs training is not implemented (escx_create_rvq handles run encode / decode / eval forward only)");
     if (!grad_flat) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null gradient buffer");
     TrainRoot& R = *root_of(h);
     if (!R.valid) ESCX_FAIL(ESCX_ERR_STATE, "escx_train_backward without a preceding escx_train_forward");

@@ -11,6 +11,6 @@ from . import _native as _native_mod  # noqa: E402
 
 _native_mod.ensure_hw_queues()             # also called by _native.load(), i.e. by esc.distributed / scripts.* users that never import this module first
 
-from .models import ESC, make_model  # noqa: F401,E402
+from .models import ESC, RVQCodecs, make_model  # noqa: F401,E402
 
-__all__ = ["ESC", "make_model"]
+__all__ = ["ESC", "RVQCodecs", "make_model"]

@@ -22,6 +22,11 @@ class EscxConfig(Structure):
     ]
 
 
+class EscxRvqConfig(Structure):
+    """include/escx.h escx_rvq_config: the rvq+swinT codec (RVQCodecs)."""
+    _fields_ = [("base", EscxConfig), ("num_rvqs", c_int32), ("codebook_dim", c_int32)]
+
+
 class EscxDiscConfig(Structure):
     _fields_ = [("sample_rate", c_int32), ("n_rates", c_int32), ("n_periods", c_int32), ("periods", c_int32 * 8), ("n_ffts", c_int32),
                 ("fft_sizes", c_int32 * 8), ("n_bands", c_int32), ("bands", (c_float * 2) * 8)]
@@ -32,6 +37,8 @@ SIGNATURES = {
     "escx_last_error": (c_char_p, []),
     "escx_version": (c_char_p, []),
     "escx_create": (c_int, [POINTER(EscxConfig), c_int, POINTER(c_void_p)]),
+    "escx_create_rvq": (c_int, [POINTER(EscxRvqConfig), c_int, POINTER(c_void_p)]),
+    "escx_quantizer_kind": (c_int, [c_void_p]),
     "escx_destroy": (None, [c_void_p]),
     "escx_set_param": (c_int, [c_void_p, c_char_p, c_void_p, POINTER(c_int64), c_int]),
     "escx_finalize_params": (c_int, [c_void_p]),
@@ -56,6 +63,8 @@ SIGNATURES = {
     "escx_transformer_layer": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, POINTER(c_int), c_void_p]),
     "escx_pvq_encode": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p]),
     "escx_pvq_decode": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "escx_rvq_encode": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "escx_rvq_decode": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "escx_patch_deembed": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "escx_profile_enable": (c_int, [c_void_p, c_int]),
     "escx_profile_report": (c_char_p, [c_void_p]),

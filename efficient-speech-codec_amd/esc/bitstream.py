@@ -131,7 +131,7 @@ def unpack_codes(blob: bytes, device="cuda", model=None):
     B, S, G, T, H, W, need = parse_header(blob)
     if model is not None:
         c = model.cfg
-        if G != c["group_size"] or S > c["max_streams"] or T * c["overlap"] != W or c["codebook_size"] > (1 << BITS):
+        if G != c["group_size"] or S > model._code_streams or T * c["overlap"] != W or c["codebook_size"] > (1 << BITS):     # RVQCodecs: num_rvqs
             raise ValueError(f"ESC1 header {(B, S, G, T, H, W)} does not match the model (group_size {c['group_size']}, "
                              f"max_streams {c['max_streams']}, overlap {c['overlap']})")
     n = B * S * G * T
@@ -152,7 +152,7 @@ def _unpack_codes_streams(blob: bytes, device, model):
     B, S, G, T, H, W, counts, head, need = parse_header2(blob)
     if model is not None:
         c = model.cfg
-        if G != c["group_size"] or S > c["max_streams"] or T * c["overlap"] != W or c["codebook_size"] > (1 << BITS):
+        if G != c["group_size"] or S > model._code_streams or T * c["overlap"] != W or c["codebook_size"] > (1 << BITS):     # RVQCodecs: num_rvqs
             raise ValueError(f"ESC2 header {(B, S, G, T, H, W)} does not match the model (group_size {c['group_size']}, "
                              f"max_streams {c['max_streams']}, overlap {c['overlap']})")
     n = sum(counts) * G * T

@@ -1,2 +1,2 @@
-from .codecs import ESC, make_model, model_dict  # noqa: F401
+from .codecs import ESC, RVQCodecs, make_model, model_dict  # noqa: F401
 from .discriminator import Discriminator  # noqa: F401

@@ -19,7 +19,7 @@ import torch.nn as nn
 
 from .. import _native
 
-__all__ = ["ESC", "make_model", "model_dict", "state_manifest"]
+__all__ = ["ESC", "RVQCodecs", "make_model", "model_dict", "state_manifest", "rvq_state_manifest"]
 
 
 def _rel_pos_index(ws: int) -> torch.Tensor:
@@ -85,6 +85,32 @@ def state_manifest(cfg: dict) -> Dict[str, Tuple[int, ...]]:
     man["decoder.patch_deembed.de_proj2.weight"] = (cfg["in_dim"], h[0], 3, 3)
     man["decoder.patch_deembed.de_proj2.bias"] = (cfg["in_dim"],)
     block("decoder.post_nn.", dec[-1], rh[-1])
+    return man
+
+
+def _split_dimension(total: int, num: int) -> List[int]:
+    """quantization.py:380-386: equal slices, the remainder goes to the last one."""
+    dims = [total // num] * num
+    dims[-1] = total - (total // num) * (num - 1)
+    return dims
+
+
+def rvq_state_manifest(cfg: dict) -> Dict[str, Tuple[int, ...]]:
+    """key -> shape of the reference RVQCodecs state_dict (codecs.py:96-127): ESC's backbone keys and, at the bottleneck, one
+    ResidualVectorQuantize per product group (base.py:73-84, quantization.py:139-164, 292-315)."""
+    S, G, d = cfg["max_streams"], cfg["group_size"], cfg["codebook_dim"]
+    base = state_manifest(dict(cfg, codebook_dims=[d] * S))
+    man: Dict[str, Tuple[int, ...]] = {"ft.window": base["ft.window"], "ift.window": base["ift.window"]}
+    Hq = cfg["in_freq"] // cfg["patch_size"][0] // 2 ** (S - 1)
+    for m, dm in enumerate(_split_dimension(cfg["overlap"] * Hq * cfg["h_dims"][-1], G)):
+        p = f"quantizers.vqs.{m}."
+        man[p + "proj_down.weight"] = (d, dm)
+        man[p + "proj_up.weight"] = (dm, d)
+        for i in range(cfg["num_rvqs"]):
+            man[p + f"vqs.{i}.embedding.weight"] = (cfg["codebook_size"], d)
+    for k, v in base.items():
+        if not k.startswith("quantizers.") and k not in man:
+            man[k] = v
     return man
 
 
@@ -155,7 +181,7 @@ class ESC(nn.Module):
         if len(codebook_dims) < max_streams or len(swin_heads) < len(h_dims) - 1:
             raise ValueError("codebook_dims / swin_heads shorter than the number of streams / scales")
 
-        for key, shape in state_manifest(self.cfg).items():
+        for key, shape in self._state_manifest().items():
             is_buf = key.endswith("relative_position_index") or key.endswith(".window")
             _attach(self, key, _init_tensor(key, shape), is_buf)
 
@@ -166,6 +192,18 @@ class ESC(nn.Module):
         self._flat_grad_mode = False
         self._carry: Dict[int, tuple] = {}               # flat gradient buffers that survive a handle rebuild (see _handle)
         self._precision = None                           # None = the library's default (ESCX_PRECISION, else "f16x2"); see set_precision
+
+    def _state_manifest(self) -> Dict[str, Tuple[int, ...]]:
+        return state_manifest(self.cfg)
+
+    @property
+    def _code_streams(self) -> int:
+        """Largest stream count a call accepts (ESC: max_streams; RVQCodecs: num_rvqs)."""
+        return self.max_streams
+
+    def _create_handle(self, lib, idx: int, hd: ctypes.c_void_p):
+        cc = self._c_config()
+        _native.check(lib.escx_create(ctypes.byref(cc), idx, ctypes.byref(hd)))
 
     # ---- weight management ------------------------------------------------------------------
     def _apply(self, fn, *a, **k):
@@ -316,8 +354,7 @@ class ESC(nn.Module):
             self._dirty = False
         if idx not in self._handles:
             hd = ctypes.c_void_p()
-            cc = self._c_config()
-            _native.check(lib.escx_create(ctypes.byref(cc), idx, ctypes.byref(hd)))
+            self._create_handle(lib, idx, hd)
             try:
                 for key, t in self.state_dict().items():
                     if not t.is_floating_point():
@@ -395,7 +432,7 @@ class ESC(nn.Module):
         return isinstance(num_streams, (list, tuple, range))
 
     def _per_clip_streams(self, num_streams, B: int) -> Optional[List[int]]:
-        """None when `num_streams` is one count for the whole batch; else the per-clip counts (length B, each in [1, max_streams])."""
+        """None when `num_streams` is one count for the whole batch; else the per-clip counts (length B, each in [1, max_streams]; RVQCodecs: num_rvqs)."""
         if not self._is_per_clip(num_streams):
             return None
         if isinstance(num_streams, torch.Tensor):
@@ -417,8 +454,8 @@ class ESC(nn.Module):
         if len(out) != B:
             raise ValueError(f"per-clip num_streams has {len(out)} entries for a batch of {B} clips")
         for b, v in enumerate(out):
-            if not 1 <= v <= self.max_streams:
-                raise ValueError(f"num_streams[{b}]={v} outside [1, {self.max_streams}]")
+            if not 1 <= v <= self._code_streams:
+                raise ValueError(f"num_streams[{b}]={v} outside [1, {self._code_streams}]")
         return out
 
     # ---- public API (codecs.py:48-94) ---------------------------------------------------------
@@ -673,16 +710,95 @@ class _TrainStep(torch.autograd.Function):
         return (None, None, None, None, None) + grads
 
 
-model_dict = {"csvq+swinT": ESC}
+class RVQCodecs(ESC):
+    """The rvq+swinT ablation codec (codecs.py:96-181): ESC's Swin encoder and decoder with plain product-residual VQ at the bottleneck
+    (quantization.py:292-431) in place of the cross-scale quantisers, MI355X-native execution (fused_prvq.h: one HIP launch per batch part for
+    the whole quantiser).  Inference only: encode, decode and the eval-mode forward, with per-clip num_streams as in ESC; training raises."""
+
+    def __init__(self, in_dim: int = 2, in_freq: int = 192, h_dims: list = [45, 72, 96, 144, 192, 384], max_streams: int = 6,
+                 backbone: Literal['transformer', 'convolution'] = 'transformer', kernel_size: list = [5, 2], conv_depth: int = 1,
+                 patch_size: list = [3, 2], swin_heads: list = [3, 6, 12, 24, 24], swin_depth: int = 2, window_size: int = 4,
+                 mlp_ratio: float = 4., overlap: int = 2, num_rvqs: int = 6, group_size: int = 3, codebook_dim: int = 8,
+                 codebook_size: int = 1024, l2norm: bool = True, win_len: int = 20, hop_len: int = 5, sr: int = 16000) -> None:
+        if backbone != "transformer":
+            raise NotImplementedError("only backbone='transformer' (rvq+swinT) is implemented; the convolution "
+                                      "backbone is an ablation outside the accelerated path")
+        if int(num_rvqs) < 1:
+            raise ValueError(f"num_rvqs={num_rvqs}: at least one residual stage")
+        object.__setattr__(self, "_rvq", dict(num_rvqs=int(num_rvqs), codebook_dim=int(codebook_dim)))     # read by _state_manifest during ESC.__init__
+        super().__init__(in_dim=in_dim, in_freq=in_freq, h_dims=h_dims, max_streams=max_streams, win_len=win_len, hop_len=hop_len, sr=sr,
+                         patch_size=patch_size, swin_heads=swin_heads, swin_depth=swin_depth, window_size=window_size, mlp_ratio=mlp_ratio,
+                         overlap=overlap, group_size=group_size, codebook_size=codebook_size, codebook_dims=[codebook_dim] * max_streams,
+                         l2norm=l2norm, backbone=backbone, kernel_size=kernel_size, conv_depth=conv_depth)
+        self.cfg.update(self._rvq)
+        self.num_rvqs, self.codebook_dim = self._rvq["num_rvqs"], self._rvq["codebook_dim"]
+        # max_bps: base.py:81 is ESC's expression (base.py:70) with num_product_vqs = group_size, set by ESC.__init__
+
+    def _state_manifest(self) -> Dict[str, Tuple[int, ...]]:
+        return rvq_state_manifest(dict(self.cfg, **self._rvq))
+
+    @property
+    def _code_streams(self) -> int:
+        return self._rvq["num_rvqs"]
+
+    def _create_handle(self, lib, idx: int, hd: ctypes.c_void_p):
+        rc = _native.EscxRvqConfig()
+        rc.base = self._c_config()
+        rc.num_rvqs, rc.codebook_dim = self._rvq["num_rvqs"], self._rvq["codebook_dim"]
+        _native.check(lib.escx_create_rvq(ctypes.byref(rc), idx, ctypes.byref(hd)))
+
+    def _streams_arg(self, num_streams):
+        """An integer count above num_rvqs gives num_rvqs streams, as the reference's quantize_to_code loop does (quantization.py:230-243);
+        a count below 1 is refused.  Per-clip sequences pass through (ESC's checks, bounded by num_rvqs)."""
+        if self._is_per_clip(num_streams):
+            return num_streams
+        try:
+            S = operator.index(num_streams)
+        except TypeError:
+            raise ValueError(f"num_streams must be an integer (got {num_streams!r})") from None
+        if S < 1:
+            raise ValueError(f"num_streams={S}: at least one residual stage")
+        return min(S, self._rvq["num_rvqs"])
+
+    @torch.no_grad()
+    def encode(self, x: torch.Tensor, num_streams=6):
+        """(Bs, L) waveform -> codes (Bs, min(num_streams, num_rvqs), group_size, W/overlap) int64, feat_shape (H, W) (codecs.py:166-171).
+        Per-clip counts as in ESC.encode (each in [1, num_rvqs])."""
+        return super().encode(x, self._streams_arg(num_streams))
+
+    def forward(self, x, x_feat, num_streams, freeze_codebook=False):
+        """codecs.py:129-164 in eval mode: the ESC dict, codes (Bs, min(num_streams, num_rvqs), group_size, T),
+        cm_loss = cb_loss = sum over groups and stages of mse(z_q_i, residual_i).mean([1, 2]) / group_size."""
+        if self.training:
+            raise NotImplementedError("RVQCodecs training is not implemented in the MI355X build (encode, decode and eval-mode forward only)")
+        if freeze_codebook:
+            raise NotImplementedError("RVQCodecs: freeze_codebook is a training option (quantization.py:326-328); not implemented")
+        with torch.no_grad():
+            return self.forward_one_step(x, x_feat, self._streams_arg(num_streams), False)
+
+
+model_dict = {"csvq+swinT": ESC, "rvq+swinT": RVQCodecs}
+
+
+# kwargs an rvq+swinT configuration must state for make_model: the quantiser that distinguishes the ablation from ESC
+# (configs/ablations/9kbps_rvq_swinT.yaml names both)
+_RVQ_REQUIRED = ("num_rvqs", "codebook_dim")
 
 
 def make_model(model_config, model_name: str = "csvq+swinT"):
     """codecs.py:190-200.  `model_name` defaults to the ESC codec so that scripts/compress.py:22 (which passes only the
-    config) works."""
+    config) works.  "rvq+swinT" is built from a configuration that states its bottleneck quantiser (num_rvqs, codebook_dim, as
+    the ablation yaml does); a configuration without them raises NotImplementedError - RVQCodecs() itself keeps the reference's
+    defaults."""
     if model_name not in model_dict:
-        raise NotImplementedError(f"{model_name} is not available in the MI355X build (only csvq+swinT); "
-                                  "rvq+* and *+conv are ablation models outside the accelerated path")
+        raise NotImplementedError(f"{model_name} is not available in the MI355X build (csvq+swinT and rvq+swinT); "
+                                  "the *+conv models are ablations outside the accelerated path")
     m = model_dict[model_name]
-    if isinstance(model_config, dict):
-        return m(**model_config)
-    return m(**vars(model_config))
+    cfg = dict(model_config) if isinstance(model_config, dict) else dict(vars(model_config))
+    if m is RVQCodecs:
+        missing = [k for k in _RVQ_REQUIRED if k not in cfg]
+        if missing:
+            raise NotImplementedError(f"make_model(..., {model_name!r}) builds the rvq ablation from its configuration, which must state "
+                                      f"{', '.join(missing)} (configs/ablations/9kbps_rvq_swinT.yaml); construct RVQCodecs() for the "
+                                      "reference's defaults")
+    return m(**cfg)

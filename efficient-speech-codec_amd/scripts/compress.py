@@ -13,7 +13,6 @@ import numpy as np, torch, yaml
 from scipy.io import wavfile
 from esc.models import make_model
 from esc import bitstream, synth
-from esc.models.codecs import state_manifest
 
 
 def main():
@@ -26,13 +25,15 @@ def main():
     x = pcm.astype(np.float32) / 32768.0 if pcm.dtype == np.int16 else pcm.astype(np.float32)
     x = torch.from_numpy(np.atleast_2d(x.T if x.ndim == 2 else x)).to(a.device)          # channels are the batch (compress.py:19-20)
     if a.model_path:
-        cfg = yaml.safe_load(open(f"{a.model_path}/config.yaml"))["model"]
-        model = make_model(cfg)
+        yml = yaml.safe_load(open(f"{a.model_path}/config.yaml"))
+        cfg = yml["model"]
+        model = make_model(cfg, yml.get("model_name", "csvq+swinT"))           # csvq+swinT (ESC) or rvq+swinT (RVQCodecs)
         model.load_state_dict(torch.load(f"{a.model_path}/model.pth", map_location="cpu")["model_state_dict"])
     else:
-        cfg = json.loads(str(np.load(os.path.join(ROOT, "tests", "golden", f"{a.synthetic or 'base'}.npz"))["config_json"]))
-        model = make_model(cfg)
-        model.load_state_dict({k: torch.from_numpy(np.ascontiguousarray(synth.synth_tensor(k, s))) for k, s in state_manifest(model.cfg).items()
+        g = np.load(os.path.join(ROOT, "tests", "golden", f"{a.synthetic or 'base'}.npz"))
+        cfg = json.loads(str(g["config_json"]))
+        model = make_model(cfg, str(g["model_name"]) if "model_name" in g else "csvq+swinT")
+        model.load_state_dict({k: torch.from_numpy(np.ascontiguousarray(synth.synth_tensor(k, s))) for k, s in model._state_manifest().items()
                                if not k.endswith(".window")})
     model = model.to(a.device).eval()
     codes, size = model.encode(x, num_streams=a.num_streams)

@@ -74,11 +74,11 @@ def load_model(args):
         model.load_state_dict(torch.load(f"{args.model_path}/model.pth", map_location="cpu")["model_state_dict"])
         return model, cfg["model"]
     from esc import synth
-    from esc.models.codecs import state_manifest
     root = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    cfg = json.loads(str(np.load(os.path.join(root, "tests", "golden", f"{args.synthetic or 'base'}.npz"))["config_json"]))
-    model = make_model(cfg)
-    model.load_state_dict({k: torch.from_numpy(np.ascontiguousarray(synth.synth_tensor(k, s))) for k, s in state_manifest(model.cfg).items()
+    g = np.load(os.path.join(root, "tests", "golden", f"{args.synthetic or 'base'}.npz"))
+    cfg = json.loads(str(g["config_json"]))
+    model = make_model(cfg, str(g["model_name"]) if "model_name" in g else "csvq+swinT")     # csvq+swinT (ESC) or rvq+swinT (RVQCodecs)
+    model.load_state_dict({k: torch.from_numpy(np.ascontiguousarray(synth.synth_tensor(k, s))) for k, s in model._state_manifest().items()
                            if not k.endswith(".window")})
     return model, cfg
 

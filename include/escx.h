@@ -62,11 +62,31 @@ typedef struct {
 
 typedef struct escx_handle_s* escx_handle;
 
+/* Mirrors the kwargs of esc.RVQCodecs.__init__ (esc/models/codecs.py:96-127, the rvq+swinT ablation): the Swin backbone of ESC with a
+ * product-residual VQ at the bottleneck only (quantization.py:292-431).  base.group_size = number of product groups (num_pvqs),
+ * base.codebook_dims is ignored (every stage of every group has codebook_dim), base.max_streams = len(h_dims) as for ESC. */
+typedef struct {
+    escx_config base;
+    int32_t num_rvqs;                       /* residual stages per group = the largest num_streams (6)   */
+    int32_t codebook_dim;                   /* 8                                                          */
+} escx_rvq_config;
+
 /* ---- lifetime ------------------------------------------------------------------------------- */
 const char* escx_last_error(void);
 const char* escx_version(void);
 /* ESC.__init__ (codecs.py:11-28, base.py:12-27,49-71): validates the configuration, derives geometry. */
 int escx_create(const escx_config* cfg, int device, escx_handle* out);
+/* RVQCodecs.__init__ (codecs.py:96-127, base.py:73-84).  The quantiser runs as one fused gfx950 kernel per batch part (fused_prvq.h), instantiated
+ * for codebook_dim 5..8 with 3 or 4 groups (the ablation yaml: 3 x 8) and for codebook_dim <= 4 with up to 4 groups; another geometry, a group whose
+ * width equals codebook_dim (no projection in the reference) or num_rvqs outside [1, 16] is ESCX_ERR_UNSUPPORTED here, never wrong output later.
+ * Required keys: the backbone's (encoder.*, decoder.blocks.*, decoder.post_nn.*, decoder.patch_deembed.*) and, per group m and stage i,
+ * quantizers.vqs.{m}.proj_down.weight (d, D_m), quantizers.vqs.{m}.proj_up.weight (D_m, d), quantizers.vqs.{m}.vqs.{i}.embedding.weight (K, d).
+ * On such a handle escx_encode / escx_decode / escx_forward / escx_forward_feat and the three *_streams calls run the rvq+swinT codec with
+ * num_streams (per clip, for *_streams) in [1, num_rvqs]; codes keep the (B, S, G, T) layout.  escx_train_*, escx_pvq_encode and
+ * escx_pvq_decode return ESCX_ERR_UNSUPPORTED; the flat-parameter calls (escx_flat_param_*, escx_load_flat_params) work as for ESC. */
+int escx_create_rvq(const escx_rvq_config* cfg, int device, escx_handle* out);
+/* 0 = cross-scale product VQ (escx_create, ESC), 1 = bottleneck product-residual VQ (escx_create_rvq, RVQCodecs); negative for a null handle. */
+int escx_quantizer_kind(escx_handle h);
 void escx_destroy(escx_handle h);
 
 /* nn.Module.load_state_dict (compress.py:23-25): one call per state_dict entry, HOST fp32, C-contiguous.
@@ -169,6 +189,12 @@ int escx_pvq_encode(escx_handle h, int stream_id, const float* enc_dev, const fl
 /* CrossScaleRVQ.csrvq_decode / PVQ.decode (csrvq.py:56-60, quantization.py:93-108): out = dec + dequant(codes). */
 int escx_pvq_decode(escx_handle h, int stream_id, const int64_t* codes_dev, int64_t code_batch_stride,
                     const float* dec_dev, int batch, int W, float* out_dev, void* stream);
+/* ProductResidualVectorQuantize.encode / .forward in eval mode (quantization.py:292-378) on an rvq handle: tokens (B, Hq*W, C) of the bottleneck
+ * (reference layout) -> codes (B, S, G, W/overlap) int64, 1 <= S <= num_rvqs; zq_out (optional, (B, Hq*W, C)) = post_process(proj_up(sum of the
+ * raw rows of the S stages)), the decoder's input.  Synchronous with respect to `stream` only. */
+int escx_rvq_encode(escx_handle h, const float* tokens_dev, int batch, int W, int num_streams, int64_t* codes_dev, float* zq_out_dev, void* stream);
+/* ProductResidualVectorQuantize.decode (quantization.py:406-420): codes (B, S, G, W/overlap) -> tokens (B, Hq*W, C). */
+int escx_rvq_decode(escx_handle h, const int64_t* codes_dev, int batch, int num_streams, int W, float* tokens_out_dev, void* stream);
 /* PatchDeEmbed.forward (scale.py:73-81): tokens (B,H0*W,C0) -> spec (B, 2W, 2, F) frame-major */
 int escx_patch_deembed(escx_handle h, const float* tokens_dev, int batch, int W, float* spec_dev, void* stream);
 
