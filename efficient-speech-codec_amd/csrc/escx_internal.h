@@ -161,6 +161,7 @@ struct escx_handle_s : escx::WsFields {      // the inherited fields are the CUR
     void* dch_x2 = nullptr;          // ... as the two-term fp16 stream of deembed7_x2_kernel (derived inference state, rebuilt with the tables; active pointer / owning buffer)
     void* dch_x2_buf = nullptr;
     float *dc1_wT = nullptr, *idft_wT = nullptr;     // training: conv5x5 dX weights, transposed inverse-DFT matrix
+    float* dft_wT = nullptr;                         // training: transposed DFT matrix ([winP][2Fp]), the STFT adjoint of an input gradient
 
     // ---- training step (train.hip) ----
     std::vector<std::string> flat_keys;          // canonical flat order of the trainable parameters (== required keys)

@@ -595,6 +595,14 @@ static int pack_image(escx_handle_s* h, std::vector<float>& image, std::vector<s
             const size_t oi = fix[fix.size() - 2].second;
             for (int j = 0; j < h->winP; ++j) for (int f = 0; f < 2 * Fp; ++f) pk.host[ot + (size_t)f * h->winP + j] = pk.host[oi + (size_t)j * 2 * Fp + f];
         }
+        {   // forward DFT matrix transposed ([winP][2Fp], the same values) for the spectrum -> waveform gradient of an input
+            const size_t ot = cslot(&h->dft_wT, (size_t)h->winP * 2 * Fp);
+            for (int f = 0; f < F; ++f) for (int k = 0; k < win; ++k) {
+                const double ang = 2.0 * M_PI * (double)((long long)f * (k + left) % N) / (double)N;
+                pk.host[ot + (size_t)k * 2 * Fp + f] = (float)(w[k] * std::cos(ang));
+                pk.host[ot + (size_t)k * 2 * Fp + Fp + f] = (float)(-w[k] * std::sin(ang));
+            }
+        }
         o = cslot(&h->win2, h->winP);
         for (int j = 0; j < win; ++j) { const float wf = (float)wi[j]; pk.host[o + j] = wf * wf; }
     }

@@ -42,6 +42,7 @@ struct TrainTape {
     Shapes shp;
     float *spec = nullptr, *pe_pre = nullptr, *tok0 = nullptr, *deemb = nullptr, *rspec = nullptr, *terms = nullptr;
     bool composed = false;                   // the forward ran the folded de-embedding: no fine map (deemb) on the tape
+    bool from_feat = false;                  // the forward was given the spectrum (escx_train_forward_feat): an input gradient stops at the spectrum
     long long* codes = nullptr;              // (B, max_streams, G, Tq)
     std::vector<LayerTape> layers;           // 2n
     std::vector<float*> enc_hs;              // n
@@ -249,6 +250,7 @@ int ln_bwd(int mode, const float* x, const float* dy, const float* gamma, const 
     if (mode == 0) hipLaunchKernelGGL((ln_bwd_kernel<1, 0>), dim3(grid), dim3(256), shm, st, x, dy, gamma, map, add, dx, part, rows_per_clip, src_rows_per_clip, dy_rows_per_clip, total_rows, C, Cp, 1e-5f, dx_slots, slot_of, slots_per_clip);
     else if (mode == 1) hipLaunchKernelGGL((ln_bwd_kernel<1, 1>), dim3(grid), dim3(256), shm, st, x, dy, gamma, map, add, dx, part, rows_per_clip, src_rows_per_clip, dy_rows_per_clip, total_rows, C, Cp, 1e-5f, dx_slots, slot_of, slots_per_clip);
     else hipLaunchKernelGGL((ln_bwd_kernel<2, 2>), dim3(grid), dim3(256), shm, st, x, dy, gamma, map, add, dx, part, rows_per_clip, src_rows_per_clip, dy_rows_per_clip, total_rows, C, Cp, 1e-5f, dx_slots, slot_of, slots_per_clip);
+    if (!dg) return 0;                       // input-only backward: the kernel's gamma / beta partials stay in the scratch
     // part: [grid][2][RW] -> reduce over grid (fixed order) into a [2][RW] row, then to the two destinations
     float* red = part + (size_t)grid * 2 * RW;
     reduce_partials(part, grid, (long long)2 * RW, red, 0, st);
@@ -279,6 +281,7 @@ void gemm_ln_bwd_rows(const float* A, int lda, int M, const float* Wt, int Cp, i
     else if (Cp == 384) launch_tile<64, 384, 16>(la, Wt, M, Cp, Kp, 1, ep, st);
     else if (big) launch_gemm<128>(la, Wt, M, Cp, Kp, ep, st, 1, bk);
     else launch_gemm<64>(la, Wt, M, Cp, Kp, ep, st, 1, bk);
+    if (!dg) return;                         // input-only backward: the epilogue's gamma / beta partials stay in the scratch
     float* red = part + (size_t)rows * 2 * Cp;
     launch_reduce_partials(part, rows, (long long)2 * Cp, red, 0, st, red + 2 * Cp);
     hipLaunchKernelGGL(copy2_kernel, dim3(blocks_for(2 * Cp)), dim3(256), 0, st, red, dg, dbt, Cp);
@@ -319,7 +322,7 @@ int attn_bwd(const float* qkv, const float* bias, const float* dout, float* dqkv
     }
     if (lrc) return lrc;
 #undef ESCX_ATB
-    reduce_partials(part, gx, (long long)nH * 256, dbias, 0, st);
+    if (dbias) reduce_partials(part, gx, (long long)nH * 256, dbias, 0, st);
     return 0;
 }
 constexpr size_t ATT_PART_FLOATS = (size_t)512 * 64 * 256;
@@ -360,7 +363,7 @@ int pack_train_mlp_images(escx_handle_s* h, hipStream_t st) {
 // C = 72: 18 hidden tiles as 2 x 9 (grid.y = 2): the workgroups write d xn partial slabs (`slabs`: 2 * M * Cp floats), which are summed into `dxn`
 // and go through the stand-alone LayerNorm backward.  `part`: grid.x x (2 * hiddenP * Cp + hiddenP + Cp) floats + the reduced E.
 int mlp_bwd_fused(escx_handle_s* h, const Layer& L, const BlockW& bw, const float* x1, const float* dy, float* dx1, float* dx1s, const int* slot_of,
-                  int tokens, int slots, int M, float* part, float* dxn, float* slabs, float* lnpart, hipStream_t st) {
+                  int tokens, int slots, int M, float* part, float* dxn, float* slabs, float* lnpart, hipStream_t st, bool gw = true) {
     const int ntiles = (M + 15) / 16;
     const bool split = L.Cp == 80;
     const int grid = std::min(ntiles, split ? 128 : 256);
@@ -375,14 +378,17 @@ int mlp_bwd_fused(escx_handle_s* h, const Layer& L, const BlockW& bw, const floa
     if (split) { if (x2) hipLaunchKernelGGL((mlp_bwd_fused_kernel<80, 9, 2, true>), dim3(grid, 2), dim3(64 * 12), 0, st, a); else hipLaunchKernelGGL((mlp_bwd_fused_kernel<80, 9, 2>), dim3(grid, 2), dim3(64 * 12), 0, st, a); }
     else { if (x2) hipLaunchKernelGGL((mlp_bwd_fused_kernel<48, 12, 1, true>), dim3(grid), dim3(64 * 15), 0, st, a); else hipLaunchKernelGGL((mlp_bwd_fused_kernel<48, 12, 1>), dim3(grid), dim3(64 * 15), 0, st, a); }
     float* Etot = part + (size_t)grid * per;
+    if (gw) {                                // input-only backward: the dW / db partials stay in `part`
     hipLaunchKernelGGL(mlp_bwd_reduce_kernel, dim3((unsigned)((per + 255) / 256)), dim3(256), 0, st, part, grid, n1, L.hiddenP, L.Cp, Etot, G(h, bw.w2),
                        G(h, bw.b1), G(h, bw.b2));
     hipLaunchKernelGGL(mlp_bwd_finish_kernel, dim3(1), dim3(1024), 0, st, Etot, G(h, bw.b1), bw.w1, bw.ln2_g, bw.ln2_b, G(h, bw.w1),
                        split ? nullptr : G(h, bw.ln2_g), split ? nullptr : G(h, bw.ln2_b), L.hiddenP, L.Cp);
+    }
     if (split) {
         const long long n4 = (long long)M * L.Cp / 4;
         hipLaunchKernelGGL(slab_sum_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, slabs, 2, n4, dxn);
-        ln_bwd(0, x1, dxn, bw.ln2_g, nullptr, dy, dx1, G(h, bw.ln2_g), G(h, bw.ln2_b), tokens, tokens, tokens, M, L.C, L.Cp, lnpart, st, dx1s, slot_of, slots);
+        ln_bwd(0, x1, dxn, bw.ln2_g, nullptr, dy, dx1, gw ? G(h, bw.ln2_g) : nullptr, gw ? G(h, bw.ln2_b) : nullptr, tokens, tokens, tokens, M, L.C, L.Cp, lnpart, st,
+               dx1s, slot_of, slots);
     }
     return 0;
 }
@@ -435,6 +441,7 @@ size_t tape_bytes(escx_handle_s* h, const Shapes& s) {
     const size_t fine = (size_t)B * T2 * F2 * h->C0p;
     tot += 12 * pad256(act_max) + 2 * pad256(hid_max) + 2 * pad256(qkv_max) + pad256(zp_max) + 2 * pad256(fine) + 2 * pad256(DW_PART_FLOATS) +
            pad256(LN_PART_FLOATS) + pad256(ATT_PART_FLOATS) + 3 * pad256((size_t)B * T2 * std::max(h->winP, c.in_dim * h->Fp)) + (size_t)n * pad256(act_max) + (64 << 20);
+    tot += 2 * pad256((size_t)B * s.T * std::max(h->winP, c.in_dim * h->Fp));       // input gradient: spectrum and frames of all T frames
     return tot;
 }
 
@@ -711,6 +718,7 @@ int train_forward_impl(escx_handle_s* h, const float* wave, const float* feat, i
     // reference remain for geometries without a folded form and as the A/B baseline (ESCX_TRAIN_DEEMBED_COMPOSED=0).
     const int F2 = c.patch_f * s.H0;
     T.composed = train_deembed_composed(h);
+    T.from_feat = feat != nullptr;
     if (T.composed && h->composed_stale) ESCX_FAIL(ESCX_ERR_STATE, "folded de-embedding is stale in a training forward (refresh_from_flat did not run)");
     T.deemb = T.composed ? nullptr : tp.take((size_t)B * T2 * F2 * h->C0p);
     T.rspec = tp.take((size_t)B * T2 * c.in_dim * h->Fp);
@@ -863,7 +871,9 @@ int layer_bwd(escx_handle_s* h, const Layer& L, const LayerTape& LT, const float
     float* dbias = sc.take((size_t)L.nH * 256);
     float* dprev = sc.take((size_t)M * L.Cp);
     if (!dprev) ESCX_FAIL(ESCX_ERR_STATE, "training tape too small (backward scratch)");
-    int rc;
+    int rc = 0;
+    const bool gw = gflat != nullptr;                       // parameter gradients wanted (an input-only backward launches no dW work)
+    auto GW = [&](const float* w) -> float* { return gw ? G(h, w) : nullptr; };
     const std::string tg = h->prof ? "[C=" + std::to_string(L.C) + "]" : std::string();
     const float* x_last = LT.blk.back().x2;
     const float* dlast;                                     // gradient w.r.t. the last block's output
@@ -873,17 +883,17 @@ int layer_bwd(escx_handle_s* h, const Layer& L, const LayerTape& LT, const float
         if ((rc = get_map(h, H, W, -1, &map))) return rc;
         float* dsub = sc.take((size_t)M2 * 2 * L.Cp);
         if (!dsub) ESCX_FAIL(ESCX_ERR_STATE, "training tape too small (backward scratch)");
-        if ((rc = dw_rows(h, gy, L.CoutP, LT.sub_xn, 2 * L.Cp, M2, L.CoutP, 2 * L.Cp, G(h, L.sub_w), nullptr, part, st))) return rc;
+        if (gw && (rc = dw_rows(h, gy, L.CoutP, LT.sub_xn, 2 * L.Cp, M2, L.CoutP, 2 * L.Cp, G(h, L.sub_w), nullptr, part, st))) return rc;
         gemm_rows(gy, L.CoutP, M2, L.sub_wT, 2 * L.Cp, L.CoutP, EpiStore{dsub, 2 * L.Cp, nullptr}, st);
-        ln_bwd(2, x_last, dsub, L.sub_g, map, nullptr, dcur, G(h, L.sub_g), G(h, L.sub_b), H2 * W, tokens, 0, M2, L.C, L.Cp, lnpart, st);
+        ln_bwd(2, x_last, dsub, L.sub_g, map, nullptr, dcur, GW(L.sub_g), GW(L.sub_b), H2 * W, tokens, 0, M2, L.C, L.Cp, lnpart, st);
         dlast = dcur;
     } else if (L.scale == 2) {
         float* dsub = sc.take((size_t)M * L.Cp);
         if (!dsub) ESCX_FAIL(ESCX_ERR_STATE, "training tape too small (backward scratch)");
         SplitGatherA ga{gy, H, W, L.CoutP, M, FastDiv(H * W), FastDiv(W), FastDiv(L.CoutP)};
-        if ((rc = dw_launch(h, ga, PlainA{LT.sub_xn, L.Cp, M}, M, 2 * L.CoutP, L.Cp, G(h, L.sub_w), nullptr, part, st))) return rc;
+        if (gw && (rc = dw_launch(h, ga, PlainA{LT.sub_xn, L.Cp, M}, M, 2 * L.CoutP, L.Cp, G(h, L.sub_w), nullptr, part, st))) return rc;
         gemm_any(ga, L.sub_wT, M, L.Cp, 2 * L.CoutP, EpiStore{dsub, L.Cp, nullptr}, st, 16);
-        ln_bwd(0, x_last, dsub, L.sub_g, nullptr, nullptr, dcur, G(h, L.sub_g), G(h, L.sub_b), tokens, tokens, tokens, M, L.C, L.Cp, lnpart, st);
+        ln_bwd(0, x_last, dsub, L.sub_g, nullptr, nullptr, dcur, GW(L.sub_g), GW(L.sub_b), tokens, tokens, tokens, M, L.C, L.Cp, lnpart, st);
         dlast = dcur;
     } else {
         dlast = gy;
@@ -902,52 +912,52 @@ int layer_bwd(escx_handle_s* h, const Layer& L, const LayerTape& LT, const float
         if (fmlp) {
             if (slots != tokens) ESCX_HIP(hipMemsetAsync(dx1s, 0, (size_t)Ms * L.Cp * sizeof(float), st));      // pad slots carry no gradient
             PROF("B.mlp_fused" + tg, 10.0 * M * L.C * L.hidden, (3.0 * M + Ms) * L.Cp * 4,
-                 rc = mlp_bwd_fused(h, L, bw, bt.x1, dy, dx1, dx1s, inv, tokens, slots, M, part, dxn, dhpre, lnpart, st));
+                 rc = mlp_bwd_fused(h, L, bw, bt.x1, dy, dx1, dx1s, inv, tokens, slots, M, part, dxn, dhpre, lnpart, st, gw));
             if (rc) return rc;
         } else {
-        PROF("B.dw_fc2" + tg, 2.0 * M * L.C * L.hidden, (double)M * (L.Cp + L.hiddenP) * 4,
-             rc = dw_rows(h, dy, L.Cp, bt.hact, L.hiddenP, M, L.Cp, L.hiddenP, G(h, bw.w2), G(h, bw.b2), part, st));
+        if (gw) PROF("B.dw_fc2" + tg, 2.0 * M * L.C * L.hidden, (double)M * (L.Cp + L.hiddenP) * 4,
+                     rc = dw_rows(h, dy, L.Cp, bt.hact, L.hiddenP, M, L.Cp, L.hiddenP, G(h, bw.w2), G(h, bw.b2), part, st));
         if (rc) return rc;
         PROF("B.dx_fc2" + tg, 2.0 * M * L.C * L.hidden, (double)M * (L.Cp + 2 * L.hiddenP) * 4,
              gemm_rows(dy, L.Cp, M, bw.w2T, L.hiddenP, L.Cp, EpiGeluBwd{dhpre, L.hiddenP, bt.hpre}, st));
-        PROF("B.dw_fc1" + tg, 2.0 * M * L.C * L.hidden, (double)M * (L.Cp + L.hiddenP) * 4,
-             rc = dw_rows(h, dhpre, L.hiddenP, bt.xn2, L.Cp, M, L.hiddenP, L.Cp, G(h, bw.w1), G(h, bw.b1), part, st));
+        if (gw) PROF("B.dw_fc1" + tg, 2.0 * M * L.C * L.hidden, (double)M * (L.Cp + L.hiddenP) * 4,
+                     rc = dw_rows(h, dhpre, L.hiddenP, bt.xn2, L.Cp, M, L.hiddenP, L.Cp, G(h, bw.w1), G(h, bw.b1), part, st));
         if (rc) return rc;
         if (slots != tokens) ESCX_HIP(hipMemsetAsync(dx1s, 0, (size_t)Ms * L.Cp * sizeof(float), st));      // pad slots carry no gradient
         if (ln_fused && ln_rows_fusable(L.Cp)) {       // LN2's backward rides in the epilogue of the GEMM that produces its upstream gradient
             PROF("B.dx_fc1+ln2" + tg, 2.0 * M * L.C * L.hidden, ((double)M * (L.hiddenP + 3 * L.Cp) + (double)Ms * L.Cp) * 4,
-                 gemm_ln_bwd_rows(dhpre, L.hiddenP, M, bw.w1T, L.Cp, L.hiddenP, bt.x1, bw.ln2_g, dy, dx1, dx1s, inv, tokens, slots, L.C, G(h, bw.ln2_g),
-                                  G(h, bw.ln2_b), part, st));
+                 gemm_ln_bwd_rows(dhpre, L.hiddenP, M, bw.w1T, L.Cp, L.hiddenP, bt.x1, bw.ln2_g, dy, dx1, dx1s, inv, tokens, slots, L.C, GW(bw.ln2_g),
+                                  GW(bw.ln2_b), part, st));
         } else {
             PROF("B.dx_fc1" + tg, 2.0 * M * L.C * L.hidden, (double)M * (L.hiddenP + L.Cp) * 4,
                  gemm_rows(dhpre, L.hiddenP, M, bw.w1T, L.Cp, L.hiddenP, EpiStore{dxn, L.Cp, nullptr}, st));
             PROF("B.ln2" + tg, 0, 5.0 * M * L.C * 4,
-                 ln_bwd(0, bt.x1, dxn, bw.ln2_g, nullptr, dy, dx1, G(h, bw.ln2_g), G(h, bw.ln2_b), tokens, tokens, tokens, M, L.C, L.Cp, lnpart, st, dx1s, inv, slots));
+                 ln_bwd(0, bt.x1, dxn, bw.ln2_g, nullptr, dy, dx1, GW(bw.ln2_g), GW(bw.ln2_b), tokens, tokens, tokens, M, L.C, L.Cp, lnpart, st, dx1s, inv, slots));
         }
         }
         // ---- attention: x1 = x0 + scatter(Wp attn(Wqkv gather(LN1(x0)))) ----
-        PROF("B.dw_proj" + tg, 2.0 * Ms * L.C * L.C, (double)Ms * (L.Cp + L.Ko) * 4,
-             rc = dw_rows(h, dx1s, L.Cp, bt.obuf, L.Ko, Ms, L.Cp, L.Ko, G(h, bw.wproj), G(h, bw.bproj), part, st));
+        if (gw) PROF("B.dw_proj" + tg, 2.0 * Ms * L.C * L.C, (double)Ms * (L.Cp + L.Ko) * 4,
+                     rc = dw_rows(h, dx1s, L.Cp, bt.obuf, L.Ko, Ms, L.Cp, L.Ko, G(h, bw.wproj), G(h, bw.bproj), part, st));
         if (rc) return rc;
         PROF("B.dx_proj" + tg, 2.0 * Ms * L.C * L.C, (double)Ms * (L.Cp + L.Ko) * 4, gemm_rows(dx1s, L.Cp, Ms, bw.wprojT, L.Ko, L.Cp, EpiStore{dobuf, L.Ko, nullptr}, st));
         int arc = 0;
         PROF("B.attn_core" + tg, 10.0 * Ms * 16 * L.C, (double)Ms * (2 * L.Nqkv + L.Ko) * 4,
-             arc = attn_bwd(bt.qkv, bw.bias_tab, dobuf, dqkv, dbias, attpart, Ms / 16, L.nH, L.hdp, L.Nqkv, L.Ko, Hp / 4, Wp / 4, shift > 0,
+             arc = attn_bwd(bt.qkv, bw.bias_tab, dobuf, dqkv, gw ? dbias : nullptr, attpart, Ms / 16, L.nH, L.hdp, L.Nqkv, L.Ko, Hp / 4, Wp / 4, shift > 0,
                             1.0f / std::sqrt((float)L.hd), st));
         if (arc) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, arc == -2 ? "batch too large for the attention backward kernel's 32-bit offsets (head_dim %d)" : "head_dim %d unsupported by the attention backward kernel", L.hd);
-        if (bw.tab_off >= 0)
+        if (gw && bw.tab_off >= 0)
             hipLaunchKernelGGL(bias_table_grad_kernel, dim3(blocks_for(49 * L.nH)), dim3(256), 0, st, dbias, gflat + bw.tab_off, L.nH);
-        PROF("B.dw_qkv" + tg, 2.0 * Ms * L.C * 3 * L.C, (double)Ms * (L.Nqkv + L.Cp) * 4,
-             rc = dw_rows(h, dqkv, L.Nqkv, bt.xn1, L.Cp, Ms, L.Nqkv, L.Cp, G(h, bw.wqkv), G(h, bw.bqkv), part, st));
+        if (gw) PROF("B.dw_qkv" + tg, 2.0 * Ms * L.C * 3 * L.C, (double)Ms * (L.Nqkv + L.Cp) * 4,
+                     rc = dw_rows(h, dqkv, L.Nqkv, bt.xn1, L.Cp, Ms, L.Nqkv, L.Cp, G(h, bw.wqkv), G(h, bw.bqkv), part, st));
         if (rc) return rc;
         if (ln_fused && ln_rows_fusable(L.Cp)) {       // LN1's backward in the epilogue of the QKV dX GEMM: its rows are window slots, map = slot -> token
             PROF("B.dx_qkv+ln1" + tg, 2.0 * Ms * L.C * 3 * L.C, ((double)Ms * L.Nqkv + 3.0 * M * L.Cp) * 4,
-                 gemm_ln_bwd_rows(dqkv, L.Nqkv, Ms, bw.wqkvT, L.Cp, L.Nqkv, bt.x0, bw.ln1_g, dx1, dprev, nullptr, nullptr, tokens, slots, L.C, G(h, bw.ln1_g),
-                                  G(h, bw.ln1_b), part, st, map));
+                 gemm_ln_bwd_rows(dqkv, L.Nqkv, Ms, bw.wqkvT, L.Cp, L.Nqkv, bt.x0, bw.ln1_g, dx1, dprev, nullptr, nullptr, tokens, slots, L.C, GW(bw.ln1_g),
+                                  GW(bw.ln1_b), part, st, map));
         } else {
             PROF("B.dx_qkv" + tg, 2.0 * Ms * L.C * 3 * L.C, (double)Ms * (L.Nqkv + L.Cp) * 4, gemm_rows(dqkv, L.Nqkv, Ms, bw.wqkvT, L.Cp, L.Nqkv, EpiStore{dxn, L.Cp, nullptr}, st));
             PROF("B.ln1" + tg, 0, 4.0 * M * L.C * 4,
-                 ln_bwd(1, bt.x0, dxn, bw.ln1_g, inv, dx1, dprev, G(h, bw.ln1_g), G(h, bw.ln1_b), tokens, tokens, slots, M, L.C, L.Cp, lnpart, st));
+                 ln_bwd(1, bt.x0, dxn, bw.ln1_g, inv, dx1, dprev, GW(bw.ln1_g), GW(bw.ln1_b), tokens, tokens, slots, M, L.C, L.Cp, lnpart, st));
         }
         std::swap(dcur, dprev);
         dy = dcur;
@@ -959,7 +969,7 @@ int layer_bwd(escx_handle_s* h, const Layer& L, const LayerTape& LT, const float
 // backward of one transmitted quantiser step: gref = gradient of the refined map (post_fuse output).  Accumulates into d_enc (gradient of the
 // encoder map) and, if ddec != nullptr, subtracts from it (pre_fuse: residual = enc - dec).  The +dec path of post_fuse is the caller's.
 int quant_bwd(escx_handle_s* h, TrainTape& T, int sid, const float* gref, float* d_enc, float* ddec, const float* dcm, const float* dcb, Scratch& sc,
-              hipStream_t st) {
+              hipStream_t st, bool gw = true) {
     const escx_config& c = h->cfg;
     const Quant& q = h->quants[sid];
     const QuantTape& Q = T.q[sid];
@@ -972,15 +982,15 @@ int quant_bwd(escx_handle_s* h, TrainTape& T, int sid, const float* gref, float*
     float* dze = sc.take((size_t)M * q.Nz);
     float* gq = sc.take((size_t)M * q.Nz);
     if (!gq) ESCX_FAIL(ESCX_ERR_STATE, "training tape too small (backward scratch)");
-    int rc;
+    int rc = 0;
     ResidualGatherA gfr{gref, nullptr, q.Hq, W, q.Cp, Tq, c.overlap, M, FastDiv(Tq), FastDiv(q.Cp), FastDiv(q.Hq)};        // framed view of the map gradient
     // up-projection: out_frames = zup . Wup^T   (Wup packed [Kq][Kup])
-    if ((rc = dw_launch(h, gfr, PlainA{Q.zup, q.Nz, M}, M, q.Kq, q.Kup, G(h, q.wup), nullptr, part, st))) return rc;
+    if (gw && (rc = dw_launch(h, gfr, PlainA{Q.zup, q.Nz, M}, M, q.Kq, q.Kup, G(h, q.wup), nullptr, part, st))) return rc;
     gemm_any(gfr, q.wupT, M, q.Kup, q.Kq, EpiStore{dzup, q.Nz, nullptr}, st, pick_bk(q.Cp));
     const float scale = 1.0f / ((float)Tq * q.d * Gr);
     hipLaunchKernelGGL(pvq_train_bwd_kernel, dim3(blocks_for((long long)M * Gr)), dim3(256), 0, st, Q.ze, codes, bstride, q.cbraw, dzup, dcm, dcb, dze, gq,
                        M, Gr, c.codebook_size, q.d, q.dt, q.Nz, Tq, scale, T.freeze);
-    {
+    if (gw) {                                   // codebook gradient (gq is the kernel's by-product; an input-only backward leaves it)
         const dim3 cg(Gr * ((c.codebook_size + CBG_CODES - 1) / CBG_CODES));
         float* dcbw = G(h, q.cbraw);
         if (q.dt <= 8) hipLaunchKernelGGL(codebook_grad_kernel<8>, cg, dim3(256), 0, st, codes, bstride, gq, dcbw, M, Gr, c.codebook_size, q.dt, q.Nz, Tq);
@@ -991,7 +1001,7 @@ int quant_bwd(escx_handle_s* h, TrainTape& T, int sid, const float* gref, float*
     }
     // down-projection: ze = residual_frames . Wd^T   (Wd packed [Nz][Kq])
     ResidualGatherA rfr{Q.enc, Q.dec, q.Hq, W, q.Cp, Tq, c.overlap, M, FastDiv(Tq), FastDiv(q.Cp), FastDiv(q.Hq)};
-    if ((rc = dw_launch(h, PlainA{dze, q.Nz, M}, rfr, M, q.Nz, q.Kq, G(h, q.wd), nullptr, part, st))) return rc;
+    if (gw && (rc = dw_launch(h, PlainA{dze, q.Nz, M}, rfr, M, q.Nz, q.Kq, G(h, q.wd), nullptr, part, st))) return rc;
     gemm_rows(dze, q.Nz, M, q.wdT, q.Kq, q.Nz, EpiPvqGrad{d_enc, ddec, q.Hq, W, q.Cp, Tq, c.overlap, FastDiv(Tq), FastDiv(q.Cp), FastDiv(q.Hq)}, st);
     return launch_ok("quant_bwd");
 }
@@ -1003,7 +1013,10 @@ void add_inplace(float* dst, const float* src, size_t n, hipStream_t st) {
 }  // namespace
 
 namespace {
-int train_backward_impl(escx_handle_s* h, const float* d_wave, const float* d_recon_feat, const float* d_cm, const float* d_cb, float* grad_flat, hipStream_t st) {
+// grad_flat == nullptr: no parameter gradient (nothing whose only product is one is launched); d_input != nullptr: d loss / d input, (B, L) after a
+// waveform forward, (B, T, in_dim, F) after a spectrum forward; d_raw_feat (B, T, in_dim, F, optional) = upstream gradient of the raw spectrum output
+int train_backward_impl(escx_handle_s* h, const float* d_wave, const float* d_recon_feat, const float* d_raw_feat, const float* d_cm, const float* d_cb,
+                        float* grad_flat, float* d_input, hipStream_t st) {
     int rc = 0;
     TrainTape& T = *tape_of(h);
     if (!T.valid) ESCX_FAIL(ESCX_ERR_STATE, "escx_train_backward without a preceding escx_train_forward");
@@ -1014,8 +1027,11 @@ int train_backward_impl(escx_handle_s* h, const float* d_wave, const float* d_re
     tp.used = T.fwd_mark;
     const int n = h->n, B = T.B;
     const int T2 = c.patch_t * s.W, F2 = c.patch_f * s.H0, out_len = c.hop_length * (T2 - 1);
-    ESCX_HIP(hipMemsetAsync(h->garena, 0, h->wts.cap, st));
-    ESCX_HIP(hipMemsetAsync(grad_flat, 0, h->flat_total * sizeof(float), st));
+    const bool gw = grad_flat != nullptr;
+    if (gw) {
+        ESCX_HIP(hipMemsetAsync(h->garena, 0, h->wts.cap, st));
+        ESCX_HIP(hipMemsetAsync(grad_flat, 0, h->flat_total * sizeof(float), st));
+    }
     Scratch top(&tp);
     // gradients of the encoder maps (two consumers each: the next encoder layer and a quantiser)
     std::vector<float*> d_enc(n);
@@ -1062,19 +1078,23 @@ int train_backward_impl(escx_handle_s* h, const float* d_wave, const float* d_re
         else hipLaunchKernelGGL(deembed_p_kernel, dim3(blocks_for((long long)Mt * LD)), dim3(256), 0, st, drspec, P, B, s.H0, s.W, pf, pt, c.in_dim, h->Fp);
         ConvA ctok{T.post, s.H0, s.W, h->C0p, 5, 5, Mt};
         float* Rb = R + (size_t)LD * K1;
+        if (gw) {
         PROF("B.dw_conv5", 2.0 * Mt * 25 * h->C0 * (slots ? c.in_dim * (pf + 2) * (pt + 2) : Q * c.in_dim * 9), 0,
              rc = slots ? (dw_launch_wide<3, 4, 1, 4>(h, PlainA{P, LD, Mt}, ctok, Mt, LD, K1, R, Rb, part, st))          // 48 x 256 workgroup tiles
                         : (dw_launch_wide<4, 4>(h, PlainA{P, LD, Mt}, ctok, Mt, LD, K1, R, Rb, part, st)));
         if (rc) return rc;
         hipLaunchKernelGGL(deembed_fold_dw_kernel, dim3(blocks_for((long long)Q * h->C0p * K1)), dim3(256), 0, st, R, h->dc2_w, G(h, h->dc1_w), Q, h->C0, h->C0p, K1, c.in_dim, pf, pt, slots);
         hipLaunchKernelGGL(deembed_fold_dw_kernel, dim3(blocks_for((long long)Q * h->C0p)), dim3(256), 0, st, Rb, h->dc2_w, G(h, h->dc1_b), Q, h->C0, h->C0p, 1, c.in_dim, pf, pt, slots);
+        }
         if (slots) hipLaunchKernelGGL(deembed_weff_slots_kernel, dim3(blocks_for((long long)h->C0p * 25 * LD)), dim3(256), 0, st, h->dc1_w, h->dc2_w, weff, h->C0, h->C0p, pf, pt, c.in_dim);
         else hipLaunchKernelGGL(deembed_weff_kernel, dim3(blocks_for((long long)h->C0p * 25 * LD)), dim3(256), 0, st, h->dc1_w, h->dc2_w, weff, Q, h->C0, h->C0p, c.in_dim);
         // conv3x3 weight gradient with the same P: only the Q diagonal blocks of P^T . Y1 (Y1 = the saved fine map viewed per coarse pixel) are
         // needed - one 20 x C0p contraction per sub-pixel q instead of the full 128 x Q*C0p product; db2 = the centre-tap column sums of P
         float* X = sc.take((size_t)Q * DEP_J * h->C0p);
         if (!X) ESCX_FAIL(ESCX_ERR_STATE, "training tape too small (backward scratch)");
-        if (T.composed) {               // no saved fine map: X from R, the conv5x5 weights and the column sums of P (train_kernels.h)
+        if (!gw) {
+            // input-only backward: the two convolutions' weight gradients are skipped, conv5x5's dX below is all the decoder needs
+        } else if (T.composed) {               // no saved fine map: X from R, the conv5x5 weights and the column sums of P (train_kernels.h)
             ESCX_HIP(hipMemsetAsync(X, 0, (size_t)Q * DEP_J * h->C0p * sizeof(float), st));
             const int nj = c.in_dim * 9;
             PROF("B.dw_conv3", 2.0 * Q * nj * h->C0 * K1, 0,
@@ -1088,8 +1108,9 @@ int train_backward_impl(escx_handle_s* h, const float* d_wave, const float* d_re
                                 X + (size_t)q * DEP_J * h->C0p, nullptr, part, st); });
         if (rc) return rc;
         }
-        hipLaunchKernelGGL(deembed_fold_dw2_kernel, dim3(blocks_for((long long)c.in_dim * 9 * h->C0p + c.in_dim)), dim3(256), 0, st, X, Rb, G(h, h->dc2_w),
-                           G(h, h->dc2_b), Q, h->C0, h->C0p, c.in_dim, pf, pt, slots);
+        if (gw)
+            hipLaunchKernelGGL(deembed_fold_dw2_kernel, dim3(blocks_for((long long)c.in_dim * 9 * h->C0p + c.in_dim)), dim3(256), 0, st, X, Rb, G(h, h->dc2_w),
+                               G(h, h->dc2_b), Q, h->C0, h->C0p, c.in_dim, pf, pt, slots);
         ConvA cp{P, s.H0, s.W, LD, 5, 5, Mt};
         PROF("B.dx_conv5", 2.0 * Mt * 25 * h->C0 * (slots ? c.in_dim * (pf + 2) * (pt + 2) : Q * c.in_dim * 9), 0,
              gemm_any(cp, weff, Mt, h->C0p, 25 * LD, EpiStore{gtok, h->C0p, nullptr}, st, pick_bk(LD)));
@@ -1119,12 +1140,12 @@ int train_backward_impl(escx_handle_s* h, const float* d_wave, const float* d_re
         // the refined map = dec + residual_q: the +dec path keeps gdec as it is; the quantiser adds to d_enc and subtracts its residual gradient from gdec
         if (T.q[i + 1].transmit) {           // (every read of the map gradient inside quant_bwd precedes the epilogue that updates it: one buffer serves as both)
             Scratch sc(&tp);
-            if ((rc = quant_bwd(h, T, i + 1, gdec, d_enc[n - 1 - i], gdec, d_cm, d_cb, sc, st))) return rc;
+            if ((rc = quant_bwd(h, T, i + 1, gdec, d_enc[n - 1 - i], gdec, d_cm, d_cb, sc, st, gw))) return rc;
         }
     }
     {   // stream 0: the refined map is residual_q alone (dec = 0.0)
         Scratch sc(&tp);
-        if ((rc = quant_bwd(h, T, 0, gdec, d_enc[n - 1], nullptr, d_cm, d_cb, sc, st))) return rc;
+        if ((rc = quant_bwd(h, T, 0, gdec, d_enc[n - 1], nullptr, d_cm, d_cb, sc, st, gw))) return rc;
     }
     // ---- encoder ----
     for (int i = n - 2; i >= 0; --i) {
@@ -1136,16 +1157,40 @@ int train_backward_impl(escx_handle_s* h, const float* d_wave, const float* d_re
     {
         Scratch sc(&tp);
         if ((rc = layer_bwd(h, h->layers[0], T.layers[0], d_enc[0], B, s.W, grad_flat, sc, &gcur, st))) return rc;
-        // patch embedding: LN + strided conv as a GEMM over gathered patches (scale.py:42-50); the input is data: no dX
+        // patch embedding: LN + strided conv as a GEMM over gathered patches (scale.py:42-50)
         float* dpre = sc.take(tok0);
         float* lnpart = sc.take(LN_PART_FLOATS);
         float* part = sc.take(DW_PART_FLOATS);
         if (!part) ESCX_FAIL(ESCX_ERR_STATE, "training tape too small (backward scratch)");
         const int Mt = B * s.H0 * s.W;
-        ln_bwd(0, T.pe_pre, gcur, h->pe_g, nullptr, nullptr, dpre, G(h, h->pe_g), G(h, h->pe_beta), s.H0 * s.W, s.H0 * s.W, s.H0 * s.W, Mt, h->C0, h->C0p, lnpart, st);
+        ln_bwd(0, T.pe_pre, gcur, h->pe_g, nullptr, nullptr, dpre, gw ? G(h, h->pe_g) : nullptr, gw ? G(h, h->pe_beta) : nullptr, s.H0 * s.W, s.H0 * s.W, s.H0 * s.W,
+               Mt, h->C0, h->C0p, lnpart, st);
         PatchA pa{T.spec, s.T, c.in_dim * h->Fp, h->Fp, s.H0, s.W, c.patch_f, c.patch_t, c.in_dim * c.patch_f * c.patch_t, Mt};
-        if ((rc = dw_launch(h, PlainA{dpre, h->C0p, Mt}, pa, Mt, h->C0p, h->Kpe, G(h, h->pe_w), G(h, h->pe_b), part, st))) return rc;
+        if (gw && (rc = dw_launch(h, PlainA{dpre, h->C0p, Mt}, pa, Mt, h->C0p, h->Kpe, G(h, h->pe_w), G(h, h->pe_b), part, st))) return rc;
+        if (d_input) {
+            // input gradient: the patch embedding's dX (non-overlapping patches: one dot product per spectrum value) plus d raw_feat gives d spectrum;
+            // after a waveform forward the STFT adjoint follows - the transposed windowed-DFT GEMM, then the frame adjoint with the reflect-pad fold
+            const long long nrow = (long long)B * s.T * c.in_dim;
+            if (T.from_feat) {
+                PROF("B.dx_patch", 2.0 * nrow * h->F * h->C0, (double)nrow * h->F * 4,
+                     hipLaunchKernelGGL(patch_dx_kernel, dim3(blocks_for(nrow * h->F)), dim3(256), 0, st, dpre, h->pe_w, d_raw_feat, d_input, B, s.T, c.in_dim,
+                                        h->F, h->F, s.H0, s.W, c.patch_f, c.patch_t, h->C0, h->C0p, h->Kpe));
+            } else {
+                float* dspec = sc.take((size_t)nrow * h->Fp);
+                float* dframes = sc.take((size_t)B * s.T * h->winP);
+                if (!dframes) ESCX_FAIL(ESCX_ERR_STATE, "training tape too small (backward scratch)");
+                PROF("B.dx_patch", 2.0 * nrow * h->F * h->C0, (double)nrow * h->Fp * 4,
+                     hipLaunchKernelGGL(patch_dx_kernel, dim3(blocks_for(nrow * h->Fp)), dim3(256), 0, st, dpre, h->pe_w, d_raw_feat, dspec, B, s.T, c.in_dim,
+                                        h->F, h->Fp, s.H0, s.W, c.patch_f, c.patch_t, h->C0, h->C0p, h->Kpe));
+                PROF("B.stft_adjoint", 2.0 * B * s.T * c.win_length * 2 * h->F, ((double)nrow * h->Fp + (double)B * s.T * h->winP) * 4,
+                     gemm_rows(dspec, c.in_dim * h->Fp, B * s.T, h->dft_wT, h->winP, c.in_dim * h->Fp, EpiStore{dframes, h->winP, nullptr}, st));
+                PROF("B.frames_adjoint", 0, ((double)B * s.T * h->winP + (double)B * T.L) * 4,
+                     hipLaunchKernelGGL(frames_bwd_kernel, dim3(blocks_for((long long)B * T.L)), dim3(256), 0, st, dframes, d_input, B, T.L, s.T, c.hop_length,
+                                        c.win_length, h->winP, 0, h->n_fft / 2 - h->left));
+            }
+        }
     }
+    if (!gw) return launch_ok("train_backward");
     // ---- packed gradients -> flat reference layout ----
     if (!h->grad_seg && !h->grad_regions.empty()) {              // one table for all primary layouts (344 launches per step before)
         std::vector<long long> seg;
@@ -1162,23 +1207,23 @@ int train_backward_impl(escx_handle_s* h, const float* d_wave, const float* d_re
 }
 }  // namespace
 
-extern "C" int escx_train_backward(escx_handle h, const float* d_wave, const float* d_recon_feat, const float* d_cm, const float* d_cb,
-                                   float* grad_flat, void* stream) {
-    int rc = check_ready(h); if (rc) return rc;
-    if (h->kind != 0) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "RVQCodecs training is not implemented (escx_create_rvq handles run encode / decode / eval forward only)");
-    if (!grad_flat) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null gradient buffer");
+static int train_backward_entry(escx_handle h, const float* d_wave, const float* d_recon_feat, const float* d_raw_feat, const float* d_cm, const float* d_cb,
+                                float* grad_flat, float* d_input, void* stream) {
+    int rc = 0;
     TrainRoot& R = *root_of(h);
     if (!R.valid) ESCX_FAIL(ESCX_ERR_STATE, "escx_train_backward without a preceding escx_train_forward");
     R.valid = false;
     hipStream_t st = (hipStream_t)stream;
-    if (R.parts == 1) { R.cur = &R.single; return train_backward_impl(h, d_wave, d_recon_feat, d_cm, d_cb, grad_flat, st); }
+    if (R.parts == 1) { R.cur = &R.single; return train_backward_impl(h, d_wave, d_recon_feat, d_raw_feat, d_cm, d_cb, grad_flat, d_input, st); }
     const escx_config& c = h->cfg;
     const Shapes& s1 = R.part[0].shp;
     const size_t per_wave = (size_t)c.hop_length * (c.patch_t * s1.W - 1), per_recon = (size_t)c.patch_t * s1.W * c.in_dim * h->F;
+    const size_t per_raw = (size_t)s1.T * c.in_dim * h->F, per_input = R.part[0].from_feat ? per_raw : (size_t)R.part[0].L;
+    const bool gw = grad_flat != nullptr;
     ESCX_HIP(hipEventRecord(R.ev_fork, st));
     for (int p = 1; p < R.parts; ++p) {
-        if (!R.garena[p]) ESCX_HIP(hipMalloc((void**)&R.garena[p], h->wts.cap));
-        if (!R.gflat[p]) ESCX_HIP(hipMalloc((void**)&R.gflat[p], h->flat_total * sizeof(float)));
+        if (gw && !R.garena[p]) ESCX_HIP(hipMalloc((void**)&R.garena[p], h->wts.cap));
+        if (gw && !R.gflat[p]) ESCX_HIP(hipMalloc((void**)&R.gflat[p], h->flat_total * sizeof(float)));
         ESCX_HIP(hipStreamWaitEvent(R.aux[p], R.ev_fork, 0));
     }
     for (int p = 0; p < R.parts; ++p) {
@@ -1186,8 +1231,9 @@ extern "C" int escx_train_backward(escx_handle h, const float* d_wave, const flo
         std::swap(h->tape, R.arena[p]);
         if (p) std::swap(h->garena, R.garena[p]);
         R.cur = &R.part[p];
-        rc = train_backward_impl(h, d_wave ? d_wave + b0 * per_wave : nullptr, d_recon_feat ? d_recon_feat + b0 * per_recon : nullptr, d_cm ? d_cm + b0 : nullptr,
-                                 d_cb ? d_cb + b0 : nullptr, p ? R.gflat[p] : grad_flat, p ? R.aux[p] : st);
+        rc = train_backward_impl(h, d_wave ? d_wave + b0 * per_wave : nullptr, d_recon_feat ? d_recon_feat + b0 * per_recon : nullptr,
+                                 d_raw_feat ? d_raw_feat + b0 * per_raw : nullptr, d_cm ? d_cm + b0 : nullptr, d_cb ? d_cb + b0 : nullptr,
+                                 gw ? (p ? R.gflat[p] : grad_flat) : nullptr, d_input ? d_input + b0 * per_input : nullptr, p ? R.aux[p] : st);
         std::swap(h->tape, R.arena[p]);
         if (p) std::swap(h->garena, R.garena[p]);
         R.cur = &R.single;
@@ -1197,7 +1243,7 @@ extern "C" int escx_train_backward(escx_handle h, const float* d_wave, const flo
     for (int p = 1; p < R.parts; ++p) {
         ESCX_HIP(hipEventRecord(R.ev_join[p], R.aux[p]));
         ESCX_HIP(hipStreamWaitEvent(st, R.ev_join[p], 0));
-        if (rc) continue;
+        if (rc || !gw) continue;
         hipLaunchKernelGGL(add_inplace_kernel, dim3(blocks_for((long long)h->flat_total / 4 + 1)), dim3(256), 0, st, grad_flat, R.gflat[p], (long long)(h->flat_total / 4));
         if (h->flat_total % 4) hipLaunchKernelGGL(add_tail_kernel, dim3(1), dim3(4), 0, st, grad_flat, R.gflat[p], (long long)(h->flat_total / 4 * 4), (long long)h->flat_total);
     }
@@ -1205,19 +1251,40 @@ extern "C" int escx_train_backward(escx_handle h, const float* d_wave, const flo
     return launch_ok("train_backward");
 }
 
+extern "C" int escx_train_backward(escx_handle h, const float* d_wave, const float* d_recon_feat, const float* d_cm, const float* d_cb,
+                                   float* grad_flat, void* stream) {
+    int rc = check_ready(h); if (rc) return rc;
+    if (h->kind != 0) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "RVQCodecs training is not implemented (escx_create_rvq handles run encode / decode / eval forward only)");
+    if (!grad_flat) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null gradient buffer");
+    return train_backward_entry(h, d_wave, d_recon_feat, nullptr, d_cm, d_cb, grad_flat, nullptr, stream);
+}
+
+// The backward with the input side: d_raw_feat (B, T, in_dim, F) is the upstream gradient of the forward's raw spectrum output, d_input receives d loss / d input
+// ((B, L) after escx_train_forward, (B, T, in_dim, F) after escx_train_forward_feat).  Either of grad_flat / d_input may be NULL, not both.
+extern "C" int escx_train_backward_ex(escx_handle h, const float* d_wave, const float* d_recon_feat, const float* d_raw_feat, const float* d_cm, const float* d_cb,
+                                      float* grad_flat, float* d_input, void* stream) {
+    int rc = check_ready(h); if (rc) return rc;
+    if (h->kind != 0) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "RVQCodecs training is not implemented (escx_create_rvq handles run encode / decode / eval forward only)");
+    if (!grad_flat && !d_input) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "neither a gradient buffer nor an input-gradient buffer");
+    return train_backward_entry(h, d_wave, d_recon_feat, d_raw_feat, d_cm, d_cb, grad_flat, d_input, stream);
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // losses (generator_loss.py) with their gradients
 // ---------------------------------------------------------------------------------------------------------
-extern "C" int escx_stft_loss(const float* raw_feat, const float* recon_feat, int B, int64_t per_clip, float* loss, float* d_recon, void* stream) {
+extern "C" int escx_stft_loss_ex(const float* raw_feat, const float* recon_feat, int B, int64_t per_clip, float* loss, float* d_recon, float* d_raw, void* stream) {
     if (!raw_feat || !recon_feat || !loss || B < 1 || per_clip < 1) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "bad argument");
     hipStream_t st = (hipStream_t)stream;
     const long long per = (long long)per_clip;
     const int bpc = (int)std::min<long long>(64, (per + 255) / 256);
     float* part = stream_scratch(st, 0, (size_t)B * bpc);
     if (!part) ESCX_FAIL(ESCX_ERR_HIP, "scratch allocation failed");
-    hipLaunchKernelGGL(stft_loss_kernel, dim3(bpc, B), dim3(256), 0, st, raw_feat, recon_feat, part, d_recon, per, bpc, 1.0f / (float)per);
+    hipLaunchKernelGGL(stft_loss_kernel, dim3(bpc, B), dim3(256), 0, st, raw_feat, recon_feat, part, d_recon, per, bpc, 1.0f / (float)per, d_raw);
     hipLaunchKernelGGL(row_sum_kernel, dim3(blocks_for(B, 64)), dim3(64), 0, st, part, bpc, loss, B, 0, 1.0f);
     return launch_ok("stft_loss");
+}
+extern "C" int escx_stft_loss(const float* raw_feat, const float* recon_feat, int B, int64_t per_clip, float* loss, float* d_recon, void* stream) {
+    return escx_stft_loss_ex(raw_feat, recon_feat, B, per_clip, loss, d_recon, nullptr, stream);
 }
 
 namespace {
@@ -1274,7 +1341,8 @@ int build_mel(int dev, int sr, MelState** out) {
 
 // MelSpectrogramLoss (generator_loss.py:37-74): 7 resolutions, L1 on mel magnitudes + L1 on log10(mel^2); d_recon (B, L) optional.
 // STFTs are windowed-DFT GEMMs (FrameA loader with reflect padding), the mel projection another GEMM; nothing leaves the device.
-extern "C" int escx_mel_loss(const float* raw_wave, const float* recon_wave, int B, int L, int sample_rate, float* loss, float* d_recon, void* stream) {
+extern "C" int escx_mel_loss_ex(const float* raw_wave, const float* recon_wave, int B, int L, int sample_rate, float* loss, float* d_recon, float* d_raw,
+                                void* stream) {
     if (!raw_wave || !recon_wave || !loss || B < 1 || sample_rate < 2) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "bad argument");
     if (L <= 1024) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "n_samples=%d too short for the 2048-sample mel window (reflect padding)", L);
     int dev = 0;
@@ -1293,11 +1361,13 @@ extern "C" int escx_mel_loss(const float* raw_wave, const float* recon_wave, int
         fr_max = std::max(fr_max, rows * m.w);
     }
     const int bpc = 64;
-    const size_t total = 2 * spec_max + 3 * mag_max + 3 * mel_max + fr_max + (size_t)B * bpc + 1024;
+    const size_t base_total = 2 * spec_max + 3 * mag_max + 3 * mel_max + fr_max + (size_t)B * bpc + 1024;
+    const size_t total = base_total + (d_raw ? spec_max + mel_max : 0);          // the raw side: its own d spec and d mel (spx stays live for it)
     float* buf = stream_scratch(st, 1, total);
     if (!buf) ESCX_FAIL(ESCX_ERR_HIP, "scratch allocation of %zu floats failed", total);
     float* spx = buf; float* spy = spx + spec_max; float* mgx = spy + spec_max; float* mgy = mgx + mag_max; float* dmg = mgy + mag_max;
     float* mlx = dmg + mag_max; float* mly = mlx + mel_max; float* gml = mly + mel_max; float* dfr = gml + mel_max; float* part = dfr + fr_max;
+    float* dspx = buf + base_total; float* gmlx = dspx + spec_max;
     for (int i = 0; i < 7; ++i) {
         const MelScale& m = ms.sc[i];
         const int Tm = 1 + L / m.hop; const long long rows = (long long)B * Tm;
@@ -1309,8 +1379,14 @@ extern "C" int escx_mel_loss(const float* raw_wave, const float* recon_wave, int
             gemm_rows(mg, m.Fq, (int)rows, m.fb, m.Mp, m.Fq, EpiStore{ml, m.Mp, nullptr}, st);
         }
         hipLaunchKernelGGL(mel_l1_kernel, dim3(bpc, B), dim3(256), 0, st, mlx, mly, part, d_recon ? gml : nullptr, Tm, m.n_mels, m.Mp, bpc,
-                           1.0f / ((float)m.n_mels * Tm), 1e-5f);
+                           1.0f / ((float)m.n_mels * Tm), 1e-5f, d_raw ? gmlx : nullptr);
         hipLaunchKernelGGL(row_sum_kernel, dim3(blocks_for(B, 64)), dim3(64), 0, st, part, bpc, loss, B, i > 0, 1.0f);
+        if (d_raw) {                    // before the recon side, which reuses spx as its d spec
+            gemm_rows(gmlx, m.Mp, (int)rows, m.fbT, m.Fq, m.Mp, EpiStore{dmg, m.Fq, nullptr}, st);
+            hipLaunchKernelGGL(complex_mag_bwd_kernel, dim3(blocks_for(rows * m.Fq)), dim3(256), 0, st, spx, dmg, dspx, rows, m.F, m.Fq, m.Fq);
+            gemm_rows(dspx, 2 * m.Fq, (int)rows, m.DT, m.w, 2 * m.Fq, EpiStore{dfr, m.w, nullptr}, st);
+            hipLaunchKernelGGL(frames_bwd_kernel, dim3(blocks_for((long long)B * L)), dim3(256), 0, st, dfr, d_raw, B, L, Tm, m.hop, m.w, m.w, i > 0);
+        }
         if (d_recon) {
             gemm_rows(gml, m.Mp, (int)rows, m.fbT, m.Fq, m.Mp, EpiStore{dmg, m.Fq, nullptr}, st);
             hipLaunchKernelGGL(complex_mag_bwd_kernel, dim3(blocks_for(rows * m.Fq)), dim3(256), 0, st, spy, dmg, spx, rows, m.F, m.Fq, m.Fq);     // spx is free: reuse as d spec
@@ -1319,6 +1395,9 @@ extern "C" int escx_mel_loss(const float* raw_wave, const float* recon_wave, int
         }
     }
     return launch_ok("mel_loss");
+}
+extern "C" int escx_mel_loss(const float* raw_wave, const float* recon_wave, int B, int L, int sample_rate, float* loss, float* d_recon, void* stream) {
+    return escx_mel_loss_ex(raw_wave, recon_wave, B, L, sample_rate, loss, d_recon, nullptr, stream);
 }
 
 extern "C" int escx_scale_rows(const float* x, const float* g, float* out, int rows, int64_t per_row, void* stream) {

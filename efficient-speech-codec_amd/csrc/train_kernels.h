@@ -1409,7 +1409,8 @@ static __global__ void deembed_weff_slots_kernel(const float* __restrict__ w1, c
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float power_law(float x) { return (x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f)) * powf(fabsf(x) + 1e-10f, 0.3f); }
 static __global__ __launch_bounds__(256) void stft_loss_kernel(const float* __restrict__ raw, const float* __restrict__ rec, float* __restrict__ part,
-                                                        float* __restrict__ grad, long long per_clip, int blocks_per_clip, float inv_n) {
+                                                        float* __restrict__ grad, long long per_clip, int blocks_per_clip, float inv_n,
+                                                        float* __restrict__ grad_raw = nullptr) {
     const int b = blockIdx.y;
     __shared__ float red[256];
     float acc = 0.f;
@@ -1420,6 +1421,10 @@ static __global__ __launch_bounds__(256) void stft_loss_kernel(const float* __re
         if (grad) {
             const float dpl = (r != 0.f) ? 0.3f * powf(fabsf(r) + 1e-10f, -0.7f) : 0.f;       // sign(r)^2 = 1 away from 0; sign(0) = 0 kills the term
             grad[(size_t)b * per_clip + i] = -2.0f * df * dpl * inv_n;
+        }
+        if (grad_raw) {                                                                       // the same derivative on the raw side, opposite sign
+            const float dpa = (a != 0.f) ? 0.3f * powf(fabsf(a) + 1e-10f, -0.7f) : 0.f;
+            grad_raw[(size_t)b * per_clip + i] = 2.0f * df * dpa * inv_n;
         }
     }
     red[threadIdx.x] = acc;
@@ -1450,7 +1455,7 @@ static __global__ void complex_mag_kernel(const float* __restrict__ spec, float*
 // per-clip mel terms: |x - y| / n  +  |log10(clamp(x)^2) - log10(clamp(y)^2)| / n ; gradient w.r.t. y (the reconstruction's mel)
 static __global__ __launch_bounds__(256) void mel_l1_kernel(const float* __restrict__ xm, const float* __restrict__ ym, float* __restrict__ part,
                                                      float* __restrict__ gy, int rows_per_clip, int n_mels, int ldm, int blocks_per_clip, float inv_n,
-                                                     float clamp_eps) {
+                                                     float clamp_eps, float* __restrict__ gx = nullptr) {
     const int b = blockIdx.y;
     __shared__ float red[256];
     const long long per = (long long)rows_per_clip * ldm;
@@ -1458,7 +1463,7 @@ static __global__ __launch_bounds__(256) void mel_l1_kernel(const float* __restr
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < per; i += (long long)blocks_per_clip * 256) {
         const int c = (int)(i % ldm);
         const size_t o = (size_t)b * per + i;
-        float gv = 0.f;
+        float gv = 0.f, gxv = 0.f;
         if (c < n_mels) {
             const float x = xm[o], y = ym[o];
             const float xc = fmaxf(x, clamp_eps), yc = fmaxf(y, clamp_eps);
@@ -1467,8 +1472,10 @@ static __global__ __launch_bounds__(256) void mel_l1_kernel(const float* __restr
             const float s1 = (y > x) ? 1.f : (y < x ? -1.f : 0.f);
             const float s2 = (ly > lx) ? 1.f : (ly < lx ? -1.f : 0.f);
             gv = s1 * inv_n + ((y >= clamp_eps) ? s2 * inv_n * 0.86858896380650365530f / yc : 0.f);      // d log10(y^2)/dy = 2 / (y ln 10)
+            gxv = -s1 * inv_n - ((x >= clamp_eps) ? s2 * inv_n * 0.86858896380650365530f / xc : 0.f);    // the raw side: both signs flip
         }
         if (gy) gy[o] = gv;
+        if (gx) gx[o] = gxv;
     }
     red[threadIdx.x] = acc;
     __syncthreads();
@@ -1508,6 +1515,34 @@ static __global__ void frames_bwd_kernel(const float* __restrict__ dframes, floa
     if (j >= 1 && j <= pad) s += gather(pad - j);                              // left mirror: padded i < pad reads sample pad - i
     if (j <= L - 2) s += gather(pad + 2 * (L - 1) - j);                        // right mirror: padded i - pad >= L reads 2(L-1) - (i - pad); gather() is 0 past the last frame
     dwave[idx] = (accumulate ? dwave[idx] : 0.f) + s;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Input gradient of the patch embedding (scale.py:42-50: a convolution with stride = kernel = (pf, pt)).  Patches do not overlap, so each
+// spectrum value is read by at most one (token, tap) and its gradient is one dot product over the C0 channels, written once (gather form, no
+// atomics, fixed order): out[b][t][c][f] = sum_n dpre[(b, f / pf, t / pt)][n] * pe_w[n][(c, f % pf, t % pt)].  Frames past pt * W and rows past
+// pf * H get zero from this path; d_raw (B, T, in_dim, F, optional) is added on top.  Row stride of out: ldo (F = the caller's layout, Fp =
+// padded, pad columns zero).
+// ------------------------------------------------------------------------------------------------
+static __global__ void patch_dx_kernel(const float* __restrict__ dpre, const float* __restrict__ pe_w, const float* __restrict__ d_raw,
+                                       float* __restrict__ out, int B, int T, int in_dim, int F, int ldo, int H, int W, int pf, int pt, int C0, int C0p,
+                                       int Kpe) {
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (long long)B * T * in_dim * ldo) return;
+    const long long r = idx / ldo; const int f = (int)(idx - r * ldo);
+    const long long bt = r / in_dim; const int c = (int)(r - bt * in_dim);
+    const int b = (int)(bt / T), t = (int)(bt - (long long)b * T);
+    float s = 0.f;
+    if (f < F) {
+        const int ph = f / pf, pw = t / pt;
+        if (ph < H && pw < W) {
+            const int k = (c * pf + (f - ph * pf)) * pt + (t - pw * pt);
+            const float* g = dpre + ((size_t)((long long)b * H + ph) * W + pw) * C0p;
+            for (int n = 0; n < C0; ++n) s += g[n] * pe_w[(size_t)n * Kpe + k];
+        }
+        if (d_raw) s += d_raw[r * F + f];
+    }
+    out[idx] = s;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -615,7 +615,8 @@ class ESC(nn.Module):
 
     def _forward_train(self, x, x_feat, S, freeze):
         """Training-mode forward (codecs.py:30-46 with csrvq.py:97-129, codebook.py:57-75, quantization.py:53-64): differentiable w.r.t.
-        every parameter through `_TrainStep`; `codes` holds all max_streams streams (every quantiser runs in training mode)."""
+        every parameter and w.r.t. the input (x, or x_feat when given) through `_TrainStep`; `codes` holds all max_streams streams (every
+        quantiser runs in training mode).  raw_feat is differentiable exactly when the input requires grad, as spec_transform(x) is in the reference."""
         if x.dim() != 2:
             raise ValueError("x must have shape (Bs, L)")
         if x_feat is not None and (x_feat.dim() != 4 or x_feat.shape[1] != self.in_freq or x_feat.shape[3] != self.in_dim or x_feat.shape[0] != x.shape[0]):
@@ -624,7 +625,7 @@ class ESC(nn.Module):
         feat = None
         if x_feat is not None:          # codecs.py:33-34: the given spectrum replaces the STFT of x; layout (Bs, F, T, 2) as in eval mode (_forward_from_feat)
             self._need_gpu(x_feat, "x_feat")
-            feat = x_feat.detach().to(torch.float32).permute(0, 2, 3, 1).contiguous()      # frame-major (Bs, T, 2, F): the library's spectrum layout
+            feat = x_feat.to(torch.float32).permute(0, 2, 3, 1).contiguous()      # frame-major (Bs, T, 2, F): the library's spectrum layout (differentiable)
         params = tuple(self.parameters())
         recon, recon_fm, raw_fm, cm, cb, codes = _TrainStep.apply(self, x.to(torch.float32).contiguous(), feat, S, freeze, *params)
         return {"cm_loss": cm, "cb_loss": cb, "raw_audio": x, "recon_audio": recon,
@@ -642,7 +643,9 @@ class ESC(nn.Module):
 
 class _TrainStep(torch.autograd.Function):
     """One training-mode pass through libescx: forward keeps its activations on the handle's tape, backward consumes them and returns
-    d loss / d parameter for every nn.Parameter (views of one flat gradient buffer, the library's canonical order)."""
+    d loss / d parameter for every nn.Parameter (views of one flat gradient buffer, the library's canonical order) and, when the input requires
+    grad, d loss / d input (x, or the spectrum `feat` when given; the gradient of raw_feat is folded in).  With no parameter requiring grad the
+    library is asked for the input gradient only (grad_flat = NULL): no p.grad is written and the flat-gradient buffers stay untouched."""
 
     @staticmethod
     def forward(ctx, model, x, feat, S, freeze, *params):
@@ -678,16 +681,28 @@ class _TrainStep(torch.autograd.Function):
                                                      model._stream(dev)))
         ctx.model, ctx.dev, ctx.idx = model, dev, idx
         ctx.tape_generation = int(lib.escx_train_tape_generation(hd))
-        ctx.mark_non_differentiable(raw_fm, codes)
+        ctx.from_feat = feat is not None
+        ctx.in_shape = tuple(feat.shape) if feat is not None else (B, L)
+        ctx.input_grad = bool(ctx.needs_input_grad[2] if feat is not None else ctx.needs_input_grad[1])
+        if ctx.input_grad:              # raw_feat = spec_transform(x) (or x_feat itself) is differentiable in the reference
+            ctx.mark_non_differentiable(codes)
+        else:
+            ctx.mark_non_differentiable(raw_fm, codes)
         return recon, recon_fm, raw_fm, cm, cb, codes
 
     @staticmethod
-    def backward(ctx, d_recon, d_recon_fm, _d_raw, d_cm, d_cb, _d_codes):
+    def backward(ctx, d_recon, d_recon_fm, d_raw, d_cm, d_cb, _d_codes):
         model, dev = ctx.model, ctx.dev
+        n_params = len(ctx.needs_input_grad) - 5
+        want_params = any(ctx.needs_input_grad[5:])
+        if not want_params and not ctx.input_grad:
+            return (None,) * (5 + n_params)
         lib, hd = model._handle(dev, for_training=True)
         if int(lib.escx_train_tape_generation(hd)) != ctx.tape_generation:
             raise RuntimeError("esc.ESC backward: the model ran another training forward after the one this graph belongs to; the library keeps ONE "
                                "activation tape per model (backward before the next forward, or use a second model instance)")
+        if ctx.input_grad:
+            return _TrainStep._backward_with_input(ctx, lib, hd, want_params, d_recon, d_recon_fm, d_raw, d_cm, d_cb)
         st = model._flat[ctx.idx]
         flat_mode = model._flat_grad_mode and "gflat" in st
         gflat = st["gflat"] if (flat_mode and st["gfresh"]) else torch.empty_like(st["flat"])
@@ -708,6 +723,37 @@ class _TrainStep(torch.autograd.Function):
         by_id = {id(params[k]): gflat[off:off + n].view(params[k].shape) for k, off, n in st["layout"]}
         grads = tuple(by_id.get(id(q)) for q in model.parameters())
         return (None, None, None, None, None) + grads
+
+    @staticmethod
+    def _backward_with_input(ctx, lib, hd, want_params, d_recon, d_recon_fm, d_raw, d_cm, d_cb):
+        """escx_train_backward_ex: the input gradient, with the parameter gradients of `backward` when any parameter requires grad."""
+        model, dev = ctx.model, ctx.dev
+        n_params = len(ctx.needs_input_grad) - 5
+        st = model._flat[ctx.idx]
+        flat_mode = model._flat_grad_mode and "gflat" in st
+        gflat = None
+        if want_params:
+            gflat = st["gflat"] if (flat_mode and st["gfresh"]) else torch.empty_like(st["flat"])
+
+        def prep(t):
+            return None if t is None else t.to(torch.float32).contiguous()
+        d_recon, d_recon_fm, d_raw, d_cm, d_cb = prep(d_recon), prep(d_recon_fm), prep(d_raw), prep(d_cm), prep(d_cb)
+        d_in = torch.empty(ctx.in_shape, dtype=torch.float32, device=dev)
+        p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        with torch.cuda.device(dev):
+            _native.check(lib.escx_train_backward_ex(hd, p(d_recon), p(d_recon_fm), p(d_raw), p(d_cm), p(d_cb), p(gflat), p(d_in), model._stream(dev)))
+        head = (None, None, d_in, None, None) if ctx.from_feat else (None, d_in, None, None, None)
+        if not want_params:
+            return head + (None,) * n_params
+        params = model._named_params()
+        if flat_mode:
+            if st["gfresh"]:
+                st["gfresh"] = False
+            else:
+                st["gflat"].add_(gflat)
+            return head + (None,) * n_params
+        by_id = {id(params[k]): gflat[off:off + n].view(params[k].shape) for k, off, n in st["layout"]}
+        return head + tuple(by_id.get(id(q)) for q in model.parameters())
 
 
 class RVQCodecs(ESC):

@@ -2,7 +2,8 @@
 
 Same classes, constructor arguments and call signatures; the arithmetic (power-law compression, the seven STFTs of the mel loss as
 windowed-DFT GEMMs, HTK filterbanks, L1 / log-L1 terms AND their gradients) runs in libescx.so.  Each forward evaluates the per-clip
-loss together with d loss_b / d reconstruction; backward only scales that by the incoming per-clip gradient.
+loss together with d loss_b / d reconstruction (and d loss_b / d raw input when the raw side requires grad, as autograd gives it in the
+reference); backward only scales that by the incoming per-clip gradient.
 """
 from __future__ import annotations
 
@@ -51,14 +52,20 @@ class _StftLossFn(torch.autograd.Function):
         loss = torch.empty(B, dtype=torch.float32, device=rec_c.device)
         need = ctx.needs_input_grad[1]
         unit = torch.empty_like(rec_c) if need else None
+        unit_raw = torch.empty_like(raw_c) if ctx.needs_input_grad[0] else None
         with torch.cuda.device(rec_c.device):
-            _native.check(lib.escx_stft_loss(_ptr(raw_c), _ptr(rec_c), B, rec_c.numel() // B, _ptr(loss), _ptr(unit), _stream(rec_c.device)))
-        ctx.unit = unit
+            if unit_raw is None:
+                _native.check(lib.escx_stft_loss(_ptr(raw_c), _ptr(rec_c), B, rec_c.numel() // B, _ptr(loss), _ptr(unit), _stream(rec_c.device)))
+            else:
+                _native.check(lib.escx_stft_loss_ex(_ptr(raw_c), _ptr(rec_c), B, rec_c.numel() // B, _ptr(loss), _ptr(unit), _ptr(unit_raw),
+                                                    _stream(rec_c.device)))
+        ctx.unit, ctx.unit_raw = unit, unit_raw
         return loss
 
     @staticmethod
     def backward(ctx, g):
-        return None, (_scale_rows(ctx.unit, g) if ctx.unit is not None else None)
+        return ((_scale_rows(ctx.unit_raw, g) if ctx.unit_raw is not None else None),
+                (_scale_rows(ctx.unit, g) if ctx.unit is not None else None))
 
 
 class ComplexSTFTLoss(nn.Module):
@@ -87,14 +94,19 @@ class _MelLossFn(torch.autograd.Function):
         loss = torch.empty(B, dtype=torch.float32, device=rec_c.device)
         need = ctx.needs_input_grad[1]
         unit = torch.empty_like(rec_c) if need else None
+        unit_raw = torch.empty_like(raw_c) if ctx.needs_input_grad[0] else None
         with torch.cuda.device(rec_c.device):
-            _native.check(lib.escx_mel_loss(_ptr(raw_c), _ptr(rec_c), B, L, int(sr), _ptr(loss), _ptr(unit), _stream(rec_c.device)))
-        ctx.unit = unit
+            if unit_raw is None:
+                _native.check(lib.escx_mel_loss(_ptr(raw_c), _ptr(rec_c), B, L, int(sr), _ptr(loss), _ptr(unit), _stream(rec_c.device)))
+            else:
+                _native.check(lib.escx_mel_loss_ex(_ptr(raw_c), _ptr(rec_c), B, L, int(sr), _ptr(loss), _ptr(unit), _ptr(unit_raw), _stream(rec_c.device)))
+        ctx.unit, ctx.unit_raw = unit, unit_raw
         return loss
 
     @staticmethod
     def backward(ctx, g):
-        return None, (_scale_rows(ctx.unit, g) if ctx.unit is not None else None), None
+        return ((_scale_rows(ctx.unit_raw, g) if ctx.unit_raw is not None else None),
+                (_scale_rows(ctx.unit, g) if ctx.unit is not None else None), None)
 
 
 class MelSpectrogramLoss(nn.Module):

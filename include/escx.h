@@ -258,6 +258,13 @@ int escx_train_forward_feat(escx_handle h, const float* flat_params_dev, const f
  * d_cm_loss / d_cb_loss (B,).  grad_flat_dev receives d loss / d parameter in the flat layout (overwritten, not accumulated). */
 int escx_train_backward(escx_handle h, const float* d_wave_dev, const float* d_recon_feat_dev, const float* d_cm_loss_dev,
                         const float* d_cb_loss_dev, float* grad_flat_dev, void* stream);
+/* escx_train_backward with the input side (the reference's autograd through spec_transform and the straight-through estimator).
+ * d_raw_feat_dev (B,T,2,F), optional: upstream gradient of the forward's raw spectrum output.  d_input_dev, optional: receives d loss / d input,
+ * (B, n_samples) after escx_train_forward (patch-embedding dX + d_raw_feat, then the STFT adjoint), (B,T,2,F) after escx_train_forward_feat.
+ * grad_flat_dev may be NULL: no parameter gradient, and no launch whose only product is one (a frozen codec in a larger graph).
+ * ESCX_ERR_INVALID_ARG when both outputs are NULL; ESCX_ERR_UNSUPPORTED on an RVQCodecs handle. */
+int escx_train_backward_ex(escx_handle h, const float* d_wave_dev, const float* d_recon_feat_dev, const float* d_raw_feat_dev,
+                           const float* d_cm_loss_dev, const float* d_cb_loss_dev, float* grad_flat_dev, float* d_input_dev, void* stream);
 int64_t escx_train_tape_bytes(escx_handle h);
 /* Number of escx_train_forward calls on this handle so far.  The handle holds ONE tape: escx_train_backward consumes the activations of the
  * LAST forward.  A caller that interleaves several forwards (autograd graphs alive at the same time) records this value after its forward
@@ -267,11 +274,17 @@ int64_t escx_train_tape_generation(escx_handle h);
  * same for both inputs) of (pl(raw) - pl(recon))^2, pl = power-law compression; optionally d loss_b / d recon_feat. */
 int escx_stft_loss(const float* raw_feat_dev, const float* recon_feat_dev, int batch, int64_t per_clip, float* loss_dev,
                    float* d_recon_feat_dev, void* stream);
+/* The same with d loss_b / d raw_feat as well (d_raw_feat_dev optional; the recon side is computed exactly as escx_stft_loss does). */
+int escx_stft_loss_ex(const float* raw_feat_dev, const float* recon_feat_dev, int batch, int64_t per_clip, float* loss_dev,
+                      float* d_recon_feat_dev, float* d_raw_feat_dev, void* stream);
 /* MelSpectrogramLoss (generator_loss.py:37-74; 7 resolutions, windows 32..2048, hop = window/4, HTK mel filterbanks of 5..320 bins,
  * L1 on the mel magnitudes + L1 on log10(clamp(mel)^2)): per-clip loss (B,) and, optionally, d loss_b / d recon_wave (B,L).
  * Runs on the current device; the DFT / filterbank matrices are built once per device. */
 int escx_mel_loss(const float* raw_wave_dev, const float* recon_wave_dev, int batch, int n_samples, int sample_rate, float* loss_dev,
                   float* d_recon_wave_dev, void* stream);
+/* The same with d loss_b / d raw_wave (B,L) as well (d_raw_wave_dev optional; the recon side is computed exactly as escx_mel_loss does). */
+int escx_mel_loss_ex(const float* raw_wave_dev, const float* recon_wave_dev, int batch, int n_samples, int sample_rate, float* loss_dev,
+                     float* d_recon_wave_dev, float* d_raw_wave_dev, void* stream);
 int escx_scale_rows(const float* x_dev, const float* g_dev, float* out_dev, int rows, int64_t per_row, void* stream);   /* out[r][:] = x[r][:] * g[r] */
 /* clip_grad_norm_ + AdamW on flat buffers (trainer_no_adv.py:116-117).  norm_out_dev: 2 + 1024 floats ([0] = norm, [1] = clip coefficient). */
 int escx_grad_norm_clip(const float* grad_flat_dev, int64_t n, float max_norm, float* norm_out_dev, void* stream);
