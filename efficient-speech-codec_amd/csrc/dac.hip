@@ -1,0 +1,425 @@
+// DAC baseline codec (Descript audio codec; reference baselines/descript/dac/model/dac.py:148-247, nn/quantize.py) on MI355X, inference only.
+//
+// One handle = one DAC configuration.  Parameters live in a flat fp32 device buffer owned by the caller, in the reference's named_parameters()
+// order (per layer: bias, weight_g, weight_v; Snake: alpha; codebook: weight); the weight-normalised, packed GEMM operands, the Snake reciprocals
+// and the quantiser tables are re-derived on the device whenever (buffer, version) changes.  Activations are channels-last (B, T, Cp) maps in a
+// handle-owned scratch; see dac_kernels.h for the loaders and epilogues.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <string>
+#include <vector>
+
+#include "escx_internal.h"
+#include "dac_kernels.h"
+
+using namespace escx;
+
+namespace {
+
+inline unsigned nblk(long long n, int per = 256) { return (unsigned)((n + per - 1) / per); }
+size_t pad64(size_t n) { return (n + 63) / 64 * 64; }
+inline int cpad(int C) { return rup(C, 4); }
+
+struct DacLayer {
+    int kind = 0;                   // 0: Conv1d, 1: ConvTranspose1d
+    int Cin = 0, Cout = 0, K = 0, stride = 1, pad = 0, dil = 1;
+    int CinP = 0, Np = 0, Kp = 0;   // operand geometry (Conv1d: Np = rup(Cout, 16), Kp = rup(K * CinP, 16); ConvT: per phase, Kp = rup(2 CinP, 16))
+    size_t off_b = 0, off_g = 0, off_v = 0;
+    float* W = nullptr; float* bias = nullptr;
+};
+struct DacSnake { int C = 0; size_t off = 0; float* a = nullptr; float* inv = nullptr; };
+
+}  // namespace
+
+struct escx_dac_s {
+    int device = 0;
+    escx_dac_config cfg{};
+    int latent = 0, hop = 1;
+    std::vector<std::string> keys; std::vector<size_t> offs, numels;
+    size_t total = 0;
+    // encoder: conv0, per block (3 x (snake, conv7, snake, conv1), snake, strided conv), snake, conv3; decoder: conv0, per block (snake, convT,
+    // 3 x residual unit), snake, conv7 -> tanh.  Layers and Snakes are stored in that execution order.
+    std::vector<DacLayer> enc, dec; std::vector<DacSnake> enc_sn, dec_sn;
+    std::vector<long long> qoffs;          // 6 per stage + 1 codebook per stage
+    long long* qoffs_dev = nullptr;
+    DacQTables qt{};
+    float* wbuf = nullptr; size_t wfloats = 0;
+    float* scratch = nullptr; size_t scratch_bytes = 0;
+    const float* packed_ptr = nullptr; long long packed_version = -1;
+    int snake_maps = ESCX_DAC_SNAKE_MAPS_DEFAULT;   // escx_dac_set_snake_maps: layer classes whose Snake is written to a map first
+};
+
+namespace {
+
+DacLayer make_layer(int kind, int Cin, int Cout, int K, int stride, int pad, int dil) {
+    DacLayer l; l.kind = kind; l.Cin = Cin; l.Cout = Cout; l.K = K; l.stride = stride; l.pad = pad; l.dil = dil;
+    l.CinP = cpad(Cin); l.Np = rup(Cout, 16);
+    l.Kp = kind == 0 ? rup(K * l.CinP, 16) : rup(2 * l.CinP, 16);
+    return l;
+}
+size_t layer_floats(const DacLayer& l) { return pad64((size_t)(l.kind ? l.stride : 1) * l.Np * l.Kp) + pad64(l.Np); }
+
+void add_key(escx_dac_s* d, const std::string& k, size_t n, size_t* off) {
+    d->keys.push_back(k); d->offs.push_back(*off); d->numels.push_back(n); *off += n;
+}
+void add_conv(escx_dac_s* d, std::vector<DacLayer>& v, const std::string& p, DacLayer l, size_t* off) {
+    const size_t nv = (size_t)l.Cout * l.Cin * l.K;
+    l.off_b = *off; add_key(d, p + "bias", l.Cout, off);
+    l.off_g = *off; add_key(d, p + "weight_g", l.kind ? l.Cin : l.Cout, off);
+    l.off_v = *off; add_key(d, p + "weight_v", nv, off);
+    v.push_back(l);
+}
+void add_snake(escx_dac_s* d, std::vector<DacSnake>& v, const std::string& p, int C, size_t* off) {
+    DacSnake s; s.C = C; s.off = *off; add_key(d, p + "alpha", C, off); v.push_back(s);
+}
+void add_res(escx_dac_s* d, std::vector<DacLayer>& L, std::vector<DacSnake>& S, const std::string& p, int C, int dil, size_t* off) {
+    add_snake(d, S, p + "block.0.", C, off);
+    add_conv(d, L, p + "block.1.", make_layer(0, C, C, 7, 1, 3 * dil, dil), off);
+    add_snake(d, S, p + "block.2.", C, off);
+    add_conv(d, L, p + "block.3.", make_layer(0, C, C, 1, 1, 0, 1), off);
+}
+
+// torch's length formulas.  Conv1d floors (T + 2p - dil (K - 1) - 1) / s; a negative numerator means no output frame (0 here, where the
+// reference's layer gives an empty or invalid tensor) - C++ division would truncate it toward zero and report one frame.
+int conv_out_len(int T, const DacLayer& l) {
+    if (l.kind == 0) {
+        const int num = T + 2 * l.pad - l.dil * (l.K - 1) - 1;
+        return num < 0 ? 0 : num / l.stride + 1;
+    }
+    return (T - 1) * l.stride - 2 * l.pad + l.K;
+}
+
+int pack(escx_dac_s* d, const float* flat, long long version, hipStream_t st) {
+    if (version >= 0 && version == d->packed_version && flat == d->packed_ptr) return 0;
+    d->packed_version = version; d->packed_ptr = flat;
+    for (auto* L : {&d->enc, &d->dec})
+        for (DacLayer& l : *L) {
+            if (l.kind == 0)
+                hipLaunchKernelGGL(dac_wn_conv_kernel, dim3(l.Cout), dim3(256), 0, st, flat + l.off_v, flat + l.off_g, flat + l.off_b, l.W, l.bias, l.Cin, l.K, l.CinP, l.Kp);
+            else {
+                hipLaunchKernelGGL(dac_wn_convt_kernel, dim3(l.Cin), dim3(256), 0, st, flat + l.off_v, flat + l.off_g, l.W, l.Cout, l.stride, l.pad, l.CinP, l.Np, l.Kp);
+                ESCX_HIP(hipMemcpyAsync(l.bias, flat + l.off_b, l.Cout * sizeof(float), hipMemcpyDeviceToDevice, st));
+            }
+        }
+    for (auto* S : {&d->enc_sn, &d->dec_sn})
+        for (DacSnake& s : *S) hipLaunchKernelGGL(dac_snake_pack_kernel, dim3(nblk(s.C)), dim3(256), 0, st, flat + s.off, s.a, s.inv, s.C);
+    const int S = d->cfg.n_codebooks, D = d->latent, dd = d->cfg.codebook_dim, K = d->cfg.codebook_size;
+    hipLaunchKernelGGL(dac_wn_inproj_kernel, dim3(S * dd), dim3(256), 0, st, flat, (const long long*)d->qoffs_dev, d->qt, D, dd);
+    hipLaunchKernelGGL(dac_qtables_kernel, dim3(nblk((long long)S * (D + K))), dim3(256), 0, st, flat, (const long long*)d->qoffs_dev, d->qt, S, D, dd, K);
+    return launch_ok("dac_pack");
+}
+
+int ensure_scratch(escx_dac_s* d, size_t bytes) {
+    if (d->scratch_bytes >= bytes) return 0;
+    ESCX_HIP(hipDeviceSynchronize());
+    if (d->scratch) ESCX_HIP(hipFree(d->scratch));
+    d->scratch = nullptr; d->scratch_bytes = 0;
+    ESCX_HIP(hipMalloc((void**)&d->scratch, bytes));
+    d->scratch_bytes = bytes;
+    return 0;
+}
+
+// What one pass needs besides the layer: the handle's Snake placement, a map-sized buffer for a Snaked copy, the stream.
+struct Run { int snake_maps; float* tmp; hipStream_t st; };
+
+// out = conv(snake?(x)) over (B, Tin, CinP) -> (B, Tout, cpad(Cout)) [+ res]; ConvT: one GEMM per output phase.  Snake is applied while the
+// operand is staged, or - for the layer classes set in snake_maps - once per element into r.tmp, which the GEMM then reads plain (bitwise the
+// same operand either way).
+void run_layer(const Run& run, int cls, const DacLayer& l, const DacSnake* sn, const float* x, int B, int Tin, float* out, int Tout, const float* res,
+               int tanh_out) {
+    const hipStream_t st = run.st;
+    if (sn && ((run.snake_maps >> cls) & 1)) {
+        const long long n4 = (long long)B * Tin * l.CinP / 4;
+        hipLaunchKernelGGL(dac_snake_map_kernel, dim3(nblk(n4)), dim3(256), 0, st, x, sn->a, sn->inv, run.tmp, n4, l.CinP / 4);
+        x = run.tmp; sn = nullptr;
+    }
+    const int phases = l.kind ? l.stride : 1;
+    for (int r = 0; r < phases; ++r) {
+        DacConvA ld{};
+        ld.x = x; ld.alpha = sn ? sn->a : nullptr; ld.inv = sn ? sn->inv : nullptr; ld.Tin = Tin; ld.Cp = l.CinP; ld.dCp = FastDiv(l.CinP);
+        DacEpi ep{};
+        ep.out = out; ep.res = res; ep.Cp = tanh_out ? 4 : cpad(l.Cout); ep.Tmap = Tout; ep.tanh_out = tanh_out;
+        if (l.kind == 0) {
+            ld.Trows = Tout; ld.rs = l.stride; ld.r0 = -l.pad; ld.td = l.dil; ld.ntaps = l.K;
+            ep.os = 1; ep.o0 = 0; ep.Trows = Tout; ep.bias = l.bias;
+            ld.M = B * Tout; ld.dT = FastDiv(Tout); ep.dT = ld.dT;
+            const long long tiles = (long long)((ld.M + 127) / 128) * ((l.Np + 95) / 96);
+            if (tiles >= 512) launch_gemm<128>(ld, l.W, ld.M, l.Np, l.Kp, ep, st);
+            else launch_gemm<64>(ld, l.W, ld.M, l.Np, l.Kp, ep, st);
+        } else {
+            const int s = l.stride, Q = r < Tout ? (Tout - r + s - 1) / s : 0;
+            if (Q == 0) continue;
+            ld.Trows = Q; ld.rs = 1; ld.r0 = (r + l.pad) / s; ld.td = -1; ld.ntaps = 2;
+            ep.os = s; ep.o0 = r; ep.Trows = Q; ep.bias = l.bias;
+            ld.M = B * Q; ld.dT = FastDiv(Q); ep.dT = ld.dT;
+            const float* W = l.W + (size_t)r * l.Np * l.Kp;
+            const long long tiles = (long long)((ld.M + 127) / 128) * ((l.Np + 95) / 96);
+            if (tiles >= 512) launch_gemm<128>(ld, W, ld.M, l.Np, l.Kp, ep, st);
+            else launch_gemm<64>(ld, W, ld.M, l.Np, l.Kp, ep, st);
+        }
+    }
+}
+
+// ResidualUnit in place on x: h = conv7_dil(snake(x)); x = x + conv1(snake(h))   (dac.py:24-41; the length is kept, so the crop never triggers)
+void run_res(const Run& run, const DacLayer* L, const DacSnake* S, float* x, float* h, int B, int T) {
+    run_layer(run, ESCX_DAC_SNAKE_RES7, L[0], &S[0], x, B, T, h, T, nullptr, 0);
+    run_layer(run, ESCX_DAC_SNAKE_RES1, L[1], &S[1], h, B, T, x, T, x, 0);
+}
+
+size_t map_floats(int B, int T, int C) { return pad64((size_t)B * T * cpad(C)); }
+
+// largest map of the encoder / decoder pass, for three maps (x, y, h)
+size_t enc_scratch(escx_dac_s* d, int B, int L, int* Tz) {
+    size_t mx = map_floats(B, L, 1);
+    int T = L, C = d->cfg.encoder_dim;
+    mx = std::max(mx, map_floats(B, T, C));
+    for (int i = 0; i < d->cfg.n_encoder_rates; ++i) { T = conv_out_len(T, d->enc[1 + i * 7 + 6]); C *= 2; mx = std::max(mx, map_floats(B, T, C)); }
+    *Tz = T;
+    return std::max(mx, map_floats(B, T, d->latent));
+}
+size_t dec_scratch(escx_dac_s* d, int B, int T, int* Lout) {
+    size_t mx = map_floats(B, T, d->latent);
+    int C = d->cfg.decoder_dim;
+    mx = std::max(mx, map_floats(B, T, C));
+    for (int i = 0; i < d->cfg.n_decoder_rates; ++i) { T = conv_out_len(T, d->dec[1 + i * 7]); C /= 2; mx = std::max(mx, map_floats(B, T, C)); }
+    *Lout = T;
+    return mx;
+}
+
+int check_args(escx_dac_s* d, const float* flat, int B) {
+    if (!d || !flat || B < 1) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "bad argument");
+    ESCX_HIP(hipSetDevice(d->device));
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int escx_dac_create(const escx_dac_config* cfg, int device, escx_dac* out) {
+    if (!cfg || !out) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null argument");
+    const escx_dac_config& c = *cfg;
+    if (c.encoder_dim < 1 || c.decoder_dim < 1 || c.n_codebooks < 1 || c.codebook_size < 1 || c.codebook_dim < 1 || c.n_encoder_rates < 1 || c.n_decoder_rates < 1 ||
+        c.n_encoder_rates > ESCX_DAC_MAX_RATES || c.n_decoder_rates > ESCX_DAC_MAX_RATES || c.latent_dim < 0)
+        ESCX_FAIL(ESCX_ERR_INVALID_ARG, "bad DAC configuration");
+    const int latent = c.latent_dim ? c.latent_dim : c.encoder_dim << c.n_encoder_rates;
+    for (int i = 0; i < c.n_encoder_rates; ++i) if (c.encoder_rates[i] < 1 || c.encoder_rates[i] > 16) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "encoder rate %d outside [1, 16]", c.encoder_rates[i]);
+    for (int i = 0; i < c.n_decoder_rates; ++i) if (c.decoder_rates[i] < 1 || c.decoder_rates[i] > 16) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "decoder rate %d outside [1, 16]", c.decoder_rates[i]);
+    if (c.decoder_dim % (1 << c.n_decoder_rates)) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "decoder_dim %d is not divisible by 2^%d", c.decoder_dim, c.n_decoder_rates);
+    if (latent > 1024 || latent % 4) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "latent_dim %d: the fused quantiser covers multiples of 4 up to 1024", latent);
+    if (c.codebook_dim > DAC_DMAX) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "codebook_dim %d above %d", c.codebook_dim, DAC_DMAX);
+    if (c.codebook_size > 65536) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "codebook_size %d above 65536", c.codebook_size);
+    if ((long long)c.decoder_dim * 7 > (1 << 20) || (long long)(c.encoder_dim << c.n_encoder_rates) * 7 > (1 << 20)) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "channel count too large");
+    escx_dac_s* d = new escx_dac_s();
+    d->device = device; d->cfg = c; d->latent = latent;
+    d->hop = 1; for (int i = 0; i < c.n_encoder_rates; ++i) d->hop *= c.encoder_rates[i];
+    size_t off = 0;
+    // encoder (dac.py:64-91)
+    int C = c.encoder_dim;
+    add_conv(d, d->enc, "encoder.block.0.", make_layer(0, 1, C, 7, 1, 3, 1), &off);
+    for (int i = 0; i < c.n_encoder_rates; ++i) {
+        const int s = c.encoder_rates[i];
+        const std::string p = "encoder.block." + std::to_string(i + 1) + ".block.";
+        const int dl[3] = {1, 3, 9};
+        for (int j = 0; j < 3; ++j) add_res(d, d->enc, d->enc_sn, p + std::to_string(j) + ".", C, dl[j], &off);
+        add_snake(d, d->enc_sn, p + "3.", C, &off);
+        add_conv(d, d->enc, p + "4.", make_layer(0, C, 2 * C, 2 * s, s, (s + 1) / 2, 1), &off);
+        C *= 2;
+    }
+    const int nE = c.n_encoder_rates;
+    add_snake(d, d->enc_sn, "encoder.block." + std::to_string(nE + 1) + ".", C, &off);
+    add_conv(d, d->enc, "encoder.block." + std::to_string(nE + 2) + ".", make_layer(0, C, latent, 3, 1, 1, 1), &off);
+    // quantiser (quantize.py:17-33, 127-150)
+    const int S = c.n_codebooks, dd = c.codebook_dim, K = c.codebook_size;
+    for (int i = 0; i < S; ++i) {
+        const std::string p = "quantizer.quantizers." + std::to_string(i) + ".";
+        long long o[7];
+        o[0] = (long long)off; add_key(d, p + "in_proj.bias", dd, &off);
+        o[1] = (long long)off; add_key(d, p + "in_proj.weight_g", dd, &off);
+        o[2] = (long long)off; add_key(d, p + "in_proj.weight_v", (size_t)dd * latent, &off);
+        o[3] = (long long)off; add_key(d, p + "out_proj.bias", latent, &off);
+        o[4] = (long long)off; add_key(d, p + "out_proj.weight_g", latent, &off);
+        o[5] = (long long)off; add_key(d, p + "out_proj.weight_v", (size_t)latent * dd, &off);
+        o[6] = (long long)off; add_key(d, p + "codebook.weight", (size_t)K * dd, &off);
+        for (int k = 0; k < 6; ++k) d->qoffs.push_back(o[k]);
+        d->qoffs.push_back(o[6]);            // re-ordered below: 6 per stage, then the codebooks
+    }
+    {
+        std::vector<long long> q; for (int i = 0; i < S; ++i) for (int k = 0; k < 6; ++k) q.push_back(d->qoffs[7 * i + k]);
+        for (int i = 0; i < S; ++i) q.push_back(d->qoffs[7 * i + 6]);
+        d->qoffs = q;
+    }
+    // decoder (dac.py:113-145)
+    C = c.decoder_dim;
+    add_conv(d, d->dec, "decoder.model.0.", make_layer(0, latent, C, 7, 1, 3, 1), &off);
+    for (int i = 0; i < c.n_decoder_rates; ++i) {
+        const int s = c.decoder_rates[i];
+        const std::string p = "decoder.model." + std::to_string(i + 1) + ".block.";
+        add_snake(d, d->dec_sn, p + "0.", C, &off);
+        add_conv(d, d->dec, p + "1.", make_layer(1, C, C / 2, 2 * s, s, (s + 1) / 2, 1), &off);
+        const int dl[3] = {1, 3, 9};
+        for (int j = 0; j < 3; ++j) add_res(d, d->dec, d->dec_sn, p + std::to_string(j + 2) + ".", C / 2, dl[j], &off);
+        C /= 2;
+    }
+    const int nD = c.n_decoder_rates;
+    add_snake(d, d->dec_sn, "decoder.model." + std::to_string(nD + 1) + ".", C, &off);
+    add_conv(d, d->dec, "decoder.model." + std::to_string(nD + 2) + ".", make_layer(0, C, 1, 7, 1, 3, 1), &off);
+    d->total = off;
+    // packed operands
+    size_t wf = 0;
+    for (auto* L : {&d->enc, &d->dec}) for (DacLayer& l : *L) wf += layer_floats(l);
+    for (auto* Sn : {&d->enc_sn, &d->dec_sn}) for (DacSnake& s : *Sn) wf += 2 * pad64(cpad(s.C));
+    const size_t qD = (size_t)S * dd * latent, qK = (size_t)S * K;
+    wf += 2 * pad64(qD) + pad64((size_t)S * dd) + pad64((size_t)S * latent) + 2 * pad64(qK * dd) + pad64(qK);
+    hipError_t e = hipSetDevice(device);
+    if (e != hipSuccess) { delete d; ESCX_FAIL(ESCX_ERR_HIP, "hipSetDevice failed"); }
+    if (hipMalloc((void**)&d->wbuf, wf * sizeof(float)) != hipSuccess || hipMalloc((void**)&d->qoffs_dev, d->qoffs.size() * sizeof(long long)) != hipSuccess) {
+        escx_dac_destroy(d); ESCX_FAIL(ESCX_ERR_HIP, "hipMalloc of the DAC weights failed");
+    }
+    (void)hipMemset(d->wbuf, 0, wf * sizeof(float));
+    (void)hipMemcpy(d->qoffs_dev, d->qoffs.data(), d->qoffs.size() * sizeof(long long), hipMemcpyHostToDevice);
+    d->wfloats = wf;
+    size_t cur = 0;
+    auto take = [&](size_t n) { float* p = d->wbuf + cur; cur += pad64(n); return p; };
+    for (auto* L : {&d->enc, &d->dec})
+        for (DacLayer& l : *L) { l.W = take((size_t)(l.kind ? l.stride : 1) * l.Np * l.Kp); l.bias = take(l.Np); }
+    for (auto* Sn : {&d->enc_sn, &d->dec_sn}) for (DacSnake& s : *Sn) { s.a = take(cpad(s.C)); s.inv = take(cpad(s.C)); }
+    d->qt.win = take(qD); d->qt.bin = take((size_t)S * dd); d->qt.wout = take(qD); d->qt.bout = take((size_t)S * latent);
+    d->qt.cbraw = take(qK * dd); d->qt.cbn = take(qK * dd); d->qt.c2 = take(qK);
+    *out = d;
+    return ESCX_OK;
+}
+
+extern "C" void escx_dac_destroy(escx_dac d) {
+    if (!d) return;
+    (void)hipSetDevice(d->device);
+    if (d->wbuf) (void)hipFree(d->wbuf);
+    if (d->qoffs_dev) (void)hipFree(d->qoffs_dev);
+    if (d->scratch) (void)hipFree(d->scratch);
+    delete d;
+}
+
+extern "C" int escx_dac_param_count(escx_dac d) { return d ? (int)d->keys.size() : 0; }
+extern "C" const char* escx_dac_param_key(escx_dac d, int i) { return (d && i >= 0 && i < (int)d->keys.size()) ? d->keys[i].c_str() : nullptr; }
+extern "C" int64_t escx_dac_param_offset(escx_dac d, int i) { return (d && i >= 0 && i < (int)d->offs.size()) ? (int64_t)d->offs[i] : -1; }
+extern "C" int64_t escx_dac_param_numel(escx_dac d, int i) { return (d && i >= 0 && i < (int)d->numels.size()) ? (int64_t)d->numels[i] : -1; }
+extern "C" int64_t escx_dac_param_total(escx_dac d) { return d ? (int64_t)d->total : 0; }
+
+extern "C" int escx_dac_set_snake_maps(escx_dac d, int mask) {
+    if (!d) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null handle");
+    if (mask < 0 || mask > ESCX_DAC_SNAKE_ALL) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "snake map mask %d outside [0, %d]", mask, ESCX_DAC_SNAKE_ALL);
+    d->snake_maps = mask;
+    return ESCX_OK;
+}
+extern "C" int escx_dac_get_snake_maps(escx_dac d) { return d ? d->snake_maps : -1; }
+
+extern "C" int escx_dac_num_frames(escx_dac d, int n_samples) {
+    if (!d || n_samples < 1) return 0;
+    int T = n_samples;
+    for (int i = 0; i < d->cfg.n_encoder_rates; ++i) {
+        T = conv_out_len(T, d->enc[1 + i * 7 + 6]);
+        if (T < 1) return 0;
+    }
+    return T;
+}
+extern "C" int escx_dac_output_samples(escx_dac d, int n_frames) {
+    if (!d || n_frames < 1) return 0;
+    int T = n_frames;
+    for (int i = 0; i < d->cfg.n_decoder_rates; ++i) T = conv_out_len(T, d->dec[1 + i * 7]);
+    return T;
+}
+
+extern "C" int escx_dac_encode(escx_dac d, const float* flat, int64_t version, const float* audio, int B, int L, int n_q, float* z, int64_t* codes,
+                               float* latents, float* losses, void* stream) {
+    int rc = check_args(d, flat, B); if (rc) return rc;
+    if (!audio || !z || !codes || !latents || !losses || n_q < 1) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "bad argument");
+    const int n = std::min(n_q, d->cfg.n_codebooks);
+    const int Tz0 = escx_dac_num_frames(d, L);
+    if (Tz0 < 1) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "%d samples give no latent frame (the hop is %d)", L, d->hop);
+    hipStream_t st = (hipStream_t)stream;
+    int Tz = 0;
+    const size_t mf = enc_scratch(d, B, L, &Tz);
+    if ((unsigned long long)mf >= (1ull << 32)) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "batch of %d x %d samples: a feature map above 2^32 elements", B, L);
+    const size_t M = (size_t)B * Tz;
+    const size_t lossf = pad64((size_t)n * M) + pad64((size_t)n * B);
+    if ((rc = ensure_scratch(d, (4 * mf + lossf) * sizeof(float)))) return rc;
+    if ((rc = pack(d, flat, (long long)version, st))) return rc;
+    float* x = d->scratch; float* y = x + mf; float* h = y + mf; float* lossb = h + mf + mf;
+    const Run run{d->snake_maps, h + mf, st};
+    hipLaunchKernelGGL(dac_wave_in_kernel, dim3(nblk((long long)B * L)), dim3(256), 0, st, audio, h, (long long)B * L);
+    const DacLayer* E = d->enc.data(); const DacSnake* SN = d->enc_sn.data();
+    run_layer(run, ESCX_DAC_SNAKE_LAST, E[0], nullptr, h, B, L, x, L, nullptr, 0);
+    int T = L;
+    for (int i = 0; i < d->cfg.n_encoder_rates; ++i) {
+        const DacLayer* Lb = E + 1 + i * 7; const DacSnake* Sb = SN + i * 7;        // 3 residual units (2 convolutions, 2 Snakes each), Snake, strided conv
+        for (int j = 0; j < 3; ++j) run_res(run, Lb + 2 * j, Sb + 2 * j, x, h, B, T);
+        const DacLayer& sc = Lb[6];
+        const int T2 = conv_out_len(T, sc);
+        run_layer(run, ESCX_DAC_SNAKE_DOWN, sc, Sb + 6, x, B, T, y, T2, nullptr, 0);
+        std::swap(x, y); T = T2;
+    }
+    run_layer(run, ESCX_DAC_SNAKE_LAST, E[d->enc.size() - 1], SN + d->enc_sn.size() - 1, x, B, T, y, T, nullptr, 0);
+    DacQArgs qa{};
+    qa.t = d->qt; qa.zmap = y; qa.z = z; qa.codes = (long long*)codes; qa.latents = latents; qa.loss = lossb;
+    qa.M = (int)M; qa.T = T; qa.D = d->latent; qa.Dp = cpad(d->latent); qa.d = d->cfg.codebook_dim; qa.K = d->cfg.codebook_size; qa.n = n;
+    const int J = (d->latent + 63) / 64;
+    const dim3 g(nblk((long long)M, 4)), blk(256);
+    if (J <= 1) hipLaunchKernelGGL((dac_rvq_kernel<1, false>), g, blk, 0, st, qa);
+    else if (J <= 2) hipLaunchKernelGGL((dac_rvq_kernel<2, false>), g, blk, 0, st, qa);
+    else if (J <= 4) hipLaunchKernelGGL((dac_rvq_kernel<4, false>), g, blk, 0, st, qa);
+    else if (J <= 8) hipLaunchKernelGGL((dac_rvq_kernel<8, false>), g, blk, 0, st, qa);
+    else hipLaunchKernelGGL((dac_rvq_kernel<16, false>), g, blk, 0, st, qa);
+    hipLaunchKernelGGL(dac_loss_kernel, dim3(1), dim3(256), 0, st, lossb, lossb + pad64((size_t)n * M), losses, B, T, n, d->cfg.codebook_dim);
+    return launch_ok("escx_dac_encode");
+}
+
+extern "C" int escx_dac_from_codes(escx_dac d, const float* flat, int64_t version, const int64_t* codes, int B, int n, int T, float* z, float* zp, void* stream) {
+    int rc = check_args(d, flat, B); if (rc) return rc;
+    if (!codes || !z || !zp || T < 1 || n < 1 || n > d->cfg.n_codebooks) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "bad argument (codes of %d codebooks, %d frames)", n, T);
+    hipStream_t st = (hipStream_t)stream;
+    if ((rc = pack(d, flat, (long long)version, st))) return rc;
+    DacQArgs qa{};
+    qa.t = d->qt; qa.codes_in = (const long long*)codes; qa.z = z; qa.latents = zp;
+    qa.M = B * T; qa.T = T; qa.D = d->latent; qa.Dp = cpad(d->latent); qa.d = d->cfg.codebook_dim; qa.K = d->cfg.codebook_size; qa.n = n;
+    const int J = (d->latent + 63) / 64;
+    const dim3 g(nblk((long long)B * T, 4)), blk(256);
+    if (J <= 1) hipLaunchKernelGGL((dac_rvq_kernel<1, true>), g, blk, 0, st, qa);
+    else if (J <= 2) hipLaunchKernelGGL((dac_rvq_kernel<2, true>), g, blk, 0, st, qa);
+    else if (J <= 4) hipLaunchKernelGGL((dac_rvq_kernel<4, true>), g, blk, 0, st, qa);
+    else if (J <= 8) hipLaunchKernelGGL((dac_rvq_kernel<8, true>), g, blk, 0, st, qa);
+    else hipLaunchKernelGGL((dac_rvq_kernel<16, true>), g, blk, 0, st, qa);
+    return launch_ok("escx_dac_from_codes");
+}
+
+extern "C" int escx_dac_decode(escx_dac d, const float* flat, int64_t version, const float* z, int B, int T, float* audio, void* stream) {
+    int rc = check_args(d, flat, B); if (rc) return rc;
+    if (!z || !audio || T < 1) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "bad argument");
+    hipStream_t st = (hipStream_t)stream;
+    int Lout = 0;
+    const size_t mf = dec_scratch(d, B, T, &Lout);
+    if (Lout < 1) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "%d latent frames decode to no sample", T);
+    if ((unsigned long long)mf >= (1ull << 32)) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "batch of %d x %d frames: a feature map above 2^32 elements", B, T);
+    if ((rc = ensure_scratch(d, 4 * mf * sizeof(float)))) return rc;
+    if ((rc = pack(d, flat, (long long)version, st))) return rc;
+    float* x = d->scratch; float* y = x + mf; float* h = y + mf;
+    const Run run{d->snake_maps, h + mf, st};
+    const int Dp = cpad(d->latent);
+    hipLaunchKernelGGL(dac_z_in_kernel, dim3(nblk((long long)B * T * Dp)), dim3(256), 0, st, z, h, B, d->latent, Dp, T);
+    const DacLayer* Dl = d->dec.data(); const DacSnake* SN = d->dec_sn.data();
+    run_layer(run, ESCX_DAC_SNAKE_LAST, Dl[0], nullptr, h, B, T, x, T, nullptr, 0);
+    for (int i = 0; i < d->cfg.n_decoder_rates; ++i) {
+        const DacLayer* Lb = Dl + 1 + i * 7; const DacSnake* Sb = SN + i * 7;
+        const int T2 = conv_out_len(T, Lb[0]);
+        run_layer(run, ESCX_DAC_SNAKE_UP, Lb[0], Sb, x, B, T, y, T2, nullptr, 0);
+        std::swap(x, y); T = T2;
+        for (int j = 0; j < 3; ++j) run_res(run, Lb + 1 + 2 * j, Sb + 1 + 2 * j, x, h, B, T);
+    }
+    run_layer(run, ESCX_DAC_SNAKE_LAST, Dl[d->dec.size() - 1], SN + d->dec_sn.size() - 1, x, B, T, audio, T, nullptr, 1);
+    return launch_ok("escx_dac_decode");
+}
+
+extern "C" int escx_dac_test_math(const float* x, const float* alpha, float* out, int64_t n, int mode, void* stream) {
+    if (!x || !out || n < 0 || mode < 0 || mode > 1 || (mode == 0 && !alpha)) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "bad argument");
+    if (n) hipLaunchKernelGGL(dac_test_math_kernel, dim3(nblk(n)), dim3(256), 0, (hipStream_t)stream, x, alpha, out, (long long)n, mode);
+    return launch_ok("escx_dac_test_math");
+}

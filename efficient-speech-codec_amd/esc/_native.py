@@ -32,6 +32,13 @@ class EscxDiscConfig(Structure):
                 ("fft_sizes", c_int32 * 8), ("n_bands", c_int32), ("bands", (c_float * 2) * 8)]
 
 
+class EscxDacConfig(Structure):
+    """include/escx.h escx_dac_config: the DAC baseline codec."""
+    _fields_ = [("encoder_dim", c_int32), ("n_encoder_rates", c_int32), ("encoder_rates", c_int32 * 8), ("latent_dim", c_int32),
+                ("decoder_dim", c_int32), ("n_decoder_rates", c_int32), ("decoder_rates", c_int32 * 8), ("n_codebooks", c_int32),
+                ("codebook_size", c_int32), ("codebook_dim", c_int32), ("sample_rate", c_int32)]
+
+
 # name -> (restype, argtypes); every symbol include/escx.h declares
 SIGNATURES = {
     "escx_last_error": (c_char_p, []),
@@ -114,6 +121,21 @@ SIGNATURES = {
     "escx_disc_get_precision": (c_int, [c_void_p]),
     "escx_disc_profile_enable": (c_int, [c_int]),
     "escx_disc_profile_report": (c_char_p, []),
+    "escx_dac_create": (c_int, [POINTER(EscxDacConfig), c_int, POINTER(c_void_p)]),
+    "escx_dac_destroy": (None, [c_void_p]),
+    "escx_dac_param_count": (c_int, [c_void_p]),
+    "escx_dac_param_key": (c_char_p, [c_void_p, c_int]),
+    "escx_dac_param_offset": (c_int64, [c_void_p, c_int]),
+    "escx_dac_param_numel": (c_int64, [c_void_p, c_int]),
+    "escx_dac_param_total": (c_int64, [c_void_p]),
+    "escx_dac_num_frames": (c_int, [c_void_p, c_int]),
+    "escx_dac_output_samples": (c_int, [c_void_p, c_int]),
+    "escx_dac_encode": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "escx_dac_from_codes": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "escx_dac_decode": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "escx_dac_set_snake_maps": (c_int, [c_void_p, c_int]),
+    "escx_dac_get_snake_maps": (c_int, [c_void_p]),
+    "escx_dac_test_math": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
     "escx_set_rccl_library": (c_int, [c_char_p]),
     "escx_allgather_codes": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p]),
 }

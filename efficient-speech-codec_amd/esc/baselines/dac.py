@@ -1,0 +1,297 @@
+"""The DAC baseline codec (Descript audio codec; reference baselines/descript/dac/model/dac.py:148-266, nn/quantize.py) on the MI355X.
+
+Same constructor keywords, same state_dict keys and shapes (`*.weight_g`, `*.weight_v`, `*.bias`, `*.alpha`,
+`quantizer.quantizers.{i}.codebook.weight`: reference checkpoints load with `load_state_dict(strict=True)`), same eval-mode
+`encode` / `decode` / `forward` / `quantizer.from_codes`.  Every convolution, the weight normalisation and the residual quantiser run in
+libescx (csrc/dac.hip); there is no PyTorch/CPU implementation here.  Inference only: training mode raises NotImplementedError.
+"""
+from __future__ import annotations
+
+import ctypes
+import math
+from typing import List, Union
+
+import torch
+import torch.nn as nn
+
+from .. import _native
+from ..models.codecs import _attach
+
+
+def _param_specs(enc_dim, enc_rates, latent, dec_dim, dec_rates, n_cb, cb_size, cb_dim):
+    """(key, shape) of every parameter in the reference's named_parameters() order."""
+    out = []
+
+    def conv(p, cin, cout, k, transposed=False):
+        out.extend([(p + "bias", (cout,)), (p + "weight_g", (cin, 1, 1) if transposed else (cout, 1, 1)),
+                    (p + "weight_v", (cin, cout, k) if transposed else (cout, cin, k))])
+
+    def snake(p, c):
+        out.append((p + "alpha", (1, c, 1)))
+
+    def res(p, c):
+        snake(p + "block.0.", c); conv(p + "block.1.", c, c, 7); snake(p + "block.2.", c); conv(p + "block.3.", c, c, 1)
+
+    c = enc_dim
+    conv("encoder.block.0.", 1, c, 7)
+    for i, s in enumerate(enc_rates):
+        p = f"encoder.block.{i + 1}.block."
+        for j in range(3):
+            res(f"{p}{j}.", c)
+        snake(f"{p}3.", c); conv(f"{p}4.", c, 2 * c, 2 * s)
+        c *= 2
+    snake(f"encoder.block.{len(enc_rates) + 1}.", c); conv(f"encoder.block.{len(enc_rates) + 2}.", c, latent, 3)
+    for i in range(n_cb):
+        p = f"quantizer.quantizers.{i}."
+        conv(p + "in_proj.", latent, cb_dim, 1); conv(p + "out_proj.", cb_dim, latent, 1)
+        out.append((p + "codebook.weight", (cb_size, cb_dim)))
+    c = dec_dim
+    conv("decoder.model.0.", latent, c, 7)
+    for i, s in enumerate(dec_rates):
+        p = f"decoder.model.{i + 1}.block."
+        snake(p + "0.", c); conv(p + "1.", c, c // 2, 2 * s, transposed=True)
+        for j in range(3):
+            res(f"{p}{j + 2}.", c // 2)
+        c //= 2
+    snake(f"decoder.model.{len(dec_rates) + 1}.", c); conv(f"decoder.model.{len(dec_rates) + 2}.", c, 1, 7)
+    return out
+
+
+def _check_device(x: torch.Tensor, what: str):
+    if not x.is_cuda:
+        raise RuntimeError(f"esc.baselines.DAC runs on the HIP device only: {what} is on {x.device}")
+
+
+class DAC(nn.Module):
+    def __init__(self, encoder_dim: int = 64, encoder_rates: List[int] = [2, 4, 8, 8], latent_dim: int = None, decoder_dim: int = 1536,
+                 decoder_rates: List[int] = [8, 8, 4, 2], n_codebooks: int = 9, codebook_size: int = 1024, codebook_dim: Union[int, list] = 8,
+                 quantizer_dropout: bool = False, sample_rate: int = 44100):
+        super().__init__()
+        if not isinstance(codebook_dim, int):
+            if len(set(codebook_dim)) != 1:
+                raise NotImplementedError("per-codebook codebook_dim lists are not implemented; give one int")
+            codebook_dim = int(codebook_dim[0])
+        if latent_dim is None:
+            latent_dim = encoder_dim * (2 ** len(encoder_rates))
+        self.encoder_dim, self.encoder_rates, self.decoder_dim, self.decoder_rates = encoder_dim, list(encoder_rates), decoder_dim, list(decoder_rates)
+        self.latent_dim, self.sample_rate = latent_dim, sample_rate
+        self.hop_length = int(math.prod(encoder_rates))
+        self.n_codebooks, self.codebook_size, self.codebook_dim, self.quantizer_dropout = n_codebooks, codebook_size, codebook_dim, quantizer_dropout
+        self.kwargs = dict(encoder_dim=encoder_dim, encoder_rates=list(encoder_rates), latent_dim=latent_dim, decoder_dim=decoder_dim,
+                           decoder_rates=list(decoder_rates), n_codebooks=n_codebooks, codebook_size=codebook_size, codebook_dim=codebook_dim,
+                           quantizer_dropout=quantizer_dropout, sample_rate=sample_rate)
+        for key, shape in _param_specs(encoder_dim, encoder_rates, latent_dim, decoder_dim, decoder_rates, n_codebooks, codebook_size, codebook_dim):
+            if key.endswith("alpha"):
+                t = torch.ones(shape)
+            elif key.endswith("weight_v"):
+                t = torch.empty(shape).normal_(0.0, 0.02)            # init_weights: trunc_normal(std 0.02), bias 0 (dac.py:18-21)
+            elif key.endswith("weight_g"):
+                t = torch.ones(shape)
+            elif key.endswith("codebook.weight"):
+                t = torch.randn(shape)
+            else:
+                t = torch.zeros(shape)
+            _attach(self, key, t, False)
+        with torch.no_grad():                                        # weight_norm's g = ||v|| over every dim but dim 0
+            for name, p in self.named_parameters():
+                if name.endswith("weight_g"):
+                    v = self.get_parameter(name[:-1] + "v")
+                    p.copy_(v.flatten(1).norm(dim=1).view(p.shape))
+        q = self.quantizer                                           # the reference's `quantizer` holds the parameters and from_codes (quantize.py:200-220)
+        q.from_codes, q.n_codebooks, q.codebook_size, q.codebook_dim = self._from_codes, n_codebooks, codebook_size, [codebook_dim] * n_codebooks
+        self._handles, self._flat = {}, {}
+
+    # ---- native handle and flat parameter buffer (same scheme as esc.models.Discriminator) ----------------------------------------------
+    def _version(self) -> int:
+        return sum(p._version for p in self.parameters())
+
+    def _apply(self, fn, *a, **k):
+        self._drop()
+        return super()._apply(fn, *a, **k)
+
+    def _drop(self):
+        if getattr(self, "_handles", None):
+            lib = _native.load()
+            for hd in self._handles.values():
+                lib.escx_dac_destroy(hd)
+        self._handles, self._flat = {}, {}
+
+    def __del__(self):
+        try:
+            self._drop()
+        except Exception:
+            pass
+
+    def __getstate__(self):
+        st = self.__dict__.copy()
+        st["_handles"], st["_flat"] = {}, {}
+        return st
+
+    def _handle(self, device):
+        lib = _native.load()
+        idx = device.index if device.index is not None else torch.cuda.current_device()
+        if idx not in self._handles:
+            if len(self.encoder_rates) > 8 or len(self.decoder_rates) > 8:
+                raise NotImplementedError("more than 8 encoder or decoder rates")
+            c = _native.EscxDacConfig()
+            c.encoder_dim, c.n_encoder_rates, c.latent_dim = self.encoder_dim, len(self.encoder_rates), self.latent_dim
+            c.decoder_dim, c.n_decoder_rates = self.decoder_dim, len(self.decoder_rates)
+            for i, s in enumerate(self.encoder_rates):
+                c.encoder_rates[i] = s
+            for i, s in enumerate(self.decoder_rates):
+                c.decoder_rates[i] = s
+            c.n_codebooks, c.codebook_size, c.codebook_dim, c.sample_rate = self.n_codebooks, self.codebook_size, self.codebook_dim, self.sample_rate
+            hd = ctypes.c_void_p()
+            _native.check(lib.escx_dac_create(ctypes.byref(c), idx, ctypes.byref(hd)))
+            self._handles[idx] = hd
+            if getattr(self, "_snake_maps", None) is not None:
+                _native.check(lib.escx_dac_set_snake_maps(hd, self._snake_maps))
+        return lib, self._handles[idx]
+
+    def _ensure_flat(self, device, lib, hd):
+        """Flat fp32 parameter buffer in the library's order; the nn.Parameters become views of it."""
+        idx = device.index if device.index is not None else torch.cuda.current_device()
+        st = self._flat.get(idx)
+        params = dict(self.named_parameters())
+        if st is None:
+            n = lib.escx_dac_param_count(hd)
+            layout = [(lib.escx_dac_param_key(hd, i).decode(), int(lib.escx_dac_param_offset(hd, i)), int(lib.escx_dac_param_numel(hd, i))) for i in range(n)]
+            if [k for k, _, _ in layout] != list(params):
+                raise RuntimeError("libescx's DAC parameter order differs from the module's")
+            st = {"flat": torch.zeros(int(lib.escx_dac_param_total(hd)), dtype=torch.float32, device=device), "layout": layout}
+            self._flat[idx] = st
+        flat, base = st["flat"], st["flat"].data_ptr()
+        with torch.no_grad():
+            for key, off, n in st["layout"]:
+                p = params[key]
+                if p.data_ptr() != base + 4 * off:
+                    flat[off:off + n].copy_(p.detach().reshape(-1).to(device=device, dtype=torch.float32))
+                    p.data = flat[off:off + n].view(p.shape)
+        return flat
+
+    def _ctx(self, x: torch.Tensor, what: str):
+        if self.training:
+            raise NotImplementedError("esc.baselines.DAC is inference only: call .eval() (DAC training is not implemented)")
+        _check_device(x, what)
+        dev = x.device
+        lib, hd = self._handle(dev)
+        flat = self._ensure_flat(dev, lib, hd)
+        return lib, hd, flat, dev, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+    def set_snake_maps(self, mask: int):
+        """Where Snake is evaluated per layer class (include/escx.h escx_dac_set_snake_maps; bitwise the same results either way).  A/B aid."""
+        self._snake_maps = int(mask)
+        for hd in self._handles.values():
+            _native.check(_native.load().escx_dac_set_snake_maps(hd, self._snake_maps))
+        return self
+
+    # ---- length arithmetic ---------------------------------------------------------------------------------------------------------------
+    def num_frames(self, n_samples: int) -> int:
+        """Latent frames of an n_samples clip (torch's Conv1d length formula through the encoder); 0 when the clip is shorter than one hop."""
+        t = int(n_samples)
+        for s in self.encoder_rates:
+            t = (t + 2 * math.ceil(s / 2) - 2 * s) // s + 1
+            if t < 1:
+                return 0
+        return t
+
+    def output_samples(self, n_frames: int) -> int:
+        """Samples decoded from n_frames latent frames: 320 T - 8 for rates [8, 5, 4, 2]."""
+        t = int(n_frames)
+        for s in self.decoder_rates:
+            t = (t - 1) * s - 2 * math.ceil(s / 2) + 2 * s
+        return t
+
+    # ---- the reference's interface -------------------------------------------------------------------------------------------------------
+    def preprocess(self, audio_data, sample_rate):
+        if sample_rate is None:
+            sample_rate = self.sample_rate
+        if sample_rate != self.sample_rate:
+            raise AssertionError(f"sample_rate {sample_rate} != the model's {self.sample_rate}")
+        length = audio_data.shape[-1]
+        right_pad = math.ceil(length / self.hop_length) * self.hop_length - length
+        return nn.functional.pad(audio_data, (0, right_pad))
+
+    def _n_quantizers(self, n_quantizers):
+        if n_quantizers is None:
+            return self.n_codebooks
+        n = int(n_quantizers)
+        if n < 1:
+            raise ValueError(f"n_quantizers must be at least 1, got {n_quantizers}")
+        return min(n, self.n_codebooks)                 # the reference's loop stops at the last codebook
+
+    @torch.no_grad()
+    def encode(self, audio_data: torch.Tensor, n_quantizers: int = None):
+        """dac.py:209-247: (z (B, D, T), codes (B, n, T) int64, latents (B, n d, T), commitment_loss, codebook_loss)."""
+        lib, hd, flat, dev, stream = self._ctx(audio_data, "audio_data")
+        n = self._n_quantizers(n_quantizers)
+        if audio_data.dim() != 3 or audio_data.shape[1] != 1:
+            raise ValueError(f"audio_data must be (B, 1, L), got {tuple(audio_data.shape)}")
+        B, _, L = audio_data.shape
+        T = self.num_frames(L)
+        if T < 1:
+            raise ValueError(f"{L} samples are shorter than one hop ({self.hop_length}): the encoder gives no frame")
+        x = audio_data.to(torch.float32).contiguous()
+        z = torch.empty(B, self.latent_dim, T, device=dev)
+        codes = torch.empty(B, n, T, dtype=torch.int64, device=dev)
+        latents = torch.empty(B, n * self.codebook_dim, T, device=dev)
+        losses = torch.empty(2, device=dev)
+        with torch.cuda.device(dev):
+            _native.check(lib.escx_dac_encode(hd, ctypes.c_void_p(flat.data_ptr()), self._version(), ctypes.c_void_p(x.data_ptr()), B, L, n,
+                                              ctypes.c_void_p(z.data_ptr()), ctypes.c_void_p(codes.data_ptr()), ctypes.c_void_p(latents.data_ptr()),
+                                              ctypes.c_void_p(losses.data_ptr()), stream))
+        return z, codes, latents, losses[0], losses[1]
+
+    @torch.no_grad()
+    def decode(self, z: torch.Tensor):
+        """dac.py:249-266: z (B, D, T) -> audio (B, 1, output_samples(T))."""
+        lib, hd, flat, dev, stream = self._ctx(z, "z")
+        if z.dim() != 3 or z.shape[1] != self.latent_dim:
+            raise ValueError(f"z must be (B, {self.latent_dim}, T), got {tuple(z.shape)}")
+        B, _, T = z.shape
+        zc = z.to(torch.float32).contiguous()
+        out = torch.empty(B, 1, self.output_samples(T), device=dev)
+        with torch.cuda.device(dev):
+            _native.check(lib.escx_dac_decode(hd, ctypes.c_void_p(flat.data_ptr()), self._version(), ctypes.c_void_p(zc.data_ptr()), B, T,
+                                              ctypes.c_void_p(out.data_ptr()), stream))
+        return out
+
+    @torch.no_grad()
+    def _from_codes(self, codes: torch.Tensor):
+        """ResidualVectorQuantize.from_codes: (z_q (B, D, T), z_p (B, n d, T), codes); `model.quantizer.from_codes` is this method."""
+        lib, hd, flat, dev, stream = self._ctx(codes, "codes")
+        if codes.dim() != 3 or not 1 <= codes.shape[1] <= self.n_codebooks:
+            raise ValueError(f"codes must be (B, n <= {self.n_codebooks}, T), got {tuple(codes.shape)}")
+        B, n, T = codes.shape
+        c = codes.to(torch.int64).contiguous()
+        if c.numel() and (int(c.min()) < 0 or int(c.max()) >= self.codebook_size):
+            raise IndexError(f"codes outside [0, {self.codebook_size}): F.embedding of the reference raises here")
+        z = torch.empty(B, self.latent_dim, T, device=dev)
+        zp = torch.empty(B, n * self.codebook_dim, T, device=dev)
+        with torch.cuda.device(dev):
+            _native.check(lib.escx_dac_from_codes(hd, ctypes.c_void_p(flat.data_ptr()), self._version(), ctypes.c_void_p(c.data_ptr()), B, n, T,
+                                                  ctypes.c_void_p(z.data_ptr()), ctypes.c_void_p(zp.data_ptr()), stream))
+        return z, zp, codes
+
+    def forward(self, audio_data: torch.Tensor, sample_rate: int = None, n_quantizers: int = None):
+        """dac.py:268-323 in eval mode: right-pad to a multiple of the hop, encode, decode, trim the audio to the input length."""
+        if self.training:
+            raise NotImplementedError("esc.baselines.DAC is inference only: call .eval() (DAC training is not implemented)")
+        _check_device(audio_data, "audio_data")
+        length = audio_data.shape[-1]
+        x = self.preprocess(audio_data, sample_rate)
+        z, codes, latents, cm, cb = self.encode(x, n_quantizers)
+        audio = self.decode(z)
+        return {"audio": audio[..., :length], "z": z, "codes": codes, "latents": latents, "vq/commitment_loss": cm, "vq/codebook_loss": cb}
+
+    @classmethod
+    def load(cls, path, map_location="cpu", strict: bool = True):
+        """A checkpoint in the layout audiotools' BaseModel.save_to_folder writes (the reference trainer's, scripts/train_customize_no_adv.py:324):
+        a torch.save'd dict with "state_dict" and "metadata": {"kwargs": constructor keywords}.  That layout is assumed from the reference's
+        code, not checked against a real file."""
+        ck = torch.load(path, map_location=map_location, weights_only=False)
+        kwargs = dict(ck["metadata"]["kwargs"])
+        model = cls(**kwargs)
+        model.load_state_dict(ck["state_dict"], strict=strict)
+        model.metadata = ck["metadata"]
+        return model

@@ -138,3 +138,30 @@ def voiced_clip_int16(tag: str, n_samples: int, sr: int = 16000) -> np.ndarray:
 
 def pcm_to_float(x_int16: np.ndarray) -> np.ndarray:
     return (x_int16.astype(np.float32) / np.float32(32768.0)).astype(np.float32)
+
+
+def dac_tensor(key: str, shape, dtype=np.float32) -> np.ndarray:
+    """Deterministic value for one entry of the DAC baseline's state_dict (esc.baselines.DAC).  Separate from synth_tensor, whose
+    weight_g rule feeds the discriminator fixtures: Snake alphas in [0.5, 1.5], weight-norm gains near unit gain, direction tensors
+    uniform (their scale cancels in the normalisation), small biases and Kaiming-like codebook rows."""
+    shape = tuple(int(s) for s in shape)
+    n = int(np.prod(shape)) if len(shape) else 1
+    u = hashed_uniform("dac:" + key, n)
+    if key.endswith(".alpha"):
+        v = 1.0 + 0.5 * u
+    elif key.endswith(".weight_g"):
+        v = 0.5 + 0.1 * u
+    elif key.endswith(".weight_v"):
+        v = u
+    elif key.endswith(".bias"):
+        v = 0.02 * u
+    elif key.endswith("codebook.weight"):
+        v = np.sqrt(6.0 / shape[1]) * u
+    else:
+        raise KeyError(f"dac_tensor: no rule for {key}")
+    return v.reshape(shape).astype(dtype)
+
+
+def dac_state_dict(manifest: dict) -> dict:
+    """manifest: key -> shape (a DAC state_dict layout).  Returns key -> numpy array."""
+    return {k: dac_tensor(k, shp) for k, shp in manifest.items()}

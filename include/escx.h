@@ -360,6 +360,63 @@ int escx_set_rccl_library(const char* path);
 int escx_allgather_codes(escx_handle h, const int64_t* codes_local_dev, int64_t n_local_codes, int64_t* codes_all_dev,
                          int world_size, void* nccl_comm, void* stream);
 
+/* ---- DAC baseline codec (Descript audio codec), inference only ---------------------------------------------------------------------------
+ * Reference: baselines/descript/dac/model/dac.py:148-247 (DAC), nn/layers.py:9-33 (WNConv1d, WNConvTranspose1d, Snake1d), nn/quantize.py:13-220
+ * (VectorQuantize, ResidualVectorQuantize).  Parameters: one caller-owned flat fp32 device buffer in the order escx_dac_param_*() reports (the
+ * reference's named_parameters(): per convolution bias, weight_g, weight_v; per Snake alpha; per codebook weight).  Weight normalisation (the
+ * transposed convolutions normalise over their INPUT channels, dim 0), the Snake reciprocals and the normalised codebooks are re-derived on the
+ * device when (buffer, params_version) changes; a negative version always re-derives.  Tensors are the reference's layouts: audio (B, 1, L),
+ * z (B, D, T), codes (B, n, T) int64, latents (B, n * codebook_dim, T).  Arithmetic is fp32.  A configuration the kernels do not cover
+ * (rates above 16, latent_dim above 1024 or not a multiple of 4, codebook_dim above 8, decoder_dim not divisible by 2^n_decoder_rates)
+ * fails at create with ESCX_ERR_UNSUPPORTED. */
+#define ESCX_DAC_MAX_RATES 8
+typedef struct {
+    int32_t encoder_dim; int32_t n_encoder_rates; int32_t encoder_rates[ESCX_DAC_MAX_RATES];
+    int32_t latent_dim;             /* 0: encoder_dim * 2^n_encoder_rates (dac.py:173-174) */
+    int32_t decoder_dim; int32_t n_decoder_rates; int32_t decoder_rates[ESCX_DAC_MAX_RATES];
+    int32_t n_codebooks; int32_t codebook_size; int32_t codebook_dim;
+    int32_t sample_rate;
+} escx_dac_config;
+typedef struct escx_dac_s* escx_dac;
+/* DAC.__init__ (dac.py:149-196) */
+int escx_dac_create(const escx_dac_config* cfg, int device, escx_dac* out);
+void escx_dac_destroy(escx_dac d);
+int escx_dac_param_count(escx_dac d);
+const char* escx_dac_param_key(escx_dac d, int i);
+int64_t escx_dac_param_offset(escx_dac d, int i);
+int64_t escx_dac_param_numel(escx_dac d, int i);
+int64_t escx_dac_param_total(escx_dac d);
+/* Latent frames of an n_samples clip through the encoder (torch's Conv1d length formula; 0 = the clip gives none), and samples decoded from
+ * n_frames frames (ConvTranspose1d's (T - 1) s - 2 p + 2 s per block: 320 T - 8 for rates [8, 5, 4, 2]). */
+int escx_dac_num_frames(escx_dac d, int n_samples);
+int escx_dac_output_samples(escx_dac d, int n_frames);
+/* DAC.encode (dac.py:209-247) with ResidualVectorQuantize.forward in eval mode (quantize.py:127-198): audio (B, L) device -> z (B, D, T),
+ * codes (B, n, T), latents (B, n * codebook_dim, T), losses[2] = (commitment_loss, codebook_loss) on the device.  n = min(n_quantizers,
+ * n_codebooks); n_quantizers < 1 is ESCX_ERR_INVALID_ARG.  The quantiser is one launch. */
+int escx_dac_encode(escx_dac d, const float* flat_params_dev, int64_t params_version, const float* audio_dev, int batch, int n_samples, int n_quantizers,
+                    float* z_dev, int64_t* codes_dev, float* latents_dev, float* losses_dev, void* stream);
+/* ResidualVectorQuantize.from_codes (quantize.py:200-220): codes (B, n, T) -> z_q (B, D, T) and z_p (B, n * codebook_dim, T).  The kernel clamps
+ * a code outside [0, codebook_size) to the nearest valid row instead of reading outside the codebook; the reference's F.embedding raises there,
+ * and the Python host (esc.baselines.DAC) checks the range and raises IndexError before calling. */
+int escx_dac_from_codes(escx_dac d, const float* flat_params_dev, int64_t params_version, const int64_t* codes_dev, int batch, int n_codes, int n_frames,
+                        float* z_dev, float* zp_dev, void* stream);
+/* DAC.decode (dac.py:249-266): z (B, D, T) -> audio (B, escx_dac_output_samples(T)). */
+int escx_dac_decode(escx_dac d, const float* flat_params_dev, int64_t params_version, const float* z_dev, int batch, int n_frames, float* audio_dev, void* stream);
+/* Where Snake (nn/layers.py:19-24) is evaluated, per layer class: bit set = written once per element into a Snaked copy of the map that the
+ * convolution then reads; bit clear = applied to the operand while the convolution stages it (once per tap and per output-column tile).  Both
+ * give bitwise the same results; the default is the faster per class on MI355X.  A/B switch, not a numerics setting. */
+#define ESCX_DAC_SNAKE_RES7 0       /* ResidualUnit's dilated 7-tap convolution (input x)            */
+#define ESCX_DAC_SNAKE_RES1 1       /* ResidualUnit's 1x1 convolution (input: the 7-tap output)      */
+#define ESCX_DAC_SNAKE_DOWN 2       /* EncoderBlock's strided convolution                           */
+#define ESCX_DAC_SNAKE_UP 3         /* DecoderBlock's transposed convolution (every phase GEMM)     */
+#define ESCX_DAC_SNAKE_LAST 4       /* the encoder's last 3-tap and the decoder's last 7-tap layer  */
+#define ESCX_DAC_SNAKE_ALL 31
+#define ESCX_DAC_SNAKE_MAPS_DEFAULT ESCX_DAC_SNAKE_ALL   /* measured faster for every class: profiles/dac_snake_ab.txt */
+int escx_dac_set_snake_maps(escx_dac d, int mask);
+int escx_dac_get_snake_maps(escx_dac d);
+/* Test hook: the kernels' Snake (mode 0: x + sin(alpha x)^2 / (alpha + 1e-9), nn/layers.py:19-24) or tanh (mode 1) over n device values. */
+int escx_dac_test_math(const float* x_dev, const float* alpha_dev, float* out_dev, int64_t n, int mode, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
