@@ -109,7 +109,7 @@ static int x3_nt(const escx_handle_s* h) { return h->prec == 3 ? 3 : 2; }       
 // 8 waves share each weight fragment between twice as many rows (half the L2->LDS traffic) and win ties.
 // `cap` = waves per SIMD the kernel's register budget allows (mlp_min_waves / attn_min_waves): at 3, an 8-wave workgroup leaves
 // the third slot of every SIMD empty (one workgroup = 2 waves per SIMD, a second one does not fit), so 4-wave workgroups it is.
-// Waves per workgroup of the split-operand MLP (fused_mlp_x3.h), measured at 36 clips (tools/ab.py, ESCX_MLP_X3_NW in tagged builds; ms per step alone, 4 -> 8 waves):
+// Waves per workgroup of the split-operand MLP (fused_mlp_x3.h), measured at 36 clips (tools/ab.py; ms per step alone, 4 -> 8 waves):
 // C = 45 1.25 -> 1.17, C = 72 0.96 -> 0.84, C = 96 1.13 -> 0.97, C = 144 1.34 -> 1.55, C = 192 0.97 -> 1.00, C = 384 1.59 -> 1.11 (8 waves cap the kernel at 256
 // registers with a small spill, but put two waves on every SIMD).  Small grids keep the fp32 kernel's rule (`variant`): a wave per SIMD first.
 static int mlp_x3_nw(int M, int Cp, int variant) {
@@ -120,8 +120,7 @@ static int mlp_x3_nw(int M, int Cp, int variant) {
 }
 
 static int pick_nw(long long tiles, int units, int cap = 4) {
-    static const bool cap_rule = [] { const char* e = ESCX_TUNE_ENV("ESCX_NW_CAP_RULE"); return !(e && e[0] == '0'); }();
-    if (cap == 3 && cap_rule) return 4;
+    if (cap == 3) return 4;
     auto cost = [&](int nw) { const long long wg = (tiles / units + nw - 1) / nw; return ((wg + 255) / 256) * ((nw + 3) / 4) * units; };
     return cost(8) <= cost(4) ? 8 : 4;
 }
@@ -132,7 +131,7 @@ static int attn_cap(int Cp, int tmw) { const int v = Cp * tmw; return v <= 96 ? 
 // and a combine pass adds their fc2 partial sums in fixed order.  The rule depends on the layer geometry only - never on the
 // batch - so that a clip's arithmetic (and therefore its codes) is identical in any batch or shard it is processed in.
 // The partial sums live in the (otherwise unused) hidden-activation buffer of the unfused path: needs hiddenP >= 3 * Cp.
-static int mlp_hs_for(int tokens_per_clip, int HT, int Cp) { static const int lim = [] { const char* e = ESCX_TUNE_ENV("ESCX_MLP_HS_TOKENS"); return e && e[0] ? atoi(e) : 1200; }(); return (tokens_per_clip <= lim && HT % 3 == 0 && HT * 16 >= 3 * Cp) ? 3 : 1; }
+static int mlp_hs_for(int tokens_per_clip, int HT, int Cp) { return (tokens_per_clip <= 1200 && HT % 3 == 0 && HT * 16 >= 3 * Cp) ? 3 : 1; }
 // The same split over the head groups of the fused attention (partials share the buffer; an MLP always follows on the same
 // stream).  Like the hidden split it would have to depend on the clip's geometry only, never on the batch (it re-associates the projection
 // sum).  Measured with ESCX_ATTN_GS_TOKENS=600 (the C = 384 scale of a 3 s clip; tools/small_batch.py): one clip 3.52 -> 3.12 ms, 4 clips
@@ -156,6 +155,11 @@ static int mlp_split_nw(int M, int hs) {
     const long long tiles = (M + 15) / 16;
     return ((tiles + 3) / 4) * hs <= 192 ? 4 : 8;
 }
+// variant of the LDS-staged fused MLP (fused_swin.hip: 1 = 4 waves, 3 = 8 waves per workgroup) for a layer's hidden split hs
+static int mlp_variant_choice(int hs, int M, int Cp) {
+    if (hs > 1) return (Cp >= 384 && mlp_split_nw(M, hs) == 8) ? 3 : 1;
+    return mlp_variant_for(M, Cp);
+}
 
 // One TransformerLayer on padded token maps.  x_in is read-only; y receives (B, H'*W, CoutP).
 // attention.py:48-91 (layer), 129-178 (block): LN1 -> pad -> roll -> windows -> attention -> reverse -> residual -> MLP.
@@ -166,23 +170,6 @@ static int run_layer(escx_handle_s* h, const Layer& L, const float* x_in, float*
     float* cur = L.scale ? h->work : y;
     const float* src = x_in;
     int rc;
-    // Combine of a hidden-split MLP (fused_mlp.h), alternative form: not a launch of its own - the NEXT kernel of the layer (the following block's
-    // fused attention, or the merge / split) forms x + (((P0 + P1) + P2) + bias) while it loads its rows (same arithmetic, same order: bit-identical).
-    // Motivation: in the two-stream execution the 20 short combine launches per step cost 2.6x their isolated time (they queue behind the other batch
-    // part's resident workgroups).  Consumers without a combine-on-load instantiation get the explicit rows_combine launch.
-    // OPT-IN (ESCX_COMBINE_ON_LOAD=1).  MEASURED (round 4, B = 36, profiles/r4_mlp_combine_ab.txt): bit-identical, and slower - the consumers' gather
-    // prologues are latency-bound and badly coalesced (64-byte pieces), four row reads there (twice in the attention: LayerNorm input and shortcut) cost
-    // more than the streaming combine launch at 6 TB/s: attention C = 192 / 384 +0.14 / +0.13, merge / split +0.18 ms per step against 0.30 removed.
-    static const bool comb_on_load = [] { const char* e = ESCX_TUNE_ENV("ESCX_COMBINE_ON_LOAD"); return e && e[0] == '1'; }();
-    CombineOnLoad pend{nullptr, nullptr, 0, 0};
-    std::string pend_tag;
-    auto flush_pending = [&]() {                        // explicit combine launch (fallback)
-        if (pend.n > 0) {
-            const double dMp = M;
-            PROF("mlp_combine" + pend_tag, 0, (pend.n + 2) * dMp * L.Cp * sizeof(float), rows_combine(cur, cur, pend.partial, pend.bias, M, L.Cp, pend.n, st));
-            pend.n = 0;
-        }
-    };
     for (size_t j = 0; j < L.blocks.size(); ++j) {
         const BlockW& bw = L.blocks[j];
         const int shift = (j % 2 == 0) ? 0 : ws / 2;                          // attention.py:29
@@ -193,30 +180,18 @@ static int run_layer(escx_handle_s* h, const Layer& L, const float* x_in, float*
         bool attn_done = false;
         if (h->use_fused && h->use_fused_attn && L.attn_mode >= 0) {
             int frc = 0;
-            int nw = h->attn_nw ? h->attn_nw : ((L.Cp > 192 || (L.Cp == 192 && bw.x3a)) ? 4 : pick_nw(Ms / 16, attn_windows_per_wave(L.Cp), attn_cap(L.Cp, attn_windows_per_wave(L.Cp))));    // 8 waves cap the kernel at 256 VGPRs: spills above C = 192
-            if (H == 2 && W % 4 == 0 && h->attn_pack) nw = -(h->attn_nw ? h->attn_nw : (L.Cp > 192 ? 4 : pick_nw((Ms / 16 + 1) / 2, 1)));    // packed half-window pairs
+            int nw = (L.Cp > 192 || (L.Cp == 192 && bw.x3a)) ? 4 : pick_nw(Ms / 16, attn_windows_per_wave(L.Cp), attn_cap(L.Cp, attn_windows_per_wave(L.Cp)));    // 8 waves cap the kernel at 256 VGPRs: spills above C = 192
+            if (H == 2 && W % 4 == 0) nw = -(L.Cp > 192 ? 4 : pick_nw((Ms / 16 + 1) / 2, 1));    // packed half-window pairs
             const double proj_rows = nw < 0 ? dM : dMs;         // packed pairs project only the real tokens
-            int gs = h->attn_gs > 0 ? (L.hiddenP >= h->attn_gs * L.Cp ? h->attn_gs : 1) : attn_gs_for(h, tokens, L.n_groups, L.hiddenP, L.Cp);
-            bool launched = false;
-            if (pend.n > 0) {                           // block input still split over the previous MLP's slabs: combine on load if this kernel can
-                int gs0 = gs;
-                const size_t n_recs = h->prof_recs.size();
-                PROF("attn_fused" + tag, 2 * proj_rows * dC * 4 * dC + 4 * dMs * 16 * dC, (2 + pend.n) * dM * dC * f4,
-                     frc = attn_fused(src, cur, L.Cp, L.C, L.attn_mode, L.n_groups, bw.ln1_g, bw.ln1_b, bw.waf, bw.baf, bw.bias_tab_f, bw.bproj,
-                                      map, slots, tokens, Ms / 16, Hp / 4, Wp / 4, shift > 0, 1.0f / std::sqrt((float)L.hd), nw, &gs0, h->hid, M, st, &pend));
-                if (frc == 0) { pend.n = 0; gs = gs0; launched = true; }
-                else { if (h->prof_recs.size() > n_recs) h->prof_recs.pop_back(); flush_pending(); }      // nothing was launched: no record, explicit combine
-            }
-            if (!launched)
+            int gs = attn_gs_for(h, tokens, L.n_groups, L.hiddenP, L.Cp);
             PROF("attn_fused" + tag, 2 * proj_rows * dC * 4 * dC + 4 * dMs * 16 * dC, 2 * dM * dC * f4,
                  frc = attn_fused(src, cur, L.Cp, L.C, L.attn_mode, L.n_groups, bw.ln1_g, bw.ln1_b, bw.waf, bw.baf, bw.bias_tab_f, bw.bproj,
-                                  map, slots, tokens, Ms / 16, Hp / 4, Wp / 4, shift > 0, 1.0f / std::sqrt((float)L.hd), nw, &gs, h->hid, M, st, nullptr, nullptr, (nw > 0 || L.Cp == 384) ? bw.x3a : nullptr, bw.x3a_pairs ? 1 : (x3_nt(h) == 2 ? 2 : 0)));      // C = 384: the split stream exists for the packed (nw < 0) kernel only
+                                  map, slots, tokens, Ms / 16, Hp / 4, Wp / 4, shift > 0, 1.0f / std::sqrt((float)L.hd), nw, &gs, h->hid, M, st, nullptr, (nw > 0 || L.Cp == 384) ? bw.x3a : nullptr, x3_nt(h)));      // C = 384: the split stream exists for the packed (nw < 0) kernel only
             attn_done = (frc == 0);
             if (attn_done && gs > 1)
                 PROF("attn_combine" + tag, 0, (gs + 2) * dM * L.Cp * f4, rows_combine(cur, src, h->hid, bw.bproj, M, L.Cp, gs, st));
         }
         if (!attn_done) {
-        flush_pending();
         PROF("ln1_gather" + tag, 0, (dM + dMs) * dC * f4,
              ln_rows(1, src, h->xn, bw.ln1_g, bw.ln1_b, map, slots, tokens, Ms, L.C, L.Cp, st));
         PROF("gemm_qkv" + tag, 2 * dMs * dC * 3 * dC, (dMs * 4 * dC + 3 * dC * dC) * f4,
@@ -234,49 +209,39 @@ static int run_layer(escx_handle_s* h, const Layer& L, const float* x_in, float*
         }
         if (h->use_fused) {
             int frc = 0;
-            static const int hs_nw8_cp = [] { const char* e = ESCX_TUNE_ENV("ESCX_MLP_HS_NW8_CP"); return e && e[0] ? atoi(e) : 384; }();
-            static const int tm2_max = [] { const char* e = ESCX_TUNE_ENV("ESCX_MLP_TM2_MAXCP"); return e && e[0] ? atoi(e) : 0; }();
-            static const int tm2_nw8 = [] { const char* e = ESCX_TUNE_ENV("ESCX_MLP_TM2_NW8"); return e && e[0] == '1'; }();
-            bool combined = false;
-            int hs = (h->mlp_hs > 0 && L.hiddenP >= h->mlp_hs * L.Cp) ? h->mlp_hs : mlp_hs_for(tokens, L.hiddenP / 16, L.Cp);
-            const int variant = h->mlp_variant >= 0 ? h->mlp_variant : (hs > 1 ? ((L.Cp >= hs_nw8_cp && mlp_split_nw(M, hs) == 8) ? 3 : 1) : (L.Cp <= tm2_max ? (tm2_nw8 ? 5 : 4) : mlp_variant_for(M, L.Cp)));
-            static const int x3_nw_force = [] { const char* e = ESCX_TUNE_ENV("ESCX_MLP_X3_NW"); return e && e[0] ? atoi(e) : 0; }();
-            if (bw.x3w && pend.n == 0) {       // three-term bf16 split on the bf16 matrix cores (fused_mlp_x3.h); same hidden-split rule and combine
+            int hs = mlp_hs_for(tokens, L.hiddenP / 16, L.Cp);
+            const int variant = mlp_variant_choice(hs, M, L.Cp);
+            if (bw.x3w) {       // three-term bf16 split on the bf16 matrix cores (fused_mlp_x3.h); same hidden-split rule and combine
                 if (h->mlp_split_fold && L.scale == 2 && j + 1 == L.blocks.size() && hs == 1 && L.sub_x3s) {      // PatchSplit in the epilogue of the layer's last MLP
                     const MlpSplit sp{reinterpret_cast<const float*>(L.sub_x3s), L.sub_g, L.sub_b, y, 2 * L.CoutP / 16, H, W, L.CoutP};
                     int src3 = -1, one = 1;
                     PROF("mlp_x3_split" + tag, 4 * dM * dC * L.hidden + 2.0 * dM * dC * 2 * L.Cout, (dM * dC + dM * 2 * L.Cout) * f4,
-                         src3 = mlp_x3(cur, M, L.C, L.Cp, bw.ln2_g, bw.ln2_b, bw.b1, bw.b2, bw.x3w, L.hiddenP, x3_nw_force ? x3_nw_force : mlp_x3_nw(M, L.Cp, variant), &one, nullptr, st, &sp, x3_nt(h)));
+                         src3 = mlp_x3(cur, M, L.C, L.Cp, bw.ln2_g, bw.ln2_b, bw.b1, bw.b2, bw.x3w, L.hiddenP, mlp_x3_nw(M, L.Cp, variant), &one, nullptr, st, &sp, x3_nt(h)));
                     if (src3 == 0) { *Hout = 2 * H; return launch_ok(L.prefix.c_str()); }
                     if (h->prof && !h->prof_recs.empty()) h->prof_recs.pop_back();
                 }
                 int xrc = -1, xhs = hs;
                 PROF("mlp_x3" + tag, 4 * dM * dC * L.hidden, 2 * dM * dC * f4,
-                     xrc = mlp_x3(cur, M, L.C, L.Cp, bw.ln2_g, bw.ln2_b, bw.b1, bw.b2, bw.x3w, L.hiddenP, x3_nw_force ? x3_nw_force : mlp_x3_nw(M, L.Cp, variant), &xhs, h->hid, st, nullptr, x3_nt(h)));
+                     xrc = mlp_x3(cur, M, L.C, L.Cp, bw.ln2_g, bw.ln2_b, bw.b1, bw.b2, bw.x3w, L.hiddenP, mlp_x3_nw(M, L.Cp, variant), &xhs, h->hid, st, nullptr, x3_nt(h)));
                 if (xrc == 0) {
-                    if (xhs > 1) { pend = CombineOnLoad{h->hid, bw.b2, (long long)M * L.Cp, xhs}; pend_tag = tag; flush_pending(); }
+                    if (xhs > 1) PROF("mlp_combine" + tag, 0, (xhs + 2) * dM * L.Cp * f4, rows_combine(cur, cur, h->hid, bw.b2, M, L.Cp, xhs, st));
                     src = cur; continue;
                 }
                 if (h->prof && !h->prof_recs.empty()) h->prof_recs.pop_back();
             }
             // PatchSplit in the epilogue of the layer's last MLP (fused_mlp.h SPLIT): one launch and one HBM round trip of the
             // pre-split map less.  ESCX_MLP_SPLIT_FOLD=0: the separate LN + linear launch (rowgemm_fused_kernel), as before.
-            if (h->mlp_split_fold && L.scale == 2 && j + 1 == L.blocks.size() && hs == 1 && pend.n == 0) {
+            if (h->mlp_split_fold && L.scale == 2 && j + 1 == L.blocks.size() && hs == 1) {
                 const MlpSplit sp{L.sub_wf, L.sub_g, L.sub_b, y, 2 * L.CoutP / 16, H, W, L.CoutP};
                 int sfrc = -1;
                 PROF("mlp_split_fused" + tag, 4 * dM * dC * L.hidden + 2.0 * dM * dC * 2 * L.Cout, (dM * dC + dM * 2 * L.Cout) * f4,
-                     sfrc = mlp_fused(cur, M, L.C, L.Cp, bw.ln2_g, bw.ln2_b, bw.w1f, bw.b1, bw.w2f, bw.b2, bw.wcf, L.hiddenP, variant, &hs, h->hid, st, nullptr,
-                                     nullptr, 0, nullptr, &sp));
+                     sfrc = mlp_fused(cur, M, L.C, L.Cp, bw.ln2_g, bw.ln2_b, bw.w1f, bw.b1, bw.w2f, bw.b2, bw.wcf, L.hiddenP, variant, &hs, h->hid, st, nullptr, &sp));
                 if (sfrc == 0) { *Hout = 2 * H; return launch_ok(L.prefix.c_str()); }
                 if (h->prof && !h->prof_recs.empty()) h->prof_recs.pop_back();      // no SPLIT instantiation for this width: nothing was launched
             }
             PROF("mlp_fused" + tag, 4 * dM * dC * L.hidden, 2 * dM * dC * f4,
-                 frc = mlp_fused(cur, M, L.C, L.Cp, bw.ln2_g, bw.ln2_b, bw.w1f, bw.b1, bw.w2f, bw.b2, bw.wcf, L.hiddenP, variant, &hs, h->hid, st, nullptr,
-                                 h->tickets, WsFields::N_TICKETS, &combined));
-            if (frc == 0 && hs > 1 && !combined) {
-                pend = CombineOnLoad{h->hid, bw.b2, (long long)M * L.Cp, hs}; pend_tag = tag;
-                if (!comb_on_load) flush_pending();
-            }
+                 frc = mlp_fused(cur, M, L.C, L.Cp, bw.ln2_g, bw.ln2_b, bw.w1f, bw.b1, bw.w2f, bw.b2, bw.wcf, L.hiddenP, variant, &hs, h->hid, st));
+            if (frc == 0 && hs > 1) PROF("mlp_combine" + tag, 0, (hs + 2) * dM * L.Cp * f4, rows_combine(cur, cur, h->hid, bw.b2, M, L.Cp, hs, st));
             if (frc == 0) { src = cur; continue; }
         }
         PROF("ln2" + tag, 0, 2 * dM * dC * f4,
@@ -292,16 +257,9 @@ static int run_layer(escx_handle_s* h, const Layer& L, const float* x_in, float*
         const int* map;
         if ((rc = get_map(h, H, W, -1, &map))) return rc;
         int mrc = -1;
-        if (h->use_fused && pend.n > 0) {
-            const size_t n_recs = h->prof_recs.size();
-            PROF("merge_fused" + (h->prof ? "[C=" + std::to_string(L.C) + "]" : std::string()), 2.0 * B * H2 * W * 2 * L.C * L.Cout, ((double)M * L.C * (1 + pend.n) + (double)B * H2 * W * L.Cout) * 4,
-                 mrc = rowgemm_fused(2, cur, y, L.sub_g, L.sub_b, L.sub_wf, map, B * H2 * W, H2 * W, tokens, L.C, L.Cp, L.CoutP, 0, 0, 0, 0, st, &pend));
-            if (mrc == 0) pend.n = 0; else if (h->prof_recs.size() > n_recs) h->prof_recs.pop_back();
-        }
-        flush_pending();
-        if (h->use_fused && mrc != 0)
+        if (h->use_fused)
             PROF("merge_fused" + (h->prof ? "[C=" + std::to_string(L.C) + "]" : std::string()), 2.0 * B * H2 * W * 2 * L.C * L.Cout, ((double)M * L.C + (double)B * H2 * W * L.Cout) * 4,
-                 mrc = rowgemm_fused(2, cur, y, L.sub_g, L.sub_b, L.sub_wf, map, B * H2 * W, H2 * W, tokens, L.C, L.Cp, L.CoutP, 0, 0, 0, 0, st, nullptr, L.sub_x3, x3_nt(h)));
+                 mrc = rowgemm_fused(2, cur, y, L.sub_g, L.sub_b, L.sub_wf, map, B * H2 * W, H2 * W, tokens, L.C, L.Cp, L.CoutP, 0, 0, 0, 0, st, L.sub_x3, x3_nt(h)));
         if (mrc != 0) {
         PROF("merge_ln", 0, 2.0 * M * L.C * 4,
              ln_rows(2, cur, h->xn, L.sub_g, L.sub_b, map, H2 * W, tokens, B * H2 * W, L.C, L.Cp, st));
@@ -311,16 +269,9 @@ static int run_layer(escx_handle_s* h, const Layer& L, const float* x_in, float*
         *Hout = H2;
     } else if (L.scale == 2) {
         int src2 = -1;
-        if (h->use_fused && pend.n > 0) {
-            const size_t n_recs = h->prof_recs.size();
-            PROF("split_fused" + (h->prof ? "[C=" + std::to_string(L.C) + "]" : std::string()), 2.0 * M * L.C * 2 * L.Cout, (double)M * (L.C * (1 + pend.n) + 2 * L.Cout) * 4,
-                 src2 = rowgemm_fused(1, cur, y, L.sub_g, L.sub_b, L.sub_wf, nullptr, M, tokens, tokens, L.C, L.Cp, 2 * L.CoutP, 1, H, W, L.CoutP, st, &pend));
-            if (src2 == 0) pend.n = 0; else if (h->prof_recs.size() > n_recs) h->prof_recs.pop_back();
-        }
-        flush_pending();
-        if (h->use_fused && src2 != 0)
+        if (h->use_fused)
             PROF("split_fused" + (h->prof ? "[C=" + std::to_string(L.C) + "]" : std::string()), 2.0 * M * L.C * 2 * L.Cout, (double)M * (L.C + 2 * L.Cout) * 4,
-                 src2 = rowgemm_fused(1, cur, y, L.sub_g, L.sub_b, L.sub_wf, nullptr, M, tokens, tokens, L.C, L.Cp, 2 * L.CoutP, 1, H, W, L.CoutP, st, nullptr, L.sub_x3, x3_nt(h)));
+                 src2 = rowgemm_fused(1, cur, y, L.sub_g, L.sub_b, L.sub_wf, nullptr, M, tokens, tokens, L.C, L.Cp, 2 * L.CoutP, 1, H, W, L.CoutP, st, L.sub_x3, x3_nt(h)));
         if (src2 != 0) {
         PROF("split_ln", 0, 2.0 * M * L.C * 4,
              ln_rows(0, cur, h->xn, L.sub_g, L.sub_b, nullptr, tokens, tokens, M, L.C, L.Cp, st));
@@ -329,7 +280,6 @@ static int run_layer(escx_handle_s* h, const Layer& L, const float* x_in, float*
         }
         *Hout = 2 * H;
     } else {
-        flush_pending();
         *Hout = H;
     }
     return launch_ok(L.prefix.c_str());
@@ -391,8 +341,6 @@ static int ensure_pvq_tables(escx_handle_s* h, hipStream_t st) {
     }
     const int nt = x3_nt(h);
     const bool split_on = h->prec != 0;
-    // tagged builds only: the two-term images WITHOUT the activation scales of the range rule (what tests/test_gpu_parity.py test_range_stress_checkpoints guards against)
-    static const bool no_act_scale = [] { const char* e = ESCX_TUNE_ENV("ESCX_X2_NO_ACT_SCALE"); return e && e[0] == '1'; }();
     const int x3_max = split_on ? h->mlp_x3_max : 0;
     // the two-term fp16 stream of the halo-tiled de-embedding (fused_deembed.h deembed7_x2_kernel): in the two-term mode only - the three-term mode and the fp32-MFMA
     // mode keep the fp32 kernel (the latter stays bit-identical to round 4)
@@ -407,7 +355,7 @@ static int ensure_pvq_tables(escx_handle_s* h, hipStream_t st) {
             const bool want = x3_max > 0 && L.Cp <= x3_max && (L.Cp == 48 || L.Cp == 80 || L.Cp == 96 || L.Cp == 144 || L.Cp == 192 || L.Cp == 384) && L.hiddenP % 32 == 0;
             bw.x3w = nullptr;
             if (want && grab(&bw.x3w_buf, mlp_x3_bytes(L.Cp, L.hiddenP, 3)) &&         // sized for the larger (three-term) image
-                mlp_x3_pack(bw.w1, bw.w2, bw.x3w_buf, L.Cp, L.hiddenP, st, nt, no_act_scale ? nullptr : bw.ln2_g, bw.ln2_b, bw.b1, L.C) == 0) bw.x3w = bw.x3w_buf;
+                mlp_x3_pack(bw.w1, bw.w2, bw.x3w_buf, L.Cp, L.hiddenP, st, nt, bw.ln2_g, bw.ln2_b, bw.b1, L.C) == 0) bw.x3w = bw.x3w_buf;
         }
     // the split Q / K / V weight streams of the fused attention (fused_attn.h X3)
     const int ax3_max = split_on ? h->attn_x3_max : 0;
@@ -417,12 +365,7 @@ static int ensure_pvq_tables(escx_handle_s* h, hipStream_t st) {
                               ((L.Cp == 48 && L.attn_mode == 0) || (L.Cp == 80 && L.attn_mode != 1) || (L.Cp == 96 && L.attn_mode != 2) || (L.Cp == 144 && L.attn_mode != 2) || (L.Cp == 192 && L.attn_mode == 1) || (L.Cp == 384 && L.attn_mode == 0));      // 384: the packed H = 2 kernel only (the launcher falls back to fp32 elsewhere)
             bw.x3a = nullptr;
             if (!want || !grab(&bw.x3a_buf, attn_x3_bytes(L.Cp, L.attn_mode, L.n_groups))) continue;
-            // pair order (the output projection in split form too) where two head groups always travel together: mode 0 / 1, group counts that stay even under the 3-way head-group split
-            // OPT-IN, tagged builds (ESCX_ATTN_X3_PAIRS=1): measured no faster - the operand split of the O^T tiles and the two extra stage barriers per pair eat the
-            // matrix time saved, and at C = 192 the kernel drops to one wave per SIMD (profiles/r5_attn_ab.txt)
-            static const bool pairs_on = [] { const char* e = ESCX_TUNE_ENV("ESCX_ATTN_X3_PAIRS"); return e && e[0] == '1'; }();
-            bw.x3a_pairs = pairs_on && nt == 3 && L.attn_mode != 2 && L.Cp != 48 && L.n_groups % 2 == 0 && (L.n_groups % 3 != 0 || (L.n_groups / 3) % 2 == 0);
-            if (attn_x3_pack(bw.waf, bw.x3a_buf, L.Cp, L.attn_mode, L.n_groups, st, bw.x3a_pairs ? 1 : (nt == 2 ? 2 : 0), no_act_scale ? nullptr : bw.ln1_g, bw.ln1_b, L.C, bw.baf) == 0) bw.x3a = bw.x3a_buf;
+            if (attn_x3_pack(bw.waf, bw.x3a_buf, L.Cp, L.attn_mode, L.n_groups, st, nt, bw.ln1_g, bw.ln1_b, L.C, bw.baf) == 0) bw.x3a = bw.x3a_buf;
         }
     // the split weight streams of PatchMerge / PatchSplit (fused_rowgemm.h rowgemm_x3_kernel)
     for (Layer& L : h->layers) {
@@ -430,7 +373,7 @@ static int ensure_pvq_tables(escx_handle_s* h, hipStream_t st) {
         const bool want = split_on && h->rowgemm_x3 && L.scale != 0 && L.sub_wf && (KP == 80 || KP == 96 || KP == 144 || KP == 160 || KP == 192 || KP == 288 || KP == 384);
         L.sub_x3 = nullptr; L.sub_x3s = nullptr;
         if (!want || !grab(&L.sub_x3_buf, rowgemm_x3_bytes(KP, Np))) continue;
-        if (rowgemm_x3_pack(L.sub_wf, L.sub_x3_buf, KP, Np, st, nt, no_act_scale ? nullptr : L.sub_g, L.sub_b, (L.scale == 1 ? 2 : 1) * L.C) == 0) L.sub_x3 = L.sub_x3_buf;
+        if (rowgemm_x3_pack(L.sub_wf, L.sub_x3_buf, KP, Np, st, nt, L.sub_g, L.sub_b, (L.scale == 1 ? 2 : 1) * L.C) == 0) L.sub_x3 = L.sub_x3_buf;
         if (L.scale == 2 && (L.Cp == 80 || L.Cp == 96 || L.Cp == 144) && L.Cp <= x3_max && grab(&L.sub_x3s_buf, mlp_x3_split_bytes(L.Cp, Np)) &&       // PatchSplit folded into the split-operand MLP's epilogue
             mlp_x3_split_pack(L.sub_wf, L.sub_x3s_buf, L.Cp, Np, st) == 0) L.sub_x3s = L.sub_x3s_buf;
     }
@@ -456,16 +399,8 @@ static int run_pvq_encode(escx_handle_s* h, const Quant& q, const float* enc, co
     const int splits = pvq_down_splits(M, q.Kq, q.Cp);
     if ((size_t)splits * M * q.Nz > h->zpart_cap) ESCX_FAIL(ESCX_ERR_STATE, "split-K scratch too small");
     const double vec = (double)c.overlap * q.Hq * q.C;
-    static const bool special = [] { const char* e = ESCX_TUNE_ENV("ESCX_PVQ_DOWN_KERNEL"); return e && e[0] == '1'; }();   // opt-in: bit-identical but slower than the engine form (profiles/r4_pvq_ab.txt)
-    int drc = -1;
-    if (special)
-        PROF("pvq_down_gemm", 2.0 * M * vec * q.d, (double)M * vec * (dec ? 2 : 1) * 4,
-             drc = pvq_down(enc, dec, B, q.Hq, W, q.Cp, c.overlap, q.wd, q.Nz, q.Kq, h->zpart, splits, pvq_down_bk(q.Cp), st));
-    if (drc != 0) {
-        if (special && h->prof && !h->prof_recs.empty()) h->prof_recs.pop_back();
     PROF("pvq_down_gemm", 2.0 * M * vec * q.d, (double)M * vec * (dec ? 2 : 1) * 4,
          gemm_pvq_down(enc, dec, B, q.Hq, W, q.Cp, c.overlap, q.wd, q.Nz, q.Kq, h->zpart, splits, st));
-    }
     int src_rc = 0;
     PROF("pvq_search", 2.0 * M * c.group_size * c.codebook_size * q.d, ((double)c.group_size * c.codebook_size * q.d + (double)M * c.group_size * q.d) * 4,
          src_rc = pvq_search(h->zpart, splits, M, q.Nz, q.cbn, q.c2, q.cbraw, c.group_size, c.codebook_size, q.d, q.dt, Tq, codes, bstride,

@@ -39,7 +39,6 @@ struct BlockW {                      // one SwinBlock, packed
     float *waf, *baf, *bias_tab_f;   // fused attention: weight stream [group][tile][KK][64][4], tile biases, padded bias table
     float *wqkvT = nullptr, *wprojT = nullptr, *w1T = nullptr, *w2T = nullptr;     // transposed copies for the dX GEMMs of the training step
     long long tab_off = -1;          // flat offset of attn.relative_position_bias_table (its gradient is written there directly)
-    bool x3a_pairs = false;          // x3a is in pair order (output projection split as well: fused_attn.h X3P)
     // Split-operand weight images (derived state, rebuilt by ensure_derived() in escx_api.cpp whenever the parameters or the precision mode change).  `x3a` / `x3w` are the
     // ACTIVE images (null = this block runs the fp32-MFMA kernel); the `_buf` pointers own the allocations, which are made once and kept across mode switches.
     void* x3a = nullptr;             // fused_attn.h X3: Q / K / V tiles split into terms
@@ -92,8 +91,6 @@ struct WsFields {                    // one workspace: every scratch buffer of t
     float *decA = nullptr, *decB = nullptr, *zpart = nullptr, *deemb = nullptr, *rspec = nullptr, *frames = nullptr;
     float *stageA = nullptr, *stageB = nullptr, *loss = nullptr, *loss_terms = nullptr;     // loss_terms: [max_streams][G][B*Tq] per-vector commitment terms
     long long* codes_tmp = nullptr;
-    int* tickets = nullptr;          // arrival counters of the in-launch combine of the hidden-split MLP (fused_mlp.h): zero between launches
-    static constexpr int N_TICKETS = 16384;
     std::vector<float*> enc_hs;
     size_t zpart_cap = 0;
 };
@@ -131,10 +128,6 @@ struct escx_handle_s : escx::WsFields {      // the inherited fields are the CUR
     std::vector<std::string> required;
     bool finalized = false;
     bool use_fused = true;           // ESCX_NO_FUSED=1 selects the unfused GEMM pipeline (A/B and fallback)
-    int mlp_variant = -1;            // ESCX_MLP_VARIANT overrides the per-layer choice (tuning)
-    int attn_gs = 0;                 // ESCX_ATTN_GS: same for the head groups of the fused attention
-    int mlp_hs = 0;                  // ESCX_MLP_HS: 0 = automatic hidden split, 1 = off, n = force n-way (tuning)
-    int attn_nw = 0;                 // ESCX_ATTN_NW: waves per workgroup of the fused attention kernel (4 or 8)
     bool use_fused_attn = true;      // ESCX_NO_FUSED_ATTN=1
     // Arithmetic of the dense contractions with K = C (MLPs, Q / K / V, PatchMerge / PatchSplit, de-embedding): escx_set_precision (include/escx.h).
     //   0 = fp32 MFMA, 3 = three bf16 terms per fp32 operand (exact split), 2 = two fp16 terms (range rule of split_terms.h).  The environment only sets the DEFAULT.
@@ -142,13 +135,12 @@ struct escx_handle_s : escx::WsFields {      // the inherited fields are the CUR
     int mlp_x3_max = 384, attn_x3_max = 384;     // ESCX_MLP_X3 / ESCX_ATTN_X3: largest padded width that runs split (A/B and fallback switches; 0 = that family on the fp32 MFMA)
     bool rowgemm_x3 = true, pvq_table = true;    // ESCX_ROWGEMM_X3=0 / ESCX_PVQ_TABLE=0
     // The remaining fallback / A-B switches of the launch sequences.  Round 6: EVERY product switch is a field of the handle, filled once by env_defaults() in escx_params.cpp -
-    // the one place of the inference host code that reads the environment (train.hip / disc.hip keep their own few; tuning switches of rejected forms: tune_env.h).
+    // the one place of the inference host code that reads the environment (train.hip / disc.hip keep their own few).
     int attn_gs_tokens = 600;        // ESCX_ATTN_GS_TOKENS: head-group split of the attention for maps of up to this many tokens per clip (0 = off)
     bool mlp_split_fold = true;      // ESCX_MLP_SPLIT_FOLD=0: PatchSplit as its own launch instead of the MLP epilogue
     bool pvq_fused = true, pvq_up_kernel = true;      // ESCX_PVQ_FUSED=0: three-launch quantiser; ESCX_PVQ_UP_KERNEL=0: the GEMM engine's generic up-projection
     bool prof_serial = false;        // ESCX_PROF_SERIAL=1: profiled runs put the batch parts back to back
     int ws = 4;                      // window_size of the configuration (4: fused kernels; other sizes: unfused sequence with window_attention_any_kernel)
-    bool attn_pack = true;           // ESCX_NO_ATTN_PACK=1: do not pack half-real windows of the H == 2 scale
 
     escx::Arena wts;                 // packed weights
     std::vector<escx::Layer> layers; // 2n entries (see escx_transformer_layer)

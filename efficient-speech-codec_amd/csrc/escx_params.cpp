@@ -152,7 +152,7 @@ static int build_geometry(escx_handle_s* h) {
 
 // The ONE place of the inference host code that reads the environment (round 6; VERDICT r5 hygiene #14): defaults of a new handle.  Product switches are documented fallbacks and
 // A/B arms the tests exercise (tests/test_gpu_parity.py test_fallback_kernel_forms_against_the_default); the precision mode has a C-ABI setter (escx_set_precision), the
-// environment only names its default.  Tuning switches of measured-and-rejected kernel forms go through ESCX_TUNE_ENV (null in the default build, tune_env.h).
+// environment only names its default.  Every switch the library reads is a product switch.
 static int env_defaults(escx_handle_s* h) {
     auto flag = [](const char* name, bool dflt) { const char* e = getenv(name); return (e && e[0]) ? e[0] == '1' : dflt; };
     auto off = [](const char* name) { const char* e = getenv(name); return e && e[0] == '0'; };
@@ -172,11 +172,6 @@ static int env_defaults(escx_handle_s* h) {
     h->pvq_fused = !off("ESCX_PVQ_FUSED");
     h->pvq_up_kernel = !off("ESCX_PVQ_UP_KERNEL");
     h->prof_serial = flag("ESCX_PROF_SERIAL", false);
-    { const char* e = ESCX_TUNE_ENV("ESCX_MLP_VARIANT"); if (e && e[0]) h->mlp_variant = atoi(e); }
-    { const char* e = ESCX_TUNE_ENV("ESCX_MLP_HS"); if (e && e[0]) h->mlp_hs = atoi(e); }
-    { const char* e = ESCX_TUNE_ENV("ESCX_ATTN_GS"); if (e && e[0]) h->attn_gs = atoi(e); }
-    { const char* e = ESCX_TUNE_ENV("ESCX_ATTN_NW"); if (e && e[0]) h->attn_nw = atoi(e); }
-    { const char* e = ESCX_TUNE_ENV("ESCX_NO_ATTN_PACK"); h->attn_pack = !(e && e[0] == '1'); }
     // precision DEFAULT of new handles (escx_set_precision changes it per handle): ESCX_PRECISION=fp32|bf16x3|f16x2 (or 0|3|2); ESCX_X3_TERMS=3 is the round-5 spelling of bf16x3
     if (num("ESCX_X3_TERMS", 2) == 3) h->prec = 3;
     if (const char* e = getenv("ESCX_PRECISION")) {
@@ -942,7 +937,7 @@ static int reserve_frames(escx_handle_s* h, int Btotal, int T, int set_clips_min
     add(spec); for (int i = 0; i < n; ++i) add(ehs[i]);
     add(work); add(xn); add(qkv); add(ob); add(hid); add(dec); add(dec); add(zp); add(deemb); add(rspec); add(frames);
     const size_t lterms = (size_t)std::max(c.max_streams, h->num_rvqs) * c.group_size * B * s.Tq;
-    add(stage); add(stage); add(codes); add(B); add(lterms); add(WsFields::N_TICKETS);
+    add(stage); add(stage); add(codes); add(B); add(lterms);
 
     ESCX_HIP(hipDeviceSynchronize());
     for (int si = 0; si < escx_handle_s::MAX_PARTS; ++si) {
@@ -962,7 +957,6 @@ static int reserve_frames(escx_handle_s* h, int Btotal, int T, int set_clips_min
         S.stageA = S.ws.take(stage); S.stageB = S.ws.take(stage);
         S.codes_tmp = reinterpret_cast<long long*>(S.ws.take(codes));
         S.loss = S.ws.take(B); S.loss_terms = S.ws.take(lterms);
-        S.tickets = reinterpret_cast<int*>(S.ws.take(WsFields::N_TICKETS));     // zero from the hipMemset above; every launch leaves them zero
         if (!S.loss) ESCX_FAIL(ESCX_ERR_STATE, "workspace sizing bug");
         S.shp = s;
     }

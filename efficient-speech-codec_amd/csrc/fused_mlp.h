@@ -29,16 +29,12 @@ struct MlpArgs {
     const f32x4* wcf;                           // per hidden tile: [HT][KK fc1 fragments | KK fc2 fragments][64] (LDS-staged variant)
     int M, C, HT;
     float eps;
-    unsigned long long* trace;                  // debug (ABL bit 64): per-wave cycle sums of the main-loop phases
+    unsigned long long* unused;                 // no kernel reads it: without this slot hipcc schedules mlp_x3_kernel differently (profiles/exp_removal_isa_diff.txt)
     // Hidden split (LDS-staged kernel only): with fewer row tiles than SIMDs (deep layers at small batch) the grid is
     // row-blocks x HS and workgroup (rb, hs) walks hidden tiles [hs*HT/HS, (hs+1)*HT/HS); the fc2 partial sums go to
     // partial[hs][M][CP] and mlp_combine_kernel adds them in fixed order (deterministic, no atomics).
     int HS; float* partial;
     float* out;                 // nullptr: in place; otherwise x is left untouched and x + mlp(x) goes to out (training forward: x1 stays on the tape)
-    // Hidden split with the combine INSIDE the launch (round 4): one arrival counter per row block (zero between launches).  Every workgroup
-    // publishes its slab write-through and takes a ticket; the LAST arriver adds the slabs in slab-index order - ((P0 + P1) + P2) + bias, then
-    // + x, the arithmetic of rows_combine_kernel - and writes x.  nullptr: slabs only, the caller runs rows_combine_kernel.
-    int* tickets;
     // PatchSplit in the epilogue (SPLIT instantiations, round 5; scale.py:131-145): the wave still owns its 16 rows x + mlp(x) in registers after the
     // residual add, and nothing else reads the pre-split map (csrvq.py:173-181), so LayerNorm(C) -> Linear(C -> 2 C', no bias) -> two-row scatter
     // runs right there: the split weights (fragment order, Layer::sub_wf) stream through the same LDS ring as further stages, two output tiles per
@@ -48,12 +44,6 @@ struct MlpArgs {
     int sp_NT, sp_H, sp_W, sp_C2p;
     const void* x3_w;           // fused_mlp_x3.h: split (3 x bf16) weight image [pair of hidden tiles][fragment][lane][8 bf16], or nullptr
 };
-
-// buffer descriptor over [p, p + bytes): raw (stride 0) addressing; for write-through (sc1) stores of hand-off data
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(float* p, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(p, (short)0, (int)bytes, 0x00020000);
-}
 
 template <int CP, int TM>
 __global__ __launch_bounds__(256) void mlp_fused_kernel(MlpArgs a) {
@@ -172,12 +162,9 @@ __global__ __launch_bounds__(256) void mlp_fused_kernel(MlpArgs a) {
 // hidden tile takes ~5600 cycles for 3072 cycles of MFMA work).
 template <int CP, int TM> constexpr int mlp_min_waves() { return (CP * TM <= ESCX_MLP_OCC4) ? 4 : ((CP * TM <= 192) ? 3 : 1); }
 
-// FC: compile the in-launch combine of the hidden split (a.tickets).  A SEPARATE instantiation on purpose: with that code in the body, hipcc
-// allocates registers differently for the whole kernel and the plain (slabs + rows_combine_kernel) path of every hidden-split width gets
-// 10-12 % slower (measured, profiles/r4_mlp_combine_ab.txt).
-template <int CP, int TM, int NW, int ABL = 0, bool FC = false, bool SPLIT = false>      // ABL: timing-only ablation bits (never used by the product path)
+template <int CP, int TM, int NW, bool SPLIT = false>
 __global__ __launch_bounds__(64 * NW, (mlp_min_waves<CP, TM>())) void mlp_fused_lds_kernel(MlpArgs a) {
-    static_assert(!SPLIT || (TM == 1 && ABL == 0 && !FC), "the PatchSplit epilogue exists for the plain one-tile form only");
+    static_assert(!SPLIT || TM == 1, "the PatchSplit epilogue exists for the one-tile form only");
 #ifdef ESCX_MLP_PRIO
     __builtin_amdgcn_s_setprio(ESCX_MLP_PRIO);      // tuning builds: static wave priority against co-running launches of the other batch part
 #endif
@@ -249,31 +236,21 @@ __global__ __launch_bounds__(64 * NW, (mlp_min_waves<CP, TM>())) void mlp_fused_
         for (int t = 0; t < TM; ++t) acc[o][t] = zero4();
 
     f32x4 bias_next = ld4(a.b1 + 16 * ht0 + 4 * lg);      // fc1 bias of the first tile; later tiles are fetched one stage ahead
-    unsigned long long tr[6] = {0, 0, 0, 0, 0, 0};
-#define ESCX_TS(var) unsigned long long var = 0; if (ABL & 64) { __builtin_amdgcn_sched_barrier(0); var = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); }
-    ESCX_TS(t_begin)
     for (int ht = ht0; ht < ht1; ++ht) {
-        ESCX_TS(t0)
-        if (!(ABL & 2)) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();                    // tile ht is in LDS for every wave; nobody still reads the other buffer
-        }
-        ESCX_TS(t1)
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();                    // tile ht is in LDS for every wave; nobody still reads the other buffer
         // The next stage's DMA is not issued in one burst after the barrier (each 1 KiB global_load_lds costs 70-180 issue cycles during
         // which this wave feeds no MFMA, and the burst's landing slows the fc1 LDS reads) but one piece every DSTEP fragments of fc1.
-        constexpr bool SPREAD = (ABL & 256) == 0;
-        if (!SPREAD && ht + 1 < ht1 && !(ABL & 32)) issue(ht + 1, (ht + 1) & 1);
-        // SPREAD: the last stage re-loads its own tile into the idle buffer (harmless) so that the loop body stays branch-free
+        // The last stage re-loads its own tile into the idle buffer (harmless) so that the loop body stays branch-free
         const f32x4* dsrc = (SPLIT && ht + 1 == ht1) ? a.sp_wf + lane                         // SPLIT: the stage after the last hidden tile is the first pair of split tiles
                                                      : a.wcf + (size_t)min(ht + 1, ht1 - 1) * CH * 64 + lane;
         f32x4* ddst = &wbuf[(ht + 1) & 1][0];
-        ESCX_TS(t2)
         // The no-op pin makes the compiler wait for this tile's bias HERE, behind the vmcnt(0) above (free), instead of at its first
         // use after the fc1 MFMAs - where a vmcnt(0) would also wait out the DMA pieces issued in between (an L2 round trip per tile).
         f32x4 bb = bias_next;
         asm volatile("" : "+v"(bb));
         bias_next = ld4(a.b1 + 16 * min(ht + 1, ht1 - 1) + 4 * lg);
-        const f32x4* wb = (ABL & 4) ? &wbuf[0][0] : &wbuf[ht & 1][lane];
+        const f32x4* wb = &wbuf[ht & 1][lane];
 
         // fragment ring: the LDS read of fragment f + PD is in flight while fragment f feeds the MFMAs
         f32x4 ring[PD];
@@ -286,7 +263,7 @@ __global__ __launch_bounds__(64 * NW, (mlp_min_waves<CP, TM>())) void mlp_fused_
         for (int f = 0; f < KK; ++f) {
             const f32x4 w = ring[f % PD];
             if (f + PD < CH) ring[f % PD] = wb[(f + PD) * 64];
-            if constexpr (SPREAD && !(ABL & 32)) {             // one 1 KiB DMA every DSTEP fragments, all issued within the fc1 phase
+            {       // one 1 KiB DMA every DSTEP fragments, all issued within the fc1 phase
                 constexpr int NDMA = (CH + NW - 1) / NW, DSTEP = KK / NDMA > 0 ? KK / NDMA : 1;
                 if (f % DSTEP == 0 && f / DSTEP < NDMA) {
                     int c = wave + (f / DSTEP) * NW;
@@ -302,14 +279,12 @@ __global__ __launch_bounds__(64 * NW, (mlp_min_waves<CP, TM>())) void mlp_fused_
                     else h[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[r], xf[t][f][r], h[t], 0, 0, 0);
                 }
         }
-        ESCX_TS(t3)
 #pragma unroll
         for (int t = 0; t < TM; ++t) {
             if (TM == 1) h[t] += h2[t];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) h[t][e] = (ABL & 1) ? h[t][e] * 0.5f : gelu_bf(h[t][e]);
+            for (int e = 0; e < 4; ++e) h[t][e] = gelu_bf(h[t][e]);
         }
-        ESCX_TS(t4)
         // fc2: two output tiles per step so that consecutive MFMAs never hit the same accumulator
 #pragma unroll
         for (int o = 0; o < KK; o += 2) {
@@ -329,37 +304,23 @@ __global__ __launch_bounds__(64 * NW, (mlp_min_waves<CP, TM>())) void mlp_fused_
                     if (o + 1 < KK) acc[o + 1][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(wn[r], h[t][r], acc[o + 1][t], 0, 0, 0);
                 }
         }
-        ESCX_TS(t5)
-        if (ABL & 64) { tr[0] += t1 - t0; tr[1] += t2 - t1; tr[2] += t3 - t2; tr[3] += t4 - t3; tr[4] += t5 - t4; }
         // Pin the software pipeline: hipcc otherwise sinks every ds_read to just before its first use and
         // waits lgkmcnt(0) there, idling the matrix pipe for a full LDS round trip every 8 MFMAs.
-        if (!(ABL & 64)) {
-            __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);         // next tile's fc1 bias
+        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);         // next tile's fc1 bias
 #pragma unroll
-            for (int i = 0; i < PD; ++i) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+        for (int i = 0; i < PD; ++i) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
 #pragma unroll
-            for (int f = 0; f < CH; ++f) {
-                if (f + PD < CH) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                if constexpr (SPREAD && !(ABL & 32)) {     // the DMA pieces stay where they are issued (unpinned, the scheduler sinks them to the end of the stage)
-                    constexpr int NDMA = (CH + NW - 1) / NW, DSTEP = KK / NDMA > 0 ? KK / NDMA : 1;
-                    if (f < KK && f % DSTEP == 0 && f / DSTEP < NDMA) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-                }
-                __builtin_amdgcn_sched_group_barrier(0x008, 4 * TM, 0);
+        for (int f = 0; f < CH; ++f) {
+            if (f + PD < CH) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+            {       // the DMA pieces stay where they are issued (unpinned, the scheduler sinks them to the end of the stage)
+                constexpr int NDMA = (CH + NW - 1) / NW, DSTEP = KK / NDMA > 0 ? KK / NDMA : 1;
+                if (f < KK && f % DSTEP == 0 && f / DSTEP < NDMA) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
             }
+            __builtin_amdgcn_sched_group_barrier(0x008, 4 * TM, 0);
         }
     }
-    if (ABL & 64) {
-        ESCX_TS(t_end)
-        tr[5] = t_end - t_begin;
-        if (lane == 0 && a.trace) {
-            unsigned long long* o = a.trace + (size_t)(blockIdx.x * NW + wave) * 8;
-            for (int i = 0; i < 6; ++i) o[i] = tr[i];
-            o[6] = t_begin; o[7] = t_end;
-        }
-    }
-#undef ESCX_TS
 
-    if (HS > 1 && (!FC || a.tickets == nullptr)) {       // raw fc2 partial sums; bias + residual are applied by rows_combine_kernel
+    if (HS > 1) {       // raw fc2 partial sums; bias + residual are applied by rows_combine_kernel
 #pragma unroll
         for (int t = 0; t < TM; ++t) {
             const int row = m0 + t * 16 + l15;
@@ -367,56 +328,6 @@ __global__ __launch_bounds__(64 * NW, (mlp_min_waves<CP, TM>())) void mlp_fused_
             float* pr = a.partial + ((size_t)hs * a.M + row) * CP + 4 * lg;
 #pragma unroll
             for (int o = 0; o < KK; ++o) st4(pr + 16 * o, acc[o][t]);
-        }
-        return;
-    }
-    if constexpr (FC) if (HS > 1) {
-        // ---- combine by the last arriver (MI355X_MICROARCH.md, splitk-seam / publish-large rows; cdna_hip_programming.md Guideline 16 R1) ----
-        // Publish: 16-byte sc1 (write-through) stores, so no release fence is needed; EVERY storing wave drains its stores, then ONE lane takes
-        // the ticket with an agent-scope atomic.  The slab bytes are out of this XCD's L2 and in memory before the ticket is visible.
-        const size_t slab = (size_t)a.M * CP;                   // floats per slab; HS * slab * 4 < 2^32 is checked by the launcher
-        const __amdgpu_buffer_rsrc_t rsrc = make_rsrc(a.partial, (unsigned)((size_t)HS * slab * sizeof(float)));
-#pragma unroll
-        for (int t = 0; t < TM; ++t) {
-            const int row = m0 + t * 16 + l15;
-            if (row >= a.M) continue;
-            const unsigned off = (unsigned)((((size_t)hs * a.M + row) * CP + 4 * lg) * sizeof(float));
-#pragma unroll
-            for (int o = 0; o < KK; ++o) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, acc[o][t]), rsrc, off + 64 * o, 0, 16 /* sc1 */);
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __shared__ int ticket_s;
-        __syncthreads();
-        if (threadIdx.x == 0) ticket_s = __hip_atomic_fetch_add(a.tickets + rb, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __syncthreads();
-        if (ticket_s != HS - 1) return;
-        // Last arriver: every other slab of this row block is complete in memory.  ONE agent-scope acquire drops this CU's L1 (nobody on this
-        // XCD has read these lines in this launch, and launch boundaries invalidate L2), then plain loads.  The counter goes back to zero for
-        // the next launch (stream-ordered).
-        if (threadIdx.x == 0) {
-            __hip_atomic_store(a.tickets + rb, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        }
-        __syncthreads();
-#pragma unroll
-        for (int t = 0; t < TM; ++t) {
-            const int row = m0 + t * 16 + l15;
-            if (row >= a.M) continue;
-            const float* xr = a.x + (size_t)row * CP + 4 * lg;
-            f32x4 res[KK], v[KK];
-#pragma unroll
-            for (int o = 0; o < KK; ++o) res[o] = ld4(xr + 16 * o);
-            for (int h2 = 0; h2 < HS; ++h2) {                   // slab-index order, NOT arrival order: bit-identical to rows_combine_kernel
-                const float* pr = a.partial + ((size_t)h2 * a.M + row) * CP + 4 * lg;
-#pragma unroll
-                for (int o = 0; o < KK; ++o) {
-                    const f32x4 p = (h2 == hs) ? acc[o][t] : ld4(pr + 16 * o);      // this workgroup's own slab is still in registers
-                    v[o] = h2 == 0 ? p : v[o] + p;
-                }
-            }
-            float* orow = a.x + (size_t)row * CP + 4 * lg;
-#pragma unroll
-            for (int o = 0; o < KK; ++o) { v[o] += ld4(a.b2 + 16 * o + 4 * lg); st4(orow + 16 * o, res[o] + v[o]); }
         }
         return;
     }
@@ -499,7 +410,6 @@ __global__ __launch_bounds__(64 * NW, (mlp_min_waves<CP, TM>())) void mlp_fused_
         for (int o = 0; o < KK; ++o) st4(orow + 16 * o, res[o] + acc[o][t]);
     }
 }
-
 
 // dst = src + (((P0 + P1) + ... + P_{n-1}) + bias) : fixed summation order, 16 B per lane, HBM-bound ((n + 2) * M * CP * 4 bytes).
 // Second pass of the hidden-split MLP and of the head-group-split attention (dst may alias src).

@@ -201,15 +201,10 @@ inline void launch_gemm_bf16(const Loader& ld, const float* Wt, const __bf16* Wt
         else hipLaunchKernelGGL((gemm_bf16_kernel<128, 128, false, Loader, Epi, 1, 3>), grid, dim3(256), 0, s, ld, Wt, Wt16, M, Np, Kp, Np / 128, ep, (size_t)0);
         return;
     }
-    static const int env_bm = [] { const char* e = ESCX_TUNE_ENV("ESCX_BF16_BM"); return e ? atoi(e) : 0; }();       // tuning aid: 128 / 256 rows per workgroup
-    static const int env_ks = [] { const char* e = ESCX_TUNE_ENV("ESCX_BF16_KS"); return e ? atoi(e) : 1; }();        // tuning aid: 2 = 64-deep staged tiles
     const int nbn = Np / 128;
     // 128 rows: 156 registers, three workgroups per CU; 256 rows: 272 registers, ONE wave per SIMD - measured on the 1024 -> 1024 period layer: 409 against
     // 271 TFLOP/s forward, 384 against 252 dX (the K step is one memory round trip deep, so the bytes in flight per CU decide)
-    const bool big = env_bm == 256;
-    if (big) hipLaunchKernelGGL((gemm_bf16_kernel<256, 128, false, Loader, Epi>), dim3(((M + 255) / 256) * nbn), dim3(256), 0, s, ld, Wt, Wt16, M, Np, Kp, nbn, ep);
-    else if (Wt16 && env_ks == 2 && Kp % 64 == 0) hipLaunchKernelGGL((gemm_bf16_kernel<128, 128, true, Loader, Epi, 2>), dim3(((M + 127) / 128) * nbn), dim3(256), 0, s, ld, Wt, Wt16, M, Np, Kp, nbn, ep);
-    else if (Wt16) hipLaunchKernelGGL((gemm_bf16_kernel<128, 128, true, Loader, Epi>), dim3(((M + 127) / 128) * nbn), dim3(256), 0, s, ld, Wt, Wt16, M, Np, Kp, nbn, ep);
+    if (Wt16) hipLaunchKernelGGL((gemm_bf16_kernel<128, 128, true, Loader, Epi>), dim3(((M + 127) / 128) * nbn), dim3(256), 0, s, ld, Wt, Wt16, M, Np, Kp, nbn, ep);
     else hipLaunchKernelGGL((gemm_bf16_kernel<128, 128, false, Loader, Epi>), dim3(((M + 127) / 128) * nbn), dim3(256), 0, s, ld, Wt, Wt16, M, Np, Kp, nbn, ep);
 }
 

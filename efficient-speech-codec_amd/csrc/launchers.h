@@ -1,7 +1,6 @@
 // Host-callable launchers (one per kernel group); implemented in gemm_swin.hip / gemm_misc.hip / kernels_misc.hip.
 #pragma once
 #include <hip/hip_runtime.h>
-#include "tune_env.h"
 
 namespace escx {
 
@@ -34,9 +33,8 @@ struct MlpSplit { const float* wf; const float* gamma; const float* beta; float*
 int mlp_fused(float* x, int M, int C, int Cp, const float* gamma, const float* beta, const float* w1f, const float* b1,
               const float* w2f, const float* b2, const float* wcf, int hiddenP, int variant, int* hs_io, float* partial, hipStream_t s,
               float* out = nullptr,       // out != nullptr: x untouched, x + mlp(x) goes to out (not with a hidden split)
-              int* tickets = nullptr, int n_tickets = 0, bool* combined = nullptr,     // hidden split: arrival counters (zeroed) -> *combined = the launch did the combine itself
               const MlpSplit* split = nullptr);   // ESCX_COMB_UNSUPPORTED (nothing launched) when this width / variant has no SPLIT instantiation
-unsigned long long* debug_trace_buffer();      // device buffer set by escx_debug_mlp_trace (tuning builds: in-kernel phase stamps), or nullptr
+unsigned long long* debug_trace_buffer();      // device buffer set by escx_debug_mlp_trace (phase-trace builds: in-kernel phase stamps), or nullptr
 // Fused MLP on the bf16 matrix cores with fp32 operands split into three bf16 terms (fused_mlp_x3.h).  mlp_x3_pack builds the split weight image from the row-major
 // fp32 weights (w1 [hiddenP][Cp], w2 [Cp][hiddenP]); mlp_x3_bytes = its size.  -1: width not instantiated.
 // nt: terms per operand - 3 = bf16 (exact split, six cross products), 2 = fp16 with per-matrix power-of-two scales (three cross products); image and kernel must agree
@@ -51,12 +49,8 @@ int mlp_x3_split_pack(const float* wf, void* image, int Cp, int Np, hipStream_t 
 void rows_combine(float* dst, const float* src, const float* partial, const float* bias, long long M, int Cp, int n, hipStream_t s);
 
 // LN + linear for PatchMerge (segs = 2, map gives the two source rows) / PatchSplit (segs = 1, split = 1: pixel-shuffled store)
-// Pending combine of a hidden-split MLP (fused_mlp.h): the consumer forms x + (((P0 + P1) + ...) + bias) while it loads its rows.  Kernels without a
-// combine-on-load instantiation return ESCX_COMB_UNSUPPORTED without launching: the caller then runs rows_combine and calls again without it.
-struct CombineOnLoad { const float* partial; const float* bias; long long stride; int n; };
 int rowgemm_fused(int segs, const float* x, float* out, const float* gamma, const float* beta, const float* wf, const int* map, int M,
                   int rows_per_clip, int src_rows_per_clip, int C, int Cp, int Np, int split, int H, int W, int C2p, hipStream_t s,
-                  const CombineOnLoad* comb = nullptr,
                   const void* x3_wf = nullptr, int x3_nt = 3);      // split weight stream (rowgemm_x3_pack, x3_nt terms: 3 = bf16, 2 = fp16 + scales), or nullptr = fp32 MFMA
 size_t rowgemm_x3_bytes(int KP, int Np);
 int rowgemm_x3_pack(const float* wf, void* image, int KP, int Np, hipStream_t s, int nt = 3, const float* gamma = nullptr, const float* beta = nullptr, int C = 0);   // gamma / beta over KP channels, C real ones: the LayerNorm whose output is split (nt = 2 range rule)
@@ -72,10 +66,10 @@ int deembed7_x2_pack(const float* wfrag, void* image, int Cp, hipStream_t s);
 int attn_fused(const float* src, float* dst, int Cp, int C, int mode, int n_groups, const float* gamma, const float* beta,
                const float* wf, const float* bqkv, const float* bias_tab, const float* bproj, const int* map, int slots, int tokens,
                int n_windows, int nWh, int nWw, int shifted, float scale, int nw, int* gs_io, float* partial, int rows, hipStream_t s,
-               const CombineOnLoad* comb = nullptr, const struct AttnTape* tape = nullptr,
-               const void* x3_wf = nullptr, int x3_pairs = 0);     // split (3 x bf16) weight stream of this block (attn_x3_pack; pairs: its pair-order form), nullptr = fp32 MFMA
+               const struct AttnTape* tape = nullptr,
+               const void* x3_wf = nullptr, int x3_nt = 3);     // split weight stream of this block (attn_x3_pack, x3_nt terms: 3 = bf16, 2 = fp16 + scales), nullptr = fp32 MFMA
 size_t attn_x3_bytes(int Cp, int mode, int n_groups);
-int attn_x3_pack(const float* waf, void* image, int Cp, int mode, int n_groups, hipStream_t s, int pairs = 0, const float* gamma = nullptr, const float* beta = nullptr, int C = 0, const float* bqkv = nullptr);   // norm1's gamma / beta and the tile biases (pairs == 2: range rule; the output projection in two-term form too)
+int attn_x3_pack(const float* waf, void* image, int Cp, int mode, int n_groups, hipStream_t s, int nt = 3, const float* gamma = nullptr, const float* beta = nullptr, int C = 0, const float* bqkv = nullptr);   // norm1's gamma / beta and the tile biases (nt == 2: range rule; the output projection in two-term form too)
 // training forward: the fused attention also writes what the backward reads (fused_attn.h, TAPE); returns ESCX_COMB_UNSUPPORTED when the width has
 // no TAPE instantiation (the caller runs the unfused sequence)
 struct AttnTape { float* xn; float* qkv; float* o; int ldq, ldo, hdp, nH; };
@@ -126,9 +120,6 @@ int prvq_fused(const float* enc, const long long* codes_in, int B, int Hq, int W
 // out = dec + tab[(h, ov * code_g + o)][c] (g = group of element (o, h, c)): the de-quantise + up-projection + un-frame + add of one stream as a table-row add
 void pvq_tab_add(const long long* codes, long long bstride, const float* tab, const float* gq, int G, int Ksz, int B, int Hq, int Wd, int Cp, int ov,
                  const float* dec, float* out, hipStream_t s);
-// specialised PVQ framing + residual + down-projection (split-K partial sums, kernels.h); -1: geometry not covered, the caller falls back to gemm_pvq_down
-int pvq_down(const float* enc, const float* dec, int B, int Hq, int Wd, int Cp, int ov, const float* W, int Np, int Kp, float* zpart, int splits,
-             int bk, hipStream_t s);
 int pvq_down_bk(int Cp);        // the K step the engine would use for this map width (fixes the slice boundaries)
 // specialised PVQ de-quantise + up-project + un-frame + add (kernels.h); -1: geometry not covered, the caller falls back to gemm_pvq_up
 int pvq_up(const long long* codes, long long bstride, const float* cbraw, int G, int Ksz, int dt, int B, int Hq, int Wd, int Cp, int ov,

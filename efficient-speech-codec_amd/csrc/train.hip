@@ -105,7 +105,7 @@ bool train_x3() {
     return on;
 }
 inline bool train_x3_shape(int Np, int Kp) {          // by the layer's geometry only: the arithmetic of a clip must not depend on the batch it is in (two-part passes, DDP shards)
-    static const int min_k = [] { const char* e = ESCX_TUNE_ENV("ESCX_TRAIN_X3_MIN_K"); return e ? atoi(e) : 96; }();       // tuning aid (tagged builds)
+    constexpr int min_k = 96;
     return Kp % 16 == 0 && Kp >= min_k && Np >= min_k;
 }
 
@@ -117,8 +117,7 @@ void gemm_any(const Ld& ld, const float* W, int M, int Np, int Kp, const Epi& ep
     // 128-row tiles halve the weight traffic per output row; 64 when the grid would not fill the chip (same rule as gemm_swin.hip)
     const long long tiles128 = (long long)((M + 127) / 128) * ((Np + 95) / 96);
     // K steps of 16 keep the workgroup's LDS image small (more resident workgroups): 98.0 -> 96.1 ms/step over the engine's default steps
-    static const int env_bk = [] { const char* e = ESCX_TUNE_ENV("ESCX_TRAIN_BK"); return e ? atoi(e) : 16; }();
-    if (!force_bk && env_bk > 0 && Kp % env_bk == 0) force_bk = env_bk;
+    if (!force_bk && Kp % 16 == 0) force_bk = 16;
     if (tiles128 >= 512) launch_gemm<128>(ld, W, M, Np, Kp, ep, st, 1, force_bk);
     else launch_gemm<64>(ld, W, M, Np, Kp, ep, st, 1, force_bk);
 }
@@ -142,10 +141,9 @@ int dw_launch(escx_handle_s* h, const LdA& la, const LdB& lb, int M, int Np, int
     const int nbn = (Np + 47) / 48, nbk = (Kp + 47) / 48, blocks = nbn * nbk;
     // Workgroups per launch.  A workgroup's fixed cost (cold first chunk, cross-wave add of 9 accumulator tiles, 9 KB partial tile that the reduction reads
     // back) is paid per slice, so the narrow matrices - few output tiles, i.e. many slices each - want FEWER, longer slices even if that leaves slots empty
-    // (measured, B = 36, ESCX_DW_TARGET sweep in profiles/r3_dw_target_sweep.txt: dw_proj[C=45] (1 tile) 0.631 / 0.535 / 0.444 ms at 2048 / 1024 / 512,
-    // dw_qkv[C=45] (3 tiles) 1.218 / 1.137 / 1.026; from 10 tiles up 2048 wins: dw_fc1[C=72] 1.275 / 1.270 / 1.793).  ESCX_DW_TARGET overrides (tuning aid).
-    static const int env_target = [] { const char* e = ESCX_TUNE_ENV("ESCX_DW_TARGET"); return e ? atoi(e) : 0; }();
-    const int target = env_target > 0 ? env_target : (blocks <= 3 ? 512 : (blocks <= 4 ? 1024 : 2048));
+    // (measured, B = 36, target sweep in profiles/r3_dw_target_sweep.txt: dw_proj[C=45] (1 tile) 0.631 / 0.535 / 0.444 ms at 2048 / 1024 / 512,
+    // dw_qkv[C=45] (3 tiles) 1.218 / 1.137 / 1.026; from 10 tiles up 2048 wins: dw_fc1[C=72] 1.275 / 1.270 / 1.793).
+    const int target = blocks <= 3 ? 512 : (blocks <= 4 ? 1024 : 2048);
     int slices = std::max(1, std::min((target + blocks - 1) / blocks, (M + 127) / 128));
     const size_t per = (size_t)Np * Kp + Np;
     slices = (int)std::min<size_t>(slices, DW_PART_FLOATS / per);
@@ -165,11 +163,10 @@ template <int TA, int TB, int WN = 2, int WK = 2, class LdA, class LdB>
 int dw_launch_wide(escx_handle_s* h, const LdA& la, const LdB& lb, int M, int Np, int Kp, float* dW, float* db, float* part, hipStream_t st) {
     constexpr int WA = 16 * TA * WN, WB = 16 * TB * WK;
     const int nbn = (Np + WA - 1) / WA, nbk = (Kp + WB - 1) / WB, blocks = nbn * nbk;
-    static const int env_target = [] { const char* e = ESCX_TUNE_ENV("ESCX_DW_WIDE_TARGET"); return e ? atoi(e) : 0; }();
     // ONE round of resident workgroups (2 per CU at 65-74 KB of LDS each): a partly filled extra round costs a whole slice time, and every further slice
-    // another partial tile (up to 64 KB) written and read back (ESCX_DW_WIDE_TARGET sweep, 36 clips: 512 -> 79.6 ms/step, 768 -> 80.9, 2560 -> 80.4)
+    // another partial tile (up to 64 KB) written and read back (target sweep, 36 clips: 512 -> 79.6 ms/step, 768 -> 80.9, 2560 -> 80.4)
     constexpr int LDS_BYTES = 2 * 32 * ((WA % 32 == 0 ? WA + 16 : WA) + (WB % 32 == 0 ? WB + 16 : WB)) * 4;
-    const int target = env_target > 0 ? env_target : 256 * std::max(1, std::min(2, 163840 / LDS_BYTES));
+    const int target = 256 * std::max(1, std::min(2, 163840 / LDS_BYTES));
     int slices = std::max(1, std::min(target / blocks, (M + 255) / 256));
     const size_t per = (size_t)Np * Kp + Np;
     slices = (int)std::max<size_t>(1, std::min<size_t>(slices, DW_PART_FLOATS / per));
@@ -186,13 +183,11 @@ int dw_launch_wide(escx_handle_s* h, const LdA& la, const LdB& lb, int M, int Np
 // plain row-major operands (the linear layers): the workgroup tile (128 / 96 / 64 per side) with the least padding, wide tiles preferred;
 // the 48 x 48 kernel where none fits within 15 % (C = 45, 72, 144: multiples of 48) or the matrix is small
 int dw_rows(escx_handle_s* h, const float* A, int lda, const float* Bm, int ldb, int M, int Np, int Kp, float* dW, float* db, float* part, hipStream_t st) {
-    static const bool wide_ok = [] { const char* e = ESCX_TUNE_ENV("ESCX_DW_WIDE"); return !(e && e[0] == '0'); }();
-    static const double pad_limit = [] { const char* e = ESCX_TUNE_ENV("ESCX_DW_WIDE_PAD"); return e ? atof(e) : 1.15; }();      // tile padding a wide tile may add
+    constexpr double pad_limit = 1.15;      // tile padding a wide tile may add
     const PlainA la{A, lda, M}, lb{Bm, ldb, M};
     // split-operand dW (gemm_bf16.h gemm_dw_bf16_kernel<.., 3>: 128 x 128 tiles of dW, both operands as three bf16 terms, slices of M added in a fixed order) where the
     // tiles carry no padding - the C = 384 blocks; the narrower matrices keep the fp32 kernels with their fitted tile shapes below
-    static const bool dw_x3 = [] { const char* e = ESCX_TUNE_ENV("ESCX_TRAIN_X3_DW"); return !(e && e[0] == '0'); }();
-    if (train_x3() && dw_x3 && Np % 128 == 0 && Kp % 128 == 0) {
+    if (train_x3() && Np % 128 == 0 && Kp % 128 == 0) {
         const int nbn = Np / 128, nbk = Kp / 128, blocks = nbn * nbk;
         const size_t per = (size_t)Np * Kp + Np;
         int slices = std::max(1, std::min((1024 + blocks / 2) / blocks, (M + 255) / 256));
@@ -206,15 +201,12 @@ int dw_rows(escx_handle_s* h, const float* A, int lda, const float* Bm, int ldb,
         return 0;
     }
     // the 144- and 80-wide maps (C = 144, 72) fit none of the 32-multiple tiles: one side of the workgroup tile IS the map width (9 or 5 accumulator tiles per
-    // wave, all four waves along the other side).  ESCX_DW_ODD=0: the 48 x 48 kernel as before.
-    static const bool odd_ok = [] { const char* e = ESCX_TUNE_ENV("ESCX_DW_ODD"); return !(e && e[0] == '0'); }();
-    if (wide_ok && odd_ok) {
-        if (Kp == 144 && Np >= 256) return dw_launch_wide<2, 9, 4, 1>(h, la, lb, M, Np, Kp, dW, db, part, st);         // 128 x 144
-        if (Np == 144 && Kp >= 256) return dw_launch_wide<9, 2, 1, 4>(h, la, lb, M, Np, Kp, dW, db, part, st);         // 144 x 128
-        if (Kp == 80 && Np > 192 && Np <= 256) return dw_launch_wide<4, 5, 4, 1>(h, la, lb, M, Np, Kp, dW, db, part, st);      // 256 x 80: the whole QKV gradient of C = 72
-    }
+    // wave, all four waves along the other side).
+    if (Kp == 144 && Np >= 256) return dw_launch_wide<2, 9, 4, 1>(h, la, lb, M, Np, Kp, dW, db, part, st);         // 128 x 144
+    if (Np == 144 && Kp >= 256) return dw_launch_wide<9, 2, 1, 4>(h, la, lb, M, Np, Kp, dW, db, part, st);         // 144 x 128
+    if (Kp == 80 && Np > 192 && Np <= 256) return dw_launch_wide<4, 5, 4, 1>(h, la, lb, M, Np, Kp, dW, db, part, st);      // 256 x 80: the whole QKV gradient of C = 72
     int bestA = 0, bestB = 0; double best = 1e30;
-    if (wide_ok && Np >= 96 && Kp >= 96 && (long long)Np * Kp >= 96 * 288) {
+    if (Np >= 96 && Kp >= 96 && (long long)Np * Kp >= 96 * 288) {
         const int cand[3] = {128, 96, 64};
         for (int wa : cand) for (int wb : cand) {
             const double padded = (double)((Np + wa - 1) / wa * wa) * ((Kp + wb - 1) / wb * wb);
@@ -243,7 +235,7 @@ int ln_bwd(int mode, const float* x, const float* dy, const float* gamma, const 
            int rows_per_clip, int src_rows_per_clip, int dy_rows_per_clip, int total_rows, int C, int Cp, float* part, hipStream_t st,
            float* dx_slots = nullptr, const int* slot_of = nullptr, int slots_per_clip = 0) {
     const int segs = mode == 2 ? 2 : 1;
-    static const int grid_cap = [] { const char* e = ESCX_TUNE_ENV("ESCX_LN_BWD_GRID"); const int v = e ? atoi(e) : 512; return std::max(1, std::min(v, LN_BWD_MAX_GRID)); }();
+    constexpr int grid_cap = 512;
     const int grid = (int)std::min<long long>(grid_cap, ((long long)total_rows + 15) / 16);
     const size_t shm = (size_t)16 * 2 * segs * Cp * sizeof(float);
     const int RW = segs * Cp;
@@ -261,26 +253,17 @@ constexpr size_t LN_PART_FLOATS = (size_t)(LN_BWD_MAX_GRID + 1) * 2 * 2 * 384;
 
 // dx_fc1 GEMM with the LayerNorm backward as its row epilogue (EpiLnBwdRows; Cp <= 96): out = add + LNbwd(dh . W; x), dgamma / dbeta.
 // `part` needs ceil(M / 64) * 4 * 2 * Cp floats (+ 2 * Cp for the reduced row): the dW partial-sum scratch is used.
-// Round 4: also for the wide maps (Cp = 144 / 192 / 384) - one workgroup tile spans the row there too (BN = Cp), with the register-lean form of the epilogue.
-bool ln_rows_fusable(int Cp) {
-    static const bool wide = [] { const char* e = ESCX_TUNE_ENV("ESCX_LN_FUSED_WIDE"); return e && e[0] == '1'; }();          // opt-in: measured slower than the stand-alone LayerNorm backward above Cp = 96
-    return Cp <= 96 || (wide && (Cp == 144 || Cp == 192 || Cp == 384));
-}
+// The wide maps (Cp = 144 / 192 / 384) keep the stand-alone LayerNorm backward: the fused form measured slower above Cp = 96.
+bool ln_rows_fusable(int Cp) { return Cp <= 96; }
 void gemm_ln_bwd_rows(const float* A, int lda, int M, const float* Wt, int Cp, int Kp, const float* x, const float* gamma, const float* add, float* dx,
                       float* dx_slots, const int* slot_of, int rows_per_clip, int slots_per_clip, int C, float* dg, float* dbt, float* part, hipStream_t st,
                       const int* row_map = nullptr) {
     EpiLnBwdRows ep{x, gamma, add, dx, dx_slots, slot_of, part, C, Cp, rows_per_clip, slots_per_clip, 1e-5f, row_map};
-    static const int wide_bm = [] { const char* e = ESCX_TUNE_ENV("ESCX_LNBWD_WIDE_BM"); return e ? atoi(e) : 0; }();       // tuning aid: 64 / 128 rows per workgroup for the 144 / 192-wide tiles
-    const bool big = Cp > 96 ? (Cp != 384 && (wide_bm ? wide_bm == 128 : (long long)((M + 127) / 128) >= 512)) : (long long)((M + 127) / 128) >= 512;
+    const bool big = (long long)((M + 127) / 128) >= 512;
     const int rows = (big ? (M + 127) / 128 : (M + 63) / 64) * 4;
-    static const int env_bk = [] { const char* e = ESCX_TUNE_ENV("ESCX_LNBWD_BK"); return e ? atoi(e) : 16; }();
-    const int bk = (env_bk > 0 && Kp % env_bk == 0) ? env_bk : 16;
     const PlainA la{A, lda, M};
-    if (Cp == 144) { if (big) launch_tile<128, 144, 16>(la, Wt, M, Cp, Kp, 1, ep, st); else launch_tile<64, 144, 16>(la, Wt, M, Cp, Kp, 1, ep, st); }
-    else if (Cp == 192) { if (big) launch_tile<128, 192, 16>(la, Wt, M, Cp, Kp, 1, ep, st); else launch_tile<64, 192, 16>(la, Wt, M, Cp, Kp, 1, ep, st); }
-    else if (Cp == 384) launch_tile<64, 384, 16>(la, Wt, M, Cp, Kp, 1, ep, st);
-    else if (big) launch_gemm<128>(la, Wt, M, Cp, Kp, ep, st, 1, bk);
-    else launch_gemm<64>(la, Wt, M, Cp, Kp, ep, st, 1, bk);
+    if (big) launch_gemm<128>(la, Wt, M, Cp, Kp, ep, st, 1, 16);
+    else launch_gemm<64>(la, Wt, M, Cp, Kp, ep, st, 1, 16);
     if (!dg) return;                         // input-only backward: the epilogue's gamma / beta partials stay in the scratch
     float* red = part + (size_t)rows * 2 * Cp;
     launch_reduce_partials(part, rows, (long long)2 * Cp, red, 0, st, red + 2 * Cp);
@@ -292,23 +275,18 @@ int attn_bwd(const float* qkv, const float* bias, const float* dout, float* dqkv
     // Persistent waves striding over the windows, each doing HPW heads per window (the heads of a window share its rows: in one wave every cache line is
     // fetched once).  Grid: ONE workgroup per CU in total - measured at 36 clips (profiles/r3_attn_bwd_grid_sweep.txt): the kernel moves 1.06 GB per launch
     // at C = 45 and runs at 5.0 TB/s with 256 workgroups, 4.1 TB/s with 384 and 3.0 TB/s with the chip full (1 536, one head per wave): more concurrent row
-    // streams only cost DRAM efficiency, there is no latency left to hide.  ESCX_ATTN_BWD_GX = n: n window chunks; ESCX_ATTN_BWD_HPW=1: one head per wave.
-    static const int gx_env = [] { const char* e = ESCX_TUNE_ENV("ESCX_ATTN_BWD_GX"); return e ? atoi(e) : 0; }();
-    static const int hpw_env = [] { const char* e = ESCX_TUNE_ENV("ESCX_ATTN_BWD_HPW"); return e ? atoi(e) : 3; }();
+    // streams only cost DRAM efficiency, there is no latency left to hide.
     static const int cus = [] {
         int dev = 0, n = 256;
         if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
         return n;
     }();
-    const int hpw = (hpw_env == 3 && nH % 3 == 0) ? 3 : 1;
+    const int hpw = nH % 3 == 0 ? 3 : 1;
     const int gy = nH / hpw;
     int gx = (int)std::min<long long>(512, ((long long)total_windows + 3) / 4);
-    if (gx_env > 0) gx = std::min(gx, gx_env);
-    else {
-        int cap = std::max(1, cus / gy);
-        if (cap >= 16) cap &= ~7;                            // the chunks of one window range land on the same XCD for every head group (workgroup id mod 8)
-        gx = std::min(gx, cap);
-    }
+    int cap = std::max(1, cus / gy);
+    if (cap >= 16) cap &= ~7;                            // the chunks of one window range land on the same XCD for every head group (workgroup id mod 8)
+    gx = std::min(gx, cap);
     auto launch = [&](auto kern) {
         if ((unsigned long long)(total_windows + 4 * gx) * 16ull * (unsigned long long)std::max(ldq, ldo) >= (1ull << 32)) return -2;    // 32-bit element offsets in the kernel
         hipLaunchKernelGGL(kern, dim3(gx, gy), dim3(256), 0, st, qkv, bias, dout, dqkv, part, total_windows, nH, ldq, ldo, nWh, nWw, shifted, scale);
@@ -333,8 +311,7 @@ inline float* G(escx_handle_s* h, const float* w) { return h->garena + (w - rein
 // path's kernel (only x1 stays on the tape), backward = train_mlp_fused.h (hidden tile recomputed on the fly).  ESCX_TRAIN_MLP_FUSED=0: unfused.
 inline bool mlp_train_fused(const Layer& L) {
     static const bool on = [] { const char* e = getenv("ESCX_TRAIN_MLP_FUSED"); return !(e && e[0] == '0'); }();
-    static const bool on72 = [] { const char* e = ESCX_TUNE_ENV("ESCX_TRAIN_MLP_FUSED_C72"); return !(e && e[0] == '0'); }();
-    return on && ((L.Cp == 48 && L.hiddenP == 192) || (on72 && L.Cp == 80 && L.hiddenP == 288));
+    return on && ((L.Cp == 48 && L.hiddenP == 192) || (L.Cp == 80 && L.hiddenP == 288));
 }
 
 // Forward of those layers (round 6): the split-operand kernel of the inference path (fused_mlp_x3.h) in its EXACT three-term bf16 form - fp32 results up to summation
@@ -371,7 +348,6 @@ int mlp_bwd_fused(escx_handle_s* h, const Layer& L, const BlockW& bw, const floa
     const size_t per = 2 * (size_t)n1 + L.hiddenP + L.Cp;
     if ((size_t)grid * per + n1 > DW_PART_FLOATS) ESCX_FAIL(ESCX_ERR_STATE, "dW scratch too small for the fused MLP backward");
     MlpBwdArgs a{x1, dy, dx1, dx1s, slot_of, bw.ln2_g, bw.ln2_b, bw.w1, bw.b1, bw.w2T, bw.w1T, part, slabs, M, L.C, L.hiddenP, tokens, slots, 1e-5f, 0};
-    { static const int dbg = [] { const char* e = ESCX_TUNE_ENV("ESCX_MLPBWD_DBG"); return e ? atoi(e) : 0; }(); a.dbg = dbg; }
     // two-term fp16 form of the two channel contractions (train_mlp_fused.h X2; ESCX_TRAIN_MLPBWD_X2=0: all five contractions on the fp32 MFMA, as before)
     const char* x2e = getenv("ESCX_TRAIN_MLPBWD_X2");            // read per call: tests switch it
     const bool x2 = !(x2e && x2e[0] == '0');
@@ -475,11 +451,10 @@ int layer_fwd(escx_handle_s* h, const Layer& L, LayerTape& LT, const float* x_in
         // (fused_attn.h, TAPE): 1.73 GB -> 0.93 GB of HBM traffic per C = 45 block at 36 clips.  ESCX_TRAIN_ATTN_FUSED=0: the four launches.
         static const bool attn_fused_ok = [] { const char* e = getenv("ESCX_TRAIN_ATTN_FUSED"); return !(e && e[0] == '0'); }();
         int afrc = -1;
-        static const int attn_fused_max = [] { const char* e = ESCX_TUNE_ENV("ESCX_TRAIN_ATTN_FUSED_MAXCP"); return e && e[0] ? atoi(e) : 96; }();
         // the TAPE instantiation zeroes 16 pad columns of the q|k|v and attention-output rows; a wider pad (no ESC geometry has one) keeps the unfused launches, whose
         // GEMM epilogues write whole rows - the backward contracts over the full Nqkv / Ko width
         const bool tape_pad_ok = L.Nqkv - 3 * L.nH * L.hdp <= 16 && L.Ko - L.nH * L.hdp <= 16;
-        if (attn_fused_ok && tape_pad_ok && L.attn_mode >= 0 && L.Cp <= attn_fused_max) {
+        if (attn_fused_ok && tape_pad_ok && L.attn_mode >= 0 && L.Cp <= 96) {
             const AttnTape tape{bt.xn1, bt.qkv, bt.obuf, L.Nqkv, L.Ko, L.hdp, L.nH};
             const int tmw = attn_windows_per_wave(L.Cp);
             const long long wg4 = (Ms / 16 / tmw + 3) / 4;
@@ -488,7 +463,7 @@ int layer_fwd(escx_handle_s* h, const Layer& L, LayerTape& LT, const float* x_in
             const size_t n_recs = h->prof_recs.size();
             PROF("T.attn_fused" + tg, 8 * dMs * dC * dC + 4 * dMs * 16 * dC, (dM * 2 + dMs * 6) * dC * f4,
                  afrc = attn_fused(x, bt.x1, L.Cp, L.C, L.attn_mode, L.n_groups, bw.ln1_g, bw.ln1_b, bw.waf, bw.baf, bw.bias_tab_f, bw.bproj, map, slots, tokens,
-                                   Ms / 16, Hp / 4, Wp / 4, shift > 0, 1.0f / std::sqrt((float)L.hd), nw, &gs, nullptr, M, st, nullptr, &tape));
+                                   Ms / 16, Hp / 4, Wp / 4, shift > 0, 1.0f / std::sqrt((float)L.hd), nw, &gs, nullptr, M, st, &tape));
             if (afrc != 0 && h->prof_recs.size() > n_recs) h->prof_recs.pop_back();
         }
         if (afrc != 0) {
@@ -908,7 +883,6 @@ int layer_bwd(escx_handle_s* h, const Layer& L, const LayerTape& LT, const float
         if ((rc = get_map(h, H, W, 10 + shift, &inv))) return rc;
         // ---- MLP: x2 = x1 + W2 gelu(W1 LN2(x1) + b1) + b2 ----
         const bool fmlp = mlp_train_fused(L);
-        static const bool ln_fused = [] { const char* e = ESCX_TUNE_ENV("ESCX_LN_FUSED"); return !(e && e[0] == '0'); }();
         if (fmlp) {
             if (slots != tokens) ESCX_HIP(hipMemsetAsync(dx1s, 0, (size_t)Ms * L.Cp * sizeof(float), st));      // pad slots carry no gradient
             PROF("B.mlp_fused" + tg, 10.0 * M * L.C * L.hidden, (3.0 * M + Ms) * L.Cp * 4,
@@ -924,7 +898,7 @@ int layer_bwd(escx_handle_s* h, const Layer& L, const LayerTape& LT, const float
                      rc = dw_rows(h, dhpre, L.hiddenP, bt.xn2, L.Cp, M, L.hiddenP, L.Cp, G(h, bw.w1), G(h, bw.b1), part, st));
         if (rc) return rc;
         if (slots != tokens) ESCX_HIP(hipMemsetAsync(dx1s, 0, (size_t)Ms * L.Cp * sizeof(float), st));      // pad slots carry no gradient
-        if (ln_fused && ln_rows_fusable(L.Cp)) {       // LN2's backward rides in the epilogue of the GEMM that produces its upstream gradient
+        if (ln_rows_fusable(L.Cp)) {       // LN2's backward rides in the epilogue of the GEMM that produces its upstream gradient
             PROF("B.dx_fc1+ln2" + tg, 2.0 * M * L.C * L.hidden, ((double)M * (L.hiddenP + 3 * L.Cp) + (double)Ms * L.Cp) * 4,
                  gemm_ln_bwd_rows(dhpre, L.hiddenP, M, bw.w1T, L.Cp, L.hiddenP, bt.x1, bw.ln2_g, dy, dx1, dx1s, inv, tokens, slots, L.C, GW(bw.ln2_g),
                                   GW(bw.ln2_b), part, st));
@@ -950,7 +924,7 @@ int layer_bwd(escx_handle_s* h, const Layer& L, const LayerTape& LT, const float
         if (gw) PROF("B.dw_qkv" + tg, 2.0 * Ms * L.C * 3 * L.C, (double)Ms * (L.Nqkv + L.Cp) * 4,
                      rc = dw_rows(h, dqkv, L.Nqkv, bt.xn1, L.Cp, Ms, L.Nqkv, L.Cp, G(h, bw.wqkv), G(h, bw.bqkv), part, st));
         if (rc) return rc;
-        if (ln_fused && ln_rows_fusable(L.Cp)) {       // LN1's backward in the epilogue of the QKV dX GEMM: its rows are window slots, map = slot -> token
+        if (ln_rows_fusable(L.Cp)) {       // LN1's backward in the epilogue of the QKV dX GEMM: its rows are window slots, map = slot -> token
             PROF("B.dx_qkv+ln1" + tg, 2.0 * Ms * L.C * 3 * L.C, ((double)Ms * L.Nqkv + 3.0 * M * L.Cp) * 4,
                  gemm_ln_bwd_rows(dqkv, L.Nqkv, Ms, bw.wqkvT, L.Cp, L.Nqkv, bt.x0, bw.ln1_g, dx1, dprev, nullptr, nullptr, tokens, slots, L.C, GW(bw.ln1_g),
                                   GW(bw.ln1_b), part, st, map));

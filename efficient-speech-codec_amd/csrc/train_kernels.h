@@ -192,85 +192,9 @@ struct EpiLnBwdRows {
     const int* row_map;         // optional: the GEMM's rows are window SLOTS (LN1: the upstream gradient comes out of the QKV GEMM in slot order);
                                 // row_map[slot] = token of the clip or -1 for a pad slot, x / add / dx are indexed by token
     __device__ __forceinline__ void store(int, int, f32x4, int) const {}
-    // Wide maps (Cp = 144 / 192 / 384, round 4): the narrow form below keeps x, gamma and both column-sum accumulators of a whole row tile in
-    // registers (4 x TN float4 next to the accumulators) - at TN = 12..24 that is beyond the register file.  Here phase 1 takes the row statistics and
-    // the two projection sums per row tile (x held for ONE row tile at a time), phase 2 walks the column tiles, re-reads x (an L2 hit) and finishes
-    // each column tile's rows and column sums before the next: the same per-element arithmetic in the same order, accumulators + ~60 registers.
-    template <int TN, int TM>
-    __device__ __forceinline__ void finish_wide(f32x4 (&acc)[TN][TM], int row0, int lane, int M) const {
-        const int l15 = lane & 15, lg = lane >> 4;
-        const float invC = 1.0f / (float)C;
-        int mrow[TM], dsrow[TM]; bool lv[TM]; float mean[TM], rstd[TM], c1[TM], c2[TM];
-#pragma unroll
-        for (int b = 0; b < TM; ++b) {
-            int m = row0 + 16 * b + l15;
-            bool live = m < M;
-            if (row_map && live) {
-                const int bi = m / slots_per_clip; const int tok = row_map[m - bi * slots_per_clip];
-                live = tok >= 0; m = bi * rows_per_clip + tok;
-            }
-            mrow[b] = live ? m : 0; lv[b] = live; dsrow[b] = -1;
-            if (live && dx_slots) { const int bi = m / rows_per_clip, rr = m - bi * rows_per_clip; dsrow[b] = bi * slots_per_clip + slot_of[rr]; }
-            f32x4 xv[TN];
-            float s = 0.f;
-#pragma unroll
-            for (int a = 0; a < TN; ++a) {
-                const int n = 16 * a + 4 * lg;
-                xv[a] = (live && n < Cp) ? ld4(x + (size_t)m * Cp + n) : zero4();
-#pragma unroll
-                for (int e = 0; e < 4; ++e) if (n + e < C) s += xv[a][e];
-            }
-            mean[b] = sum_groups(s) * invC;
-            float var = 0.f;
-#pragma unroll
-            for (int a = 0; a < TN; ++a)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) if (16 * a + 4 * lg + e < C) { const float d = xv[a][e] - mean[b]; var += d * d; }
-            rstd[b] = 1.0f / sqrtf(sum_groups(var) * invC + eps);
-            float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-            for (int a = 0; a < TN; ++a) {
-                const int n = 16 * a + 4 * lg;
-                const f32x4 gm = n < Cp ? ld4(gamma + n) : zero4();
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    if (n + e < C) { const float xh = (xv[a][e] - mean[b]) * rstd[b], t = acc[a][b][e] * gm[e]; s1 += t; s2 += t * xh; }
-            }
-            c1[b] = sum_groups(s1) * invC; c2[b] = sum_groups(s2) * invC;
-        }
-        float* pr = part + ((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 2 * Cp;
-#pragma unroll
-        for (int a = 0; a < TN; ++a) {
-            const int n = 16 * a + 4 * lg;
-            const f32x4 gm = n < Cp ? ld4(gamma + n) : zero4();
-            f32x4 ag = zero4(), ab = zero4();
-#pragma unroll
-            for (int b = 0; b < TM; ++b) {
-                if (!lv[b] || n >= Cp) continue;
-                const f32x4 xr = ld4(x + (size_t)mrow[b] * Cp + n);
-                f32x4 o = add ? ld4(add + (size_t)mrow[b] * Cp + n) : zero4();
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float xh = (xr[e] - mean[b]) * rstd[b], g = acc[a][b][e];
-                    if (n + e < C) { ag[e] += g * xh; ab[e] += g; o[e] = o[e] + rstd[b] * (g * gm[e] - c1[b] - xh * c2[b]); }
-                    else o[e] = 0.f;
-                }
-                st4(dx + (size_t)mrow[b] * Cp + n, o);
-                if (dsrow[b] >= 0) st4(dx_slots + (size_t)dsrow[b] * Cp + n, o);
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float u = ag[e], w = ab[e];
-#pragma unroll
-                for (int o = 8; o >= 1; o >>= 1) { u += __shfl_xor(u, o, 16); w += __shfl_xor(w, o, 16); }
-                ag[e] = u; ab[e] = w;
-            }
-            if (l15 == 0 && n < Cp) { st4(pr + n, ag); st4(pr + Cp + n, ab); }
-        }
-    }
     template <int TN, int TM>
     __device__ __forceinline__ void finish(f32x4 (&acc)[TN][TM], int row0, int lane, int M) const {
-        if constexpr (TN > 6) { finish_wide<TN, TM>(acc, row0, lane, M); return; }
+        static_assert(TN <= 6, "x, gamma and both column-sum accumulators of a row tile live in registers: Cp <= 96");
         const int l15 = lane & 15, lg = lane >> 4;
         const float invC = 1.0f / (float)C;
         f32x4 gm[TN], ag[TN], ab[TN];

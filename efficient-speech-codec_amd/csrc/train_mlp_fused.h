@@ -51,7 +51,7 @@ struct MlpBwdArgs {
     float* dxn_part;            // hidden split (grid.y = HS > 1): slab [HS][M][CP] of d xn partial sums; the LayerNorm backward then runs as a separate pass
     int M, C, hiddenP, tokens, slots;
     float eps;
-    int dbg;                    // timing experiments only (ESCX_MLPBWD_DBG): 1 = finisher idle, 2 = stagers stage only the first tile, 4 = compute waves skip the partial-sum writes
+    int dbg;                    // always 0 in the library (mlp_bwd_fused, train.hip); bits of past timing experiments, kept because dropping them changes this kernel: 1 = finisher idle, 2 = stagers stage only the first tile, 4 = compute waves skip the partial-sum writes
 };
 
 // NC compute waves (= hidden tiles) + 3 service waves: wave NC stages x1 (LayerNorm), wave NC + 1 stages dy, wave NC + 2 finishes the PREVIOUS

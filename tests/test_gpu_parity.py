@@ -970,8 +970,8 @@ def test_range_stress_checkpoints(case, precision):
       fc1_x1e6         every fc1 weight / bias x 1e6       -> GELU outputs of ~1e6
       all_small_x1e-4  LayerNorm gamma / beta and fc1 x 1e-4 -> every split activation ~1e-4: low terms of an unscaled split would be fp16 subnormals (14-bit operands)
       deembed_in_x1e6  last decoder block's fc2 weight / bias x 1e6 -> the un-normalised tokens entering PatchDeEmbed reach ~1e6
-    (tagged builds: ESCX_X2_NO_ACT_SCALE=1 switches the activation scales of the two-term mode off - the first two cases then fail, which is what makes this a test:
-    profiles/r6_range_rule_off.txt)
+    (negative control, recorded in profiles/r6_range_rule_off.txt: with the activation scales of the two-term mode switched off the first two cases fail, which is
+    what makes this a test)
     Requirement (the same rule as everywhere): finite outputs, no code differs from the oracle except on an attributed reference near-tie, audio of the reference's
     codes within 1e-4 RMS relative to the reference audio's own RMS (the stressed networks emit audio of arbitrary scale)."""
     ln = ("norm1.weight", "norm1.bias", "norm2.weight", "norm2.bias", "subsample.norm.weight", "subsample.norm.bias")
@@ -1043,31 +1043,6 @@ def test_fallback_kernel_forms_against_the_default(tmp_path):
     # the environment variables only set the DEFAULT mode of new handles (escx_set_precision is the contract); both spellings select the same arithmetic
     assert np.array_equal(got["all_fp32_mfma"]["wave"], got["per_family_switches_fp32"]["wave"]) and np.array_equal(got["bf16_three_terms"]["wave"], got["bf16_three_terms_r5_spelling"]["wave"])
     for name in ("attn_gs_off", "all_fp32_mfma", "bf16_three_terms"):
-        assert np.array_equal(got[name]["codes"], ref["codes"]), f"{name}: codes differ from the default"
-        rms = float(np.sqrt(np.mean((got[name]["wave"].astype(np.float64) - ref["wave"]) ** 2)))
-        assert rms <= 1e-6, f"{name}: audio rms {rms}"
-
-
-@pytest.mark.gpu
-def test_experimental_kernel_forms_against_the_default(tmp_path):
-    """The measured-and-rejected kernel forms of rounds 3-4 are compiled into TAGGED builds only (tune_env.h: ESCX_BUILD_TAG=exp
-    ESCX_EXTRA_CXXFLAGS=-DESCX_EXPERIMENTAL python efficient-speech-codec_amd/build.py -> libescx_exp.so).  When that library is present they are
-    checked against the default library: the in-launch combine of the hidden-split MLP, the combine-on-load consumers and the specialised
-    down-projection kernel bit for bit; the weight-stationary / shared-rows merge-split kernels pin their LayerNorm contraction explicitly, so
-    they may differ in low-order bits: identical codes, audio within 1e-6 RMS."""
-    from conftest import ROOT
-    if not os.path.exists(os.path.join(ROOT, "efficient-speech-codec_amd", "esc", "lib", "libescx_exp.so")):
-        pytest.skip("no tagged experimental build (libescx_exp.so): the product library does not contain the rejected forms")
-    # the rejected forms are variants of the fp32-MFMA kernels: both sides run with the split-operand kernels off (ESCX_MLP_X3=0, ESCX_ATTN_X3=0)
-    f32 = {"ESCX_MLP_X3": "0", "ESCX_ATTN_X3": "0", "ESCX_ROWGEMM_X3": "0"}
-    ref = _ab_arms({"default": {}}, tmp_path, f32)["default"]
-    arms = {"mlp_fused_combine": {"ESCX_MLP_FUSED_COMBINE": "1"}, "combine_on_load": {"ESCX_COMBINE_ON_LOAD": "1"},
-            "rowgemm_ws": {"ESCX_ROWGEMM_WS": "4"}, "rowgemm_xs": {"ESCX_ROWGEMM_XS": "1"},
-            "pvq_down_kernel": {"ESCX_PVQ_FUSED": "0", "ESCX_PVQ_DOWN_KERNEL": "1"}}
-    got = _ab_arms(arms, tmp_path, dict(f32, ESCX_LIB_TAG="exp"))
-    for name in ("mlp_fused_combine", "combine_on_load", "pvq_down_kernel"):
-        assert np.array_equal(got[name]["codes"], ref["codes"]) and np.array_equal(got[name]["wave"], ref["wave"]), f"{name} is not bit-identical to the default"
-    for name in ("rowgemm_ws", "rowgemm_xs"):
         assert np.array_equal(got[name]["codes"], ref["codes"]), f"{name}: codes differ from the default"
         rms = float(np.sqrt(np.mean((got[name]["wave"].astype(np.float64) - ref["wave"]) ** 2)))
         assert rms <= 1e-6, f"{name}: audio rms {rms}"

@@ -4,7 +4,7 @@ over rounds; per arm: SHA-256 of the codes + decoded audio of the bench batch (a
 encode+decode step, and optionally the per-kernel event breakdown of selected launch groups.
 
     python tools/ab.py [--rounds 3] [--steps 20] [--batch 36] [--groups merge_fused,split_fused] NAME:ENV=VAL,ENV=VAL  NAME2:...
-    python tools/ab.py base: ws4:ESCX_ROWGEMM_WS=4          # "base:" = no extra environment
+    python tools/ab.py base: three_launch:ESCX_PVQ_FUSED=0  # "base:" = no extra environment
 Child mode (internal): ab.py --child
 """
 import hashlib
