@@ -13,6 +13,7 @@
 
 #include "escx_internal.h"
 #include "dac_kernels.h"
+#include "dac_x3.h"
 
 using namespace escx;
 
@@ -49,6 +50,10 @@ struct escx_dac_s {
     float* scratch = nullptr; size_t scratch_bytes = 0;
     const float* packed_ptr = nullptr; long long packed_version = -1;
     int snake_maps = ESCX_DAC_SNAKE_MAPS_DEFAULT;   // escx_dac_set_snake_maps: layer classes whose Snake is written to a map first
+    int precision = ESCX_PRECISION_FP32;            // escx_dac_set_precision, read at each call
+    // bf16x3: three bf16 planes of the packed convolution weights wbuf[0, conv_floats), plane p at w16 + p * conv_floats.  Allocated at the first
+    // call in that mode; w16_valid is cleared by every re-pack of the fp32 image and set by refresh_w16, so the image can never be older than wbuf.
+    __bf16* w16 = nullptr; size_t conv_floats = 0; bool w16_valid = false;
 };
 
 namespace {
@@ -93,7 +98,7 @@ int conv_out_len(int T, const DacLayer& l) {
 
 int pack(escx_dac_s* d, const float* flat, long long version, hipStream_t st) {
     if (version >= 0 && version == d->packed_version && flat == d->packed_ptr) return 0;
-    d->packed_version = version; d->packed_ptr = flat;
+    d->packed_version = version; d->packed_ptr = flat; d->w16_valid = false;
     for (auto* L : {&d->enc, &d->dec})
         for (DacLayer& l : *L) {
             if (l.kind == 0)
@@ -111,6 +116,22 @@ int pack(escx_dac_s* d, const float* flat, long long version, hipStream_t st) {
     return launch_ok("dac_pack");
 }
 
+// The three-term image of the packed convolution weights, for the calls that run in bf16x3.  Called after pack() on the same stream: it splits
+// whatever fp32 image is current, once per re-pack (in-place parameter changes, another buffer) and once after the mode is first switched on.
+int refresh_w16(escx_dac_s* d, hipStream_t st) {
+    if (d->precision != ESCX_PRECISION_BF16X3 || d->w16_valid) return 0;
+    if (!d->w16) ESCX_HIP(hipMalloc((void**)&d->w16, 3 * d->conv_floats * sizeof(__bf16)));
+    const size_t n4 = d->conv_floats / 4;
+    hipLaunchKernelGGL(split3_bf16_kernel, dim3((unsigned)std::min<size_t>((n4 + 255) / 256, 4096)), dim3(256), 0, st, (const float*)d->wbuf, d->w16, n4, d->conv_floats);
+    d->w16_valid = true;
+    return launch_ok("dac_split_weights");
+}
+
+// Which layers run on the bf16 matrix cores in bf16x3, by geometry alone: every convolution with more than one input and more than one output
+// channel.  The one-channel first layer (K = 7 real values per row) and the one-channel tanh layer (one real output column) stay on the fp32 MFMA,
+// which is the same arithmetic grade; DESIGN.md section 13 has the measurements.
+inline bool x3_layer(const DacLayer& l) { return l.Cin > 1 && l.Cout > 1; }
+
 int ensure_scratch(escx_dac_s* d, size_t bytes) {
     if (d->scratch_bytes >= bytes) return 0;
     ESCX_HIP(hipDeviceSynchronize());
@@ -122,7 +143,7 @@ int ensure_scratch(escx_dac_s* d, size_t bytes) {
 }
 
 // What one pass needs besides the layer: the handle's Snake placement, a map-sized buffer for a Snaked copy, the stream.
-struct Run { int snake_maps; float* tmp; hipStream_t st; };
+struct Run { int snake_maps; float* tmp; hipStream_t st; const float* wbuf; const __bf16* w16; size_t plane; };     // w16 == nullptr: fp32 mode
 
 // out = conv(snake?(x)) over (B, Tin, CinP) -> (B, Tout, cpad(Cout)) [+ res]; ConvT: one GEMM per output phase.  Snake is applied while the
 // operand is staged, or - for the layer classes set in snake_maps - once per element into r.tmp, which the GEMM then reads plain (bitwise the
@@ -136,6 +157,7 @@ void run_layer(const Run& run, int cls, const DacLayer& l, const DacSnake* sn, c
         x = run.tmp; sn = nullptr;
     }
     const int phases = l.kind ? l.stride : 1;
+    const __bf16* W16 = (run.w16 && x3_layer(l)) ? run.w16 + (l.W - run.wbuf) : nullptr;
     for (int r = 0; r < phases; ++r) {
         DacConvA ld{};
         ld.x = x; ld.alpha = sn ? sn->a : nullptr; ld.inv = sn ? sn->inv : nullptr; ld.Tin = Tin; ld.Cp = l.CinP; ld.dCp = FastDiv(l.CinP);
@@ -146,7 +168,8 @@ void run_layer(const Run& run, int cls, const DacLayer& l, const DacSnake* sn, c
             ep.os = 1; ep.o0 = 0; ep.Trows = Tout; ep.bias = l.bias;
             ld.M = B * Tout; ld.dT = FastDiv(Tout); ep.dT = ld.dT;
             const long long tiles = (long long)((ld.M + 127) / 128) * ((l.Np + 95) / 96);
-            if (tiles >= 512) launch_gemm<128>(ld, l.W, ld.M, l.Np, l.Kp, ep, st);
+            if (W16) launch_dac_x3(ld, W16, run.plane, ld.M, l.Np, l.Kp, ep, st);
+            else if (tiles >= 512) launch_gemm<128>(ld, l.W, ld.M, l.Np, l.Kp, ep, st);
             else launch_gemm<64>(ld, l.W, ld.M, l.Np, l.Kp, ep, st);
         } else {
             const int s = l.stride, Q = r < Tout ? (Tout - r + s - 1) / s : 0;
@@ -156,7 +179,8 @@ void run_layer(const Run& run, int cls, const DacLayer& l, const DacSnake* sn, c
             ld.M = B * Q; ld.dT = FastDiv(Q); ep.dT = ld.dT;
             const float* W = l.W + (size_t)r * l.Np * l.Kp;
             const long long tiles = (long long)((ld.M + 127) / 128) * ((l.Np + 95) / 96);
-            if (tiles >= 512) launch_gemm<128>(ld, W, ld.M, l.Np, l.Kp, ep, st);
+            if (W16) launch_dac_x3(ld, W16 + (size_t)r * l.Np * l.Kp, run.plane, ld.M, l.Np, l.Kp, ep, st);
+            else if (tiles >= 512) launch_gemm<128>(ld, W, ld.M, l.Np, l.Kp, ep, st);
             else launch_gemm<64>(ld, W, ld.M, l.Np, l.Kp, ep, st);
         }
     }
@@ -283,6 +307,7 @@ extern "C" int escx_dac_create(const escx_dac_config* cfg, int device, escx_dac*
     auto take = [&](size_t n) { float* p = d->wbuf + cur; cur += pad64(n); return p; };
     for (auto* L : {&d->enc, &d->dec})
         for (DacLayer& l : *L) { l.W = take((size_t)(l.kind ? l.stride : 1) * l.Np * l.Kp); l.bias = take(l.Np); }
+    d->conv_floats = cur;                   // the layers come first in wbuf: the region the bf16x3 image mirrors
     for (auto* Sn : {&d->enc_sn, &d->dec_sn}) for (DacSnake& s : *Sn) { s.a = take(cpad(s.C)); s.inv = take(cpad(s.C)); }
     d->qt.win = take(qD); d->qt.bin = take((size_t)S * dd); d->qt.wout = take(qD); d->qt.bout = take((size_t)S * latent);
     d->qt.cbraw = take(qK * dd); d->qt.cbn = take(qK * dd); d->qt.c2 = take(qK);
@@ -294,6 +319,7 @@ extern "C" void escx_dac_destroy(escx_dac d) {
     if (!d) return;
     (void)hipSetDevice(d->device);
     if (d->wbuf) (void)hipFree(d->wbuf);
+    if (d->w16) (void)hipFree(d->w16);
     if (d->qoffs_dev) (void)hipFree(d->qoffs_dev);
     if (d->scratch) (void)hipFree(d->scratch);
     delete d;
@@ -312,6 +338,17 @@ extern "C" int escx_dac_set_snake_maps(escx_dac d, int mask) {
     return ESCX_OK;
 }
 extern "C" int escx_dac_get_snake_maps(escx_dac d) { return d ? d->snake_maps : -1; }
+
+extern "C" int escx_dac_set_precision(escx_dac d, int mode) {
+    if (!d) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null handle");
+    if (mode == ESCX_PRECISION_F16X2)
+        ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "DAC has no f16x2 mode: two fp16 terms need an a-priori bound on every operand (csrc/split_terms.h) and Snake outputs "
+                                        "have none; bf16x3 keeps fp32's exponent range and needs no bound");
+    if (mode != ESCX_PRECISION_FP32 && mode != ESCX_PRECISION_BF16X3) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "DAC precision %d: expected fp32 (0) or bf16x3 (3)", mode);
+    d->precision = mode;
+    return ESCX_OK;
+}
+extern "C" int escx_dac_get_precision(escx_dac d) { return d ? d->precision : -1; }
 
 extern "C" int escx_dac_num_frames(escx_dac d, int n_samples) {
     if (!d || n_samples < 1) return 0;
@@ -343,9 +380,9 @@ extern "C" int escx_dac_encode(escx_dac d, const float* flat, int64_t version, c
     const size_t M = (size_t)B * Tz;
     const size_t lossf = pad64((size_t)n * M) + pad64((size_t)n * B);
     if ((rc = ensure_scratch(d, (4 * mf + lossf) * sizeof(float)))) return rc;
-    if ((rc = pack(d, flat, (long long)version, st))) return rc;
+    if ((rc = pack(d, flat, (long long)version, st)) || (rc = refresh_w16(d, st))) return rc;
     float* x = d->scratch; float* y = x + mf; float* h = y + mf; float* lossb = h + mf + mf;
-    const Run run{d->snake_maps, h + mf, st};
+    const Run run{d->snake_maps, h + mf, st, d->wbuf, d->precision == ESCX_PRECISION_BF16X3 ? d->w16 : nullptr, d->conv_floats};
     hipLaunchKernelGGL(dac_wave_in_kernel, dim3(nblk((long long)B * L)), dim3(256), 0, st, audio, h, (long long)B * L);
     const DacLayer* E = d->enc.data(); const DacSnake* SN = d->enc_sn.data();
     run_layer(run, ESCX_DAC_SNAKE_LAST, E[0], nullptr, h, B, L, x, L, nullptr, 0);
@@ -400,9 +437,9 @@ extern "C" int escx_dac_decode(escx_dac d, const float* flat, int64_t version, c
     if (Lout < 1) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "%d latent frames decode to no sample", T);
     if ((unsigned long long)mf >= (1ull << 32)) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "batch of %d x %d frames: a feature map above 2^32 elements", B, T);
     if ((rc = ensure_scratch(d, 4 * mf * sizeof(float)))) return rc;
-    if ((rc = pack(d, flat, (long long)version, st))) return rc;
+    if ((rc = pack(d, flat, (long long)version, st)) || (rc = refresh_w16(d, st))) return rc;
     float* x = d->scratch; float* y = x + mf; float* h = y + mf;
-    const Run run{d->snake_maps, h + mf, st};
+    const Run run{d->snake_maps, h + mf, st, d->wbuf, d->precision == ESCX_PRECISION_BF16X3 ? d->w16 : nullptr, d->conv_floats};
     const int Dp = cpad(d->latent);
     hipLaunchKernelGGL(dac_z_in_kernel, dim3(nblk((long long)B * T * Dp)), dim3(256), 0, st, z, h, B, d->latent, Dp, T);
     const DacLayer* Dl = d->dec.data(); const DacSnake* SN = d->dec_sn.data();

@@ -1,0 +1,133 @@
+// The DAC convolutions in the exact split-operand grade (escx_dac_set_precision(d, ESCX_PRECISION_BF16X3)): the implicit GEMMs of dac_kernels.h on
+// v_mfma_f32_16x16x32_bf16 with every fp32 operand split exactly into three bf16 terms (gemm_bf16.h split3_bf16x4: v = t0 + t1 + t2) and the six leading
+// cross products accumulated in fp32, smallest first.  Derived from gemm_bf16_kernel<.., WB16 = true, KS = 1, NTERM = 3>; what DAC needs beyond it:
+//   * N tiles of 32, 64, 96 and 128 columns (Np = rup(Cout, 16) is 16 ... 1536; a tile's columns behind Np read zero weights and are not stored);
+//   * any Kp that is a multiple of 16: the weight pieces (8 bf16) behind Kp are zero, and DacConvA returns zero for a tap behind the last one, so the
+//     half-empty last 32-deep step adds exact zeros;
+//   * any M: rows behind M are staged as zeros and not stored; DacConvA zeroes a tap outside its own clip.
+// The weights come from a three-plane bf16 image of the packed, weight-normalised fp32 weights (dac.hip refresh_w16: split3_bf16_kernel over the whole
+// packed-weight region, rebuilt whenever the fp32 image is).  The activation terms are formed while the operand is staged, from the fp32 value the loader
+// returns - the Snake value when Snake is on this operand - so they do not depend on where Snake was evaluated.
+// Every output element sees the same sequence of MFMAs whatever the tile shape: K in steps of 32 from 0, per step the cross terms (0,2) (2,0) (1,1) (0,1)
+// (1,0) (0,0) (weight term, activation term).  A row's result therefore does not depend on the batch it is computed in.
+#pragma once
+#include <hip/hip_runtime.h>
+#include "gemm_bf16.h"
+
+namespace escx {
+
+template <int BM, int BN, class Loader, class Epi>
+__global__ __launch_bounds__(256) void dac_x3_kernel(Loader ld, const __bf16* __restrict__ W16, size_t plane, int M, int Np, int Kp, int nblk_n, Epi ep) {
+    static_assert(BM % 64 == 0 && BN % 16 == 0, "tile shape");
+    constexpr int BK = 32;
+    constexpr int LD = BK + 8;                 // bf16 per LDS row: 80 B, the 16 rows of a fragment read start 20 banks apart
+    constexpr int TM = BM / 64, TN = BN / 16;
+    constexpr int KV = BK / 4;                 // float4 per activation-tile row and K step
+    constexpr int AJ = BM * KV / 256;
+    constexpr int WP = BN * (BK / 8);          // 16-byte pieces (8 bf16) per weight-tile plane
+    constexpr int WJ = (WP + 255) / 256;       // ... per thread (the last round is partial for 96 and 32 columns)
+
+    __shared__ __attribute__((aligned(16))) __bf16 As[3 * BM * LD];
+    __shared__ __attribute__((aligned(16))) __bf16 Bs[3 * BN * LD];
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, lg = lane >> 4;
+    const int bm = blockIdx.x / nblk_n, bn = blockIdx.x - bm * nblk_n;
+    const int m0 = bm * BM, n0 = bn * BN;
+
+    typename Loader::Ctx ctx[AJ];
+#pragma unroll
+    for (int j = 0; j < AJ; ++j) ctx[j] = ld.make_ctx(m0 + (tid + j * 256) / KV);
+
+    f32x4 acc[TN][TM];
+#pragma unroll
+    for (int a = 0; a < TN; ++a)
+#pragma unroll
+        for (int b = 0; b < TM; ++b) acc[a][b] = zero4();
+
+    f32x4 ra[AJ];
+    uint4 rw[3 * WJ];
+    auto fetch = [&](int k0) {
+#pragma unroll
+        for (int j = 0; j < AJ; ++j) ra[j] = ld.load4(ctx[j], k0, 4 * ((tid + j * 256) % KV));
+#pragma unroll
+        for (int j = 0; j < WJ; ++j) {
+            const int i = tid + j * 256, row = i >> 2, c8 = i & 3;
+            const bool ok = (WP % 256 == 0 || i < WP) && n0 + row < Np && k0 + 8 * c8 < Kp;
+#pragma unroll
+            for (int p = 0; p < 3; ++p)
+                rw[p * WJ + j] = ok ? *reinterpret_cast<const uint4*>(W16 + p * plane + (size_t)(n0 + row) * Kp + k0 + 8 * c8) : make_uint4(0, 0, 0, 0);
+        }
+    };
+    fetch(0);
+    for (int k0 = 0; k0 < Kp; k0 += BK) {
+#pragma unroll
+        for (int j = 0; j < AJ; ++j) {
+            const int i = tid + j * 256;
+            bf16x4 t0, t1, t2; split3_bf16x4(ra[j], t0, t1, t2);
+            *reinterpret_cast<bf16x4*>(&As[(i / KV) * LD + 4 * (i % KV)]) = t0;
+            *reinterpret_cast<bf16x4*>(&As[BM * LD + (i / KV) * LD + 4 * (i % KV)]) = t1;
+            *reinterpret_cast<bf16x4*>(&As[2 * BM * LD + (i / KV) * LD + 4 * (i % KV)]) = t2;
+        }
+#pragma unroll
+        for (int j = 0; j < WJ; ++j) {
+            const int i = tid + j * 256;
+            if (WP % 256 == 0 || i < WP) {
+#pragma unroll
+                for (int p = 0; p < 3; ++p) *reinterpret_cast<uint4*>(&Bs[p * BN * LD + (i >> 2) * LD + 8 * (i & 3)]) = rw[p * WJ + j];
+            }
+        }
+        __syncthreads();
+        if (k0 + BK < Kp) fetch(k0 + BK);
+        bf16x8 af3[3][TM];
+#pragma unroll
+        for (int p = 0; p < 3; ++p)
+#pragma unroll
+            for (int b = 0; b < TM; ++b) af3[p][b] = *reinterpret_cast<const bf16x8*>(&As[p * BM * LD + (wave * (BM / 4) + b * 16 + l15) * LD + 8 * lg]);
+#pragma unroll
+        for (int a = 0; a < TN; ++a) {
+            bf16x8 wf3[3];
+#pragma unroll
+            for (int p = 0; p < 3; ++p) wf3[p] = *reinterpret_cast<const bf16x8*>(&Bs[p * BN * LD + (a * 16 + l15) * LD + 8 * lg]);
+#define ESCX_DX3(I, J) _Pragma("unroll") for (int b = 0; b < TM; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf3[I], af3[J][b], acc[a][b], 0, 0, 0);
+            ESCX_DX3(0, 2) ESCX_DX3(2, 0) ESCX_DX3(1, 1) ESCX_DX3(0, 1) ESCX_DX3(1, 0) ESCX_DX3(0, 0)
+#undef ESCX_DX3
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int b = 0; b < TM; ++b) {
+        const int m = m0 + wave * (BM / 4) + b * 16 + l15;
+        if (m >= M) continue;
+#pragma unroll
+        for (int a = 0; a < TN; ++a) {
+            const int n = n0 + a * 16 + 4 * lg;
+            if (n < Np) ep.store(m, n, acc[a][b], 0);
+        }
+    }
+}
+
+// The dispatch rule, on the layer geometry alone (never on the batch):
+//   columns per tile   Np <= 32: 32;  Np <= 64: 64;  else 96 or 128, whichever pads Np less (128 on a tie)
+//   rows per tile      128 when that gives at least 512 tiles (two resident workgroups per CU, twice over), else 64.  The row tile does depend on M;
+//                      it changes which workgroup computes an element, not the element's arithmetic (see the head of this file).
+inline int dac_x3_bn(int Np) {
+    if (Np <= 32) return 32;
+    if (Np <= 64) return 64;
+    return (Np + 127) / 128 * 128 <= (Np + 95) / 96 * 96 ? 128 : 96;
+}
+
+template <class Loader, class Epi>
+inline void launch_dac_x3(const Loader& ld, const __bf16* W16, size_t plane, int M, int Np, int Kp, const Epi& ep, hipStream_t s) {
+    const int bn = dac_x3_bn(Np), nbn = (Np + bn - 1) / bn;
+    const bool big = (long long)((M + 127) / 128) * nbn >= 512;
+    const dim3 grid(((M + (big ? 127 : 63)) / (big ? 128 : 64)) * nbn);
+#define ESCX_DX3_LAUNCH(BM, BN) hipLaunchKernelGGL((dac_x3_kernel<BM, BN, Loader, Epi>), grid, dim3(256), 0, s, ld, W16, plane, M, Np, Kp, nbn, ep)
+    if (big) {
+        if (bn == 128) ESCX_DX3_LAUNCH(128, 128); else if (bn == 96) ESCX_DX3_LAUNCH(128, 96); else if (bn == 64) ESCX_DX3_LAUNCH(128, 64); else ESCX_DX3_LAUNCH(128, 32);
+    } else {
+        if (bn == 128) ESCX_DX3_LAUNCH(64, 128); else if (bn == 96) ESCX_DX3_LAUNCH(64, 96); else if (bn == 64) ESCX_DX3_LAUNCH(64, 64); else ESCX_DX3_LAUNCH(64, 32);
+    }
+#undef ESCX_DX3_LAUNCH
+}
+
+}  // namespace escx

@@ -135,6 +135,8 @@ SIGNATURES = {
     "escx_dac_decode": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "escx_dac_set_snake_maps": (c_int, [c_void_p, c_int]),
     "escx_dac_get_snake_maps": (c_int, [c_void_p]),
+    "escx_dac_set_precision": (c_int, [c_void_p, c_int]),
+    "escx_dac_get_precision": (c_int, [c_void_p]),
     "escx_dac_test_math": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
     "escx_set_rccl_library": (c_int, [c_char_p]),
     "escx_allgather_codes": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p]),

@@ -100,6 +100,7 @@ class DAC(nn.Module):
         q = self.quantizer                                           # the reference's `quantizer` holds the parameters and from_codes (quantize.py:200-220)
         q.from_codes, q.n_codebooks, q.codebook_size, q.codebook_dim = self._from_codes, n_codebooks, codebook_size, [codebook_dim] * n_codebooks
         self._handles, self._flat = {}, {}
+        self._precision = "fp32"
 
     # ---- native handle and flat parameter buffer (same scheme as esc.models.Discriminator) ----------------------------------------------
     def _version(self) -> int:
@@ -146,6 +147,7 @@ class DAC(nn.Module):
             self._handles[idx] = hd
             if getattr(self, "_snake_maps", None) is not None:
                 _native.check(lib.escx_dac_set_snake_maps(hd, self._snake_maps))
+            _native.check(lib.escx_dac_set_precision(hd, _native.PRECISIONS[self._precision]))
         return lib, self._handles[idx]
 
     def _ensure_flat(self, device, lib, hd):
@@ -184,6 +186,27 @@ class DAC(nn.Module):
         for hd in self._handles.values():
             _native.check(_native.load().escx_dac_set_snake_maps(hd, self._snake_maps))
         return self
+
+    # ---- arithmetic of the convolutions (include/escx.h escx_dac_set_precision) --------------------------------------------------------------
+    def set_precision(self, mode: str) -> "DAC":
+        """Operand form of the convolutions of encode / decode / eval forward, with ESC.set_precision's names: "fp32" (fp32 MFMA, the default, the
+        reference's operand precision) or "bf16x3" (every fp32 operand split exactly into three bf16 terms, six cross products accumulated in
+        fp32: fp32-grade results up to summation order, on the 16-bit matrix cores).  "f16x2" is refused: two fp16 terms need a bound on every
+        operand and Snake outputs have none.  The quantiser is fp32 in both modes.  Not part of the reference's surface."""
+        if mode not in _native.PRECISIONS:
+            raise ValueError(f"precision {mode!r}: expected one of {sorted(_native.PRECISIONS)}")
+        if mode == "f16x2":
+            raise NotImplementedError("DAC has no f16x2 mode: two fp16 terms need an a-priori bound on every operand (csrc/split_terms.h) and Snake "
+                                      "outputs have none; use bf16x3, which keeps fp32's exponent range and needs no bound")
+        self._precision = mode
+        for hd in self._handles.values():
+            _native.check(_native.load().escx_dac_set_precision(hd, _native.PRECISIONS[mode]))
+        return self
+
+    @property
+    def precision(self) -> str:
+        """The mode in effect: what set_precision chose ("fp32" until then); every live handle is in it."""
+        return self._precision
 
     # ---- length arithmetic ---------------------------------------------------------------------------------------------------------------
     def num_frames(self, n_samples: int) -> int:

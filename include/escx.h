@@ -366,7 +366,7 @@ int escx_allgather_codes(escx_handle h, const int64_t* codes_local_dev, int64_t 
  * reference's named_parameters(): per convolution bias, weight_g, weight_v; per Snake alpha; per codebook weight).  Weight normalisation (the
  * transposed convolutions normalise over their INPUT channels, dim 0), the Snake reciprocals and the normalised codebooks are re-derived on the
  * device when (buffer, params_version) changes; a negative version always re-derives.  Tensors are the reference's layouts: audio (B, 1, L),
- * z (B, D, T), codes (B, n, T) int64, latents (B, n * codebook_dim, T).  Arithmetic is fp32.  A configuration the kernels do not cover
+ * z (B, D, T), codes (B, n, T) int64, latents (B, n * codebook_dim, T).  Arithmetic is fp32 (escx_dac_set_precision offers an exact split-operand form).  A configuration the kernels do not cover
  * (rates above 16, latent_dim above 1024 or not a multiple of 4, codebook_dim above 8, decoder_dim not divisible by 2^n_decoder_rates)
  * fails at create with ESCX_ERR_UNSUPPORTED. */
 #define ESCX_DAC_MAX_RATES 8
@@ -414,6 +414,17 @@ int escx_dac_decode(escx_dac d, const float* flat_params_dev, int64_t params_ver
 #define ESCX_DAC_SNAKE_MAPS_DEFAULT ESCX_DAC_SNAKE_ALL   /* measured faster for every class: profiles/dac_snake_ab.txt */
 int escx_dac_set_snake_maps(escx_dac d, int mask);
 int escx_dac_get_snake_maps(escx_dac d);
+/* Arithmetic of the convolutions of encode / decode, per handle, read at each call; the modes carry escx_set_precision's numbers:
+ *   ESCX_PRECISION_FP32    (default) every convolution on v_mfma_f32_16x16x4_f32 with fp32 operands; bitwise what the library computed before this switch existed.
+ *   ESCX_PRECISION_BF16X3  every fp32 operand (packed weight-normalised weights, feature maps after Snake) split EXACTLY into three bf16 terms, six cross
+ *                          products accumulated in fp32 on v_mfma_f32_16x16x32_bf16: fp32-grade results that differ from ESCX_PRECISION_FP32 by summation
+ *                          order and the three dropped cross terms (below 2^-24 relative).  The one-channel first and last convolutions stay on the fp32
+ *                          MFMA and the quantiser on the fp32 VALU (the rule is on the layer geometry, never on the batch).
+ *   ESCX_PRECISION_F16X2   ESCX_ERR_UNSUPPORTED: two fp16 terms need an a-priori bound on every operand (csrc/split_terms.h) and Snake outputs have none.
+ * Any other value is ESCX_ERR_INVALID_ARG.  In both modes a clip's codes and audio do not depend on the batch, and both Snake placements give the same bits.
+ * The three-term weight image is rebuilt whenever the packed fp32 weights are (params_version, buffer) and when the mode is first switched on. */
+int escx_dac_set_precision(escx_dac d, int mode);
+int escx_dac_get_precision(escx_dac d);
 /* Test hook: the kernels' Snake (mode 0: x + sin(alpha x)^2 / (alpha + 1e-9), nn/layers.py:19-24) or tanh (mode 1) over n device values. */
 int escx_dac_test_math(const float* x_dev, const float* alpha_dev, float* out_dev, int64_t n, int mode, void* stream);
 

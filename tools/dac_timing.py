@@ -3,9 +3,12 @@ DAC-Tiny and DAC-Base (16 kHz / 9 kbps configurations, name-keyed weights from e
 same batches (bench.py's model, all streams), and the torch-eager restatement (tests/dac_util.py) on the same GPU.  FLOPs are counted from the
 convolution shapes (2 * MACs; the quantiser's projections and search are included in encode); TFLOP/s = FLOPs / time.  Host wall clock around
 `--steps` synchronised calls, the same count for native and eager.  --snake-ab instead times native encode and decode for each Snake placement
-(include/escx.h escx_dac_set_snake_maps: Snake on the staged operand, or a Snaked copy of the map, per layer class).
+(include/escx.h escx_dac_set_snake_maps: Snake on the staged operand, or a Snaked copy of the map, per layer class).  --precision-ab times native
+encode / decode / forward in "fp32" and "bf16x3" (DAC.set_precision), the two modes alternating over --rounds rounds in one process with the same
+warm-up and step counts; the spread of the fp32 rounds, (max - min) / min, is the noise a difference has to exceed.  ESC-Base's forward in
+"bf16x3" is timed next to it for the like-for-like line.
 
-    python tools/dac_timing.py [--steps 10] [--warmup 3] [--json OUT] [--snake-ab]
+    python tools/dac_timing.py [--steps 10] [--warmup 3] [--json OUT] [--snake-ab | --precision-ab [--rounds 3]]
 """
 import argparse
 import json
@@ -105,16 +108,58 @@ def snake_ab(a, dev):
     return rows
 
 
+def precision_ab(a, dev):
+    """Per model and batch: ms per call of each mode (mean and every round), the fp32 run-to-run spread and fp32 / bf16x3."""
+    from esc import synth
+    rows = []
+    ops = ("encode", "decode", "forward")
+    for name in CONFIGS:
+        m, _ = dac_model(name, dev)
+        for B in (36, 1):
+            pcm = np.stack([synth.voiced_clip_int16(f"dac-time-{i}", 48000) if i % 2 else synth.noise_clip_int16(f"dac-time-{i}", 48000) for i in range(B)])
+            x = torch.from_numpy(synth.pcm_to_float(pcm))[:, None].to(dev)
+            z = m.encode(x)[0]
+            fns = {"encode": lambda: m.encode(x), "decode": lambda: m.decode(z), "forward": lambda: m(x)}
+            t = {mode: {op: [] for op in ops} for mode in ("fp32", "bf16x3")}
+            for _ in range(a.rounds):
+                for mode in ("fp32", "bf16x3"):
+                    m.set_precision(mode)
+                    for op in ops:
+                        t[mode][op].append(timed(fns[op], a.steps, a.warmup))
+            m.set_precision("fp32")
+            for op in ops:
+                f, b = t["fp32"][op], t["bf16x3"][op]
+                r = {"model": name, "batch": B, "op": op, "fp32_ms": round(sum(f) / len(f), 3), "bf16x3_ms": round(sum(b) / len(b), 3),
+                     "fp32_rounds": [round(v, 3) for v in f], "bf16x3_rounds": [round(v, 3) for v in b],
+                     "fp32_spread": round((max(f) - min(f)) / min(f), 4), "speedup": round(sum(f) / sum(b), 3)}
+                rows.append(r)
+                print(json.dumps(r), flush=True)
+        del m
+        torch.cuda.empty_cache()
+    esc_model = bench.build_model(dev)[0]
+    esc_model.set_precision("bf16x3")
+    s = getattr(esc_model, "max_streams", 6)
+    for B in (36, 1):
+        xe = bench.synth_batch(B, 0).to(dev)
+        f = [timed(lambda: esc_model(xe, None, s), a.steps, a.warmup) for _ in range(a.rounds)]
+        r = {"model": "esc_base", "batch": B, "op": "forward", "bf16x3_ms": round(sum(f) / len(f), 3), "bf16x3_rounds": [round(v, 3) for v in f]}
+        rows.append(r)
+        print(json.dumps(r), flush=True)
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--json", default=None)
     ap.add_argument("--snake-ab", action="store_true")
+    ap.add_argument("--precision-ab", action="store_true")
+    ap.add_argument("--rounds", type=int, default=3)
     a = ap.parse_args()
     dev = torch.device("cuda:0")
-    if a.snake_ab:
-        rows = snake_ab(a, dev)
+    if a.snake_ab or a.precision_ab:
+        rows = snake_ab(a, dev) if a.snake_ab else precision_ab(a, dev)
         if a.json:
             with open(a.json, "w") as f:
                 json.dump(rows, f, indent=1)
