@@ -54,6 +54,7 @@ struct escx_dac_s {
     // bf16x3: three bf16 planes of the packed convolution weights wbuf[0, conv_floats), plane p at w16 + p * conv_floats.  Allocated at the first
     // call in that mode; w16_valid is cleared by every re-pack of the fp32 image and set by refresh_w16, so the image can never be older than wbuf.
     __bf16* w16 = nullptr; size_t conv_floats = 0; bool w16_valid = false;
+    int* counts = nullptr; size_t counts_cap = 0;   // per-clip stage counts / snapshot stages of the _ex calls, uploaded on the call's stream
 };
 
 namespace {
@@ -212,6 +213,43 @@ size_t dec_scratch(escx_dac_s* d, int B, int T, int* Lout) {
     return mx;
 }
 
+// Host counts -> the handle's device buffer on the call's stream (as rvq_upload of escx_api.cpp does for RVQCodecs); nullptr stays nullptr.
+int upload_counts(escx_dac_s* d, const int32_t* host, int count, const int** dev, hipStream_t st) {
+    *dev = nullptr;
+    if (!host) return 0;
+    if (d->counts_cap < (size_t)count) {
+        ESCX_HIP(hipDeviceSynchronize());
+        if (d->counts) ESCX_HIP(hipFree(d->counts));
+        d->counts = nullptr; d->counts_cap = 0;
+        const size_t cap = pad64((size_t)count);
+        ESCX_HIP(hipMalloc((void**)&d->counts, cap * sizeof(int)));
+        d->counts_cap = cap;
+    }
+    ESCX_HIP(hipMemcpyAsync(d->counts, host, (size_t)count * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    *dev = d->counts;
+    return 0;
+}
+
+template <bool FROM_CODES, int EXT>
+void launch_rvq(int latent, long long M, const DacQArgs& qa, hipStream_t st) {
+    const int J = (latent + 63) / 64;
+    const dim3 g(nblk(M, 4)), blk(256);
+    if (J <= 1) hipLaunchKernelGGL((dac_rvq_kernel<1, FROM_CODES, EXT>), g, blk, 0, st, qa);
+    else if (J <= 2) hipLaunchKernelGGL((dac_rvq_kernel<2, FROM_CODES, EXT>), g, blk, 0, st, qa);
+    else if (J <= 4) hipLaunchKernelGGL((dac_rvq_kernel<4, FROM_CODES, EXT>), g, blk, 0, st, qa);
+    else if (J <= 8) hipLaunchKernelGGL((dac_rvq_kernel<8, FROM_CODES, EXT>), g, blk, 0, st, qa);
+    else hipLaunchKernelGGL((dac_rvq_kernel<16, FROM_CODES, EXT>), g, blk, 0, st, qa);
+}
+
+// per-clip counts of an _ex call: each in [1, n_codebooks] and at most the n slots the call has
+int check_clip_counts(escx_dac_s* d, const int32_t* clip_n, int B, int n) {
+    for (int b = 0; b < B; ++b) {
+        if (clip_n[b] < 1 || clip_n[b] > d->cfg.n_codebooks) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "clip_n[%d]=%d outside [1, %d]", b, clip_n[b], d->cfg.n_codebooks);
+        if (clip_n[b] > n) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "clip_n[%d]=%d above the %d code slots of the call", b, clip_n[b], n);
+    }
+    return 0;
+}
+
 int check_args(escx_dac_s* d, const float* flat, int B) {
     if (!d || !flat || B < 1) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "bad argument");
     ESCX_HIP(hipSetDevice(d->device));
@@ -322,6 +360,7 @@ extern "C" void escx_dac_destroy(escx_dac d) {
     if (d->w16) (void)hipFree(d->w16);
     if (d->qoffs_dev) (void)hipFree(d->qoffs_dev);
     if (d->scratch) (void)hipFree(d->scratch);
+    if (d->counts) (void)hipFree(d->counts);
     delete d;
 }
 
@@ -368,9 +407,23 @@ extern "C" int escx_dac_output_samples(escx_dac d, int n_frames) {
 
 extern "C" int escx_dac_encode(escx_dac d, const float* flat, int64_t version, const float* audio, int B, int L, int n_q, float* z, int64_t* codes,
                                float* latents, float* losses, void* stream) {
+    return escx_dac_encode_ex(d, flat, version, audio, B, L, n_q, nullptr, nullptr, 0, z, codes, latents, losses, nullptr, stream);
+}
+
+extern "C" int escx_dac_encode_ex(escx_dac d, const float* flat, int64_t version, const float* audio, int B, int L, int n_q, const int32_t* clip_n,
+                                  const int32_t* snap_n, int n_snaps, float* z, int64_t* codes, float* latents, float* losses, float* zsnap, void* stream) {
     int rc = check_args(d, flat, B); if (rc) return rc;
     if (!audio || !z || !codes || !latents || !losses || n_q < 1) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "bad argument");
+    if (clip_n && snap_n) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "per-clip counts and snapshots are not combined in one call");
+    if (clip_n && n_q > d->cfg.n_codebooks) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "%d code slots above the %d codebooks", n_q, d->cfg.n_codebooks);
     const int n = std::min(n_q, d->cfg.n_codebooks);
+    if (clip_n && (rc = check_clip_counts(d, clip_n, B, n))) return rc;
+    if (snap_n) {
+        if (n_snaps < 1 || !zsnap) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "snapshots need n_snaps >= 1 and a zsnap buffer");
+        for (int r = 0; r < n_snaps; ++r)
+            if (snap_n[r] < 1 || snap_n[r] > n || (r && snap_n[r] <= snap_n[r - 1]))
+                ESCX_FAIL(ESCX_ERR_INVALID_ARG, "snap_n[%d]=%d: strictly increasing stage counts in [1, %d] expected", r, snap_n[r], n);
+    }
     const int Tz0 = escx_dac_num_frames(d, L);
     if (Tz0 < 1) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "%d samples give no latent frame (the hop is %d)", L, d->hop);
     hipStream_t st = (hipStream_t)stream;
@@ -380,6 +433,7 @@ extern "C" int escx_dac_encode(escx_dac d, const float* flat, int64_t version, c
     const size_t M = (size_t)B * Tz;
     const size_t lossf = pad64((size_t)n * M) + pad64((size_t)n * B);
     if ((rc = ensure_scratch(d, (4 * mf + lossf) * sizeof(float)))) return rc;
+    const int* cdev; if ((rc = upload_counts(d, clip_n ? clip_n : snap_n, clip_n ? B : n_snaps, &cdev, st))) return rc;
     if ((rc = pack(d, flat, (long long)version, st)) || (rc = refresh_w16(d, st))) return rc;
     float* x = d->scratch; float* y = x + mf; float* h = y + mf; float* lossb = h + mf + mf;
     const Run run{d->snake_maps, h + mf, st, d->wbuf, d->precision == ESCX_PRECISION_BF16X3 ? d->w16 : nullptr, d->conv_floats};
@@ -399,32 +453,30 @@ extern "C" int escx_dac_encode(escx_dac d, const float* flat, int64_t version, c
     DacQArgs qa{};
     qa.t = d->qt; qa.zmap = y; qa.z = z; qa.codes = (long long*)codes; qa.latents = latents; qa.loss = lossb;
     qa.M = (int)M; qa.T = T; qa.D = d->latent; qa.Dp = cpad(d->latent); qa.d = d->cfg.codebook_dim; qa.K = d->cfg.codebook_size; qa.n = n;
-    const int J = (d->latent + 63) / 64;
-    const dim3 g(nblk((long long)M, 4)), blk(256);
-    if (J <= 1) hipLaunchKernelGGL((dac_rvq_kernel<1, false>), g, blk, 0, st, qa);
-    else if (J <= 2) hipLaunchKernelGGL((dac_rvq_kernel<2, false>), g, blk, 0, st, qa);
-    else if (J <= 4) hipLaunchKernelGGL((dac_rvq_kernel<4, false>), g, blk, 0, st, qa);
-    else if (J <= 8) hipLaunchKernelGGL((dac_rvq_kernel<8, false>), g, blk, 0, st, qa);
-    else hipLaunchKernelGGL((dac_rvq_kernel<16, false>), g, blk, 0, st, qa);
+    if (clip_n) { qa.clip_n = cdev; launch_rvq<false, DAC_Q_CLIPS>(d->latent, (long long)M, qa, st); }
+    else if (snap_n) { qa.snap_n = cdev; qa.n_snaps = n_snaps; qa.zsnap = zsnap; launch_rvq<false, DAC_Q_SNAPS>(d->latent, (long long)M, qa, st); }
+    else launch_rvq<false, DAC_Q_PLAIN>(d->latent, (long long)M, qa, st);
     hipLaunchKernelGGL(dac_loss_kernel, dim3(1), dim3(256), 0, st, lossb, lossb + pad64((size_t)n * M), losses, B, T, n, d->cfg.codebook_dim);
     return launch_ok("escx_dac_encode");
 }
 
 extern "C" int escx_dac_from_codes(escx_dac d, const float* flat, int64_t version, const int64_t* codes, int B, int n, int T, float* z, float* zp, void* stream) {
+    return escx_dac_from_codes_ex(d, flat, version, codes, B, n, T, nullptr, z, zp, stream);
+}
+
+extern "C" int escx_dac_from_codes_ex(escx_dac d, const float* flat, int64_t version, const int64_t* codes, int B, int n, int T, const int32_t* clip_n,
+                                      float* z, float* zp, void* stream) {
     int rc = check_args(d, flat, B); if (rc) return rc;
     if (!codes || !z || !zp || T < 1 || n < 1 || n > d->cfg.n_codebooks) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "bad argument (codes of %d codebooks, %d frames)", n, T);
+    if (clip_n && (rc = check_clip_counts(d, clip_n, B, n))) return rc;
     hipStream_t st = (hipStream_t)stream;
+    const int* cdev; if ((rc = upload_counts(d, clip_n, B, &cdev, st))) return rc;
     if ((rc = pack(d, flat, (long long)version, st))) return rc;
     DacQArgs qa{};
     qa.t = d->qt; qa.codes_in = (const long long*)codes; qa.z = z; qa.latents = zp;
     qa.M = B * T; qa.T = T; qa.D = d->latent; qa.Dp = cpad(d->latent); qa.d = d->cfg.codebook_dim; qa.K = d->cfg.codebook_size; qa.n = n;
-    const int J = (d->latent + 63) / 64;
-    const dim3 g(nblk((long long)B * T, 4)), blk(256);
-    if (J <= 1) hipLaunchKernelGGL((dac_rvq_kernel<1, true>), g, blk, 0, st, qa);
-    else if (J <= 2) hipLaunchKernelGGL((dac_rvq_kernel<2, true>), g, blk, 0, st, qa);
-    else if (J <= 4) hipLaunchKernelGGL((dac_rvq_kernel<4, true>), g, blk, 0, st, qa);
-    else if (J <= 8) hipLaunchKernelGGL((dac_rvq_kernel<8, true>), g, blk, 0, st, qa);
-    else hipLaunchKernelGGL((dac_rvq_kernel<16, true>), g, blk, 0, st, qa);
+    if (clip_n) { qa.clip_n = cdev; launch_rvq<true, DAC_Q_CLIPS>(d->latent, (long long)B * T, qa, st); }
+    else launch_rvq<true, DAC_Q_PLAIN>(d->latent, (long long)B * T, qa, st);
     return launch_ok("escx_dac_from_codes");
 }
 

@@ -175,8 +175,15 @@ __global__ void dac_qtables_kernel(const float* __restrict__ flat, const long lo
 //   o = out_proj(q);  z_q += o;  residual -= o;  sum_j (z_e - raw_k)^2 goes to the per-(stage, row) loss slot
 // The codebook-dimension loops run to DAC_DMAX with a guard, so ze / e / q stay in registers (the order of the operations is that of the d-loop).
 // FROM_CODES: z_q = sum over stages, in stage order from 0, of out_proj(raw_{code}) (quantize.py:200-220); z_p gets the raw rows.
+// EXT selects one optional input (never both); DAC_Q_PLAIN is the kernel without either, instruction for instruction:
+//   DAC_Q_CLIPS  clip_n[b] stages for the rows of clip b (the per-item mask of quantize.py:181-190; wave-uniform, a wave owns one row).  The
+//                slots clip_n[b] <= i < n get code -1, zero latents and a zero loss term, so dac_loss_kernel's sum_i mean_b is the reference's
+//                masked mean.  FROM_CODES never reads those slots and writes zero z_p there.
+//   DAC_Q_SNAPS  after stage i with i + 1 == snap_n[r] the running sum goes to zsnap[r] (B, D, T) with the store pattern of the final z:
+//                the same registers at the same point of the same sum as a call that stops at n = snap_n[r].
 // ------------------------------------------------------------------------------------------------
 constexpr int DAC_DMAX = 8;
+constexpr int DAC_Q_PLAIN = 0, DAC_Q_CLIPS = 1, DAC_Q_SNAPS = 2;
 
 struct DacQArgs {
     DacQTables t;
@@ -187,6 +194,10 @@ struct DacQArgs {
     float* latents;                 // (B, n * d, T)  (from_codes form: z_p)
     float* loss;                    // [n][M] squared-error sums
     int M, T, D, Dp, d, K, n;
+    const int* clip_n;              // DAC_Q_CLIPS: [B] stage counts, each in [1, n]
+    const int* snap_n;              // DAC_Q_SNAPS: [n_snaps] strictly increasing stage counts in [1, n]
+    float* zsnap;                   // DAC_Q_SNAPS: (n_snaps, B, D, T)
+    int n_snaps;
 };
 
 __device__ __forceinline__ float wave_sum(float v) {
@@ -195,7 +206,7 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
-template <int J, bool FROM_CODES>
+template <int J, bool FROM_CODES, int EXT = DAC_Q_PLAIN>
 __global__ __launch_bounds__(256) void dac_rvq_kernel(DacQArgs a) {
 #pragma clang fp contract(off)
     const int lane = threadIdx.x & 63;
@@ -210,7 +221,10 @@ __global__ __launch_bounds__(256) void dac_rvq_kernel(DacQArgs a) {
         zq[j] = 0.f;
         res[j] = (!FROM_CODES && c < D) ? a.zmap[((size_t)b * a.T + t) * a.Dp + c] : 0.f;
     }
-    for (int i = 0; i < a.n; ++i) {
+    int nb = a.n;                                               // stages of this row
+    if constexpr (EXT == DAC_Q_CLIPS) nb = max(0, min(a.clip_n[b], a.n));
+    [[maybe_unused]] int snap = 0;
+    for (int i = 0; i < nb; ++i) {
         float q[DAC_DMAX];
         int best = 0;
         if constexpr (FROM_CODES) {
@@ -273,6 +287,23 @@ __global__ __launch_bounds__(256) void dac_rvq_kernel(DacQArgs a) {
             const float o = s + bo[c];
             zq[j] = zq[j] + o;
             res[j] = res[j] - o;
+        }
+        if constexpr (EXT == DAC_Q_SNAPS) {
+            if (snap < a.n_snaps && i + 1 == a.snap_n[snap]) {                  // wave-uniform
+                float* zs = a.zsnap + (size_t)snap * a.M * D;
+#pragma unroll
+                for (int j = 0; j < J; ++j) {
+                    const int c = lane + 64 * j;
+                    if (c < D) zs[((size_t)b * D + c) * a.T + t] = zq[j];
+                }
+                ++snap;
+            }
+        }
+    }
+    if constexpr (EXT == DAC_Q_CLIPS) {
+        for (int i = nb; i < a.n; ++i) {                                        // the slots past this clip's count
+            if (lane < d) a.latents[((size_t)b * a.n * d + (size_t)i * d + lane) * a.T + t] = 0.f;
+            if constexpr (!FROM_CODES) if (lane == 0) { a.codes[((size_t)b * a.n + i) * a.T + t] = -1; a.loss[(size_t)i * a.M + row] = 0.f; }
         }
     }
 #pragma unroll

@@ -9,8 +9,9 @@ from __future__ import annotations
 
 import ctypes
 import math
-from typing import List, Union
+from typing import List, Sequence, Union
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -243,9 +244,111 @@ class DAC(nn.Module):
             raise ValueError(f"n_quantizers must be at least 1, got {n_quantizers}")
         return min(n, self.n_codebooks)                 # the reference's loop stops at the last codebook
 
+    @staticmethod
+    def _int_entries(n_quantizers, what: str) -> List[int]:
+        """The entries of a sequence or 1-D integer tensor of codebook counts as Python ints; anything else raises ValueError."""
+        if isinstance(n_quantizers, torch.Tensor):
+            if n_quantizers.dim() != 1 or n_quantizers.is_floating_point() or n_quantizers.is_complex() or n_quantizers.dtype == torch.bool:
+                raise ValueError(f"{what} must be a 1-D integer tensor, got {n_quantizers.dtype} of shape {tuple(n_quantizers.shape)}")
+            return [int(v) for v in n_quantizers.tolist()]
+        vals = list(n_quantizers)
+        for v in vals:
+            if isinstance(v, torch.Tensor) and v.dim() == 0 and not (v.is_floating_point() or v.is_complex() or v.dtype == torch.bool):
+                continue
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"{what} must hold integers, got {v!r}")
+        return [int(v) for v in vals]
+
+    @staticmethod
+    def _is_per_clip(n_quantizers) -> bool:
+        return isinstance(n_quantizers, (list, tuple, np.ndarray)) or (isinstance(n_quantizers, torch.Tensor) and n_quantizers.dim() >= 1)
+
+    def _clip_counts(self, n_quantizers, batch: int) -> List[int]:
+        """Per-clip codebook counts (the per-item mask of quantize.py:181-190): `batch` integers, each at least 1, clamped to n_codebooks."""
+        vals = self._int_entries(n_quantizers, "per-clip n_quantizers")
+        if len(vals) != batch:
+            raise ValueError(f"per-clip n_quantizers has {len(vals)} entries for a batch of {batch}")
+        for v in vals:
+            if v < 1:
+                raise ValueError(f"n_quantizers must be at least 1 for every clip, got {v}")
+        return [min(v, self.n_codebooks) for v in vals]
+
+    def _sweep_counts(self, n_quantizers) -> List[int]:
+        """encode_sweep's stage counts: strictly increasing integers from 1 up, each clamped to n_codebooks; duplicates after the clamp raise."""
+        if not self._is_per_clip(n_quantizers):
+            raise ValueError("encode_sweep takes a sequence of codebook counts")
+        vals = self._int_entries(n_quantizers, "encode_sweep's n_quantizers")
+        if not vals:
+            raise ValueError("encode_sweep needs at least one codebook count")
+        if vals[0] < 1:
+            raise ValueError(f"n_quantizers must be at least 1, got {vals[0]}")
+        if any(b <= a for a, b in zip(vals, vals[1:])):
+            raise ValueError(f"encode_sweep's n_quantizers must be strictly increasing, got {vals}")
+        out = [min(v, self.n_codebooks) for v in vals]
+        if len(set(out)) != len(out):
+            raise ValueError(f"encode_sweep's n_quantizers {vals} repeat a count once clamped to the {self.n_codebooks} codebooks")
+        return out
+
+    def _audio_shape(self, audio_data):
+        if audio_data.dim() != 3 or audio_data.shape[1] != 1:
+            raise ValueError(f"audio_data must be (B, 1, L), got {tuple(audio_data.shape)}")
+        B, _, L = audio_data.shape
+        T = self.num_frames(L)
+        if T < 1:
+            raise ValueError(f"{L} samples are shorter than one hop ({self.hop_length}): the encoder gives no frame")
+        return B, L, T
+
     @torch.no_grad()
-    def encode(self, audio_data: torch.Tensor, n_quantizers: int = None):
-        """dac.py:209-247: (z (B, D, T), codes (B, n, T) int64, latents (B, n d, T), commitment_loss, codebook_loss)."""
+    def _encode_counts(self, audio_data: torch.Tensor, counts: List[int]):
+        """encode with one codebook count per clip (include/escx.h escx_dac_encode_ex, clip_n)."""
+        lib, hd, flat, dev, stream = self._ctx(audio_data, "audio_data")
+        B, L, T = self._audio_shape(audio_data)
+        n = max(counts)
+        x = audio_data.to(torch.float32).contiguous()
+        z = torch.empty(B, self.latent_dim, T, device=dev)
+        codes = torch.empty(B, n, T, dtype=torch.int64, device=dev)
+        latents = torch.empty(B, n * self.codebook_dim, T, device=dev)
+        losses = torch.empty(2, device=dev)
+        cn = (ctypes.c_int32 * B)(*counts)
+        with torch.cuda.device(dev):
+            _native.check(lib.escx_dac_encode_ex(hd, ctypes.c_void_p(flat.data_ptr()), self._version(), ctypes.c_void_p(x.data_ptr()), B, L, n, cn, None, 0,
+                                                 ctypes.c_void_p(z.data_ptr()), ctypes.c_void_p(codes.data_ptr()), ctypes.c_void_p(latents.data_ptr()),
+                                                 ctypes.c_void_p(losses.data_ptr()), None, stream))
+        return z, codes, latents, losses[0], losses[1]
+
+    @torch.no_grad()
+    def encode_sweep(self, audio_data: torch.Tensor, n_quantizers: Sequence[int]):
+        """One encode for a whole bitrate sweep: (zs (R, B, D, T), codes (B, n_max, T), latents (B, n_max d, T)) with zs[r] bitwise the z of
+        encode(audio_data, n_quantizers[r]) and codes / latents those of the largest count (the codes are prefix codes; the quantiser stores its
+        running sum, quantize.py:185, after each requested stage: include/escx.h escx_dac_encode_ex, snap_n).  Not part of the reference's surface."""
+        if self.training:
+            raise NotImplementedError("esc.baselines.DAC is inference only: call .eval() (DAC training is not implemented)")
+        ns = self._sweep_counts(n_quantizers)
+        lib, hd, flat, dev, stream = self._ctx(audio_data, "audio_data")
+        B, L, T = self._audio_shape(audio_data)
+        n, R = ns[-1], len(ns)
+        x = audio_data.to(torch.float32).contiguous()
+        z = torch.empty(B, self.latent_dim, T, device=dev)
+        zs = torch.empty(R, B, self.latent_dim, T, device=dev)
+        codes = torch.empty(B, n, T, dtype=torch.int64, device=dev)
+        latents = torch.empty(B, n * self.codebook_dim, T, device=dev)
+        losses = torch.empty(2, device=dev)
+        sn = (ctypes.c_int32 * R)(*ns)
+        with torch.cuda.device(dev):
+            _native.check(lib.escx_dac_encode_ex(hd, ctypes.c_void_p(flat.data_ptr()), self._version(), ctypes.c_void_p(x.data_ptr()), B, L, n, None, sn, R,
+                                                 ctypes.c_void_p(z.data_ptr()), ctypes.c_void_p(codes.data_ptr()), ctypes.c_void_p(latents.data_ptr()),
+                                                 ctypes.c_void_p(losses.data_ptr()), ctypes.c_void_p(zs.data_ptr()), stream))
+        return zs, codes, latents
+
+    @torch.no_grad()
+    def encode(self, audio_data: torch.Tensor, n_quantizers: Union[int, Sequence[int], torch.Tensor] = None):
+        """dac.py:209-247: (z (B, D, T), codes (B, n, T) int64, latents (B, n d, T), commitment_loss, codebook_loss).  n_quantizers may also be
+        one count per clip (a sequence or 1-D integer tensor of B entries, the per-item mask of quantize.py:181-190): n = max(counts), codes hold
+        -1 and latents 0 past a clip's count, the losses are the reference's masked means."""
+        if self._is_per_clip(n_quantizers):
+            if self.training:
+                raise NotImplementedError("esc.baselines.DAC is inference only: call .eval() (DAC training is not implemented)")
+            return self._encode_counts(audio_data, self._clip_counts(n_quantizers, audio_data.shape[0]))
         lib, hd, flat, dev, stream = self._ctx(audio_data, "audio_data")
         n = self._n_quantizers(n_quantizers)
         if audio_data.dim() != 3 or audio_data.shape[1] != 1:
@@ -280,26 +383,46 @@ class DAC(nn.Module):
         return out
 
     @torch.no_grad()
-    def _from_codes(self, codes: torch.Tensor):
-        """ResidualVectorQuantize.from_codes: (z_q (B, D, T), z_p (B, n d, T), codes); `model.quantizer.from_codes` is this method."""
+    def _from_codes(self, codes: torch.Tensor, n_quantizers: Union[Sequence[int], torch.Tensor] = None):
+        """ResidualVectorQuantize.from_codes: (z_q (B, D, T), z_p (B, n d, T), codes); `model.quantizer.from_codes` is this method.  With
+        n_quantizers (one count per clip, as encode takes them) clip b sums its first n_b codebooks and the slots past its count are ignored,
+        whatever they hold (encode's per-clip form writes -1 there); z_p is 0 in them."""
+        counts = None
+        if n_quantizers is not None:
+            if self.training:
+                raise NotImplementedError("esc.baselines.DAC is inference only: call .eval() (DAC training is not implemented)")
+            counts = self._clip_counts(n_quantizers if self._is_per_clip(n_quantizers) else [n_quantizers] * codes.shape[0], codes.shape[0])
         lib, hd, flat, dev, stream = self._ctx(codes, "codes")
         if codes.dim() != 3 or not 1 <= codes.shape[1] <= self.n_codebooks:
             raise ValueError(f"codes must be (B, n <= {self.n_codebooks}, T), got {tuple(codes.shape)}")
         B, n, T = codes.shape
         c = codes.to(torch.int64).contiguous()
-        if c.numel() and (int(c.min()) < 0 or int(c.max()) >= self.codebook_size):
+        if counts is not None and max(counts) > n:
+            raise ValueError(f"per-clip n_quantizers up to {max(counts)} for codes of {n} codebooks")
+        used = c
+        if counts is not None:                                   # the range check covers the slots that are read
+            live = torch.arange(n, device=dev)[None, :, None] < torch.tensor(counts, device=dev)[:, None, None]
+            used = c[live.expand_as(c)]
+        if used.numel() and (int(used.min()) < 0 or int(used.max()) >= self.codebook_size):
             raise IndexError(f"codes outside [0, {self.codebook_size}): F.embedding of the reference raises here")
         z = torch.empty(B, self.latent_dim, T, device=dev)
         zp = torch.empty(B, n * self.codebook_dim, T, device=dev)
         with torch.cuda.device(dev):
-            _native.check(lib.escx_dac_from_codes(hd, ctypes.c_void_p(flat.data_ptr()), self._version(), ctypes.c_void_p(c.data_ptr()), B, n, T,
-                                                  ctypes.c_void_p(z.data_ptr()), ctypes.c_void_p(zp.data_ptr()), stream))
+            if counts is None:
+                _native.check(lib.escx_dac_from_codes(hd, ctypes.c_void_p(flat.data_ptr()), self._version(), ctypes.c_void_p(c.data_ptr()), B, n, T,
+                                                      ctypes.c_void_p(z.data_ptr()), ctypes.c_void_p(zp.data_ptr()), stream))
+            else:
+                _native.check(lib.escx_dac_from_codes_ex(hd, ctypes.c_void_p(flat.data_ptr()), self._version(), ctypes.c_void_p(c.data_ptr()), B, n, T,
+                                                         (ctypes.c_int32 * B)(*counts), ctypes.c_void_p(z.data_ptr()), ctypes.c_void_p(zp.data_ptr()), stream))
         return z, zp, codes
 
-    def forward(self, audio_data: torch.Tensor, sample_rate: int = None, n_quantizers: int = None):
-        """dac.py:268-323 in eval mode: right-pad to a multiple of the hop, encode, decode, trim the audio to the input length."""
+    def forward(self, audio_data: torch.Tensor, sample_rate: int = None, n_quantizers: Union[int, Sequence[int], torch.Tensor] = None):
+        """dac.py:268-323 in eval mode: right-pad to a multiple of the hop, encode, decode, trim the audio to the input length.  n_quantizers
+        may be one count per clip, as in encode."""
         if self.training:
             raise NotImplementedError("esc.baselines.DAC is inference only: call .eval() (DAC training is not implemented)")
+        if self._is_per_clip(n_quantizers):
+            n_quantizers = self._clip_counts(n_quantizers, audio_data.shape[0])
         _check_device(audio_data, "audio_data")
         length = audio_data.shape[-1]
         x = self.preprocess(audio_data, sample_rate)

@@ -395,11 +395,30 @@ int escx_dac_output_samples(escx_dac d, int n_frames);
  * n_codebooks); n_quantizers < 1 is ESCX_ERR_INVALID_ARG.  The quantiser is one launch. */
 int escx_dac_encode(escx_dac d, const float* flat_params_dev, int64_t params_version, const float* audio_dev, int batch, int n_samples, int n_quantizers,
                     float* z_dev, int64_t* codes_dev, float* latents_dev, float* losses_dev, void* stream);
+/* escx_dac_encode with one of two optional HOST arrays (both NULL: escx_dac_encode itself, the same bits; both given: ESCX_ERR_INVALID_ARG).  They
+ * are copied to a handle-owned device buffer on the call's stream.
+ *   clip_n[batch]    per-clip stage counts, the per-item mask the reference's quantiser applies for quantiser dropout (quantize.py:181-190): clip b
+ *                    runs codebooks i < clip_n[b].  Each entry lies in [1, n_codebooks]; n_quantizers is then the number of code slots per clip and
+ *                    must lie in [max(clip_n), n_codebooks].  codes (B, n_quantizers, T) hold -1 and latents (B, n_quantizers * codebook_dim, T) hold
+ *                    0 in the slots at or past a clip's count; losses are sum_i mean_b(loss_ib * [i < clip_n[b]]) (quantize.py:189-190).  z, codes
+ *                    and latents of clip b up to its count are bitwise those of a call with n_quantizers = clip_n[b] (one wave per latent row).
+ *   snap_n[n_snaps]  strictly increasing stage counts in [1, min(n_quantizers, n_codebooks)]: zsnap (n_snaps, B, D, T) receives the running sum z_q
+ *                    (quantize.py:185) after snap_n[r] codebooks, bitwise the z of a call with n_quantizers = snap_n[r].  Both codecs' codes are
+ *                    prefix codes, so one encode serves every bitrate of an evaluation sweep.  zsnap_dev is ignored without snap_n.
+ * A bad count (0, above n_codebooks, above n_quantizers, snapshots not increasing) is ESCX_ERR_INVALID_ARG and leaves the handle usable. */
+int escx_dac_encode_ex(escx_dac d, const float* flat_params_dev, int64_t params_version, const float* audio_dev, int batch, int n_samples, int n_quantizers,
+                       const int32_t* clip_n, const int32_t* snap_n, int n_snaps, float* z_dev, int64_t* codes_dev, float* latents_dev, float* losses_dev,
+                       float* zsnap_dev, void* stream);
 /* ResidualVectorQuantize.from_codes (quantize.py:200-220): codes (B, n, T) -> z_q (B, D, T) and z_p (B, n * codebook_dim, T).  The kernel clamps
  * a code outside [0, codebook_size) to the nearest valid row instead of reading outside the codebook; the reference's F.embedding raises there,
  * and the Python host (esc.baselines.DAC) checks the range and raises IndexError before calling. */
 int escx_dac_from_codes(escx_dac d, const float* flat_params_dev, int64_t params_version, const int64_t* codes_dev, int batch, int n_codes, int n_frames,
                         float* z_dev, float* zp_dev, void* stream);
+/* escx_dac_from_codes (quantize.py:200-220) with optional per-clip counts clip_n[batch] (HOST array, each in [1, min(n_codes, n_codebooks)]; NULL:
+ * escx_dac_from_codes itself): clip b sums the codebooks i < clip_n[b], the slots past its count are never read whatever they hold, and z_p is 0
+ * there - the inverse of escx_dac_encode_ex's per-clip form (quantize.py:181-185). */
+int escx_dac_from_codes_ex(escx_dac d, const float* flat_params_dev, int64_t params_version, const int64_t* codes_dev, int batch, int n_codes, int n_frames,
+                           const int32_t* clip_n, float* z_dev, float* zp_dev, void* stream);
 /* DAC.decode (dac.py:249-266): z (B, D, T) -> audio (B, escx_dac_output_samples(T)). */
 int escx_dac_decode(escx_dac d, const float* flat_params_dev, int64_t params_version, const float* z_dev, int batch, int n_frames, float* audio_dev, void* stream);
 /* Where Snake (nn/layers.py:19-24) is evaluated, per layer class: bit set = written once per element into a Snaked copy of the map that the
