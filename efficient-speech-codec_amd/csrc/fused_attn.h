@@ -136,12 +136,8 @@ struct AttnArgs {
     // window attention and output projection are ONE launch and nothing is read back (train.hip, layer_fwd).
     float* tape_xn; float* tape_qkv; float* tape_o; int ldq, ldo, hdp, nH;
     const void* x3_wf;          // X3 instantiations: the split weight stream (attn_x3_pack_kernel), else unused
-    int unused;                 // no kernel reads it: without this slot hipcc schedules kept instantiations differently (profiles/exp_removal_isa_diff.txt)
     const float* x3_scale;      // NT = 2 instantiations: {2^-k / sx, 2^k sx, sx, so | 2^-kp / so} of the block's weight stream (its last 32 bytes; sx / so = scales of the LayerNorm output / of the O^T tiles, split_terms.h)
 };
-
-// One 16-byte piece of a block-input row (LayerNorm input and shortcut)
-__device__ __forceinline__ f32x4 load_block_input(const AttnArgs& a, size_t elem) { return ld4(a.src + elem); }
 
 // Shift mask of one window for this lane's (query l15, keys 4lg..4lg+3): -100 where query and key carry different region labels
 // (attention.py:56-75, 233-236).  It only depends on the window, so it is built once per window, not once per head.
@@ -298,7 +294,7 @@ __global__ __launch_bounds__(64 * NW, (attn_min_waves_x<CP, TMW, X3>())) void at
         float s = 0.f;
 #pragma unroll
         for (int kk = 0; kk < KK; ++kk) {
-            xf[t][kk] = tok[t] >= 0 ? load_block_input(a, xoff + 16 * kk) : zero4();
+            xf[t][kk] = tok[t] >= 0 ? ld4(a.src + xoff + 16 * kk) : zero4();
 #pragma unroll
             for (int e = 0; e < 4; ++e) s += xf[t][kk][e];            // pad channels are exact zeros
         }
@@ -564,7 +560,6 @@ __global__ __launch_bounds__(64 * NW, (attn_min_waves_x<CP, TMW, X3>())) void at
 #pragma unroll
     for (int t = 0; t < TMW; ++t) shmask[t] = window_shift_mask(l15, lg, lastH[t], lastW[t]);
     GroupConst cur = load_consts(g0);
-    f32x4 spare[1];         // never used; without this declaration hipcc schedules the C = 144 split-operand instantiations differently (profiles/exp_removal_isa_diff.txt)
     for (int g = g0; g < g1; ++g) {
         tile = 0;
         ESCX_TS(t0)
@@ -720,7 +715,7 @@ __global__ __launch_bounds__(64 * NW, (attn_min_waves_x<CP, TMW, X3>())) void at
         float* dr = a.dst + (size_t)tok[t] * CP + 4 * lg;
         f32x4 res[KK];          // all loads, then all stores (dst may alias src: interleaved, every store fences the next load)
 #pragma unroll
-        for (int o = 0; o < KK; ++o) { res[o] = load_block_input(a, soff + 16 * o); acc[o][t] += ld4(a.bproj + 16 * o + 4 * lg); }
+        for (int o = 0; o < KK; ++o) { res[o] = ld4(a.src + soff + 16 * o); acc[o][t] += ld4(a.bproj + 16 * o + 4 * lg); }
 #pragma unroll
         for (int o = 0; o < KK; ++o) st4(dr + 16 * o, res[o] + acc[o][t]);
     }
@@ -838,7 +833,7 @@ __global__ __launch_bounds__(64 * NW, (attn_min_waves_x<CP, 1, X3>())) void attn
         float s = 0.f;
 #pragma unroll
         for (int kk = 0; kk < KK; ++kk) {
-            xf[kk] = tok >= 0 ? load_block_input(a, xoff + 16 * kk) : zero4();
+            xf[kk] = tok >= 0 ? ld4(a.src + xoff + 16 * kk) : zero4();
 #pragma unroll
             for (int e = 0; e < 4; ++e) s += xf[kk][e];
         }
@@ -1052,7 +1047,7 @@ __global__ __launch_bounds__(64 * NW, (attn_min_waves_x<CP, 1, X3>())) void attn
         float* dr = a.dst + (size_t)tok * CP + 4 * lg;
         f32x4 res[KK];
 #pragma unroll
-        for (int o = 0; o < KK; ++o) { res[o] = load_block_input(a, soff + 16 * o); acc[o] += ld4(a.bproj + 16 * o + 4 * lg); }
+        for (int o = 0; o < KK; ++o) { res[o] = ld4(a.src + soff + 16 * o); acc[o] += ld4(a.bproj + 16 * o + 4 * lg); }
 #pragma unroll
         for (int o = 0; o < KK; ++o) st4(dr + 16 * o, res[o] + acc[o]);
     }

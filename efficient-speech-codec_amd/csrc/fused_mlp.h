@@ -29,7 +29,6 @@ struct MlpArgs {
     const f32x4* wcf;                           // per hidden tile: [HT][KK fc1 fragments | KK fc2 fragments][64] (LDS-staged variant)
     int M, C, HT;
     float eps;
-    unsigned long long* unused;                 // no kernel reads it: without this slot hipcc schedules mlp_x3_kernel differently (profiles/exp_removal_isa_diff.txt)
     // Hidden split (LDS-staged kernel only): with fewer row tiles than SIMDs (deep layers at small batch) the grid is
     // row-blocks x HS and workgroup (rb, hs) walks hidden tiles [hs*HT/HS, (hs+1)*HT/HS); the fc2 partial sums go to
     // partial[hs][M][CP] and mlp_combine_kernel adds them in fixed order (deterministic, no atomics).
@@ -256,6 +255,7 @@ __global__ __launch_bounds__(64 * NW, (mlp_min_waves<CP, TM>())) void mlp_fused_
         f32x4 ring[PD];
 #pragma unroll
         for (int i = 0; i < PD; ++i) ring[i] = wb[i * 64];
+        constexpr int NDMA = (CH + NW - 1) / NW, DSTEP = KK / NDMA > 0 ? KK / NDMA : 1;       // DMA pieces per wave and stage, and their spacing in fragments
         f32x4 h[TM], h2[TM];
 #pragma unroll
         for (int t = 0; t < TM; ++t) { h[t] = bb; h2[t] = zero4(); }   // the fc1 bias rides in the accumulator (one VALU add less per tile)
@@ -263,13 +263,10 @@ __global__ __launch_bounds__(64 * NW, (mlp_min_waves<CP, TM>())) void mlp_fused_
         for (int f = 0; f < KK; ++f) {
             const f32x4 w = ring[f % PD];
             if (f + PD < CH) ring[f % PD] = wb[(f + PD) * 64];
-            {       // one 1 KiB DMA every DSTEP fragments, all issued within the fc1 phase
-                constexpr int NDMA = (CH + NW - 1) / NW, DSTEP = KK / NDMA > 0 ? KK / NDMA : 1;
-                if (f % DSTEP == 0 && f / DSTEP < NDMA) {
-                    int c = wave + (f / DSTEP) * NW;
-                    if (CH % NW != 0) c = min(c, CH - 1);       // tail: a duplicate of the last piece (same bytes) keeps the loop body branch-free
-                    __builtin_amdgcn_global_load_lds((const void*)(dsrc + c * 64), (__attribute__((address_space(3))) void*)(ddst + c * 64), 16, 0, 0);
-                }
+            if (f % DSTEP == 0 && f / DSTEP < NDMA) {       // one 1 KiB DMA every DSTEP fragments, all issued within the fc1 phase
+                int c = wave + (f / DSTEP) * NW;
+                if (CH % NW != 0) c = min(c, CH - 1);       // tail: a duplicate of the last piece (same bytes) keeps the loop body branch-free
+                __builtin_amdgcn_global_load_lds((const void*)(dsrc + c * 64), (__attribute__((address_space(3))) void*)(ddst + c * 64), 16, 0, 0);
             }
 #pragma unroll
             for (int r = 0; r < 4; ++r)
@@ -312,10 +309,8 @@ __global__ __launch_bounds__(64 * NW, (mlp_min_waves<CP, TM>())) void mlp_fused_
 #pragma unroll
         for (int f = 0; f < CH; ++f) {
             if (f + PD < CH) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-            {       // the DMA pieces stay where they are issued (unpinned, the scheduler sinks them to the end of the stage)
-                constexpr int NDMA = (CH + NW - 1) / NW, DSTEP = KK / NDMA > 0 ? KK / NDMA : 1;
-                if (f < KK && f % DSTEP == 0 && f / DSTEP < NDMA) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-            }
+            // the DMA pieces stay where they are issued (unpinned, the scheduler sinks them to the end of the stage)
+            if (f < KK && f % DSTEP == 0 && f / DSTEP < NDMA) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
             __builtin_amdgcn_sched_group_barrier(0x008, 4 * TM, 0);
         }
     }

@@ -3,16 +3,16 @@
 //   ->  up-projection of the SUM  ->  un-framed store into the decoder's input map
 //                                   (quantization.py:139-431 ResidualVectorQuantize / ProductResidualVectorQuantize; codebook.py:20-55)
 //
-// It reuses the structure of pvq_fused_kernel (fused_pvq.h) phase for phase:
-//   P1 / P2  identical: wave z is split-K slice z of the down-projection (partials in LDS), the slices are added in slice order, so the projected
-//            vector is bit for bit what ESC's stream-0 quantiser computes for the same weights.  The projected vector is the stage-0 residual.
+// Every phase that decides a code index is pvq_fused_kernel's own code: the shared device functions of fused_pvq.h, called from both kernels.
+//   P1 / P2  pvq_down_slice, pvq_sum_slices: wave z is split-K slice z of the down-projection (partials in LDS), the slices are added in slice order,
+//            so the projected vector is bit for bit what ESC's stream-0 quantiser computes for the same weights.  It is the stage-0 residual.
 //   P3       a loop over the stages s < S_b (S_b = the clip's own count: a per-clip device array, or one uniform S).  Each stage normalises the
-//            residual (same fmaf chain, IEEE sqrt and division as P2), searches the stage's normalised codebook with the same MFMA dot products,
-//            running argmin and cross-wave combine (tie -> lowest index, NaN semantics of torch.min), writes the code, gathers the RAW row
-//            (codebook.py:52-53), subtracts it from the residual and adds it to the running sum (quantization.py:180-186: residual - z_q_i,
-//            z_q + z_q_i, the sum starting from 0).  The optional per-vector commitment term mse(z_q_i, residual_i) goes to a per-stage slot
-//            loss[s][g][m], reduced per clip afterwards by loss_reduce (fixed order, no atomics).  Slots S_b .. Smax-1 get code -1 and loss 0.
-//   P4       (forward) the MFMA up-projection of pvq_fused_kernel's P4, with the summed vector as the operand instead of one codebook row
+//            residual (pvq_normalise), searches the stage's normalised codebooks (pvq_search_group, pvq_combine_waves: tie -> lowest index, NaN
+//            semantics of torch.min), writes the code, gathers the RAW row (codebook.py:52-53), subtracts it from the residual and adds it to the
+//            running sum (quantization.py:180-186: residual - z_q_i, z_q + z_q_i, the sum starting from 0).  The optional per-vector commitment
+//            term mse(z_q_i, residual_i) goes to a per-stage slot loss[s][g][m], reduced per clip afterwards by loss_reduce (fixed order, no
+//            atomics).  Slots S_b .. Smax-1 get code -1 and loss 0.
+//   P4       (forward) pvq_up_mfma with the summed vector as the operand instead of one codebook row
 //            (quantization.py:320: proj_up of the SUM, not the sum of up-projections); no residual map is added.
 // DECODE = true is the codes-in form of the same kernel (escx_decode): P1-P3 are replaced by the gather-sum of the raw rows in stage order from
 // 0.f, and P4 is the same code - so eval forward's audio equals decode(encode(x)) bit for bit.
@@ -43,8 +43,8 @@ template <int NT, int STEPS, bool DECODE>
 __global__ __launch_bounds__(64 * PVQF_WAVES) void prvq_fused_kernel(PrvqArgs a) {
 #pragma clang fp contract(off)
     ESCX_SET_PRIO_SMALL();
-    constexpr int NP = 16 * NT, NPS = NP + 4, DT = 4 * STEPS, KC = NT;
-    extern __shared__ __attribute__((aligned(16))) float prvq_part[];           // [16 slices][16 rows][NPS] (encode form only)
+    constexpr int NP = 16 * NT, DT = 4 * STEPS, KC = NT;
+    extern __shared__ __attribute__((aligned(16))) float prvq_part[];           // [16 slices][16 rows][NP + 4] (encode form only)
     __shared__ float res[16][NP + 1];               // residual entering the current stage
     __shared__ float zsum[16][NP + 1];              // running sum of the raw rows (the operand of the up-projection)
     __shared__ float zn2[PVQF_GMAX][16][DT];
@@ -93,59 +93,9 @@ __global__ __launch_bounds__(64 * PVQF_WAVES) void prvq_fused_kernel(PrvqArgs a)
         }
         __syncthreads();
     } else {
-        // ---- P1: split-K slice `wave` of the down-projection (pvq_fused_kernel's P1 without a residual map) ----
-        {
-            constexpr int PF = NT >= 6 ? 2 : (NT >= 4 ? 3 : (NT == 3 ? 4 : (NT == 2 ? 5 : 6)));
-            const int kbeg = wave * a.k_per_z, kend = min(a.Kq, kbeg + a.k_per_z);
-            if (wave < a.splits && kbeg < kend) {                  // wave-uniform
-                const int nch = (kend - kbeg) >> 4;
-                const float* wfrag = a.wd + (size_t)lane * 4;
-                f32x4 er[PF], wr[PF][NT];
-                auto issue = [&](int ci, f32x4& e, f32x4 (&wf)[NT]) {
-                    const int k0 = kbeg + 16 * min(ci, nch - 1);                               // past the end: re-read the last chunk (never consumed)
-                    const int oh = k0 / a.Cp, cc = k0 - oh * a.Cp, o = oh / a.Hq, h = oh - o * a.Hq;
-                    e = ld4(a.enc + vecbase + (size_t)(h * a.Wd + o) * a.Cp + cc);
-#pragma unroll
-                    for (int n = 0; n < NT; ++n) wf[n] = ld4(wfrag + ((size_t)(k0 >> 4) * NT + n) * 256);
-                };
-                f32x4 acc[NT];
-#pragma unroll
-                for (int n = 0; n < NT; ++n) acc[n] = zero4();
-                auto consume = [&](const f32x4& e, const f32x4 (&wf)[NT]) {
-                    f32x4 af = e;
-                    if (!live) af = zero4();
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-#pragma unroll
-                        for (int n = 0; n < NT; ++n) acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[n][r], af[r], acc[n], 0, 0, 0);
-                };
-#pragma unroll
-                for (int j = 0; j < PF; ++j) issue(j, er[j], wr[j]);
-                const int rounds = nch / PF, tail = nch - rounds * PF;
-                for (int rd = 0; rd < rounds; ++rd) {
-#pragma unroll
-                    for (int j = 0; j < PF; ++j) {
-                        consume(er[j], wr[j]);
-                        issue((rd + 1) * PF + j, er[j], wr[j]);
-                    }
-                }
-#pragma unroll
-                for (int j = 0; j < PF - 1; ++j)
-                    if (j < tail) consume(er[j], wr[j]);
-                float* pr = prvq_part + ((size_t)wave * 16 + l15) * NPS + 4 * lg;
-#pragma unroll
-                for (int n = 0; n < NT; ++n) st4(pr + 16 * n, acc[n]);
-            }
-        }
+        pvq_down_slice<NT, false>(a.enc, nullptr, a.wd, vecbase, live, lane, wave, a.Kq, a.k_per_z, a.splits, a.Hq, a.Wd, a.Cp, prvq_part);      // P1
         __syncthreads();
-        // ---- P2: slices added in slice order: the stage-0 residual ----
-        for (int e = tid; e < 16 * NP; e += 64 * PVQF_WAVES) {
-            const int r = e / NP, n = e - r * NP;
-            float z = 0.f;
-#pragma unroll
-            for (int s = 0; s < 16; ++s) z += (s < a.splits) ? prvq_part[((size_t)s * 16 + r) * NPS + n] : 0.f;
-            res[r][n] = z;
-        }
+        pvq_sum_slices<NT>(prvq_part, a.splits, tid, res);                                                                                        // P2: the stage-0 residual
         __syncthreads();
 
         // ---- P3: the residual stages ----
@@ -153,90 +103,14 @@ __global__ __launch_bounds__(64 * PVQF_WAVES) void prvq_fused_kernel(PrvqArgs a)
 #pragma unroll
         for (int i = 0; i < 16; ++i) s_hi = max(s_hi, nst[i]);
         for (int s = 0; s < s_hi; ++s) {
-            if (tid < 16 * a.G) {           // F.normalize and sum(zn^2) of the residual (P2's arithmetic)
-                const int g = tid >> 4, vi = tid & 15;
-                float zr[DT];
-#pragma unroll
-                for (int j = 0; j < DT; ++j) zr[j] = res[vi][g * DT + j];
-                float ss = 0.f;
-#pragma unroll
-                for (int j = 0; j < DT; ++j) ss = (j < a.d) ? __builtin_fmaf(zr[j], zr[j], ss) : ss;
-                const float den = a.l2norm ? fmaxf(sqrtf(ss), 1e-12f) : 1.0f;
-                float s2 = 0.f;
-#pragma unroll
-                for (int j = 0; j < DT; ++j) {
-                    const float zn = (j < a.d) ? zr[j] / den : 0.f;
-                    s2 = __builtin_fmaf(zn, zn, s2);
-                    zn2[g][vi][j] = 2.0f * zn;
-                }
-                asum[g][vi] = s2;
-            }
+            pvq_normalise<NT, STEPS>(res, tid, a.G, a.d, a.l2norm, zn2, asum);
             __syncthreads();
-            {                               // distances + running argmin (pvq_fused_kernel's P3 on stage s's codebooks)
-                constexpr int TB = 4;
-                const int per_wave = ((a.Ksz + PVQF_WAVES - 1) / PVQF_WAVES + 15) & ~15;
-                const int cbeg = wave * per_wave, cend = min(a.Ksz, cbeg + per_wave);
-                for (int g = 0; g < a.G; ++g) {
-                    float zf[STEPS];
-#pragma unroll
-                    for (int r = 0; r < STEPS; ++r) zf[r] = zn2[g][l15][STEPS * lg + r];
-                    const float av = asum[g][l15];
-                    const float* cb = a.cbn + ((size_t)s * a.G + g) * a.Ksz * DT;
-                    const float* c2 = a.c2 + ((size_t)s * a.G + g) * a.Ksz;
-                    float bd = __builtin_inff();
-                    int bi = 0x7fffffff;
-                    bool have = false;
-                    for (int cb0 = cbeg; cb0 < cend; cb0 += 16 * TB) {
-                        float cf[TB][STEPS], c2v[TB][4];
-#pragma unroll
-                        for (int u = 0; u < TB; ++u) {
-                            const int c0 = cb0 + 16 * u;
-                            const float* p = cb + (size_t)min(c0 + l15, a.Ksz - 1) * DT + STEPS * lg;
-#pragma unroll
-                            for (int r = 0; r < STEPS; ++r) cf[u][r] = p[r];
-#pragma unroll
-                            for (int r = 0; r < 4; ++r) c2v[u][r] = c2[min(c0 + 4 * lg + r, a.Ksz - 1)];
-                        }
-#pragma unroll
-                        for (int u = 0; u < TB; ++u) {
-                            const int c0 = cb0 + 16 * u;
-                            f32x4 dot = zero4();
-#pragma unroll
-                            for (int r = 0; r < STEPS; ++r) dot = __builtin_amdgcn_mfma_f32_16x16x4f32(cf[u][r], zf[r], dot, 0, 0, 0);
-#pragma unroll
-                            for (int r = 0; r < 4; ++r) {
-                                const int code = c0 + 4 * lg + r;
-                                const float dist = (av - dot[r]) + c2v[u][r];
-                                const bool in = code < cend;
-                                const bool take = in & (!have | (!(dist >= bd) & (bd == bd)));
-                                bd = take ? dist : bd; bi = take ? code : bi; have = have | in;
-                            }
-                        }
-                    }
-#pragma unroll
-                    for (int o = 16; o <= 32; o <<= 1) {
-                        const float od = __shfl_xor(bd, o);
-                        const int oi = __shfl_xor(bi, o);
-                        const bool n1 = od != od, n2 = bd != bd;
-                        const bool better = (n1 | n2) ? (n1 & (!n2 | (oi < bi))) : ((od < bd) | ((od == bd) & (oi < bi)));
-                        bd = better ? od : bd; bi = better ? oi : bi;
-                    }
-                    if (lg == 0) { bestd[wave][g][l15] = bd; besti[wave][g][l15] = bi; }
-                }
-            }
+            for (int g = 0; g < a.G; ++g)
+                pvq_search_group<STEPS>(a.cbn + ((size_t)s * a.G + g) * a.Ksz * DT, a.c2 + ((size_t)s * a.G + g) * a.Ksz, a.Ksz, g, wave, l15, lg, zn2, asum, bestd, besti);
             __syncthreads();
             if (tid < 16 * a.G) {           // cross-wave argmin, code, commitment term, residual update, running sum
                 const int g = tid >> 4, vi = tid & 15;
-                float wd_[PVQF_WAVES]; int wi_[PVQF_WAVES];
-#pragma unroll
-                for (int w = 0; w < PVQF_WAVES; ++w) { wd_[w] = bestd[w][g][vi]; wi_[w] = besti[w][g][vi]; }
-                float d0 = wd_[0]; int i0 = wi_[0];
-#pragma unroll
-                for (int w = 1; w < PVQF_WAVES; ++w) {
-                    const bool n1 = wd_[w] != wd_[w], n2 = d0 != d0;
-                    const bool better = (n1 | n2) ? (n1 & (!n2 | (wi_[w] < i0))) : ((wd_[w] < d0) | ((wd_[w] == d0) & (wi_[w] < i0)));
-                    d0 = better ? wd_[w] : d0; i0 = better ? wi_[w] : i0;
-                }
+                int i0 = pvq_combine_waves(bestd, besti, g, vi);
                 const int mm = m0 + vi;
                 if (mm < a.M && s < nst[vi]) {
                     i0 = i0 < 0 ? 0 : (i0 >= a.Ksz ? a.Ksz - 1 : i0);        // a NaN-only row keeps the lowest index; never outside the codebook
@@ -273,38 +147,13 @@ __global__ __launch_bounds__(64 * PVQF_WAVES) void prvq_fused_kernel(PrvqArgs a)
     }
     if (!a.out) return;
 
-    // ---- P4: up-projection of the summed vector + un-framed store (pvq_fused_kernel's MFMA form of P4, no residual map) ----
-    {
-        constexpr int UNR = KC >= 6 ? 2 : (KC >= 4 ? 3 : (KC == 3 ? 4 : 6));
-        f32x4 zf[KC];
+    // ---- P4: up-projection of the summed vector + un-framed store ----
+    f32x4 zf[KC];
 #pragma unroll
-        for (int c = 0; c < KC; ++c)
+    for (int c = 0; c < KC; ++c)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) zf[c][r] = zsum[l15][16 * c + 4 * lg + r];       // padding elements of the sum are zero
-        const int NTo = a.Kq / 16;
-        const float* wrow = a.wup + (size_t)l15 * NP + 4 * lg;
-        for (int nt0 = wave * UNR; nt0 < NTo; nt0 += PVQF_WAVES * UNR) {
-            f32x4 wf[UNR][KC];
-            size_t idx[UNR];
-#pragma unroll
-            for (int u = 0; u < UNR; ++u) {
-                const int nt = min(nt0 + u, NTo - 1);                              // ragged tail: a duplicate tile, not stored
-#pragma unroll
-                for (int c = 0; c < KC; ++c) wf[u][c] = ld4(wrow + (size_t)(16 * nt) * NP + 16 * c);
-                const int n0 = 16 * nt, oh = n0 / a.Cp, c0 = n0 - oh * a.Cp, o = oh / a.Hq, h = oh - o * a.Hq;      // wave-uniform
-                idx[u] = vecbase + (size_t)(h * a.Wd + o) * a.Cp + c0;
-            }
-#pragma unroll
-            for (int u = 0; u < UNR; ++u) {
-                f32x4 acc = zero4();
-#pragma unroll
-                for (int c = 0; c < KC; ++c)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[u][c][r], zf[c][r], acc, 0, 0, 0);
-                if (live && nt0 + u < NTo) st4(a.out + idx[u], acc);
-            }
-        }
-    }
+        for (int r = 0; r < 4; ++r) zf[c][r] = zsum[l15][16 * c + 4 * lg + r];       // padding elements of the sum are zero
+    pvq_up_mfma<NT, false>(zf, a.wup, nullptr, a.out, vecbase, live, wave, l15, lg, a.Kq, a.Hq, a.Wd, a.Cp);
 }
 
 }  // namespace escx

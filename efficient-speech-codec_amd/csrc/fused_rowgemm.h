@@ -28,7 +28,6 @@ struct RowGemmArgs {
     int split, H, W, C2p;       // split != 0: out[(b, 2h+s, w)][c] with n = s*C2p + c ; else out[m][n], row stride 16*NT
     float eps;
     int nt_chunk;               // output tiles per workgroup column: blockIdx.y owns tiles [y * nt_chunk, (y + 1) * nt_chunk)
-    int unused;                 // no kernel reads it: without this slot hipcc schedules rowgemm_x3_kernel differently (profiles/exp_removal_isa_diff.txt)
     const void* x3_wf;          // rowgemm_x3_kernel: split weight stream [output tile][3 KS fragments] (attn_x3_pack_kernel), else unused
     const float* x3_scale;      // NT = 2: {2^-k / sx, 2^k sx, sx} of the scaled two-term stream (its last 16 bytes)
 };

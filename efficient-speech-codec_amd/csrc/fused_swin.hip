@@ -55,7 +55,7 @@ int mlp_fused(float* x, int M, int C, int Cp, const float* gamma, const float* b
         const int hs0 = hs_io ? *hs_io : 1;
         if (hs0 > 1 || out || (variant != 1 && variant != 3) || (split->NT & 1) || !(Cp == 80 || Cp == 96 || Cp == 144)) return ESCX_COMB_UNSUPPORTED;
         MlpArgs a{x, gamma, beta, reinterpret_cast<const f32x4*>(w1f), b1, reinterpret_cast<const f32x4*>(w2f), b2,
-                  reinterpret_cast<const f32x4*>(wcf), M, C, hiddenP / 16, 1e-5f, nullptr, 1, nullptr, nullptr,
+                  reinterpret_cast<const f32x4*>(wcf), M, C, hiddenP / 16, 1e-5f, 1, nullptr, nullptr,
                   reinterpret_cast<const f32x4*>(split->wf), split->gamma, split->beta, split->out, split->NT, split->H, split->W, split->C2p};
         const bool nw8 = variant == 3;
         switch (Cp) {
@@ -70,7 +70,7 @@ int mlp_fused(float* x, int M, int C, int Cp, const float* gamma, const float* b
     if (hs > 1 && (variant <= 0 || variant > 3 || !lds_width || !partial || (hiddenP / 16) % hs)) hs = 1;
     if (hs_io) *hs_io = hs;
     MlpArgs a{x, gamma, beta, reinterpret_cast<const f32x4*>(w1f), b1, reinterpret_cast<const f32x4*>(w2f), b2,
-              reinterpret_cast<const f32x4*>(wcf), M, C, hiddenP / 16, 1e-5f, nullptr, hs, partial, out,
+              reinterpret_cast<const f32x4*>(wcf), M, C, hiddenP / 16, 1e-5f, hs, partial, out,
               nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0};
     if (out && hs > 1) return -1;       // a separate output: plain epilogues only (no hidden split)
     if (variant > 0) {
@@ -255,7 +255,7 @@ int rowgemm_fused(int segs, const float* x, float* out, const float* gamma, cons
                   const void* x3_wf, int x3_nt) {
     const int KP = segs * Cp;
     RowGemmArgs a{x, out, gamma, beta, reinterpret_cast<const f32x4*>(wf), map, M, rows_per_clip, src_rows_per_clip, C, Cp, Np / 16,
-                  split, H, W, C2p, 1e-5f, Np / 16, 0, x3_wf,
+                  split, H, W, C2p, 1e-5f, Np / 16, x3_wf,
                   (x3_wf && x3_nt == 2) ? reinterpret_cast<const float*>(reinterpret_cast<const char*>(x3_wf) + rowgemm_x3_bytes(KP, Np) - 16) : nullptr};
     if (segs == 1) {
         switch (KP) {
@@ -436,7 +436,7 @@ int attn_fused(const float* src, float* dst, int Cp, int C, int mode, int n_grou
     AttnArgs a{src, dst, gamma, beta, reinterpret_cast<const f32x4*>(wf), bqkv, bias_tab, bproj, map, slots, tokens, n_windows,
                nWh, nWw, shifted, C, n_groups, scale, 1e-5f, gs, partial, rows, g_mlp_trace,
                tape ? tape->xn : nullptr, tape ? tape->qkv : nullptr, tape ? tape->o : nullptr, tape ? tape->ldq : 0, tape ? tape->ldo : 0,
-               tape ? tape->hdp : 0, tape ? tape->nH : 0, tape ? nullptr : x3_wf, 0,
+               tape ? tape->hdp : 0, tape ? tape->nH : 0, tape ? nullptr : x3_wf,
                (!tape && x3_wf && x3_nt == 2) ? reinterpret_cast<const float*>(reinterpret_cast<const char*>(x3_wf) + attn_x3_bytes(Cp, mode, n_groups) - 32) : nullptr};
     if (tape && nw < 0) return ESCX_COMB_UNSUPPORTED;      // the packed H = 2 form has no tape stores
     // H == 2 scale with no padding along W: two half-real windows share one tile (nw < 0 encodes "packing allowed", |nw| waves)

@@ -221,6 +221,12 @@ __device__ __forceinline__ bool arg_better(float d1, int i1, float d2, int i2) {
     if (n1 || n2) return n1 && (!n2 || i1 < i2);
     return d1 < d2 || (d1 == d2 && i1 < i2);
 }
+// arg_better as one branch-free expression (the same truth table, case by case: a NaN present -> n1 && (!n2 || i1 < i2), else distance then index):
+// the form of the fused quantiser kernels (fused_pvq.h), whose combine steps are straight-line selects.
+__device__ __forceinline__ bool arg_better_sel(float d1, int i1, float d2, int i2) {
+    const bool n1 = d1 != d1, n2 = d2 != d2;
+    return (n1 | n2) ? (n1 & (!n2 | (i1 < i2))) : ((d1 < d2) | ((d1 == d2) & (i1 < i2)));
+}
 
 template <int STEPS>
 __global__ __launch_bounds__(256) void pvq_search_kernel(SearchArgs a) {

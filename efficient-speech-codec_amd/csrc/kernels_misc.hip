@@ -70,6 +70,20 @@ void loss_reduce(const float* terms, int n_slots, int G, int M, int Tq, float* o
     ESCX_LAUNCH(loss_reduce_kernel, dim3(M / Tq), dim3(64), 0, s, terms, n_slots, G, M, Tq, out);
 }
 
+// Slice boundaries of the split-K down-projection that the fused quantisers run wave by wave: the engine's split-K slicing (gemm_engine.h launch_tile).
+// bk < 16 is refused for both kernels, as prvq_fused always did; pvq_fused used to divide by a zero bk (no caller passes one).
+static bool pvq_slices(int Kq, int splits, int bk, int* k_per_z) {
+    if (bk < 16 || bk % 16 || Kq % bk || splits < 1 || splits > PVQF_WAVES) return false;
+    const int kIters = Kq / bk, per = (kIters + splits - 1) / splits;
+    if ((kIters + per - 1) / per != splits) return false;
+    *k_per_z = per * bk;
+    return true;
+}
+// what pvq_fused_kernel and prvq_fused_kernel both need of a quantiser's geometry
+static bool pvq_geometry(int Np, int dt, int G, int Kq, int Cp, int splits, int bk, int* k_per_z) {
+    return !(Np % 16 || Kq % 16 || Cp % 16 || dt % 4 || G < 1 || G > PVQF_GMAX || G * dt > Np) && pvq_slices(Kq, splits, bk, k_per_z);
+}
+
 // One product-VQ stream in one launch (fused_pvq.h).  -1: geometry not covered, the caller runs the three-launch form.
 template <int NT, int STEPS, bool DEC>
 static void launch_pvq_fused_d(const PvqFusedArgs& a, hipStream_t s) {
@@ -101,10 +115,9 @@ int pvq_fused(const float* enc, const float* dec, int B, int Hq, int Wd, int Cp,
               const float* cbn, const float* c2, const float* cbraw, int G, int Ksz, int d, int dt, const float* wup, const float* tab, const float* gq,
               float* out, long long* codes, long long bstride, float* loss, float loss_scale, int l2norm, hipStream_t s) {
     const int Tq = Wd / ov, M = B * Tq;
-    if (Np % 16 || Kq % 16 || Cp % 16 || bk % 16 || Kq % bk || dt % 4 || G < 1 || G > PVQF_GMAX || G * dt > Np || splits < 1 || splits > PVQF_WAVES || Ksz < 1) return -1;
-    const int kIters = Kq / bk, per = (kIters + splits - 1) / splits;      // gemm_engine.h launch_tile: the slice boundaries of the engine's split-K
-    if ((kIters + per - 1) / per != splits) return -1;
-    PvqFusedArgs a{enc, dec, wd, cbn, c2, cbraw, wup, tab, gq, out, codes, bstride, loss, loss_scale, M, Tq, Hq, Wd, Cp, ov, Kq, per * bk, splits, G, Ksz, d, l2norm, nullptr};
+    int k_per_z = 0;
+    if (!pvq_geometry(Np, dt, G, Kq, Cp, splits, bk, &k_per_z) || Ksz < 1) return -1;
+    PvqFusedArgs a{enc, dec, wd, cbn, c2, cbraw, wup, tab, gq, out, codes, bstride, loss, loss_scale, M, Tq, Hq, Wd, Cp, ov, Kq, k_per_z, splits, G, Ksz, d, l2norm, nullptr};
 #ifdef ESCX_PVQ_TRACE
     {   // slot n of the buffer for the n-th fused launch since the buffer was (re)set: 4096 workgroups x 8 stamps per slot
         static unsigned long long* last = nullptr; static int n = 0;
@@ -218,20 +231,13 @@ void codes_widen(const short* in, long long* out, long long n, hipStream_t s) {
 
 // ---- the bottleneck product-residual quantiser of rvq+swinT (fused_prvq.h) ----
 
-// slice boundaries of the split-K down-projection (pvq_fused: the engine's split-K slicing, gemm_engine.h launch_tile)
-static bool prvq_slices(int Kq, int splits, int bk, int* k_per_z) {
-    if (bk < 16 || bk % 16 || Kq % bk || splits < 1 || splits > PVQF_WAVES) return false;
-    const int kIters = Kq / bk, per = (kIters + splits - 1) / splits;
-    if ((kIters + per - 1) / per != splits) return false;
-    *k_per_z = per * bk;
-    return true;
+static bool prvq_geometry(int Np, int dt, int G, int Kq, int Cp, int splits, int bk, int* k_per_z) {
+    const int NT = Np / 16, STEPS = dt / 4;
+    return pvq_geometry(Np, dt, G, Kq, Cp, splits, bk, k_per_z) && ((NT == 2 && STEPS == 2) || (NT == 1 && STEPS == 1));
 }
-
 bool prvq_geometry_ok(int Np, int dt, int G, int Kq, int Cp, int splits, int bk) {
     int kz = 0;
-    if (Np % 16 || Kq % 16 || Cp % 16 || dt % 4 || G < 1 || G > PVQF_GMAX || G * dt > Np || !prvq_slices(Kq, splits, bk, &kz)) return false;
-    const int NT = Np / 16, STEPS = dt / 4;
-    return (NT == 2 && STEPS == 2) || (NT == 1 && STEPS == 1);
+    return prvq_geometry(Np, dt, G, Kq, Cp, splits, bk, &kz);
 }
 
 template <int NT, int STEPS, bool DECODE>
@@ -246,12 +252,12 @@ int prvq_fused(const float* enc, const long long* codes_in, int B, int Hq, int W
                const float* cbn, const float* c2, const float* cbraw, int G, int Ksz, int d, int dt, const float* wup,
                long long* codes, long long bstride, const int* clip_S, int S, int Smax, float* loss, long long lslot, float loss_scale, int l2norm,
                float* out, hipStream_t s) {
-    if (!prvq_geometry_ok(Np, dt, G, Kq, Cp, splits, bk) || Ksz < 1 || Smax < 1 || (!codes_in && !codes)) return -1;
+    int k_per_z = 0;
+    if (!prvq_geometry(Np, dt, G, Kq, Cp, splits, bk, &k_per_z) || Ksz < 1 || Smax < 1 || (!codes_in && !codes)) return -1;
     const int Tq = Wd / ov, M = B * Tq;
     if (M < 1) return 0;
     PrvqArgs a{enc, wdf, cbn, c2, cbraw, wup, out, codes, codes_in, bstride, clip_S, S, Smax, loss, lslot, loss_scale,
-               M, Tq, Hq, Wd, Cp, ov, Kq, 0, splits, G, Ksz, d, l2norm};
-    prvq_slices(Kq, splits, bk, &a.k_per_z);
+               M, Tq, Hq, Wd, Cp, ov, Kq, k_per_z, splits, G, Ksz, d, l2norm};
     const int NT = Np / 16;
     if (codes_in) {
         if (!out) return -1;
