@@ -2,8 +2,10 @@
 //
 // One handle = one DAC configuration.  Parameters live in a flat fp32 device buffer owned by the caller, in the reference's named_parameters()
 // order (per layer: bias, weight_g, weight_v; Snake: alpha; codebook: weight); the weight-normalised, packed GEMM operands, the Snake reciprocals
-// and the quantiser tables are re-derived on the device whenever (buffer, version) changes.  Activations are channels-last (B, T, Cp) maps in a
-// handle-owned scratch; see dac_kernels.h for the loaders and epilogues.
+// and the quantiser tables are re-derived on the device whenever (buffer, version) or the padding mode changes.  Activations are channels-last
+// (B, T, Cp) maps in a handle-owned scratch; see dac_kernels.h for the loaders and epilogues.  escx_dac_set_padding(d, 0) runs every convolution
+// without padding (CodecMixin.padding, base.py:58-80) and escx_dac_encode_chunks stages the overlapping windows of the chunked compress
+// (base.py:182-214) straight from the signal; DESIGN.md section 13.2.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -51,6 +53,9 @@ struct escx_dac_s {
     const float* packed_ptr = nullptr; long long packed_version = -1;
     int snake_maps = ESCX_DAC_SNAKE_MAPS_DEFAULT;   // escx_dac_set_snake_maps: layer classes whose Snake is written to a map first
     int precision = ESCX_PRECISION_FP32;            // escx_dac_set_precision, read at each call
+    // escx_dac_set_padding, read at each call.  Off: every convolution runs with padding 0 (CodecMixin.padding = False, base.py:64-80).  The transposed
+    // convolutions' phase images depend on the padding, so the mode is part of the pack cache key: packed_padding is the mode wbuf was packed in.
+    bool padding = true; int packed_padding = -1;
     // bf16x3: three bf16 planes of the packed convolution weights wbuf[0, conv_floats), plane p at w16 + p * conv_floats.  Allocated at the first
     // call in that mode; w16_valid is cleared by every re-pack of the fp32 image and set by refresh_w16, so the image can never be older than wbuf.
     __bf16* w16 = nullptr; size_t conv_floats = 0; bool w16_valid = false;
@@ -89,23 +94,25 @@ void add_res(escx_dac_s* d, std::vector<DacLayer>& L, std::vector<DacSnake>& S, 
 
 // torch's length formulas.  Conv1d floors (T + 2p - dil (K - 1) - 1) / s; a negative numerator means no output frame (0 here, where the
 // reference's layer gives an empty or invalid tensor) - C++ division would truncate it toward zero and report one frame.
-int conv_out_len(int T, const DacLayer& l) {
+// `padding` false: the layer's padding is taken as 0 (a ConvTranspose1d then gives (T + 1) * stride).
+int conv_out_len(int T, const DacLayer& l, bool padding) {
+    const int pad = padding ? l.pad : 0;
     if (l.kind == 0) {
-        const int num = T + 2 * l.pad - l.dil * (l.K - 1) - 1;
+        const int num = T + 2 * pad - l.dil * (l.K - 1) - 1;
         return num < 0 ? 0 : num / l.stride + 1;
     }
-    return (T - 1) * l.stride - 2 * l.pad + l.K;
+    return (T - 1) * l.stride - 2 * pad + l.K;
 }
 
 int pack(escx_dac_s* d, const float* flat, long long version, hipStream_t st) {
-    if (version >= 0 && version == d->packed_version && flat == d->packed_ptr) return 0;
-    d->packed_version = version; d->packed_ptr = flat; d->w16_valid = false;
+    if (version >= 0 && version == d->packed_version && flat == d->packed_ptr && (int)d->padding == d->packed_padding) return 0;
+    d->packed_version = version; d->packed_ptr = flat; d->packed_padding = d->padding; d->w16_valid = false;
     for (auto* L : {&d->enc, &d->dec})
         for (DacLayer& l : *L) {
             if (l.kind == 0)
                 hipLaunchKernelGGL(dac_wn_conv_kernel, dim3(l.Cout), dim3(256), 0, st, flat + l.off_v, flat + l.off_g, flat + l.off_b, l.W, l.bias, l.Cin, l.K, l.CinP, l.Kp);
             else {
-                hipLaunchKernelGGL(dac_wn_convt_kernel, dim3(l.Cin), dim3(256), 0, st, flat + l.off_v, flat + l.off_g, l.W, l.Cout, l.stride, l.pad, l.CinP, l.Np, l.Kp);
+                hipLaunchKernelGGL(dac_wn_convt_kernel, dim3(l.Cin), dim3(256), 0, st, flat + l.off_v, flat + l.off_g, l.W, l.Cout, l.stride, d->padding ? l.pad : 0, l.CinP, l.Np, l.Kp);
                 ESCX_HIP(hipMemcpyAsync(l.bias, flat + l.off_b, l.Cout * sizeof(float), hipMemcpyDeviceToDevice, st));
             }
         }
@@ -143,20 +150,32 @@ int ensure_scratch(escx_dac_s* d, size_t bytes) {
     return 0;
 }
 
-// What one pass needs besides the layer: the handle's Snake placement, a map-sized buffer for a Snaked copy, the stream.
-struct Run { int snake_maps; float* tmp; hipStream_t st; const float* wbuf; const __bf16* w16; size_t plane; };     // w16 == nullptr: fp32 mode
+// What one pass needs besides the layer: the handle's Snake placement, a map-sized buffer for a Snaked copy, the stream, the padding mode.
+struct Run { int snake_maps; float* tmp; hipStream_t st; const float* wbuf; const __bf16* w16; size_t plane; bool padding; };     // w16 == nullptr: fp32 mode
+
+// The cropped skip of a ResidualUnit without padding: res has Tres rows per clip and is read `off` rows in (DacEpiCrop)
+struct Crop { int Tres, off; };
+
+template <class Epi>
+void launch_conv(const Run& run, const DacLayer& l, const __bf16* W16, const float* W, const DacConvA& ld, const Epi& ep) {
+    const long long tiles = (long long)((ld.M + 127) / 128) * ((l.Np + 95) / 96);
+    if (W16) launch_dac_x3(ld, W16, run.plane, ld.M, l.Np, l.Kp, ep, run.st);
+    else if (tiles >= 512) launch_gemm<128>(ld, W, ld.M, l.Np, l.Kp, ep, run.st);
+    else launch_gemm<64>(ld, W, ld.M, l.Np, l.Kp, ep, run.st);
+}
 
 // out = conv(snake?(x)) over (B, Tin, CinP) -> (B, Tout, cpad(Cout)) [+ res]; ConvT: one GEMM per output phase.  Snake is applied while the
 // operand is staged, or - for the layer classes set in snake_maps - once per element into r.tmp, which the GEMM then reads plain (bitwise the
-// same operand either way).
+// same operand either way).  The padding is the layer's, or 0 when run.padding is off; `crop` (Conv1d only) selects the cropped residual.
 void run_layer(const Run& run, int cls, const DacLayer& l, const DacSnake* sn, const float* x, int B, int Tin, float* out, int Tout, const float* res,
-               int tanh_out) {
+               int tanh_out, const Crop* crop = nullptr) {
     const hipStream_t st = run.st;
     if (sn && ((run.snake_maps >> cls) & 1)) {
         const long long n4 = (long long)B * Tin * l.CinP / 4;
         hipLaunchKernelGGL(dac_snake_map_kernel, dim3(nblk(n4)), dim3(256), 0, st, x, sn->a, sn->inv, run.tmp, n4, l.CinP / 4);
         x = run.tmp; sn = nullptr;
     }
+    const int pad = run.padding ? l.pad : 0;
     const int phases = l.kind ? l.stride : 1;
     const __bf16* W16 = (run.w16 && x3_layer(l)) ? run.w16 + (l.W - run.wbuf) : nullptr;
     for (int r = 0; r < phases; ++r) {
@@ -165,53 +184,99 @@ void run_layer(const Run& run, int cls, const DacLayer& l, const DacSnake* sn, c
         DacEpi ep{};
         ep.out = out; ep.res = res; ep.Cp = tanh_out ? 4 : cpad(l.Cout); ep.Tmap = Tout; ep.tanh_out = tanh_out;
         if (l.kind == 0) {
-            ld.Trows = Tout; ld.rs = l.stride; ld.r0 = -l.pad; ld.td = l.dil; ld.ntaps = l.K;
+            ld.Trows = Tout; ld.rs = l.stride; ld.r0 = -pad; ld.td = l.dil; ld.ntaps = l.K;
             ep.os = 1; ep.o0 = 0; ep.Trows = Tout; ep.bias = l.bias;
             ld.M = B * Tout; ld.dT = FastDiv(Tout); ep.dT = ld.dT;
-            const long long tiles = (long long)((ld.M + 127) / 128) * ((l.Np + 95) / 96);
-            if (W16) launch_dac_x3(ld, W16, run.plane, ld.M, l.Np, l.Kp, ep, st);
-            else if (tiles >= 512) launch_gemm<128>(ld, l.W, ld.M, l.Np, l.Kp, ep, st);
-            else launch_gemm<64>(ld, l.W, ld.M, l.Np, l.Kp, ep, st);
+            if (crop) {
+                DacEpiCrop ec{};
+                ec.out = out; ec.bias = l.bias; ec.res = res; ec.Cp = cpad(l.Cout); ec.Trows = Tout; ec.Tres = crop->Tres; ec.off = crop->off; ec.dT = ld.dT;
+                launch_conv(run, l, W16, l.W, ld, ec);
+            } else launch_conv(run, l, W16, l.W, ld, ep);
         } else {
             const int s = l.stride, Q = r < Tout ? (Tout - r + s - 1) / s : 0;
             if (Q == 0) continue;
-            ld.Trows = Q; ld.rs = 1; ld.r0 = (r + l.pad) / s; ld.td = -1; ld.ntaps = 2;
+            ld.Trows = Q; ld.rs = 1; ld.r0 = (r + pad) / s; ld.td = -1; ld.ntaps = 2;
             ep.os = s; ep.o0 = r; ep.Trows = Q; ep.bias = l.bias;
             ld.M = B * Q; ld.dT = FastDiv(Q); ep.dT = ld.dT;
-            const float* W = l.W + (size_t)r * l.Np * l.Kp;
-            const long long tiles = (long long)((ld.M + 127) / 128) * ((l.Np + 95) / 96);
-            if (W16) launch_dac_x3(ld, W16 + (size_t)r * l.Np * l.Kp, run.plane, ld.M, l.Np, l.Kp, ep, st);
-            else if (tiles >= 512) launch_gemm<128>(ld, W, ld.M, l.Np, l.Kp, ep, st);
-            else launch_gemm<64>(ld, W, ld.M, l.Np, l.Kp, ep, st);
+            launch_conv(run, l, W16 ? W16 + (size_t)r * l.Np * l.Kp : nullptr, l.W + (size_t)r * l.Np * l.Kp, ld, ep);
         }
     }
 }
 
-// ResidualUnit in place on x: h = conv7_dil(snake(x)); x = x + conv1(snake(h))   (dac.py:24-41; the length is kept, so the crop never triggers)
-void run_res(const Run& run, const DacLayer* L, const DacSnake* S, float* x, float* h, int B, int T) {
-    run_layer(run, ESCX_DAC_SNAKE_RES7, L[0], &S[0], x, B, T, h, T, nullptr, 0);
-    run_layer(run, ESCX_DAC_SNAKE_RES1, L[1], &S[1], h, B, T, x, T, x, 0);
+// ResidualUnit on x: h = conv7_dil(snake(x)); x = crop(x) + conv1(snake(h))   (dac.py:24-41).  With padding the length is kept, the crop never
+// triggers and the unit runs in place.  Without it h and the result have T - 6 dil rows and the skip is x cropped by 3 dil on each side: the
+// result goes to the free map y (a lane reads x[t + 3 dil] while another workgroup would write x[t]) and the two maps swap; T becomes the new length.
+void run_res(const Run& run, const DacLayer* L, const DacSnake* S, float*& x, float*& y, float* h, int B, int& T) {
+    if (run.padding) {
+        run_layer(run, ESCX_DAC_SNAKE_RES7, L[0], &S[0], x, B, T, h, T, nullptr, 0);
+        run_layer(run, ESCX_DAC_SNAKE_RES1, L[1], &S[1], h, B, T, x, T, x, 0);
+        return;
+    }
+    const int T2 = conv_out_len(T, L[0], false);
+    const Crop crop{T, (T - T2) / 2};
+    run_layer(run, ESCX_DAC_SNAKE_RES7, L[0], &S[0], x, B, T, h, T2, nullptr, 0);
+    run_layer(run, ESCX_DAC_SNAKE_RES1, L[1], &S[1], h, B, T2, y, T2, x, 0, &crop);
+    std::swap(x, y); T = T2;
 }
 
 size_t map_floats(int B, int T, int C) { return pad64((size_t)B * T * cpad(C)); }
 
-// largest map of the encoder / decoder pass, for three maps (x, y, h)
-size_t enc_scratch(escx_dac_s* d, int B, int L, int* Tz) {
-    size_t mx = map_floats(B, L, 1);
-    int T = L, C = d->cfg.encoder_dim;
-    mx = std::max(mx, map_floats(B, T, C));
-    for (int i = 0; i < d->cfg.n_encoder_rates; ++i) { T = conv_out_len(T, d->enc[1 + i * 7 + 6]); C *= 2; mx = std::max(mx, map_floats(B, T, C)); }
-    *Tz = T;
-    return std::max(mx, map_floats(B, T, d->latent));
+// Lengths through the encoder / decoder under the padding in effect: the output length, or 0 as soon as any layer would give no row (without
+// padding the receptive field is hundreds to thousands of samples; no kernel ever sees a non-positive row count).  *mx: the largest map of the
+// pass for a batch of B, in floats; the scratch holds four of them (x, y, h and the Snaked copy).
+int enc_walk(const escx_dac_s* d, bool padding, int B, int L, size_t* mx) {
+    size_t m = map_floats(B, L, 1);
+    int C = d->cfg.encoder_dim, T = conv_out_len(L, d->enc[0], padding);
+    if (T < 1) return 0;
+    m = std::max(m, map_floats(B, T, C));
+    for (int i = 0; i < d->cfg.n_encoder_rates; ++i) {
+        const DacLayer* Lb = &d->enc[1 + i * 7];
+        for (int j = 0; j < 3; ++j) { T = conv_out_len(T, Lb[2 * j], padding); if (T < 1) return 0; }      // the 1x1 convolution keeps the length
+        T = conv_out_len(T, Lb[6], padding); C *= 2;
+        if (T < 1) return 0;
+        m = std::max(m, map_floats(B, T, C));
+    }
+    T = conv_out_len(T, d->enc.back(), padding);
+    if (T < 1) return 0;
+    if (mx) *mx = std::max(m, map_floats(B, T, d->latent));
+    return T;
 }
-size_t dec_scratch(escx_dac_s* d, int B, int T, int* Lout) {
-    size_t mx = map_floats(B, T, d->latent);
+int dec_walk(const escx_dac_s* d, bool padding, int B, int T, size_t* mx) {
+    size_t m = map_floats(B, T, d->latent);
     int C = d->cfg.decoder_dim;
-    mx = std::max(mx, map_floats(B, T, C));
-    for (int i = 0; i < d->cfg.n_decoder_rates; ++i) { T = conv_out_len(T, d->dec[1 + i * 7]); C /= 2; mx = std::max(mx, map_floats(B, T, C)); }
-    *Lout = T;
-    return mx;
+    T = conv_out_len(T, d->dec[0], padding);
+    if (T < 1) return 0;
+    m = std::max(m, map_floats(B, T, C));
+    for (int i = 0; i < d->cfg.n_decoder_rates; ++i) {
+        const DacLayer* Lb = &d->dec[1 + i * 7];
+        T = conv_out_len(T, Lb[0], padding); C /= 2;
+        if (T < 1) return 0;
+        m = std::max(m, map_floats(B, T, C));
+        for (int j = 0; j < 3; ++j) { T = conv_out_len(T, Lb[1 + 2 * j], padding); if (T < 1) return 0; }
+    }
+    T = conv_out_len(T, d->dec.back(), padding);
+    if (T < 1) return 0;
+    if (mx) *mx = m;
+    return T;
 }
+
+// floor and ceiling of a / b for b > 0 and any a (C++ division truncates toward zero)
+inline long long floor_div(long long a, long long b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
+inline long long ceil_div(long long a, long long b) { return -floor_div(-a, b); }
+
+// CodecMixin.get_output_length (base.py:108-123): every convolution in module order, no padding, floor at every layer (negative values included,
+// as get_delay calls it with 0).  The quantiser's 1x1 projections sit between encoder and decoder and change nothing.
+long long ref_output_length(const escx_dac_s* d, long long L) {
+    for (auto* V : {&d->enc, &d->dec})
+        for (const DacLayer& l : *V) {
+            const long long reach = (long long)l.dil * (l.K - 1) + 1;
+            L = l.kind == 0 ? floor_div(L - reach, l.stride) + 1 : (L - 1) * l.stride + reach;
+        }
+    return L;
+}
+
+// One chunked-compress pass (escx_dac_encode_chunks): where the staged input map comes from instead of a (B, L) audio buffer
+struct ChunkSrc { const float* signal; long long n_signal; int n_chunks, hop; long long lead; };
 
 // Host counts -> the handle's device buffer on the call's stream (as rvq_upload of escx_api.cpp does for RVQCodecs); nullptr stays nullptr.
 int upload_counts(escx_dac_s* d, const int32_t* host, int count, const int** dev, hipStream_t st) {
@@ -389,20 +454,35 @@ extern "C" int escx_dac_set_precision(escx_dac d, int mode) {
 }
 extern "C" int escx_dac_get_precision(escx_dac d) { return d ? d->precision : -1; }
 
+extern "C" int escx_dac_set_padding(escx_dac d, int on) {
+    if (!d) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null handle");
+    if (on != 0 && on != 1) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "padding %d: expected 0 or 1", on);
+    d->padding = on != 0;
+    return ESCX_OK;
+}
+extern "C" int escx_dac_get_padding(escx_dac d) { return d ? (int)d->padding : -1; }
+
+extern "C" int escx_dac_output_length(escx_dac d, int n_samples) { return d ? (int)ref_output_length(d, n_samples) : 0; }
+
+extern "C" int escx_dac_delay(escx_dac d) {
+    if (!d) return -1;
+    const long long l_out = ref_output_length(d, 0);
+    long long L = l_out;
+    for (auto* V : {&d->dec, &d->enc})
+        for (auto it = V->rbegin(); it != V->rend(); ++it) {
+            const long long reach = (long long)it->dil * (it->K - 1) + 1;
+            L = it->kind == 1 ? ceil_div(L - reach, it->stride) + 1 : (L - 1) * it->stride + reach;
+        }
+    return (int)floor_div(L - l_out, 2);
+}
+
 extern "C" int escx_dac_num_frames(escx_dac d, int n_samples) {
     if (!d || n_samples < 1) return 0;
-    int T = n_samples;
-    for (int i = 0; i < d->cfg.n_encoder_rates; ++i) {
-        T = conv_out_len(T, d->enc[1 + i * 7 + 6]);
-        if (T < 1) return 0;
-    }
-    return T;
+    return enc_walk(d, d->padding, 1, n_samples, nullptr);
 }
 extern "C" int escx_dac_output_samples(escx_dac d, int n_frames) {
     if (!d || n_frames < 1) return 0;
-    int T = n_frames;
-    for (int i = 0; i < d->cfg.n_decoder_rates; ++i) T = conv_out_len(T, d->dec[1 + i * 7]);
-    return T;
+    return dec_walk(d, d->padding, 1, n_frames, nullptr);
 }
 
 extern "C" int escx_dac_encode(escx_dac d, const float* flat, int64_t version, const float* audio, int B, int L, int n_q, float* z, int64_t* codes,
@@ -410,10 +490,13 @@ extern "C" int escx_dac_encode(escx_dac d, const float* flat, int64_t version, c
     return escx_dac_encode_ex(d, flat, version, audio, B, L, n_q, nullptr, nullptr, 0, z, codes, latents, losses, nullptr, stream);
 }
 
-extern "C" int escx_dac_encode_ex(escx_dac d, const float* flat, int64_t version, const float* audio, int B, int L, int n_q, const int32_t* clip_n,
-                                  const int32_t* snap_n, int n_snaps, float* z, int64_t* codes, float* latents, float* losses, float* zsnap, void* stream) {
-    int rc = check_args(d, flat, B); if (rc) return rc;
-    if (!audio || !z || !codes || !latents || !losses || n_q < 1) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "bad argument");
+namespace {
+
+// escx_dac_encode_ex and escx_dac_encode_chunks: everything but where the staged (B, L, 4) input map comes from
+int encode_impl(escx_dac d, const float* flat, int64_t version, const float* audio, const ChunkSrc* chunks, int B, int L, int n_q, const int32_t* clip_n,
+                const int32_t* snap_n, int n_snaps, float* z, int64_t* codes, float* latents, float* losses, float* zsnap, void* stream) {
+    int rc = 0;
+    if (!z || !codes || !latents || !losses || n_q < 1) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "bad argument");
     if (clip_n && snap_n) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "per-clip counts and snapshots are not combined in one call");
     if (clip_n && n_q > d->cfg.n_codebooks) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "%d code slots above the %d codebooks", n_q, d->cfg.n_codebooks);
     const int n = std::min(n_q, d->cfg.n_codebooks);
@@ -424,11 +507,11 @@ extern "C" int escx_dac_encode_ex(escx_dac d, const float* flat, int64_t version
             if (snap_n[r] < 1 || snap_n[r] > n || (r && snap_n[r] <= snap_n[r - 1]))
                 ESCX_FAIL(ESCX_ERR_INVALID_ARG, "snap_n[%d]=%d: strictly increasing stage counts in [1, %d] expected", r, snap_n[r], n);
     }
-    const int Tz0 = escx_dac_num_frames(d, L);
-    if (Tz0 < 1) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "%d samples give no latent frame (the hop is %d)", L, d->hop);
+    const bool padding = d->padding;
+    size_t mf = 0;
+    const int Tz = L < 1 ? 0 : enc_walk(d, padding, B, L, &mf);
+    if (Tz < 1) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "%d samples give no latent frame (the hop is %d, padding %s)", L, d->hop, padding ? "on" : "off");
     hipStream_t st = (hipStream_t)stream;
-    int Tz = 0;
-    const size_t mf = enc_scratch(d, B, L, &Tz);
     if ((unsigned long long)mf >= (1ull << 32)) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "batch of %d x %d samples: a feature map above 2^32 elements", B, L);
     const size_t M = (size_t)B * Tz;
     const size_t lossf = pad64((size_t)n * M) + pad64((size_t)n * B);
@@ -436,20 +519,25 @@ extern "C" int escx_dac_encode_ex(escx_dac d, const float* flat, int64_t version
     const int* cdev; if ((rc = upload_counts(d, clip_n ? clip_n : snap_n, clip_n ? B : n_snaps, &cdev, st))) return rc;
     if ((rc = pack(d, flat, (long long)version, st)) || (rc = refresh_w16(d, st))) return rc;
     float* x = d->scratch; float* y = x + mf; float* h = y + mf; float* lossb = h + mf + mf;
-    const Run run{d->snake_maps, h + mf, st, d->wbuf, d->precision == ESCX_PRECISION_BF16X3 ? d->w16 : nullptr, d->conv_floats};
-    hipLaunchKernelGGL(dac_wave_in_kernel, dim3(nblk((long long)B * L)), dim3(256), 0, st, audio, h, (long long)B * L);
+    const Run run{d->snake_maps, h + mf, st, d->wbuf, d->precision == ESCX_PRECISION_BF16X3 ? d->w16 : nullptr, d->conv_floats, padding};
+    if (chunks)
+        hipLaunchKernelGGL(dac_chunk_in_kernel, dim3(nblk((long long)B * L)), dim3(256), 0, st, chunks->signal, h, (long long)B * L, chunks->n_signal, chunks->n_chunks, L,
+                           chunks->hop, chunks->lead);
+    else hipLaunchKernelGGL(dac_wave_in_kernel, dim3(nblk((long long)B * L)), dim3(256), 0, st, audio, h, (long long)B * L);
     const DacLayer* E = d->enc.data(); const DacSnake* SN = d->enc_sn.data();
-    run_layer(run, ESCX_DAC_SNAKE_LAST, E[0], nullptr, h, B, L, x, L, nullptr, 0);
-    int T = L;
+    int T = conv_out_len(L, E[0], padding);
+    run_layer(run, ESCX_DAC_SNAKE_LAST, E[0], nullptr, h, B, L, x, T, nullptr, 0);
     for (int i = 0; i < d->cfg.n_encoder_rates; ++i) {
         const DacLayer* Lb = E + 1 + i * 7; const DacSnake* Sb = SN + i * 7;        // 3 residual units (2 convolutions, 2 Snakes each), Snake, strided conv
-        for (int j = 0; j < 3; ++j) run_res(run, Lb + 2 * j, Sb + 2 * j, x, h, B, T);
+        for (int j = 0; j < 3; ++j) run_res(run, Lb + 2 * j, Sb + 2 * j, x, y, h, B, T);
         const DacLayer& sc = Lb[6];
-        const int T2 = conv_out_len(T, sc);
+        const int T2 = conv_out_len(T, sc, padding);
         run_layer(run, ESCX_DAC_SNAKE_DOWN, sc, Sb + 6, x, B, T, y, T2, nullptr, 0);
         std::swap(x, y); T = T2;
     }
-    run_layer(run, ESCX_DAC_SNAKE_LAST, E[d->enc.size() - 1], SN + d->enc_sn.size() - 1, x, B, T, y, T, nullptr, 0);
+    const int T3 = conv_out_len(T, E[d->enc.size() - 1], padding);
+    run_layer(run, ESCX_DAC_SNAKE_LAST, E[d->enc.size() - 1], SN + d->enc_sn.size() - 1, x, B, T, y, T3, nullptr, 0);
+    T = T3;
     DacQArgs qa{};
     qa.t = d->qt; qa.zmap = y; qa.z = z; qa.codes = (long long*)codes; qa.latents = latents; qa.loss = lossb;
     qa.M = (int)M; qa.T = T; qa.D = d->latent; qa.Dp = cpad(d->latent); qa.d = d->cfg.codebook_dim; qa.K = d->cfg.codebook_size; qa.n = n;
@@ -458,6 +546,24 @@ extern "C" int escx_dac_encode_ex(escx_dac d, const float* flat, int64_t version
     else launch_rvq<false, DAC_Q_PLAIN>(d->latent, (long long)M, qa, st);
     hipLaunchKernelGGL(dac_loss_kernel, dim3(1), dim3(256), 0, st, lossb, lossb + pad64((size_t)n * M), losses, B, T, n, d->cfg.codebook_dim);
     return launch_ok("escx_dac_encode");
+}
+
+}  // namespace
+
+extern "C" int escx_dac_encode_ex(escx_dac d, const float* flat, int64_t version, const float* audio, int B, int L, int n_q, const int32_t* clip_n,
+                                  const int32_t* snap_n, int n_snaps, float* z, int64_t* codes, float* latents, float* losses, float* zsnap, void* stream) {
+    int rc = check_args(d, flat, B); if (rc) return rc;
+    if (!audio) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "bad argument");
+    return encode_impl(d, flat, version, audio, nullptr, B, L, n_q, clip_n, snap_n, n_snaps, z, codes, latents, losses, zsnap, stream);
+}
+
+extern "C" int escx_dac_encode_chunks(escx_dac d, const float* flat, int64_t version, const float* signal, int rows, int64_t n_signal, int n_chunks, int n_samples,
+                                      int hop, int64_t lead, int n_q, float* z, int64_t* codes, float* latents, float* losses, void* stream) {
+    int rc = check_args(d, flat, rows); if (rc) return rc;
+    if (!signal || n_signal < 1 || n_chunks < 1 || n_samples < 1 || hop < 1) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "bad argument");
+    if ((long long)rows * n_chunks > 0x7fffffffll) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "%d rows x %d chunks in one pass", rows, n_chunks);
+    const ChunkSrc src{signal, (long long)n_signal, n_chunks, hop, (long long)lead};
+    return encode_impl(d, flat, version, nullptr, &src, rows * n_chunks, n_samples, n_q, nullptr, nullptr, 0, z, codes, latents, losses, nullptr, stream);
 }
 
 extern "C" int escx_dac_from_codes(escx_dac d, const float* flat, int64_t version, const int64_t* codes, int B, int n, int T, float* z, float* zp, void* stream) {
@@ -484,26 +590,29 @@ extern "C" int escx_dac_decode(escx_dac d, const float* flat, int64_t version, c
     int rc = check_args(d, flat, B); if (rc) return rc;
     if (!z || !audio || T < 1) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "bad argument");
     hipStream_t st = (hipStream_t)stream;
-    int Lout = 0;
-    const size_t mf = dec_scratch(d, B, T, &Lout);
-    if (Lout < 1) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "%d latent frames decode to no sample", T);
+    const bool padding = d->padding;
+    size_t mf = 0;
+    const int Lout = dec_walk(d, padding, B, T, &mf);
+    if (Lout < 1) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "%d latent frames decode to no sample (padding %s)", T, padding ? "on" : "off");
     if ((unsigned long long)mf >= (1ull << 32)) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "batch of %d x %d frames: a feature map above 2^32 elements", B, T);
     if ((rc = ensure_scratch(d, 4 * mf * sizeof(float)))) return rc;
     if ((rc = pack(d, flat, (long long)version, st)) || (rc = refresh_w16(d, st))) return rc;
     float* x = d->scratch; float* y = x + mf; float* h = y + mf;
-    const Run run{d->snake_maps, h + mf, st, d->wbuf, d->precision == ESCX_PRECISION_BF16X3 ? d->w16 : nullptr, d->conv_floats};
+    const Run run{d->snake_maps, h + mf, st, d->wbuf, d->precision == ESCX_PRECISION_BF16X3 ? d->w16 : nullptr, d->conv_floats, padding};
     const int Dp = cpad(d->latent);
     hipLaunchKernelGGL(dac_z_in_kernel, dim3(nblk((long long)B * T * Dp)), dim3(256), 0, st, z, h, B, d->latent, Dp, T);
     const DacLayer* Dl = d->dec.data(); const DacSnake* SN = d->dec_sn.data();
-    run_layer(run, ESCX_DAC_SNAKE_LAST, Dl[0], nullptr, h, B, T, x, T, nullptr, 0);
+    const int T0 = conv_out_len(T, Dl[0], padding);
+    run_layer(run, ESCX_DAC_SNAKE_LAST, Dl[0], nullptr, h, B, T, x, T0, nullptr, 0);
+    T = T0;
     for (int i = 0; i < d->cfg.n_decoder_rates; ++i) {
         const DacLayer* Lb = Dl + 1 + i * 7; const DacSnake* Sb = SN + i * 7;
-        const int T2 = conv_out_len(T, Lb[0]);
+        const int T2 = conv_out_len(T, Lb[0], padding);
         run_layer(run, ESCX_DAC_SNAKE_UP, Lb[0], Sb, x, B, T, y, T2, nullptr, 0);
         std::swap(x, y); T = T2;
-        for (int j = 0; j < 3; ++j) run_res(run, Lb + 1 + 2 * j, Sb + 1 + 2 * j, x, h, B, T);
+        for (int j = 0; j < 3; ++j) run_res(run, Lb + 1 + 2 * j, Sb + 1 + 2 * j, x, y, h, B, T);
     }
-    run_layer(run, ESCX_DAC_SNAKE_LAST, Dl[d->dec.size() - 1], SN + d->dec_sn.size() - 1, x, B, T, audio, T, nullptr, 1);
+    run_layer(run, ESCX_DAC_SNAKE_LAST, Dl[d->dec.size() - 1], SN + d->dec_sn.size() - 1, x, B, T, audio, Lout, nullptr, 1);
     return launch_ok("escx_dac_decode");
 }
 

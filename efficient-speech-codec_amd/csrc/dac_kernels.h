@@ -5,7 +5,9 @@
 //   DacConvA   A[(b, t)][k = tap * Cp + c] = snake?(X(b, t * rs + r0 + tap * td, c))     zero outside [0, Tin)
 //              Conv1d:           rs = stride, r0 = -padding, td = dilation
 //              ConvTranspose1d:  one GEMM per output phase r (t_out = q * s + r): rs = 1, r0 = floor((r + p) / s), td = -1, two taps
+//              (p is the padding in effect: the layer's own, or 0 for every layer when the handle's padding is off)
 //   DacEpi     out(b, t * os + o0, n..n+3) = [res +] (v + bias)   or   audio(b, t) = tanh(v + bias) for the one-channel last layer
+//   DacEpiCrop out(b, t, n..n+3) = res(b, t + off, n..n+3) + (v + bias): the ResidualUnit's cropped skip when the padding is off
 // Snake (nn/layers.py:19-24) is applied to the operand while it is staged: x + inv * sin(alpha * x)^2 with inv = 1 / (alpha + 1e-9) derived
 // once per parameter version, in the reference's operation order, with the accurate sinf and no contraction into fma.
 #pragma once
@@ -60,6 +62,24 @@ struct DacEpi {
         const size_t idx = ((size_t)b * Tmap + to) * Cp + n;
         if (res) v = ld4(res + idx) + v;
         st4(out + idx, v);
+    }
+};
+
+// The residual add of a ResidualUnit whose convolutions run without padding (CodecMixin.padding = False, dac.py:35-40): the 7-tap convolution at
+// dilation d loses 6d rows, so the skip input is read `off` = 3d rows further in, from a map with its own rows-per-clip count:
+//   out(b, t, n..n+3) = res(b, t + off, n..n+3) + (v + bias)        t < Trows, t + off < Tres
+// A type of its own: DacEpi, and with it every kernel of the padded path, stays what it is.  `res` must NOT alias `out`: a lane reads row t + off
+// of a map of which another workgroup writes row t.  The host writes into the free map and swaps (dac.hip run_res).
+struct DacEpiCrop {
+    float* out; const float* bias; const float* res;
+    int Cp, Trows, Tres, off; FastDiv dT;
+    __device__ __forceinline__ void store(int m, int n, f32x4 v, int) const {
+#pragma clang fp contract(off)
+        if (n >= Cp) return;
+        const int b = dT.div(m), t = m - b * Trows;
+        v += ld4(bias + n);
+        v = ld4(res + ((size_t)b * Tres + t + off) * Cp + n) + v;
+        st4(out + ((size_t)b * Trows + t) * Cp + n, v);
     }
 };
 
@@ -358,6 +378,20 @@ __global__ void dac_test_math_kernel(const float* __restrict__ x, const float* _
 __global__ void dac_wave_in_kernel(const float* __restrict__ x, float* __restrict__ out, long long n) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) st4(out + 4 * i, f32x4{x[i], 0.f, 0.f, 0.f});
+}
+// Chunked compress (base.py:197, 206-208) without the host's copies: the (rows * n_chunks, n_samples, 4) map of overlapping windows straight from
+// the (rows, n_signal) signal.  Sample j of chunk c of row r is signal[r][c * hop + j - lead], zero outside [0, n_signal): the reference's
+// zero_pad(delay, delay), its slice [c hop, c hop + n_samples) and the right zero-pad of a short last slice, with lead = delay.
+__global__ void dac_chunk_in_kernel(const float* __restrict__ sig, float* __restrict__ out, long long n, long long n_signal, int n_chunks, int n_samples,
+                                    int hop, long long lead) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const long long rc = i / n_samples;
+    const int j = (int)(i - rc * n_samples);
+    const long long r = rc / n_chunks, c = rc - r * n_chunks;
+    const long long src = c * hop + j - lead;
+    const float v = (src >= 0 && src < n_signal) ? sig[r * n_signal + src] : 0.f;
+    st4(out + 4 * i, f32x4{v, 0.f, 0.f, 0.f});
 }
 __global__ void dac_z_in_kernel(const float* __restrict__ z, float* __restrict__ out, int B, int D, int Dp, int T) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;

@@ -140,6 +140,12 @@ SIGNATURES = {
     "escx_dac_get_snake_maps": (c_int, [c_void_p]),
     "escx_dac_set_precision": (c_int, [c_void_p, c_int]),
     "escx_dac_get_precision": (c_int, [c_void_p]),
+    "escx_dac_set_padding": (c_int, [c_void_p, c_int]),
+    "escx_dac_get_padding": (c_int, [c_void_p]),
+    "escx_dac_delay": (c_int, [c_void_p]),
+    "escx_dac_output_length": (c_int, [c_void_p, c_int]),
+    "escx_dac_encode_chunks": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                               c_void_p]),
     "escx_dac_test_math": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
     "escx_set_rccl_library": (c_int, [c_char_p]),
     "escx_allgather_codes": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p]),

@@ -1,4 +1,4 @@
-"""Baseline codecs the paper measures ESC against, on the same native path: `from esc.baselines import DAC`."""
-from .dac import DAC  # noqa: F401
+"""Baseline codecs the paper measures ESC against, on the same native path: `from esc.baselines import DAC, DACFile`."""
+from .dac import DAC, DACFile  # noqa: F401
 
-__all__ = ["DAC"]
+__all__ = ["DAC", "DACFile"]

@@ -4,12 +4,17 @@ Same constructor keywords, same state_dict keys and shapes (`*.weight_g`, `*.wei
 `quantizer.quantizers.{i}.codebook.weight`: reference checkpoints load with `load_state_dict(strict=True)`), same eval-mode
 `encode` / `decode` / `forward` / `quantizer.from_codes`.  Every convolution, the weight normalisation and the residual quantiser run in
 libescx (csrc/dac.hip); there is no PyTorch/CPU implementation here.  Inference only: training mode raises NotImplementedError.
+
+`DACFile`, `DAC.padding`, `DAC.compress` and `DAC.decompress` are CodecMixin's (reference baselines/descript/dac/model/base.py:15-294): files of any
+length in overlapping windows on padding-free convolutions, all windows of a file as one batch.
 """
 from __future__ import annotations
 
 import ctypes
 import math
-from typing import List, Sequence, Union
+from dataclasses import dataclass
+from pathlib import Path
+from typing import List, Optional, Sequence, Union
 
 import numpy as np
 import torch
@@ -58,6 +63,48 @@ def _param_specs(enc_dim, enc_rates, latent, dec_dim, dec_rates, n_cb, cb_size, 
     return out
 
 
+SUPPORTED_VERSIONS = ["1.0.0"]
+_MAP_LIMIT = (1 << 32) - 64          # a feature map of one pass stays below 2^32 elements (csrc/dac.hip), rounded up to 64 floats
+
+
+@dataclass
+class DACFile:
+    """The reference's container of a compressed signal (base.py:15-54), same fields and same on-disk layout: `np.save` of
+    {"codes": uint16 (rows, n_codebooks, frames), "metadata": {input_db, original_length, sample_rate, chunk_length, channels, padding,
+    dac_version}}.  rows = batch * channels.  `input_db` is carried as given (a float, a tensor or None): this port measures no loudness."""
+    codes: torch.Tensor
+    chunk_length: int
+    original_length: int
+    input_db: object
+    channels: int
+    sample_rate: int
+    padding: bool
+    dac_version: str
+
+    def save(self, path):
+        db = self.input_db
+        if isinstance(db, torch.Tensor):
+            db = db.detach().cpu().numpy()
+        if db is not None:
+            db = np.asarray(db, dtype=np.float32)
+        artifacts = {"codes": self.codes.detach().cpu().numpy().astype(np.uint16),
+                     "metadata": {"input_db": db, "original_length": int(self.original_length), "sample_rate": int(self.sample_rate),
+                                  "chunk_length": int(self.chunk_length), "channels": int(self.channels), "padding": bool(self.padding),
+                                  "dac_version": SUPPORTED_VERSIONS[-1]}}
+        path = Path(path).with_suffix(".dac")
+        with open(path, "wb") as f:
+            np.save(f, artifacts)
+        return path
+
+    @classmethod
+    def load(cls, path):
+        artifacts = np.load(path, allow_pickle=True)[()]
+        meta = dict(artifacts["metadata"])
+        if meta.get("dac_version", None) not in SUPPORTED_VERSIONS:
+            raise RuntimeError(f"{path} has dac_version {meta.get('dac_version')!r}; this reader knows {SUPPORTED_VERSIONS}")
+        return cls(codes=torch.from_numpy(artifacts["codes"].astype(np.int64)), **meta)
+
+
 def _check_device(x: torch.Tensor, what: str):
     if not x.is_cuda:
         raise RuntimeError(f"esc.baselines.DAC runs on the HIP device only: {what} is on {x.device}")
@@ -102,6 +149,7 @@ class DAC(nn.Module):
         q.from_codes, q.n_codebooks, q.codebook_size, q.codebook_dim = self._from_codes, n_codebooks, codebook_size, [codebook_dim] * n_codebooks
         self._handles, self._flat = {}, {}
         self._precision = "fp32"
+        self._padding = True
 
     # ---- native handle and flat parameter buffer (same scheme as esc.models.Discriminator) ----------------------------------------------
     def _version(self) -> int:
@@ -149,6 +197,7 @@ class DAC(nn.Module):
             if getattr(self, "_snake_maps", None) is not None:
                 _native.check(lib.escx_dac_set_snake_maps(hd, self._snake_maps))
             _native.check(lib.escx_dac_set_precision(hd, _native.PRECISIONS[self._precision]))
+            _native.check(lib.escx_dac_set_padding(hd, int(self._padding)))
         return lib, self._handles[idx]
 
     def _ensure_flat(self, device, lib, hd):
@@ -209,10 +258,79 @@ class DAC(nn.Module):
         """The mode in effect: what set_precision chose ("fp32" until then); every live handle is in it."""
         return self._precision
 
+    # ---- CodecMixin's padding switch and geometry (base.py:58-123) ----------------------------------------------------------------------
+    @property
+    def padding(self) -> bool:
+        """True (the default): every convolution pads as constructed.  False: every Conv1d / ConvTranspose1d runs with padding 0 and a
+        ResidualUnit adds its input cropped by 3 * dilation on each side, as the reference's layers do after `model.padding = False`
+        (include/escx.h escx_dac_set_padding).  encode / decode / num_frames / output_samples follow the mode."""
+        return self._padding
+
+    @padding.setter
+    def padding(self, value):
+        assert isinstance(value, bool)
+        self._padding = value
+        for hd in self._handles.values():
+            _native.check(_native.load().escx_dac_set_padding(hd, int(value)))
+
+    @property
+    def device(self):
+        return next(self.parameters()).device
+
+    def _conv_layers(self):
+        """(transposed, kernel, stride, dilation) of every convolution of encoder and decoder in module order.  The quantiser's 1x1 projections
+        lie between them and change no length."""
+        out = [(False, 7, 1, 1)]
+        for s in self.encoder_rates:
+            for d in (1, 3, 9):
+                out += [(False, 7, 1, d), (False, 1, 1, 1)]
+            out.append((False, 2 * s, s, 1))
+        out += [(False, 3, 1, 1), (False, 7, 1, 1)]
+        for s in self.decoder_rates:
+            out.append((True, 2 * s, s, 1))
+            for d in (1, 3, 9):
+                out += [(False, 7, 1, d), (False, 1, 1, 1)]
+        out.append((False, 7, 1, 1))
+        return out
+
+    def get_output_length(self, input_length: int) -> int:
+        """base.py:108-123: samples out of encoder + decoder for input_length in with every convolution unpadded, floored at each layer (the
+        reference evaluates it at 0, where it is negative).  It is the hop between chunks of `compress`."""
+        L = int(input_length)
+        for tr, k, s, d in self._conv_layers():
+            reach = d * (k - 1) + 1
+            L = (L - 1) * s + reach if tr else (L - reach) // s + 1
+        return L
+
+    def get_delay(self) -> int:
+        """base.py:82-106: half of what the unpadded model's receptive field takes off a signal; `compress` zero-pads by it on both sides."""
+        l_out = self.get_output_length(0)
+        L = l_out
+        for tr, k, s, d in reversed(self._conv_layers()):
+            reach = d * (k - 1) + 1
+            L = -((reach - L) // s) + 1 if tr else (L - 1) * s + reach
+        return (L - l_out) // 2
+
+    @property
+    def delay(self) -> int:
+        return self.get_delay()
+
+    def _walk(self, t: int, layers) -> int:
+        """Length after `layers` without padding; 0 as soon as one of them would give no row."""
+        for tr, k, s, d in layers:
+            reach = d * (k - 1) + 1
+            t = (t - 1) * s + reach if tr else ((t - reach) // s + 1 if t >= reach else 0)
+            if t < 1:
+                return 0
+        return t
+
     # ---- length arithmetic ---------------------------------------------------------------------------------------------------------------
     def num_frames(self, n_samples: int) -> int:
-        """Latent frames of an n_samples clip (torch's Conv1d length formula through the encoder); 0 when the clip is shorter than one hop."""
+        """Latent frames of an n_samples clip (torch's Conv1d length formula through the encoder); 0 when the clip is shorter than one hop
+        (with `padding` off: shorter than the encoder's receptive field)."""
         t = int(n_samples)
+        if not self._padding:
+            return self._walk(t, self._conv_layers()[:2 + 7 * len(self.encoder_rates)]) if t >= 1 else 0
         for s in self.encoder_rates:
             t = (t + 2 * math.ceil(s / 2) - 2 * s) // s + 1
             if t < 1:
@@ -220,8 +338,10 @@ class DAC(nn.Module):
         return t
 
     def output_samples(self, n_frames: int) -> int:
-        """Samples decoded from n_frames latent frames: 320 T - 8 for rates [8, 5, 4, 2]."""
+        """Samples decoded from n_frames latent frames: 320 T - 8 for rates [8, 5, 4, 2]; with `padding` off the unpadded decoder's (0: none)."""
         t = int(n_frames)
+        if not self._padding:
+            return self._walk(t, self._conv_layers()[2 + 7 * len(self.encoder_rates):]) if t >= 1 else 0
         for s in self.decoder_rates:
             t = (t - 1) * s - 2 * math.ceil(s / 2) + 2 * s
         return t
@@ -357,6 +477,8 @@ class DAC(nn.Module):
         T = self.num_frames(L)
         if T < 1:
             raise ValueError(f"{L} samples are shorter than one hop ({self.hop_length}): the encoder gives no frame")
+        if not self._padding and lib.escx_dac_num_frames(hd, L) != T:
+            raise RuntimeError(f"libescx encodes {L} unpadded samples to {lib.escx_dac_num_frames(hd, L)} frames, the host to {T}")
         x = audio_data.to(torch.float32).contiguous()
         z = torch.empty(B, self.latent_dim, T, device=dev)
         codes = torch.empty(B, n, T, dtype=torch.int64, device=dev)
@@ -376,7 +498,12 @@ class DAC(nn.Module):
             raise ValueError(f"z must be (B, {self.latent_dim}, T), got {tuple(z.shape)}")
         B, _, T = z.shape
         zc = z.to(torch.float32).contiguous()
-        out = torch.empty(B, 1, self.output_samples(T), device=dev)
+        n_out = self.output_samples(T)
+        if n_out < 1:
+            raise ValueError(f"{T} latent frames decode to no sample with padding off")
+        if not self._padding and lib.escx_dac_output_samples(hd, T) != n_out:
+            raise RuntimeError(f"libescx decodes {T} unpadded frames to {lib.escx_dac_output_samples(hd, T)} samples, the host to {n_out}")
+        out = torch.empty(B, 1, n_out, device=dev)
         with torch.cuda.device(dev):
             _native.check(lib.escx_dac_decode(hd, ctypes.c_void_p(flat.data_ptr()), self._version(), ctypes.c_void_p(zc.data_ptr()), B, T,
                                               ctypes.c_void_p(out.data_ptr()), stream))
@@ -429,6 +556,162 @@ class DAC(nn.Module):
         z, codes, latents, cm, cb = self.encode(x, n_quantizers)
         audio = self.decode(z)
         return {"audio": audio[..., :length], "z": z, "codes": codes, "latents": latents, "vq/commitment_loss": cm, "vq/codebook_loss": cb}
+
+    # ---- CodecMixin.compress / decompress (base.py:125-294) ---------------------------------------------------------------------------------
+    def _max_map(self, n: int, decoder: bool) -> int:
+        """Elements of the largest channels-last feature map one clip of n samples (decoder: n frames) needs, an upper bound of what
+        csrc/dac.hip sizes its scratch by (lengths only shrink inside a block, so the padded lengths bound the unpadded ones)."""
+        cp = lambda c: (c + 3) // 4 * 4                                                          # noqa: E731
+        if decoder:
+            t, c, m = n, self.decoder_dim, n * max(cp(self.latent_dim), cp(self.decoder_dim))
+            for s in self.decoder_rates:
+                t, c = (t + 1) * s, c // 2
+                m = max(m, t * cp(c))
+            return m
+        t, c, m = n, self.encoder_dim, n * max(4, cp(self.encoder_dim))
+        for s in self.encoder_rates:
+            t, c = t // s + 1, 2 * c
+            m = max(m, t * cp(c))
+        return max(m, t * cp(self.latent_dim))
+
+    def chunk_schedule(self, n_signal: int, win_duration: Optional[float] = 1.0):
+        """The schedule of base.py:182-214 for a signal of n_signal samples at the model's rate, reproduced as it stands (n_samples - hop is not
+        2 * delay): {"padding", "n_samples", "hop", "starts", "chunk_length", "delay"}.  `padding` True is the unchunked pass (one window of the
+        whole signal, taken when n_signal / sample_rate <= win_duration); otherwise window c covers [starts[c], starts[c] + n_samples) of the
+        signal zero-padded by `delay` on both sides and chunk_length is the frames every window encodes to."""
+        nt = int(n_signal)
+        if nt < 1:
+            raise ValueError("an empty signal")
+        if win_duration is None or nt / self.sample_rate <= win_duration:
+            t = math.ceil(nt / self.hop_length) * self.hop_length                # preprocess, then the padded encoder's length formula
+            for s in self.encoder_rates:
+                t = max((t + 2 * math.ceil(s / 2) - 2 * s) // s + 1, 0)
+            return {"padding": True, "n_samples": nt, "hop": nt, "starts": [0], "chunk_length": t, "delay": 0}
+        n_samples = int(win_duration * self.sample_rate)
+        n_samples = int(math.ceil(n_samples / self.hop_length) * self.hop_length)
+        hop = self.get_output_length(n_samples)
+        layers = self._conv_layers()
+        n_enc = 2 + 7 * len(self.encoder_rates)
+        frames = self._walk(n_samples, layers[:n_enc]) if n_samples >= 1 else 0
+        if hop < 1 or frames < 1 or self._walk(frames, layers[n_enc:]) != hop:
+            raise ValueError(f"win_duration {win_duration} s is {n_samples} samples: below the receptive field of the unpadded model "
+                             f"(get_output_length gives {hop})")
+        return {"padding": False, "n_samples": n_samples, "hop": hop, "starts": list(range(0, nt, hop)), "chunk_length": frames,
+                "delay": self.get_delay()}
+
+    @torch.no_grad()
+    def compress(self, audio: torch.Tensor, sample_rate: int = None, win_duration: Optional[float] = 1.0, n_quantizers: int = None, input_db=None,
+                 chunks_per_pass: int = None) -> DACFile:
+        """CodecMixin.compress (base.py:125-233) for a tensor `audio` of shape (nt,), (channels, nt) or (batch, channels, nt) on the device.
+        A signal of at most win_duration seconds is one padded pass.  A longer one is encoded with `padding` off in windows of
+        n_samples = ceil(int(win_duration * sr) / hop_length) * hop_length samples that start every get_output_length(n_samples) samples of the
+        signal zero-padded by `delay` on both sides.  The windows are staged on the device straight from the signal
+        (include/escx.h escx_dac_encode_chunks) and run as one batch - the reference runs them one by one - or in passes of chunks_per_pass
+        windows; the default takes all of them, split only where a pass would exceed the kernels' 2^32-element feature maps.  The codes do not
+        depend on chunks_per_pass.  `padding` is back at its previous value on return, also after an error.
+
+        Out of scope, because they are audiotools.AudioSignal's work and audiotools is not a dependency: resampling (a sample_rate other than
+        the model's raises ValueError), loudness measurement and normalisation (input_db is stored in the file as given and not applied) and
+        peak limiting.  The caller hands in the signal the reference would encode after those steps."""
+        if self.training:
+            raise NotImplementedError("esc.baselines.DAC is inference only: call .eval() (DAC training is not implemented)")
+        if sample_rate is not None and sample_rate != self.sample_rate:
+            raise ValueError(f"sample_rate {sample_rate} != the model's {self.sample_rate}: resampling is out of scope (audiotools)")
+        if audio.dim() not in (1, 2, 3):
+            raise ValueError(f"audio must be (nt,), (channels, nt) or (batch, channels, nt), got {tuple(audio.shape)}")
+        if chunks_per_pass is not None and int(chunks_per_pass) < 1:
+            raise ValueError(f"chunks_per_pass must be at least 1, got {chunks_per_pass}")
+        x = audio.reshape((1,) * (3 - audio.dim()) + tuple(audio.shape))
+        nb, nac, nt = x.shape
+        rows = nb * nac
+        n = self._n_quantizers(n_quantizers)
+        previous = self.padding
+        try:
+            sch = self.chunk_schedule(nt, win_duration)
+            self.padding = sch["padding"]
+            x = x.reshape(rows, 1, nt)
+            if sch["padding"]:
+                codes = self.encode(self.preprocess(x, self.sample_rate), n)[1]
+            else:
+                codes = self._encode_chunks(x, sch, n, chunks_per_pass)
+            return DACFile(codes=codes, chunk_length=sch["chunk_length"], original_length=nt, input_db=input_db, channels=nac,
+                           sample_rate=self.sample_rate, padding=sch["padding"], dac_version=SUPPORTED_VERSIONS[-1])
+        finally:
+            self.padding = previous
+
+    def _encode_chunks(self, x: torch.Tensor, sch: dict, n: int, chunks_per_pass):
+        """codes (rows, n, n_chunks * chunk_length) of every window of the schedule, in passes of one batch each."""
+        lib, hd, flat, dev, stream = self._ctx(x, "audio")
+        rows, _, nt = x.shape
+        n_samples, hop, T, n_chunks = sch["n_samples"], sch["hop"], sch["chunk_length"], len(sch["starts"])
+        per = _MAP_LIMIT // (self._max_map(n_samples, False) * rows)
+        if per < 1:
+            raise NotImplementedError(f"{rows} rows of {n_samples}-sample windows: one chunk per row is above the 2^32-element feature maps")
+        per = min(n_chunks, per if chunks_per_pass is None else min(per, int(chunks_per_pass)))
+        if lib.escx_dac_num_frames(hd, n_samples) != T:
+            raise RuntimeError(f"libescx encodes a {n_samples}-sample window to {lib.escx_dac_num_frames(hd, n_samples)} frames, the host to {T}")
+        sig = x.to(torch.float32).contiguous()
+        out = []
+        for c0 in range(0, n_chunks, per):
+            nc = min(per, n_chunks - c0)
+            B = rows * nc
+            z = torch.empty(B, self.latent_dim, T, device=dev)
+            codes = torch.empty(B, n, T, dtype=torch.int64, device=dev)
+            latents = torch.empty(B, n * self.codebook_dim, T, device=dev)
+            losses = torch.empty(2, device=dev)
+            with torch.cuda.device(dev):
+                _native.check(lib.escx_dac_encode_chunks(hd, ctypes.c_void_p(flat.data_ptr()), self._version(), ctypes.c_void_p(sig.data_ptr()), rows, nt, nc,
+                                                         n_samples, hop, sch["delay"] - c0 * hop, n, ctypes.c_void_p(z.data_ptr()),
+                                                         ctypes.c_void_p(codes.data_ptr()), ctypes.c_void_p(latents.data_ptr()),
+                                                         ctypes.c_void_p(losses.data_ptr()), stream))
+            out.append(codes.reshape(rows, nc, n, T).permute(0, 2, 1, 3).reshape(rows, n, nc * T))
+        return torch.cat(out, dim=-1)
+
+    @torch.no_grad()
+    def decompress(self, obj: Union[str, Path, DACFile], chunks_per_pass: int = None) -> torch.Tensor:
+        """CodecMixin.decompress (base.py:235-294): the signal (batch, channels, original_length) of a DACFile or of a .dac file.  `padding` is
+        taken from the file; the codes are decoded chunk_length frames at a time through quantizer.from_codes and decode, all chunks as one
+        batch (or chunks_per_pass at a time, split as in compress), a shorter last chunk in a pass of its own, and the result is trimmed to
+        original_length.  With the padding off each chunk decodes to exactly the hop of compress, so the chunks' outputs in batch order are the
+        concatenated signal.  One deliberate departure: the unchunked path decodes fewer samples than it was given (320 T - 8 for rates
+        [8, 5, 4, 2]); the reference's final reshape fails there, this method right-pads with zeros.  Loudness restoration and resampling are out
+        of scope as in compress: a file of another sample rate raises ValueError.  `padding` is restored on return."""
+        if self.training:
+            raise NotImplementedError("esc.baselines.DAC is inference only: call .eval() (DAC training is not implemented)")
+        if isinstance(obj, (str, Path)):
+            obj = DACFile.load(obj)
+        if int(obj.sample_rate) != self.sample_rate:
+            raise ValueError(f"the file's sample_rate {obj.sample_rate} != the model's {self.sample_rate}: resampling is out of scope (audiotools)")
+        if chunks_per_pass is not None and int(chunks_per_pass) < 1:
+            raise ValueError(f"chunks_per_pass must be at least 1, got {chunks_per_pass}")
+        codes, cl, length = obj.codes, int(obj.chunk_length), int(obj.original_length)
+        if codes.dim() != 3 or cl < 1 or codes.shape[-1] < 1:
+            raise ValueError(f"codes must be (rows, n, frames) with a positive chunk_length, got {tuple(codes.shape)} and {cl}")
+        dev = codes.device if codes.is_cuda else self.device
+        _check_device(torch.empty(0, device=dev), "the model")
+        codes = codes.to(device=dev, dtype=torch.int64)
+        rows, n, total = codes.shape
+        previous = self.padding
+        try:
+            self.padding = bool(obj.padding)
+            full = total // cl
+            per = max(1, _MAP_LIMIT // (self._max_map(cl, True) * rows))
+            per = per if chunks_per_pass is None else min(per, int(chunks_per_pass))
+            recons = []
+            for c0 in range(0, full, per):
+                nc = min(per, full - c0)
+                c = codes[..., c0 * cl:(c0 + nc) * cl].reshape(rows, n, nc, cl).permute(0, 2, 1, 3).reshape(rows * nc, n, cl)
+                r = self.decode(self._from_codes(c)[0])
+                assert r.shape[-1] == self.output_samples(cl)
+                recons.append(r.reshape(rows, 1, nc * r.shape[-1]))
+            if total % cl:
+                recons.append(self.decode(self._from_codes(codes[..., full * cl:].contiguous())[0]))
+            out = torch.cat(recons, dim=-1)[..., :length]
+            if out.shape[-1] < length:
+                out = nn.functional.pad(out, (0, length - out.shape[-1]))
+            return out.reshape(-1, int(obj.channels), length)
+        finally:
+            self.padding = previous
 
     @classmethod
     def load(cls, path, map_location="cpu", strict: bool = True):

@@ -4,8 +4,13 @@ wav I/O through scipy.  Writes decoded_<kbps>kbps_<name>.wav and encoded_<kbps>k
 
     python -m scripts.compress --input audio.wav --model_path ./esc9kbps --num_streams 6 --device cuda
     python -m scripts.compress --input audio.wav --synthetic base --device cuda       # no checkpoint: synthetic weights
+    python -m scripts.compress --input audio.wav --dac_path ./dac/weights.pth --win_duration 1.0      # the DAC baseline: .dac file + reconstruction
+    python -m scripts.compress --input audio.wav --synthetic dac_tiny
+
+The DAC arm (esc.baselines.DAC.compress / decompress, the reference's CodecMixin) writes encoded_<name>.dac in the reference's DACFile layout
+and decoded_dac_<name>.wav.  The wav must be at the model's sample rate: resampling and loudness normalisation are audiotools' and out of scope.
 """
-import argparse, json, os, sys
+import argparse, json, math, os, sys
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(ROOT, "efficient-speech-codec_amd"))
@@ -20,7 +25,12 @@ def main():
     ap.add_argument("--input", required=True); ap.add_argument("--save_path", default="./output")
     ap.add_argument("--model_path", default=None); ap.add_argument("--synthetic", default=None, help="base|large: name-keyed synthetic weights")
     ap.add_argument("--num_streams", type=int, default=6); ap.add_argument("--device", default="cuda")
+    ap.add_argument("--dac_path", default=None, help="DAC baseline checkpoint (weights.pth, esc.baselines.DAC.load); or --synthetic dac_syn|dac_tiny|dac_base")
+    ap.add_argument("--win_duration", type=float, default=1.0, help="DAC: window of the chunked compress in seconds (a shorter file is one padded pass)")
+    ap.add_argument("--n_quantizers", type=int, default=None, help="DAC: codebooks to keep (default: all)")
     a = ap.parse_args()
+    if a.dac_path or str(a.synthetic or "").startswith("dac_"):
+        return main_dac(a)
     sr, pcm = wavfile.read(a.input)
     x = pcm.astype(np.float32) / 32768.0 if pcm.dtype == np.int16 else pcm.astype(np.float32)
     x = torch.from_numpy(np.atleast_2d(x.T if x.ndim == 2 else x)).to(a.device)          # channels are the batch (compress.py:19-20)
@@ -47,6 +57,31 @@ def main():
     dur = x.shape[1] / sr
     print(f"compression outputs saved into {a.save_path}: {len(blob)} bytes for {dur:.2f} s x {x.shape[0]} ch "
           f"= {(len(blob) - 16) * 8 / dur / x.shape[0] / 1000:.2f} kbps payload")
+
+
+def main_dac(a):
+    from esc.baselines import DAC
+    if a.dac_path:
+        model = DAC.load(a.dac_path)
+    else:
+        gold = os.path.join(ROOT, "tests", "golden")
+        model = DAC(**json.loads(str(np.load(os.path.join(gold, f"{a.synthetic}.npz"))["config_json"])))
+        man = json.load(open(os.path.join(gold, f"{a.synthetic}_manifest.json")))
+        model.load_state_dict({k: torch.from_numpy(v) for k, v in synth.dac_state_dict(man).items()}, strict=True)
+    model = model.to(a.device).eval()
+    sr, pcm = wavfile.read(a.input)
+    x = pcm.astype(np.float32) / 32768.0 if pcm.dtype == np.int16 else pcm.astype(np.float32)
+    x = torch.from_numpy(np.atleast_2d(x.T if x.ndim == 2 else x)).to(a.device)          # (channels, nt)
+    f = model.compress(x, sample_rate=sr, win_duration=a.win_duration, n_quantizers=a.n_quantizers)
+    recon = model.decompress(f)
+    os.makedirs(a.save_path, exist_ok=True)
+    fname = os.path.basename(a.input); stem = fname.rsplit(".", 1)[0]
+    path = f.save(f"{a.save_path}/encoded_{stem}.dac")
+    wavfile.write(f"{a.save_path}/decoded_dac_{fname}", sr, np.clip(recon[0].T.cpu().numpy().squeeze(), -1, 1))
+    n, frames = f.codes.shape[1], f.codes.shape[2]
+    bits = n * frames * math.log2(model.codebook_size)
+    print(f"compression outputs saved into {a.save_path}: {path.name} {os.path.getsize(path)} bytes, {frames} frames of {n} codebooks in chunks of "
+          f"{f.chunk_length} (padding {f.padding}) for {x.shape[1] / sr:.2f} s x {x.shape[0]} ch = {bits / (x.shape[1] / sr) / 1000:.2f} kbps of codes")
 
 
 if __name__ == "__main__":

@@ -444,6 +444,28 @@ int escx_dac_get_snake_maps(escx_dac d);
  * The three-term weight image is rebuilt whenever the packed fp32 weights are (params_version, buffer) and when the mode is first switched on. */
 int escx_dac_set_precision(escx_dac d, int mode);
 int escx_dac_get_precision(escx_dac d);
+/* CodecMixin.padding (base.py:58-80), per handle, read at each call; on by default.  Off: every Conv1d and ConvTranspose1d runs with padding 0, as
+ * the reference's chunked compress / decompress do (base.py:194-201, 259-260): a Conv1d gives floor((T - dilation (K - 1) - 1) / stride) + 1 rows, a
+ * ConvTranspose1d (T + 1) * stride, and a ResidualUnit adds its input cropped by 3 * dilation rows on each side (dac.py:35-40).  escx_dac_num_frames,
+ * escx_dac_output_samples, escx_dac_encode, escx_dac_encode_ex and escx_dac_decode honour the mode; a length that leaves any layer without a row is
+ * ESCX_ERR_INVALID_ARG before anything is launched.  With the padding on, every call computes bitwise what it did before this switch existed.  The
+ * packed transposed-convolution weights depend on the mode: the first call after a change re-derives the packed operands.  `on` is 0 or 1. */
+int escx_dac_set_padding(escx_dac d, int on);
+int escx_dac_get_padding(escx_dac d);
+/* CodecMixin.get_delay (base.py:82-106): (l_in - l_out) / 2 of the whole model's receptive field, whatever the padding mode; -1 for a null handle. */
+int escx_dac_delay(escx_dac d);
+/* CodecMixin.get_output_length (base.py:108-123): samples out of encoder + decoder for n_samples in, every convolution without padding, floored at
+ * every layer, whatever the padding mode.  The reference evaluates it at 0 too, so the result may be negative. */
+int escx_dac_output_length(escx_dac d, int n_samples);
+/* One pass of CodecMixin.compress's chunked loop (base.py:197, 203-214) as one batch: escx_dac_encode_ex (no per-clip counts, no snapshots) on
+ * B = rows * n_chunks windows of L = n_samples that are never materialised on the host.  Window c of signal row r (batch index r * n_chunks + c) holds
+ * signal[r][c * hop + j - lead] at sample j and 0 where that index falls outside [0, n_signal): with lead = escx_dac_delay this is the reference's
+ * zero_pad(delay, delay), its slice [c * hop, c * hop + n_samples) and the right zero-pad of a short last slice.  A pass that starts at chunk c0 passes
+ * lead = delay - c0 * hop.  signal_dev is (rows, n_signal) fp32; the outputs are escx_dac_encode's for that batch.  The padding mode is the handle's
+ * (the reference switches it off for this loop). */
+int escx_dac_encode_chunks(escx_dac d, const float* flat_params_dev, int64_t params_version, const float* signal_dev, int rows, int64_t n_signal, int n_chunks,
+                           int n_samples, int hop, int64_t lead, int n_quantizers, float* z_dev, int64_t* codes_dev, float* latents_dev, float* losses_dev,
+                           void* stream);
 /* Test hook: the kernels' Snake (mode 0: x + sin(alpha x)^2 / (alpha + 1e-9), nn/layers.py:19-24) or tanh (mode 1) over n device values. */
 int escx_dac_test_math(const float* x_dev, const float* alpha_dev, float* out_dev, int64_t n, int mode, void* stream);
 
