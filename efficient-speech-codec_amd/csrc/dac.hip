@@ -5,7 +5,8 @@
 // and the quantiser tables are re-derived on the device whenever (buffer, version) or the padding mode changes.  Activations are channels-last
 // (B, T, Cp) maps in a handle-owned scratch; see dac_kernels.h for the loaders and epilogues.  escx_dac_set_padding(d, 0) runs every convolution
 // without padding (CodecMixin.padding, base.py:58-80) and escx_dac_encode_chunks stages the overlapping windows of the chunked compress
-// (base.py:182-214) straight from the signal; DESIGN.md section 13.2.
+// (base.py:182-214) straight from the signal; DESIGN.md section 13.2.  escx_dac_decode_tape / escx_dac_decode_backward are the decoder with its maps
+// kept in a caller-owned tape and the latent gradient d audio / d z on it (dac_grad_kernels.h).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -16,6 +17,7 @@
 #include "escx_internal.h"
 #include "dac_kernels.h"
 #include "dac_x3.h"
+#include "dac_grad_kernels.h"
 
 using namespace escx;
 
@@ -31,6 +33,7 @@ struct DacLayer {
     int CinP = 0, Np = 0, Kp = 0;   // operand geometry (Conv1d: Np = rup(Cout, 16), Kp = rup(K * CinP, 16); ConvT: per phase, Kp = rup(2 CinP, 16))
     size_t off_b = 0, off_g = 0, off_v = 0;
     float* W = nullptr; float* bias = nullptr;
+    float* Wt = nullptr;            // decoder layers, once a backward has run: the transposed image [NpT = rup(Cin, 16)][KpT = rup(K * cpad(Cout), 16)]
 };
 struct DacSnake { int C = 0; size_t off = 0; float* a = nullptr; float* inv = nullptr; };
 
@@ -60,6 +63,9 @@ struct escx_dac_s {
     // call in that mode; w16_valid is cleared by every re-pack of the fp32 image and set by refresh_w16, so the image can never be older than wbuf.
     __bf16* w16 = nullptr; size_t conv_floats = 0; bool w16_valid = false;
     int* counts = nullptr; size_t counts_cap = 0;   // per-clip stage counts / snapshot stages of the _ex calls, uploaded on the call's stream
+    // escx_dac_decode_backward: the decoder's transposed weight images, allocated (zeroed) at the first backward of the handle; wt_valid is cleared by
+    // every re-pack of wbuf and set by refresh_wt, as w16_valid is.  Calls that never differentiate pay nothing.
+    float* wt = nullptr; bool wt_valid = false;
 };
 
 namespace {
@@ -106,7 +112,7 @@ int conv_out_len(int T, const DacLayer& l, bool padding) {
 
 int pack(escx_dac_s* d, const float* flat, long long version, hipStream_t st) {
     if (version >= 0 && version == d->packed_version && flat == d->packed_ptr && (int)d->padding == d->packed_padding) return 0;
-    d->packed_version = version; d->packed_ptr = flat; d->packed_padding = d->padding; d->w16_valid = false;
+    d->packed_version = version; d->packed_ptr = flat; d->packed_padding = d->padding; d->w16_valid = false; d->wt_valid = false;
     for (auto* L : {&d->enc, &d->dec})
         for (DacLayer& l : *L) {
             if (l.kind == 0)
@@ -423,6 +429,7 @@ extern "C" void escx_dac_destroy(escx_dac d) {
     (void)hipSetDevice(d->device);
     if (d->wbuf) (void)hipFree(d->wbuf);
     if (d->w16) (void)hipFree(d->w16);
+    if (d->wt) (void)hipFree(d->wt);
     if (d->qoffs_dev) (void)hipFree(d->qoffs_dev);
     if (d->scratch) (void)hipFree(d->scratch);
     if (d->counts) (void)hipFree(d->counts);
@@ -614,6 +621,170 @@ extern "C" int escx_dac_decode(escx_dac d, const float* flat, int64_t version, c
     }
     run_layer(run, ESCX_DAC_SNAKE_LAST, Dl[d->dec.size() - 1], SN + d->dec_sn.size() - 1, x, B, T, audio, Lout, nullptr, 1);
     return launch_ok("escx_dac_decode");
+}
+
+// ---- latent gradient through the decoder, eval mode, padding on (dac.py:249-266) -----------------------------------------
+namespace {
+
+inline int np_t(const DacLayer& l) { return rup(l.Cin, 16); }
+inline int kp_t(const DacLayer& l) { return rup(l.K * cpad(l.Cout), 16); }
+
+// The activation tape of one padded decode of B x T: a header, then the decoder's maps in execution order, then the audio.
+//   map 0            the first convolution's output = block 0's ConvTranspose input
+//   map 7 i + 1 + 2 j, 7 i + 2 + 2 j    ResidualUnit j of block i: its input x (j = 0: the ConvTranspose output) and its 7-tap output h
+//   map 7 i + 7      block i's output = block i + 1's ConvTranspose input, or the input of the last Snake
+// Every map is channels-last (B, T_i, cpad(C_i)), rounded up to 64 floats; offsets are in floats.
+struct TapePlan { std::vector<size_t> off; std::vector<int> Ts; size_t audio = 0, total = 0, mf = 0; int Lout = 0; };
+
+bool tape_plan(const escx_dac_s* d, int B, int T, TapePlan* p) {
+    p->Lout = dec_walk(d, true, B, T, &p->mf);
+    if (p->Lout < 1) return false;
+    size_t cur = DAC_TAPE_HEADER;
+    int C = d->cfg.decoder_dim, Tc = conv_out_len(T, d->dec[0], true);
+    p->Ts.push_back(Tc);
+    p->off.push_back(cur); cur += map_floats(B, Tc, C);
+    for (int i = 0; i < d->cfg.n_decoder_rates; ++i) {
+        Tc = conv_out_len(Tc, d->dec[1 + i * 7], true); C /= 2;
+        p->Ts.push_back(Tc);
+        for (int k = 0; k < 7; ++k) { p->off.push_back(cur); cur += map_floats(B, Tc, C); }
+    }
+    p->audio = cur; cur += pad64((size_t)B * p->Lout);
+    p->total = cur;
+    return true;
+}
+
+// The decoder's transposed weight images, after pack() on the same stream: derived from whatever fp32 image is current, once per re-pack
+int refresh_wt(escx_dac_s* d, hipStream_t st) {
+    if (d->wt_valid) return 0;
+    if (!d->wt) {
+        size_t n = 0;
+        for (const DacLayer& l : d->dec) n += pad64((size_t)np_t(l) * kp_t(l));
+        ESCX_HIP(hipMalloc((void**)&d->wt, n * sizeof(float)));
+        ESCX_HIP(hipMemsetAsync(d->wt, 0, n * sizeof(float), st));
+        size_t cur = 0;
+        for (DacLayer& l : d->dec) { l.Wt = d->wt + cur; cur += pad64((size_t)np_t(l) * kp_t(l)); }
+    }
+    for (const DacLayer& l : d->dec)
+        hipLaunchKernelGGL(dac_wt_pack_kernel, dim3(nblk((long long)l.Cin * l.K * l.Cout)), dim3(256), 0, st, (const float*)l.W, l.Wt, l.kind, l.Cin, l.Cout, l.K,
+                           l.stride, l.pad, l.CinP, cpad(l.Cout), l.Np, l.Kp, kp_t(l));
+    d->wt_valid = true;
+    return launch_ok("dac_transpose_weights");
+}
+
+// dX of layer l from dY (B, Tdy, cpad(Cout)):  out (B, Tx, cpad(Cin)) = [res +] conv^T(dY) * snake'(xs), or d_z (B, zD, Tx) when there is no Snake
+// in front (the first convolution).  The tile rule is launch_conv's: by the layer's tile count, and no output bit depends on it.
+void bwd_layer(hipStream_t st, const DacLayer& l, const DacSnake* sn, const float* dY, int B, int Tdy, int Tx, const float* xs, const float* res, float* out,
+               int zD = 0) {
+    DacConvA ld{};
+    ld.x = dY; ld.alpha = nullptr; ld.inv = nullptr; ld.Tin = Tdy; ld.Cp = cpad(l.Cout); ld.dCp = FastDiv(ld.Cp);
+    ld.Trows = Tx; ld.M = B * Tx; ld.dT = FastDiv(Tx); ld.ntaps = l.K;
+    if (l.kind == 0) { ld.rs = 1; ld.r0 = l.pad; ld.td = -l.dil; }
+    else { ld.rs = l.stride; ld.r0 = -l.pad; ld.td = 1; }
+    DacGradEpi ep{};
+    ep.out = out; ep.res = res; ep.xs = xs; ep.alpha = sn ? sn->a : nullptr; ep.inv = sn ? sn->inv : nullptr;
+    ep.Cp = cpad(l.Cin); ep.D = zD; ep.T = Tx; ep.dT = ld.dT;
+    const int Np = np_t(l), Kp = kp_t(l);
+    const long long tiles = (long long)((ld.M + 127) / 128) * ((Np + 95) / 96);
+    if (tiles >= 512) launch_gemm<128>(ld, l.Wt, ld.M, Np, Kp, ep, st);
+    else launch_gemm<64>(ld, l.Wt, ld.M, Np, Kp, ep, st);
+}
+
+int tape_args(escx_dac_s* d, int B, int T, long long tape_floats, TapePlan* p) {
+    if (!d->padding) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "the decoder's gradient is implemented with the padding on (the chunked path needs none)");
+    if (!tape_plan(d, B, T, p)) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "%d latent frames decode to no sample", T);
+    if ((unsigned long long)p->mf >= (1ull << 32)) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "batch of %d x %d frames: a feature map above 2^32 elements", B, T);
+    if (tape_floats != (long long)p->total)
+        ESCX_FAIL(ESCX_ERR_INVALID_ARG, "tape of %lld floats: a decode of %d x %d frames needs %lld (escx_dac_decode_tape_floats)", tape_floats, B, T, (long long)p->total);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int64_t escx_dac_decode_tape_floats(escx_dac d, int B, int T) {
+    if (!d || B < 1 || T < 1) return 0;
+    if (!d->padding) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "the decoder's gradient is implemented with the padding on (the chunked path needs none)");
+    TapePlan p;
+    return tape_plan(d, B, T, &p) ? (int64_t)p.total : 0;
+}
+
+extern "C" int escx_dac_decode_tape(escx_dac d, const float* flat, int64_t version, const float* z, int B, int T, float* audio, float* tape, int64_t tape_floats,
+                                    void* stream) {
+    int rc = check_args(d, flat, B); if (rc) return rc;
+    if (!z || !audio || !tape || T < 1) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "bad argument");
+    TapePlan p;
+    if ((rc = tape_args(d, B, T, (long long)tape_floats, &p))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t mf = p.mf;
+    if ((rc = ensure_scratch(d, 4 * mf * sizeof(float)))) return rc;
+    if ((rc = pack(d, flat, (long long)version, st)) || (rc = refresh_w16(d, st))) return rc;
+    float* zin = d->scratch + 2 * mf;                       // the staged latent and the Snaked copy stay in the handle's scratch: no backward reads them
+    const Run run{d->snake_maps, d->scratch + 3 * mf, st, d->wbuf, d->precision == ESCX_PRECISION_BF16X3 ? d->w16 : nullptr, d->conv_floats, true};
+    auto M = [&](int i) { return tape + p.off[i]; };
+    hipLaunchKernelGGL(dac_tape_header_kernel, dim3(1), dim3(64), 0, st, (long long*)tape, (long long)version, (long long)B, (long long)T, (long long)p.total);
+    const int Dp = cpad(d->latent);
+    hipLaunchKernelGGL(dac_z_in_kernel, dim3(nblk((long long)B * T * Dp)), dim3(256), 0, st, z, zin, B, d->latent, Dp, T);
+    const DacLayer* Dl = d->dec.data(); const DacSnake* SN = d->dec_sn.data();
+    const int nb = d->cfg.n_decoder_rates;
+    run_layer(run, ESCX_DAC_SNAKE_LAST, Dl[0], nullptr, zin, B, T, M(0), p.Ts[0], nullptr, 0);
+    for (int i = 0; i < nb; ++i) {
+        const DacLayer* Lb = Dl + 1 + i * 7; const DacSnake* Sb = SN + i * 7;
+        const int Tc = p.Ts[i + 1];
+        run_layer(run, ESCX_DAC_SNAKE_UP, Lb[0], Sb, M(7 * i), B, p.Ts[i], M(7 * i + 1), Tc, nullptr, 0);
+        for (int j = 0; j < 3; ++j) {                       // run_res with padding, x and h kept: the sum goes to the next map instead of back into x
+            float* x = M(7 * i + 1 + 2 * j); float* h = M(7 * i + 2 + 2 * j);
+            run_layer(run, ESCX_DAC_SNAKE_RES7, Lb[1 + 2 * j], &Sb[1 + 2 * j], x, B, Tc, h, Tc, nullptr, 0);
+            run_layer(run, ESCX_DAC_SNAKE_RES1, Lb[2 + 2 * j], &Sb[2 + 2 * j], h, B, Tc, M(7 * i + 3 + 2 * j), Tc, x, 0);
+        }
+    }
+    run_layer(run, ESCX_DAC_SNAKE_LAST, Dl[d->dec.size() - 1], SN + d->dec_sn.size() - 1, M(7 * nb), B, p.Ts[nb], audio, p.Lout, nullptr, 1);
+    ESCX_HIP(hipMemcpyAsync(tape + p.audio, audio, (size_t)B * p.Lout * sizeof(float), hipMemcpyDeviceToDevice, st));
+    return launch_ok("escx_dac_decode_tape");
+}
+
+extern "C" int escx_dac_decode_backward(escx_dac d, const float* flat, int64_t version, const float* tape, int64_t tape_floats, const float* d_audio, int B, int T,
+                                        float* d_z, void* stream) {
+    int rc = check_args(d, flat, B); if (rc) return rc;
+    if (!tape || !d_audio || !d_z || T < 1) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "bad argument");
+    TapePlan p;
+    if ((rc = tape_args(d, B, T, (long long)tape_floats, &p))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    // The tape says what it was made with; the handle keeps nothing per graph.  Checked before anything of the handle changes.
+    long long hdr[5] = {0, 0, 0, 0, 0};
+    ESCX_HIP(hipMemcpyAsync(hdr, tape, sizeof(hdr), hipMemcpyDeviceToHost, st));
+    ESCX_HIP(hipStreamSynchronize(st));
+    if (hdr[0] != DAC_TAPE_MAGIC || hdr[2] != B || hdr[3] != T || hdr[4] != (long long)p.total)
+        ESCX_FAIL(ESCX_ERR_INVALID_ARG, "the buffer is not a tape that escx_dac_decode_tape made for %d x %d frames", B, T);
+    if (hdr[1] != (long long)version)
+        ESCX_FAIL(ESCX_ERR_STATE, "the tape was made with parameter version %lld and the backward is called with %lld: the parameters changed between forward and backward",
+                  hdr[1], (long long)version);
+    const size_t mf = p.mf;
+    if ((rc = ensure_scratch(d, 4 * mf * sizeof(float)))) return rc;
+    if ((rc = pack(d, flat, (long long)version, st)) || (rc = refresh_wt(d, st))) return rc;
+    float* G = d->scratch; float* G2 = G + mf; float* A = G2 + mf;
+    auto M = [&](int i) { return tape + p.off[i]; };
+    const DacLayer* Dl = d->dec.data(); const DacSnake* SN = d->dec_sn.data();
+    const int nb = d->cfg.n_decoder_rates;
+    const long long n = (long long)B * p.Lout;
+    hipLaunchKernelGGL(dac_tanh_grad_in_kernel, dim3(nblk(n)), dim3(256), 0, st, d_audio, tape + p.audio, A, n);
+    bwd_layer(st, Dl[d->dec.size() - 1], SN + d->dec_sn.size() - 1, A, B, p.Lout, p.Ts[nb], M(7 * nb), nullptr, G);
+    for (int i = nb - 1; i >= 0; --i) {
+        const DacLayer* Lb = Dl + 1 + i * 7; const DacSnake* Sb = SN + i * 7;
+        const int Tc = p.Ts[i + 1];
+        for (int j = 2; j >= 0; --j) {                      // g_x = g + conv7^T(conv1^T(g) * snake'(h)) * snake'(x), in place in G
+            bwd_layer(st, Lb[2 + 2 * j], &Sb[2 + 2 * j], G, B, Tc, Tc, M(7 * i + 2 + 2 * j), nullptr, A);
+            bwd_layer(st, Lb[1 + 2 * j], &Sb[1 + 2 * j], A, B, Tc, Tc, M(7 * i + 1 + 2 * j), G, G);
+        }
+        bwd_layer(st, Lb[0], Sb, G, B, Tc, p.Ts[i], M(7 * i), nullptr, G2);
+        std::swap(G, G2);
+    }
+    bwd_layer(st, Dl[0], nullptr, G, B, p.Ts[0], T, nullptr, nullptr, d_z, d->latent);
+    return launch_ok("escx_dac_decode_backward");
+}
+
+extern "C" int escx_dac_test_grad_math(const float* x, const float* alpha, float* out, int64_t n, int mode, void* stream) {
+    if (!x || !out || n < 0 || mode < 0 || mode > 1 || (mode == 0 && !alpha)) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "bad argument");
+    if (n) hipLaunchKernelGGL(dac_test_grad_math_kernel, dim3(nblk(n)), dim3(256), 0, (hipStream_t)stream, x, alpha, out, (long long)n, mode);
+    return launch_ok("escx_dac_test_grad_math");
 }
 
 extern "C" int escx_dac_test_math(const float* x, const float* alpha, float* out, int64_t n, int mode, void* stream) {

@@ -42,6 +42,13 @@ __device__ __forceinline__ f32x4 zero4() { f32x4 z = {0.f, 0.f, 0.f, 0.f}; retur
 template <class E, class = void> struct epi_is_rowwise : std::false_type {};
 template <class E> struct epi_is_rowwise<E, std::enable_if_t<E::ROWWISE>> : std::true_type {};
 
+// An epilogue with `static constexpr bool CHUNKED_K = true` gets two-level accumulation: the MFMA chain restarts at every BK step and the step's
+// sum is added to a second accumulator, so the rounding error of one output grows with sqrt(BK) + sqrt(K / BK) instead of the sqrt(K) of one
+// k-ordered chain (K = 2000..12000 in the DAC decoder's backward).  Still one fixed order per output, whatever BM and the grid: BK is chosen
+// from Kp alone.  Every other epilogue compiles to the kernel it had before this switch existed.
+template <class E, class = void> struct epi_chunked_k : std::false_type {};
+template <class E> struct epi_chunked_k<E, std::enable_if_t<E::CHUNKED_K>> : std::true_type {};
+
 template <int BM, int BN, int BK, class Loader, class Epi>
 __global__ __launch_bounds__(256) void gemm_kernel(Loader ld, const float* __restrict__ Wt, int M, int Np,
                                                    int Kp, int k_per_z, Epi ep) {
@@ -80,6 +87,14 @@ __global__ __launch_bounds__(256) void gemm_kernel(Loader ld, const float* __res
     for (int a = 0; a < TN; ++a)
 #pragma unroll
         for (int b = 0; b < TM; ++b) acc[a][b] = zero4();
+    constexpr bool CHUNKED = epi_chunked_k<Epi>::value;
+    [[maybe_unused]] f32x4 tot[CHUNKED ? TN : 1][CHUNKED ? TM : 1];
+    if constexpr (CHUNKED) {
+#pragma unroll
+        for (int a = 0; a < TN; ++a)
+#pragma unroll
+            for (int b = 0; b < TM; ++b) tot[a][b] = zero4();
+    }
 
     // Global -> register -> LDS with the NEXT K step's loads in flight while the current one is on the MFMA: the skinny, many-step
     // GEMMs this engine serves (PVQ projections, STFT) are bound by one memory round trip per K step otherwise.
@@ -127,7 +142,19 @@ __global__ __launch_bounds__(256) void gemm_kernel(Loader ld, const float* __res
                     for (int b = 0; b < TM; ++b)
                         acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[a][r], af[b][r], acc[a][b], 0, 0, 0);
         }
+        if constexpr (CHUNKED) {
+#pragma unroll
+            for (int a = 0; a < TN; ++a)
+#pragma unroll
+                for (int b = 0; b < TM; ++b) { tot[a][b] += acc[a][b]; acc[a][b] = zero4(); }
+        }
         __syncthreads();
+    }
+    if constexpr (CHUNKED) {
+#pragma unroll
+        for (int a = 0; a < TN; ++a)
+#pragma unroll
+            for (int b = 0; b < TM; ++b) acc[a][b] = tot[a][b];
     }
 
     // row epilogues (Epi::ROWWISE): the workgroup tile spans the whole output row (Np <= BN), so the epilogue can reduce over it in registers

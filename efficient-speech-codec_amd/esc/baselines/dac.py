@@ -3,7 +3,8 @@
 Same constructor keywords, same state_dict keys and shapes (`*.weight_g`, `*.weight_v`, `*.bias`, `*.alpha`,
 `quantizer.quantizers.{i}.codebook.weight`: reference checkpoints load with `load_state_dict(strict=True)`), same eval-mode
 `encode` / `decode` / `forward` / `quantizer.from_codes`.  Every convolution, the weight normalisation and the residual quantiser run in
-libescx (csrc/dac.hip); there is no PyTorch/CPU implementation here.  Inference only: training mode raises NotImplementedError.
+libescx (csrc/dac.hip); there is no PyTorch/CPU implementation here.  Inference only: training mode raises NotImplementedError.  One
+gradient exists, for a frozen decoder inside a larger autograd graph: `decode(z)` is differentiable in `z` (eval mode, padding on; `_DecodeGrad`).
 
 `DACFile`, `DAC.padding`, `DAC.compress` and `DAC.decompress` are CodecMixin's (reference baselines/descript/dac/model/base.py:15-294): files of any
 length in overlapping windows on padding-free convolutions, all windows of a file as one batch.
@@ -490,19 +491,33 @@ class DAC(nn.Module):
                                               ctypes.c_void_p(losses.data_ptr()), stream))
         return z, codes, latents, losses[0], losses[1]
 
-    @torch.no_grad()
     def decode(self, z: torch.Tensor):
-        """dac.py:249-266: z (B, D, T) -> audio (B, 1, output_samples(T))."""
+        """dac.py:249-266: z (B, D, T) -> audio (B, 1, output_samples(T)).  When gradients are enabled and z requires one, the result carries
+        the latent gradient d audio / d z (eval mode, padding on; `_DecodeGrad` below): the same audio bits, computed by escx_dac_decode_tape,
+        which keeps the decoder's maps in a tape on the graph.  The module's parameters get no gradient whatever their requires_grad."""
+        if self.training:
+            raise NotImplementedError("esc.baselines.DAC is inference only: call .eval() (DAC training is not implemented)")
+        if torch.is_grad_enabled() and isinstance(z, torch.Tensor) and z.requires_grad:
+            return _DecodeGrad.apply(z, self)
+        with torch.no_grad():
+            return self._decode(z)
+
+    def _decode_args(self, z: torch.Tensor):
+        """decode's checks: (lib, hd, flat, dev, stream, B, T, n_out)."""
         lib, hd, flat, dev, stream = self._ctx(z, "z")
         if z.dim() != 3 or z.shape[1] != self.latent_dim:
             raise ValueError(f"z must be (B, {self.latent_dim}, T), got {tuple(z.shape)}")
         B, _, T = z.shape
-        zc = z.to(torch.float32).contiguous()
         n_out = self.output_samples(T)
         if n_out < 1:
             raise ValueError(f"{T} latent frames decode to no sample with padding off")
         if not self._padding and lib.escx_dac_output_samples(hd, T) != n_out:
             raise RuntimeError(f"libescx decodes {T} unpadded frames to {lib.escx_dac_output_samples(hd, T)} samples, the host to {n_out}")
+        return lib, hd, flat, dev, stream, B, T, n_out
+
+    def _decode(self, z: torch.Tensor):
+        lib, hd, flat, dev, stream, B, T, n_out = self._decode_args(z)
+        zc = z.to(torch.float32).contiguous()
         out = torch.empty(B, 1, n_out, device=dev)
         with torch.cuda.device(dev):
             _native.check(lib.escx_dac_decode(hd, ctypes.c_void_p(flat.data_ptr()), self._version(), ctypes.c_void_p(zc.data_ptr()), B, T,
@@ -724,3 +739,46 @@ class DAC(nn.Module):
         model.load_state_dict(ck["state_dict"], strict=strict)
         model.metadata = ck["metadata"]
         return model
+
+
+class _DecodeGrad(torch.autograd.Function):
+    """DAC.decode with the latent gradient (include/escx.h escx_dac_decode_tape / escx_dac_decode_backward): the frozen decoder inside a larger
+    autograd graph.  forward is the decode's own launch sequence with the maps the backward needs kept in a tape, a plain tensor saved on the
+    graph, so any number of graphs may be alive at once; backward is first order only and runs on the fp32 MFMA in both precision modes."""
+
+    @staticmethod
+    def forward(ctx, z, model):
+        lib, hd, flat, dev, stream, B, T, n_out = model._decode_args(z)
+        if not model._padding:
+            raise NotImplementedError("the latent gradient of DAC.decode is implemented with padding on (the chunked path needs no gradients)")
+        zc = z.detach().to(torch.float32).contiguous()
+        floats = int(lib.escx_dac_decode_tape_floats(hd, B, T))
+        if floats < 0:
+            _native.check(floats)
+        if floats < 1:
+            raise RuntimeError(f"libescx gives no tape for a decode of {B} x {T} frames")
+        tape = torch.empty(floats, dtype=torch.float32, device=dev)
+        out = torch.empty(B, 1, n_out, device=dev)
+        version = model._version()
+        with torch.cuda.device(dev):
+            _native.check(lib.escx_dac_decode_tape(hd, ctypes.c_void_p(flat.data_ptr()), version, ctypes.c_void_p(zc.data_ptr()), B, T,
+                                                   ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(tape.data_ptr()), floats, stream))
+        ctx.save_for_backward(tape)
+        ctx.model, ctx.version, ctx.dims, ctx.z_dtype = model, version, (B, T), z.dtype
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_audio):
+        model, (B, T) = ctx.model, ctx.dims
+        tape, = ctx.saved_tensors
+        if model._version() != ctx.version:
+            raise RuntimeError("a parameter of the DAC module was changed in place between decode and its backward: the tape was made with the "
+                               "earlier weights (decode again after changing parameters)")
+        lib, hd, flat, dev, stream = model._ctx(tape, "the tape")
+        g = d_audio.to(torch.float32).contiguous()
+        d_z = torch.empty(B, model.latent_dim, T, device=dev)
+        with torch.cuda.device(dev):
+            _native.check(lib.escx_dac_decode_backward(hd, ctypes.c_void_p(flat.data_ptr()), ctx.version, ctypes.c_void_p(tape.data_ptr()), tape.numel(),
+                                                       ctypes.c_void_p(g.data_ptr()), B, T, ctypes.c_void_p(d_z.data_ptr()), stream))
+        return d_z.to(ctx.z_dtype), None

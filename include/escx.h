@@ -466,8 +466,38 @@ int escx_dac_output_length(escx_dac d, int n_samples);
 int escx_dac_encode_chunks(escx_dac d, const float* flat_params_dev, int64_t params_version, const float* signal_dev, int rows, int64_t n_signal, int n_chunks,
                            int n_samples, int hop, int64_t lead, int n_quantizers, float* z_dev, int64_t* codes_dev, float* latents_dev, float* losses_dev,
                            void* stream);
+/* ---- Latent gradient through the decoder (eval mode, padding on) -------------------------------------------------------------------------------
+ * d audio / d z of DAC.decode (baselines/descript/dac/model/dac.py:249-266) for a frozen codec inside a larger autograd graph: the decoder is
+ * Decoder.forward (dac.py:115-145) over DecoderBlock (dac.py:94-112: Snake1d, WNConvTranspose1d, three ResidualUnits) and ResidualUnit
+ * (dac.py:24-41: x + conv1(snake(conv7(snake(x))))), with Snake1d and the weight-normalised layers of nn/layers.py:9-33.  Parameter gradients, the
+ * encoder and the quantiser are not differentiated.  With the handle's padding off every entry point below returns ESCX_ERR_UNSUPPORTED (the
+ * chunked path needs no gradients).  DESIGN.md section 13.3 has the launch sequence and the tape layout. */
+/* Floats of the activation tape of one padded decode of batch x n_frames (dac.py:249-266): a 64-float header, the input of every convolution
+ * that follows a Snake (each DecoderBlock's ConvTranspose input, each ResidualUnit's x and h, dac.py:24-41, 94-112) as channels-last maps, and
+ * the audio.  0 when the geometry decodes to nothing or an argument is bad; ESCX_ERR_UNSUPPORTED with the padding off. */
+int64_t escx_dac_decode_tape_floats(escx_dac d, int batch, int n_frames);
+/* DAC.decode (dac.py:249-266) with the maps a backward needs kept: the launch sequence of escx_dac_decode - same kernels, operands and order, in
+ * fp32 and in bf16x3 - with those maps written to the caller's tape_dev (tape_floats = escx_dac_decode_tape_floats, 16-byte aligned) instead of
+ * the handle's reused scratch; a ResidualUnit (dac.py:35-41) writes its sum to the next map instead of back into x.  audio_dev is bitwise what
+ * escx_dac_decode returns.  The tape lives in caller memory and records (params_version, batch, n_frames): any number of tapes may be alive at
+ * once and the handle keeps no per-graph state. */
+int escx_dac_decode_tape(escx_dac d, const float* flat_params_dev, int64_t params_version, const float* z_dev, int batch, int n_frames, float* audio_dev,
+                         float* tape_dev, int64_t tape_floats, void* stream);
+/* d_z (B, D, T) = (d audio / d z)^T d_audio for the decode that wrote tape_dev (dac.py:249-266 differentiated; d_audio_dev is (B, samples)):
+ * tanh (dac.py:138), then per layer in reverse the transposed convolution of the output gradient times the derivative of the Snake in front of
+ * it (nn/layers.py:19-33), the ResidualUnit as g + conv7^T(conv1^T(g) snake'(h)) snake'(x) (dac.py:24-41), the ConvTranspose1d (dac.py:99-105) as
+ * one strided convolution.  fp32 MFMA in both precision modes, on transposed images of the packed forward weights (derived at the first backward
+ * of a handle and after every parameter change).  No atomics: bitwise deterministic, and a clip's d_z does not depend on its batch.
+ * params_version must be the version the tape was made with: another one is ESCX_ERR_STATE with a message that says so, and a buffer that is not
+ * a tape for (batch, n_frames) is ESCX_ERR_INVALID_ARG; both are found before the handle changes.  The check reads the tape's header back, so the
+ * call waits for the stream once. */
+int escx_dac_decode_backward(escx_dac d, const float* flat_params_dev, int64_t params_version, const float* tape_dev, int64_t tape_floats,
+                             const float* d_audio_dev, int batch, int n_frames, float* d_z_dev, void* stream);
 /* Test hook: the kernels' Snake (mode 0: x + sin(alpha x)^2 / (alpha + 1e-9), nn/layers.py:19-24) or tanh (mode 1) over n device values. */
 int escx_dac_test_math(const float* x_dev, const float* alpha_dev, float* out_dev, int64_t n, int mode, void* stream);
+/* Test hook of the backward of DAC.decode (dac.py:249-266): the kernels' Snake derivative (mode 0: 1 + alpha sin(2 alpha x) / (alpha + 1e-9), the
+ * derivative of nn/layers.py:19-24) or the tanh derivative from the output (mode 1: 1 - y^2 of y = x_dev, dac.py:138) over n device values. */
+int escx_dac_test_grad_math(const float* x_dev, const float* alpha_dev, float* out_dev, int64_t n, int mode, void* stream);
 
 #ifdef __cplusplus
 }
