@@ -6,7 +6,9 @@
 // (B, T, Cp) maps in a handle-owned scratch; see dac_kernels.h for the loaders and epilogues.  escx_dac_set_padding(d, 0) runs every convolution
 // without padding (CodecMixin.padding, base.py:58-80) and escx_dac_encode_chunks stages the overlapping windows of the chunked compress
 // (base.py:182-214) straight from the signal; DESIGN.md section 13.2.  escx_dac_decode_tape / escx_dac_decode_backward are the decoder with its maps
-// kept in a caller-owned tape and the latent gradient d audio / d z on it (dac_grad_kernels.h).
+// kept in a caller-owned tape and the latent gradient d audio / d z on it (dac_grad_kernels.h); escx_dac_encode_tape /
+// escx_dac_encode_backward are the same for the encoder and the quantiser, with the audio gradient of z, latents and the commitment loss
+// (DESIGN.md section 13.4).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -33,7 +35,9 @@ struct DacLayer {
     int CinP = 0, Np = 0, Kp = 0;   // operand geometry (Conv1d: Np = rup(Cout, 16), Kp = rup(K * CinP, 16); ConvT: per phase, Kp = rup(2 CinP, 16))
     size_t off_b = 0, off_g = 0, off_v = 0;
     float* W = nullptr; float* bias = nullptr;
-    float* Wt = nullptr;            // decoder layers, once a backward has run: the transposed image [NpT = rup(Cin, 16)][KpT = rup(K * cpad(Cout), 16)]
+    // once a backward has run: the transposed image [NpT = rup(Cin, 16)][KpT = rup(K * cpad(Cout), 16)]; the encoder's strided convolutions hold
+    // `stride` phase images [NpT][rup(2 * cpad(Cout), 16)] instead (dac_wt_phase_pack_kernel)
+    float* Wt = nullptr;
 };
 struct DacSnake { int C = 0; size_t off = 0; float* a = nullptr; float* inv = nullptr; };
 
@@ -66,6 +70,7 @@ struct escx_dac_s {
     // escx_dac_decode_backward: the decoder's transposed weight images, allocated (zeroed) at the first backward of the handle; wt_valid is cleared by
     // every re-pack of wbuf and set by refresh_wt, as w16_valid is.  Calls that never differentiate pay nothing.
     float* wt = nullptr; bool wt_valid = false;
+    float* wte = nullptr; bool wte_valid = false;   // escx_dac_encode_backward: the same for the encoder's layers
 };
 
 namespace {
@@ -112,7 +117,7 @@ int conv_out_len(int T, const DacLayer& l, bool padding) {
 
 int pack(escx_dac_s* d, const float* flat, long long version, hipStream_t st) {
     if (version >= 0 && version == d->packed_version && flat == d->packed_ptr && (int)d->padding == d->packed_padding) return 0;
-    d->packed_version = version; d->packed_ptr = flat; d->packed_padding = d->padding; d->w16_valid = false; d->wt_valid = false;
+    d->packed_version = version; d->packed_ptr = flat; d->packed_padding = d->padding; d->w16_valid = false; d->wt_valid = false; d->wte_valid = false;
     for (auto* L : {&d->enc, &d->dec})
         for (DacLayer& l : *L) {
             if (l.kind == 0)
@@ -430,6 +435,7 @@ extern "C" void escx_dac_destroy(escx_dac d) {
     if (d->wbuf) (void)hipFree(d->wbuf);
     if (d->w16) (void)hipFree(d->w16);
     if (d->wt) (void)hipFree(d->wt);
+    if (d->wte) (void)hipFree(d->wte);
     if (d->qoffs_dev) (void)hipFree(d->qoffs_dev);
     if (d->scratch) (void)hipFree(d->scratch);
     if (d->counts) (void)hipFree(d->counts);
@@ -779,6 +785,211 @@ extern "C" int escx_dac_decode_backward(escx_dac d, const float* flat, int64_t v
     }
     bwd_layer(st, Dl[0], nullptr, G, B, p.Ts[0], T, nullptr, nullptr, d_z, d->latent);
     return launch_ok("escx_dac_decode_backward");
+}
+
+// ---- audio gradient through the encoder and the quantiser, eval mode, padding on (dac.py:209-247, quantize.py:58-70, 173-198) ------
+namespace {
+
+inline int kp_ph(const DacLayer& l) { return rup(2 * cpad(l.Cout), 16); }                          // one phase image of a strided Conv1d
+inline bool phased(const DacLayer& l) { return l.kind == 0 && l.stride > 1; }
+size_t wt_floats(const DacLayer& l) { return pad64(phased(l) ? (size_t)l.stride * np_t(l) * kp_ph(l) : (size_t)np_t(l) * kp_t(l)); }
+
+// The activation tape of one padded encode of B x L with n quantiser stages: a header, the encoder's maps in execution order, then what the
+// quantiser's backward reads.
+//   map 7 i + 2 j, 7 i + 2 j + 1     ResidualUnit j of block i: its input x_j (j = 0: the block's input) and its 7-tap output h_j
+//   map 7 i + 6                      the input of the Snake in front of block i's strided convolution
+//   map 7 nE                         the last block's output = the input of the last Snake
+//   latents (B, n d, T), codes (B, n, T) int64, counts [B] int32
+// Every part is rounded up to 64 floats; offsets are in floats.
+struct EncTapePlan { std::vector<size_t> off; std::vector<int> Ts; size_t latents = 0, codes = 0, counts = 0, total = 0, mf = 0; int Tz = 0, n = 0; };
+
+bool enc_tape_plan(const escx_dac_s* d, int B, int L, int n_q, EncTapePlan* p) {
+    if (L < 1 || n_q < 1) return false;
+    p->Tz = enc_walk(d, true, B, L, &p->mf);
+    if (p->Tz < 1) return false;
+    p->n = std::min(n_q, d->cfg.n_codebooks);
+    size_t cur = DAC_TAPE_HEADER;
+    int C = d->cfg.encoder_dim, Tc = conv_out_len(L, d->enc[0], true);
+    for (int i = 0; i < d->cfg.n_encoder_rates; ++i) {
+        p->Ts.push_back(Tc);
+        for (int k = 0; k < 7; ++k) { p->off.push_back(cur); cur += map_floats(B, Tc, C); }
+        Tc = conv_out_len(Tc, d->enc[7 + i * 7], true); C *= 2;
+    }
+    p->Ts.push_back(Tc);
+    p->off.push_back(cur); cur += map_floats(B, Tc, C);
+    const size_t M = (size_t)B * p->Tz;
+    p->latents = cur; cur += pad64((size_t)p->n * d->cfg.codebook_dim * M);
+    p->codes = cur; cur += pad64(2 * (size_t)p->n * M);
+    p->counts = cur; cur += pad64((size_t)B);
+    p->total = cur;
+    return true;
+}
+
+const char* const ENC_GRAD_PADDING = "the encoder's gradient is implemented with the padding on (the chunked path needs none)";
+
+// bwd_strided's two taps per phase, k0 and k0 + s, are EncoderBlock's K = 2 s (dac.py:55-58): checked with the arguments, before the handle changes
+int check_phased(const escx_dac_s* d) {
+    for (const DacLayer& l : d->enc)
+        if (phased(l) && l.K != 2 * l.stride) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "a strided convolution of %d taps at stride %d: the phase backward covers K = 2 * stride", l.K, l.stride);
+    return 0;
+}
+
+int refresh_wte(escx_dac_s* d, hipStream_t st) {
+    if (d->wte_valid) return 0;
+    if (!d->wte) {
+        size_t n = 0;
+        for (const DacLayer& l : d->enc) n += wt_floats(l);
+        ESCX_HIP(hipMalloc((void**)&d->wte, n * sizeof(float)));
+        ESCX_HIP(hipMemsetAsync(d->wte, 0, n * sizeof(float), st));
+        size_t cur = 0;
+        for (DacLayer& l : d->enc) { l.Wt = d->wte + cur; cur += wt_floats(l); }
+    }
+    for (const DacLayer& l : d->enc) {
+        if (phased(l))
+            hipLaunchKernelGGL(dac_wt_phase_pack_kernel, dim3(nblk((long long)l.stride * l.Cin * 2 * l.Cout)), dim3(256), 0, st, (const float*)l.W, l.Wt, l.Cin, l.Cout,
+                               l.stride, l.pad, l.CinP, cpad(l.Cout), l.Kp, np_t(l), kp_ph(l));
+        else
+            hipLaunchKernelGGL(dac_wt_pack_kernel, dim3(nblk((long long)l.Cin * l.K * l.Cout)), dim3(256), 0, st, (const float*)l.W, l.Wt, 0, l.Cin, l.Cout, l.K, l.stride,
+                               l.pad, l.CinP, cpad(l.Cout), l.Np, l.Kp, kp_t(l));
+    }
+    d->wte_valid = true;
+    return launch_ok("dac_transpose_encoder_weights");
+}
+
+// dX of a strided Conv1d (K = 2 stride) from dY (B, Tdy, cpad(Cout)):  out (B, Tx, cpad(Cin)) = conv^T(dY) * snake'(xs), one two-tap GEMM per input
+// phase r (rows t = q s + r).  Every row of out is written by its phase.
+void bwd_strided(hipStream_t st, const DacLayer& l, const DacSnake& sn, const float* dY, int B, int Tdy, int Tx, const float* xs, float* out) {
+    const int s = l.stride, Np = np_t(l), Kp = kp_ph(l);
+    for (int r = 0; r < s && r < Tx; ++r) {
+        const int Q = (Tx - r + s - 1) / s;
+        DacConvA ld{};
+        ld.x = dY; ld.alpha = nullptr; ld.inv = nullptr; ld.Tin = Tdy; ld.Cp = cpad(l.Cout); ld.dCp = FastDiv(ld.Cp);
+        ld.Trows = Q; ld.M = B * Q; ld.dT = FastDiv(Q); ld.ntaps = 2; ld.rs = 1; ld.r0 = (r + l.pad) / s; ld.td = -1;
+        DacGradPhaseEpi ep{};
+        ep.out = out; ep.xs = xs; ep.alpha = sn.a; ep.inv = sn.inv; ep.Cp = cpad(l.Cin); ep.Trows = Q; ep.Tmap = Tx; ep.os = s; ep.o0 = r; ep.dT = ld.dT;
+        const float* W = l.Wt + (size_t)r * Np * Kp;
+        const long long tiles = (long long)((ld.M + 127) / 128) * ((Np + 95) / 96);
+        if (tiles >= 512) launch_gemm<128>(ld, W, ld.M, Np, Kp, ep, st);
+        else launch_gemm<64>(ld, W, ld.M, Np, Kp, ep, st);
+    }
+}
+
+void launch_rvq_grad(int latent, long long M, const DacQGradArgs& qa, hipStream_t st) {
+    const int J = (latent + 63) / 64;
+    const dim3 g(nblk(M, 4)), blk(256);
+    if (J <= 1) hipLaunchKernelGGL((dac_rvq_grad_kernel<1>), g, blk, 0, st, qa);
+    else if (J <= 2) hipLaunchKernelGGL((dac_rvq_grad_kernel<2>), g, blk, 0, st, qa);
+    else if (J <= 4) hipLaunchKernelGGL((dac_rvq_grad_kernel<4>), g, blk, 0, st, qa);
+    else if (J <= 8) hipLaunchKernelGGL((dac_rvq_grad_kernel<8>), g, blk, 0, st, qa);
+    else hipLaunchKernelGGL((dac_rvq_grad_kernel<16>), g, blk, 0, st, qa);
+}
+
+}  // namespace
+
+extern "C" int64_t escx_dac_encode_tape_floats(escx_dac d, int B, int L, int n_q) {
+    if (!d || B < 1 || L < 1 || n_q < 1) return 0;
+    if (!d->padding) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "%s", ENC_GRAD_PADDING);
+    EncTapePlan p;
+    return enc_tape_plan(d, B, L, n_q, &p) ? (int64_t)p.total : 0;
+}
+
+extern "C" int escx_dac_encode_tape(escx_dac d, const float* flat, int64_t version, const float* audio, int B, int L, int n_q, const int32_t* clip_n, float* z,
+                                    int64_t* codes, float* latents, float* losses, float* tape, int64_t tape_floats, void* stream) {
+    int rc = check_args(d, flat, B); if (rc) return rc;
+    if (!audio || !z || !codes || !latents || !losses || !tape || n_q < 1) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "bad argument");
+    if (!d->padding) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "%s", ENC_GRAD_PADDING);
+    if (clip_n && n_q > d->cfg.n_codebooks) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "%d code slots above the %d codebooks", n_q, d->cfg.n_codebooks);
+    EncTapePlan p;
+    if (!enc_tape_plan(d, B, L, n_q, &p)) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "%d samples give no latent frame (the hop is %d)", L, d->hop);
+    const int n = p.n;
+    if (clip_n && (rc = check_clip_counts(d, clip_n, B, n))) return rc;
+    if ((unsigned long long)p.mf >= (1ull << 32)) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "batch of %d x %d samples: a feature map above 2^32 elements", B, L);
+    if (tape_floats != (long long)p.total)
+        ESCX_FAIL(ESCX_ERR_INVALID_ARG, "tape of %lld floats: an encode of %d x %d samples with %d codebooks needs %lld (escx_dac_encode_tape_floats)",
+                  (long long)tape_floats, B, L, n, (long long)p.total);
+    hipStream_t st = (hipStream_t)stream;
+    const size_t mf = p.mf, M = (size_t)B * p.Tz;
+    const size_t lossf = pad64((size_t)n * M) + pad64((size_t)n * B);
+    if ((rc = ensure_scratch(d, (4 * mf + lossf) * sizeof(float)))) return rc;
+    const int* cdev; if ((rc = upload_counts(d, clip_n, B, &cdev, st))) return rc;
+    if ((rc = pack(d, flat, (long long)version, st)) || (rc = refresh_w16(d, st))) return rc;
+    // the staged input, the encoder's output map and the Snaked copies stay in the handle's scratch: no backward reads them
+    float* zmap = d->scratch + mf; float* in = d->scratch + 2 * mf; float* lossb = d->scratch + 4 * mf;
+    const Run run{d->snake_maps, d->scratch + 3 * mf, st, d->wbuf, d->precision == ESCX_PRECISION_BF16X3 ? d->w16 : nullptr, d->conv_floats, true};
+    auto Mp = [&](int i) { return tape + p.off[i]; };
+    hipLaunchKernelGGL(dac_enc_tape_header_kernel, dim3(nblk(B)), dim3(256), 0, st, (long long*)tape, (long long)version, (long long)B, (long long)L, (long long)p.total,
+                       (long long)n, cdev, (int*)(tape + p.counts));
+    hipLaunchKernelGGL(dac_wave_in_kernel, dim3(nblk((long long)B * L)), dim3(256), 0, st, audio, in, (long long)B * L);
+    const DacLayer* E = d->enc.data(); const DacSnake* SN = d->enc_sn.data();
+    const int nE = d->cfg.n_encoder_rates;
+    run_layer(run, ESCX_DAC_SNAKE_LAST, E[0], nullptr, in, B, L, Mp(0), p.Ts[0], nullptr, 0);
+    for (int i = 0; i < nE; ++i) {
+        const DacLayer* Lb = E + 1 + i * 7; const DacSnake* Sb = SN + i * 7;
+        const int Tc = p.Ts[i];
+        for (int j = 0; j < 3; ++j) {                       // run_res with padding, x and h kept: the sum goes to the next map instead of back into x
+            float* x = Mp(7 * i + 2 * j); float* h = Mp(7 * i + 2 * j + 1);
+            run_layer(run, ESCX_DAC_SNAKE_RES7, Lb[2 * j], &Sb[2 * j], x, B, Tc, h, Tc, nullptr, 0);
+            run_layer(run, ESCX_DAC_SNAKE_RES1, Lb[2 * j + 1], &Sb[2 * j + 1], h, B, Tc, Mp(7 * i + 2 * j + 2), Tc, x, 0);
+        }
+        run_layer(run, ESCX_DAC_SNAKE_DOWN, Lb[6], Sb + 6, Mp(7 * i + 6), B, Tc, Mp(7 * i + 7), p.Ts[i + 1], nullptr, 0);
+    }
+    run_layer(run, ESCX_DAC_SNAKE_LAST, E[d->enc.size() - 1], SN + d->enc_sn.size() - 1, Mp(7 * nE), B, p.Ts[nE], zmap, p.Tz, nullptr, 0);
+    DacQArgs qa{};
+    qa.t = d->qt; qa.zmap = zmap; qa.z = z; qa.codes = (long long*)codes; qa.latents = latents; qa.loss = lossb;
+    qa.M = (int)M; qa.T = p.Tz; qa.D = d->latent; qa.Dp = cpad(d->latent); qa.d = d->cfg.codebook_dim; qa.K = d->cfg.codebook_size; qa.n = n;
+    if (clip_n) { qa.clip_n = cdev; launch_rvq<false, DAC_Q_CLIPS>(d->latent, (long long)M, qa, st); }
+    else launch_rvq<false, DAC_Q_PLAIN>(d->latent, (long long)M, qa, st);
+    hipLaunchKernelGGL(dac_loss_kernel, dim3(1), dim3(256), 0, st, lossb, lossb + pad64((size_t)n * M), losses, B, p.Tz, n, d->cfg.codebook_dim);
+    ESCX_HIP(hipMemcpyAsync(tape + p.latents, latents, (size_t)n * d->cfg.codebook_dim * M * sizeof(float), hipMemcpyDeviceToDevice, st));
+    ESCX_HIP(hipMemcpyAsync(tape + p.codes, codes, (size_t)n * M * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+    return launch_ok("escx_dac_encode_tape");
+}
+
+extern "C" int escx_dac_encode_backward(escx_dac d, const float* flat, int64_t version, const float* tape, int64_t tape_floats, const float* d_z,
+                                        const float* d_latents, const float* d_commitment, int B, int L, float* d_audio, void* stream) {
+    int rc = check_args(d, flat, B); if (rc) return rc;
+    if (!tape || !d_audio || L < 1 || tape_floats < DAC_TAPE_HEADER) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "bad argument");
+    if (!d->padding) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "%s", ENC_GRAD_PADDING);
+    if ((rc = check_phased(d))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    // The tape says what it was made with, the stage count included; the handle keeps nothing per graph.  Checked before anything of the handle changes.
+    long long hdr[6] = {0, 0, 0, 0, 0, 0};
+    ESCX_HIP(hipMemcpyAsync(hdr, tape, sizeof(hdr), hipMemcpyDeviceToHost, st));
+    ESCX_HIP(hipStreamSynchronize(st));
+    EncTapePlan p;
+    if (hdr[0] != DAC_ENC_TAPE_MAGIC || hdr[2] != B || hdr[3] != L || hdr[4] != (long long)tape_floats || hdr[5] < 1 || hdr[5] > d->cfg.n_codebooks ||
+        !enc_tape_plan(d, B, L, (int)hdr[5], &p) || (long long)p.total != (long long)tape_floats)
+        ESCX_FAIL(ESCX_ERR_INVALID_ARG, "the buffer of %lld floats is not a tape that escx_dac_encode_tape made for %d x %d samples", (long long)tape_floats, B, L);
+    if ((unsigned long long)p.mf >= (1ull << 32)) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "batch of %d x %d samples: a feature map above 2^32 elements", B, L);
+    if (hdr[1] != (long long)version)
+        ESCX_FAIL(ESCX_ERR_STATE, "the tape was made with parameter version %lld and the backward is called with %lld: the parameters changed between forward and backward",
+                  hdr[1], (long long)version);
+    const size_t mf = p.mf;
+    if ((rc = ensure_scratch(d, 4 * mf * sizeof(float)))) return rc;
+    if ((rc = pack(d, flat, (long long)version, st)) || (rc = refresh_wte(d, st))) return rc;
+    float* G = d->scratch; float* G2 = G + mf; float* A = G2 + mf;
+    auto Mp = [&](int i) { return tape + p.off[i]; };
+    const DacLayer* E = d->enc.data(); const DacSnake* SN = d->enc_sn.data();
+    const int nE = d->cfg.n_encoder_rates;
+    DacQGradArgs qa{};
+    qa.win = d->qt.win; qa.wout = d->qt.wout; qa.cbraw = d->qt.cbraw; qa.g_z = d_z; qa.g_lat = d_latents; qa.g_cm = d_commitment;
+    qa.latents = tape + p.latents; qa.codes = (const long long*)(tape + p.codes); qa.clip_n = (const int*)(tape + p.counts); qa.out = A;
+    qa.M = B * p.Tz; qa.T = p.Tz; qa.D = d->latent; qa.Dp = cpad(d->latent); qa.d = d->cfg.codebook_dim; qa.K = d->cfg.codebook_size; qa.n = p.n; qa.B = B;
+    launch_rvq_grad(d->latent, (long long)B * p.Tz, qa, st);
+    bwd_layer(st, E[d->enc.size() - 1], SN + d->enc_sn.size() - 1, A, B, p.Tz, p.Ts[nE], Mp(7 * nE), nullptr, G);
+    for (int i = nE - 1; i >= 0; --i) {
+        const DacLayer* Lb = E + 1 + i * 7; const DacSnake* Sb = SN + i * 7;
+        const int Tc = p.Ts[i];
+        if (phased(Lb[6])) bwd_strided(st, Lb[6], Sb[6], G, B, p.Ts[i + 1], Tc, Mp(7 * i + 6), G2);
+        else bwd_layer(st, Lb[6], &Sb[6], G, B, p.Ts[i + 1], Tc, Mp(7 * i + 6), nullptr, G2);          // a rate of 1: a plain two-tap convolution
+        std::swap(G, G2);
+        for (int j = 2; j >= 0; --j) {                      // g_x = g + conv7^T(conv1^T(g) * snake'(h)) * snake'(x), in place in G
+            bwd_layer(st, Lb[2 * j + 1], &Sb[2 * j + 1], G, B, Tc, Tc, Mp(7 * i + 2 * j + 1), nullptr, A);
+            bwd_layer(st, Lb[2 * j], &Sb[2 * j], A, B, Tc, Tc, Mp(7 * i + 2 * j), G, G);
+        }
+    }
+    bwd_layer(st, E[0], nullptr, G, B, p.Ts[0], L, nullptr, nullptr, d_audio, 1);
+    return launch_ok("escx_dac_encode_backward");
 }
 
 extern "C" int escx_dac_test_grad_math(const float* x, const float* alpha, float* out, int64_t n, int mode, void* stream) {

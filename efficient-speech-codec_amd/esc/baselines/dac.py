@@ -3,8 +3,9 @@
 Same constructor keywords, same state_dict keys and shapes (`*.weight_g`, `*.weight_v`, `*.bias`, `*.alpha`,
 `quantizer.quantizers.{i}.codebook.weight`: reference checkpoints load with `load_state_dict(strict=True)`), same eval-mode
 `encode` / `decode` / `forward` / `quantizer.from_codes`.  Every convolution, the weight normalisation and the residual quantiser run in
-libescx (csrc/dac.hip); there is no PyTorch/CPU implementation here.  Inference only: training mode raises NotImplementedError.  One
-gradient exists, for a frozen decoder inside a larger autograd graph: `decode(z)` is differentiable in `z` (eval mode, padding on; `_DecodeGrad`).
+libescx (csrc/dac.hip); there is no PyTorch/CPU implementation here.  Inference only: training mode raises NotImplementedError.  The
+frozen codec can sit inside a larger autograd graph (eval mode, padding on, input gradients only): `decode(z)` is differentiable in `z`
+(`_DecodeGrad`), `encode(x)` in `x` through the encoder and the straight-through quantiser (`_EncodeGrad`), and `forward(x)` chains the two.
 
 `DACFile`, `DAC.padding`, `DAC.compress` and `DAC.decompress` are CodecMixin's (reference baselines/descript/dac/model/base.py:15-294): files of any
 length in overlapping windows on padding-free convolutions, all windows of a file as one batch.
@@ -461,14 +462,23 @@ class DAC(nn.Module):
                                                  ctypes.c_void_p(losses.data_ptr()), ctypes.c_void_p(zs.data_ptr()), stream))
         return zs, codes, latents
 
-    @torch.no_grad()
     def encode(self, audio_data: torch.Tensor, n_quantizers: Union[int, Sequence[int], torch.Tensor] = None):
         """dac.py:209-247: (z (B, D, T), codes (B, n, T) int64, latents (B, n d, T), commitment_loss, codebook_loss).  n_quantizers may also be
         one count per clip (a sequence or 1-D integer tensor of B entries, the per-item mask of quantize.py:181-190): n = max(counts), codes hold
-        -1 and latents 0 past a clip's count, the losses are the reference's masked means."""
+        -1 and latents 0 past a clip's count, the losses are the reference's masked means.  When gradients are enabled and audio_data requires
+        one, z, latents and commitment_loss carry the audio gradient of the reference's eval-mode autograd (straight-through quantiser,
+        quantize.py:58-70; eval mode, padding on; `_EncodeGrad` below): the same bits, computed by escx_dac_encode_tape, which keeps the
+        encoder's maps in a tape on the graph.  The module's parameters get no gradient whatever their requires_grad."""
+        if self.training:
+            raise NotImplementedError("esc.baselines.DAC is inference only: call .eval() (DAC training is not implemented)")
+        if torch.is_grad_enabled() and isinstance(audio_data, torch.Tensor) and audio_data.requires_grad:
+            counts = self._clip_counts(n_quantizers, audio_data.shape[0]) if self._is_per_clip(n_quantizers) else None
+            return _EncodeGrad.apply(audio_data, self, self._n_quantizers(n_quantizers) if counts is None else max(counts), counts)
+        with torch.no_grad():
+            return self._encode(audio_data, n_quantizers)
+
+    def _encode(self, audio_data: torch.Tensor, n_quantizers):
         if self._is_per_clip(n_quantizers):
-            if self.training:
-                raise NotImplementedError("esc.baselines.DAC is inference only: call .eval() (DAC training is not implemented)")
             return self._encode_counts(audio_data, self._clip_counts(n_quantizers, audio_data.shape[0]))
         lib, hd, flat, dev, stream = self._ctx(audio_data, "audio_data")
         n = self._n_quantizers(n_quantizers)
@@ -782,3 +792,58 @@ class _DecodeGrad(torch.autograd.Function):
             _native.check(lib.escx_dac_decode_backward(hd, ctypes.c_void_p(flat.data_ptr()), ctx.version, ctypes.c_void_p(tape.data_ptr()), tape.numel(),
                                                        ctypes.c_void_p(g.data_ptr()), B, T, ctypes.c_void_p(d_z.data_ptr()), stream))
         return d_z.to(ctx.z_dtype), None
+
+
+class _EncodeGrad(torch.autograd.Function):
+    """DAC.encode with the audio gradient (include/escx.h escx_dac_encode_tape / escx_dac_encode_backward): the reference's eval-mode autograd
+    through the encoder and the quantiser's straight-through estimator (quantize.py:58-70, 173-198).  z, latents and the commitment loss are
+    differentiable; the codes are integers and the codebook loss detaches z_e.  forward is the encode's own launch sequence with the maps, latents,
+    codes and stage counts the backward needs kept in a tape, a plain tensor saved on the graph; backward is first order only and runs on the
+    fp32 MFMA in both precision modes.  counts: one stage count per clip, or None for n stages everywhere."""
+
+    @staticmethod
+    def forward(ctx, audio_data, model, n, counts):
+        lib, hd, flat, dev, stream = model._ctx(audio_data, "audio_data")
+        if not model._padding:
+            raise NotImplementedError("the audio gradient of DAC.encode is implemented with padding on (the chunked path needs no gradients)")
+        B, L, T = model._audio_shape(audio_data)
+        x = audio_data.detach().to(torch.float32).contiguous()
+        floats = int(lib.escx_dac_encode_tape_floats(hd, B, L, n))
+        if floats < 0:
+            _native.check(floats)
+        if floats < 1:
+            raise RuntimeError(f"libescx gives no tape for an encode of {B} x {L} samples")
+        tape = torch.empty(floats, dtype=torch.float32, device=dev)
+        z = torch.empty(B, model.latent_dim, T, device=dev)
+        codes = torch.empty(B, n, T, dtype=torch.int64, device=dev)
+        latents = torch.empty(B, n * model.codebook_dim, T, device=dev)
+        losses = torch.empty(2, device=dev)
+        version = model._version()
+        cn = (ctypes.c_int32 * B)(*counts) if counts is not None else None
+        with torch.cuda.device(dev):
+            _native.check(lib.escx_dac_encode_tape(hd, ctypes.c_void_p(flat.data_ptr()), version, ctypes.c_void_p(x.data_ptr()), B, L, n, cn,
+                                                   ctypes.c_void_p(z.data_ptr()), ctypes.c_void_p(codes.data_ptr()), ctypes.c_void_p(latents.data_ptr()),
+                                                   ctypes.c_void_p(losses.data_ptr()), ctypes.c_void_p(tape.data_ptr()), floats, stream))
+        cm, cb = losses[0].clone(), losses[1].clone()
+        ctx.save_for_backward(tape)
+        ctx.model, ctx.version, ctx.dims, ctx.x_dtype = model, version, (B, L), audio_data.dtype
+        ctx.mark_non_differentiable(codes, cb)
+        ctx.set_materialize_grads(False)                     # an output the loss does not use hands None to backward: a NULL cotangent, not a map of zeros
+        return z, codes, latents, cm, cb
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_z, _d_codes, d_latents, d_cm, _d_cb):
+        model, (B, L) = ctx.model, ctx.dims
+        tape, = ctx.saved_tensors
+        if model._version() != ctx.version:
+            raise RuntimeError("a parameter of the DAC module was changed in place between encode and its backward: the tape was made with the "
+                               "earlier weights (encode again after changing parameters)")
+        lib, hd, flat, dev, stream = model._ctx(tape, "the tape")
+        gs = [None if g is None else g.to(device=dev, dtype=torch.float32).contiguous() for g in (d_z, d_latents, d_cm)]
+        ptr = [None if g is None else ctypes.c_void_p(g.data_ptr()) for g in gs]
+        d_audio = torch.empty(B, 1, L, device=dev)
+        with torch.cuda.device(dev):
+            _native.check(lib.escx_dac_encode_backward(hd, ctypes.c_void_p(flat.data_ptr()), ctx.version, ctypes.c_void_p(tape.data_ptr()), tape.numel(),
+                                                       ptr[0], ptr[1], ptr[2], B, L, ctypes.c_void_p(d_audio.data_ptr()), stream))
+        return d_audio.to(ctx.x_dtype), None, None, None

@@ -493,6 +493,38 @@ int escx_dac_decode_tape(escx_dac d, const float* flat_params_dev, int64_t param
  * call waits for the stream once. */
 int escx_dac_decode_backward(escx_dac d, const float* flat_params_dev, int64_t params_version, const float* tape_dev, int64_t tape_floats,
                              const float* d_audio_dev, int batch, int n_frames, float* d_z_dev, void* stream);
+/* ---- Audio gradient through the encoder and the quantiser (eval mode, padding on) ---------------------------------------------------------------
+ * d (z, latents, commitment_loss) / d audio of DAC.encode (baselines/descript/dac/model/dac.py:209-247) for a frozen codec in the middle of a larger
+ * autograd graph: Encoder.forward (dac.py:64-91) over EncoderBlock (dac.py:44-61: three ResidualUnits, Snake1d, strided WNConv1d) and
+ * ResidualVectorQuantize.forward in eval mode (nn/quantize.py:173-198) with VectorQuantize's straight-through estimator and detached codebook
+ * vector (nn/quantize.py:58-70).  The codebook loss detaches z_e and the codes are integers: neither has an audio gradient.  Parameter gradients,
+ * training mode and quantiser dropout are not differentiated.  With the handle's padding off every entry point below returns
+ * ESCX_ERR_UNSUPPORTED.  DESIGN.md section 13.4 has the launch sequence and the tape layout. */
+/* Floats of the activation tape of one padded encode of batch x n_samples with min(n_quantizers, n_codebooks) stages (dac.py:209-247): a 64-float
+ * header, the input of every convolution that follows a Snake (each ResidualUnit's x and h, dac.py:24-41; the input of each EncoderBlock's last
+ * Snake, dac.py:55-58; the input of the encoder's last Snake, dac.py:82-85) as channels-last maps, then latents, codes and the per-clip stage counts
+ * (quantize.py:173-198).  0 when the clip gives no frame or an argument is bad; ESCX_ERR_UNSUPPORTED with the padding off. */
+int64_t escx_dac_encode_tape_floats(escx_dac d, int batch, int n_samples, int n_quantizers);
+/* DAC.encode (dac.py:209-247) with what a backward needs kept: the launch sequence of escx_dac_encode_ex - same kernels, operands and order, in fp32
+ * and in bf16x3 - with the encoder's maps written to the caller's tape_dev (tape_floats = escx_dac_encode_tape_floats, 16-byte aligned) instead of
+ * the handle's reused scratch, and latents, codes and stage counts copied behind them.  clip_n (HOST array or NULL) is escx_dac_encode_ex's; there
+ * are no snapshots.  z, codes, latents and losses are bitwise those of escx_dac_encode / escx_dac_encode_ex.  The tape lives in caller memory and
+ * records (params_version, batch, n_samples, stages): any number of tapes may be alive at once and the handle keeps no per-graph state. */
+int escx_dac_encode_tape(escx_dac d, const float* flat_params_dev, int64_t params_version, const float* audio_dev, int batch, int n_samples, int n_quantizers,
+                         const int32_t* clip_n, float* z_dev, int64_t* codes_dev, float* latents_dev, float* losses_dev, float* tape_dev, int64_t tape_floats,
+                         void* stream);
+/* d_audio (B, n_samples) = the cotangents d_z (B, D, T), d_latents (B, n * codebook_dim, T) and the DEVICE scalar d_commitment pulled back through the
+ * encode that wrote tape_dev; each may be NULL (zero).  The quantiser (quantize.py:173-198 differentiated, one launch): per latent row and stage in
+ * reverse, u = d_z - g_r, e = W_out^T u + d_latents_i + d_commitment * 2 (z_e_i - codebook_i[code]) / (batch * codebook_dim * T) (quantize.py:61, 64-68,
+ * 189), g_r += W_in^T e (quantize.py:58, 186); a clip with its own stage count runs that many stages.  Then the encoder (dac.py:64-91 differentiated)
+ * in reverse: per layer the transposed convolution of the output gradient times the derivative of the Snake in front of it (nn/layers.py:19-33), the
+ * ResidualUnit as g + conv7^T(conv1^T(g) snake'(h)) snake'(x) (dac.py:24-41), the strided convolution (dac.py:55-58) as one two-tap GEMM per input
+ * phase, every input row written.  fp32 MFMA in both precision modes; no atomics: bitwise deterministic, and without d_commitment a clip's d_audio
+ * does not depend on its batch.  params_version must be the tape's: another one is ESCX_ERR_STATE with a message naming both; a buffer that is not
+ * an encode tape for (batch, n_samples), a decode tape included, or has the wrong size is ESCX_ERR_INVALID_ARG; both are found before the handle
+ * changes.  The check reads the tape's header back, so the call waits for the stream once. */
+int escx_dac_encode_backward(escx_dac d, const float* flat_params_dev, int64_t params_version, const float* tape_dev, int64_t tape_floats, const float* d_z_dev,
+                             const float* d_latents_dev, const float* d_commitment_dev, int batch, int n_samples, float* d_audio_dev, void* stream);
 /* Test hook: the kernels' Snake (mode 0: x + sin(alpha x)^2 / (alpha + 1e-9), nn/layers.py:19-24) or tanh (mode 1) over n device values. */
 int escx_dac_test_math(const float* x_dev, const float* alpha_dev, float* out_dev, int64_t n, int mode, void* stream);
 /* Test hook of the backward of DAC.decode (dac.py:249-266): the kernels' Snake derivative (mode 0: 1 + alpha sin(2 alpha x) / (alpha + 1e-9), the
