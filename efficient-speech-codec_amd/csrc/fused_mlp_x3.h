@@ -12,6 +12,18 @@
 // Structure = fused_mlp.h: a wave owns 16 token rows end to end in registers; hidden units are walked 32 at a time (two fc1 accumulator tiles ARE
 // the 8-deep k-slots of one fc2 step); the split weight fragments ([pair][fragment][lane][8 bf16], built on the device by mlp_x3_pack_kernel from the
 // fp32 weights) stream through a double-buffered LDS ring shared by the NW waves; GELU and the operand split run on the VALU beside the matrix cores.
+//
+// Two-term mode (NT = 2), where the power-of-two factors of the range rule (split_terms.h) are applied.  Matrix and vector issue time ADD on this chip, so a multiply that only
+// carries a power of two around costs what any other instruction costs; a power of two commutes with fp32 rounding (no overflow, no subnormal: the range rule's own condition),
+// so each factor sits where it costs least and the results keep every bit:
+//   * fc1 bias: b1 2^k1 sx is stored in the image (mlp_x3_prescale_kernel) and loaded straight into the fc1 accumulators - was 8 multiplies per lane and hidden pair;
+//   * LayerNorm: gamma sx and beta sx are stored in the image; (x - mean) rstd (gamma sx) + beta sx rounds like ((x - mean) rstd gamma + beta) sx - was 8 KS per row tile;
+//   * GELU input: h 2^-k1 / sx STAYS one multiply per value - it is the variable of gelu_bf's degree-8 polynomial, whose nine constants would have to carry the factor's
+//     powers up to the 8th (2^-200 for typical weights: not representable), and its exponent step and final fma need the unscaled value;
+//   * GELU output: the factor sh is the one multiply of the split itself (split_hidden_x2).  Folding it into GELU's last fma (gelu(x) sh = fma(-|x| sh, 2^Q8, max(x sh, 0)))
+//     is NOT bit-identical: for x below about -13 the unscaled product is an fp32 subnormal and the scaled one is not - measured, the output hash moves;
+//   * fc2 accumulators: acc 2^-k2 / sh + b2 is already one fma under hipcc's contraction; res + (acc s + b2) has no exact two-instruction rewrite.  Unchanged.
+// Measured and rejected with them: GELU's last fma and the split's residual pinned to single instructions by inline assembly.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "fused_mlp.h"
@@ -51,6 +63,26 @@ __device__ __forceinline__ bf16x8 pack8h(const _Float16 (&s)[8]) { half8 r; for 
 template <int NT>
 __device__ __forceinline__ void split_rows(const float (&v)[8], bf16x8 (&out)[NT]) { split_terms<NT>(v, out); }
 
+// NT = 2, the hidden tile of the main loop: eight GELU outputs times the power-of-two scale of the range rule -> two fp16 term fragments, the values of
+// split_terms<2>(v, out, scale).  Written on PAIRS: with the scalar loop of split_terms hipcc's SLP pass mixes scalar and packed forms here once the bias multiplies are gone
+// (v_fma_mixlo_f16 for some high terms, the halves re-packed with v_alignbit / v_pack: 8 instructions per pair of hidden tiles more than the multiplies it saved); on pairs it keeps
+// one v_pk_mul_f32, two v_cvt_pk_f16_f32, two v_cvt_f32_f16 and one v_pk_add_f32 per two values, as before.
+__device__ __forceinline__ void split_hidden_x2(const float (&v)[8], float scale, bf16x8 (&out)[2]) {
+#pragma clang fp contract(off)
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    typedef _Float16 half2v __attribute__((ext_vector_type(2)));
+    half8 h0, h1;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const f32x2 a = f32x2{v[2 * q], v[2 * q + 1]} * scale;
+        const half2v hi = __builtin_convertvector(a, half2v);
+        const half2v lo = __builtin_convertvector(a - __builtin_convertvector(hi, f32x2), half2v);
+        h0[2 * q] = hi[0]; h0[2 * q + 1] = hi[1]; h1[2 * q] = lo[0]; h1[2 * q + 1] = lo[1];
+    }
+    out[0] = __builtin_bit_cast(bf16x8, h0); out[1] = __builtin_bit_cast(bf16x8, h1);
+}
+template <int NT> __device__ __forceinline__ void split_hidden_x2(const float (&)[8], float, bf16x8 (&)[NT]) {}     // never called: keeps the NT = 3 instantiations well-formed
+
 constexpr int mlp_x3_ks(int CP) { return (CP + 31) / 32; }
 constexpr int mlp_x3_frags(int CP, int NT = 3) { return 2 * NT * mlp_x3_ks(CP) + NT * (CP / 16); }       // 1 KiB fragments per pair of hidden tiles: fc1 (KS steps x 2 tiles x NT terms), fc2 (KK tiles x NT terms)
 // LDS staging.  Narrow layers (<= 36 fragments per pair): ONE stage per pair.  Wide layers: fc1 in stages of up to 6 K-steps (36 KiB), fc2 in stages of up to 6 pairs of
@@ -70,7 +102,8 @@ constexpr int mlp_x3_stage_frags(int CP, int NT = 3) {
 // (the k-slot <-> hidden unit map the kernel's two fc1 accumulator tiles dictate).  One thread per (pair, fragment triple, lane).
 // NT = 2: the image ends with three 16-byte slots - [0] bits of max |w1|, max |w2|, max_row ||w1_row||^2 (absmax_bits_kernel / rownorm2_max_bits_kernel, before this kernel),
 // [1] {2^-k1 / sx, 2^-k2 / sh, 2^k1 sx, 2^k2 sh} and [2] {sx, sh} written here: sx, sh = the power-of-two scales of the LayerNorm output and of the GELU output (split_terms.h
-// range rule; bounds from ln2's gamma / beta, the fc1 row norms and b1).
+// range rule; bounds from ln2's gamma / beta, the fc1 row norms and b1).  Behind the slots, written by mlp_x3_prescale_kernel from slot [1] / [2]'s own factors: b1 2^k1 sx [HP],
+// gamma sx [Cp], beta sx [Cp] - what the main kernel loads instead of b1 / gamma / beta (mlp_x3_bytes counts them).
 __global__ __launch_bounds__(256) void mlp_x3_pack_kernel(const float* __restrict__ w1, const float* __restrict__ w2, bf16x8* __restrict__ out, int Cp, int HP, int KS, int KK, int NT,
                                                           const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ b1, int C) {
     const int CH = 2 * NT * KS + NT * KK, triples = 2 * KS + KK;
@@ -108,19 +141,26 @@ __global__ __launch_bounds__(256) void mlp_x3_pack_kernel(const float* __restric
         split2_f16(v, t3 < 2 * KS ? sc1 : sc2, h0, h1);
         dst[0] = pack8h(h0); dst[64] = pack8h(h1);
         if (idx == 0) {
-            float sx = 1.f, sh = 1.f;             // gamma == nullptr: no activation scales (the round-5 form; profiles/r6_range_rule_off.txt)
-            if (gamma) {
-                float gb = 0.f, mb1 = 0.f;
-                const float bx = ln_out_bound(gamma, beta, Cp, C, &gb);
-                for (int i = 0; i < HP; ++i) mb1 = fmaxf(mb1, fabsf(b1[i]));
-                const float bh = sqrtf(__uint_as_float(mx[2])) * sqrtf((float)C) * gb + mb1;       // |gelu(h)| <= |h| <= ||w1_row|| ||xn|| + |b1|
-                sx = act_pow2_scale(bx); sh = act_pow2_scale(bh);
-            }
+            float gb = 0.f, mb1 = 0.f;
+            const float bx = ln_out_bound(gamma, beta, Cp, C, &gb);
+            for (int i = 0; i < HP; ++i) mb1 = fmaxf(mb1, fabsf(b1[i]));
+            const float bh = sqrtf(__uint_as_float(mx[2])) * sqrtf((float)C) * gb + mb1;           // |gelu(h)| <= |h| <= ||w1_row|| ||xn|| + |b1|
+            const float sx = act_pow2_scale(bx), sh = act_pow2_scale(bh);
             float* f = reinterpret_cast<float*>(tail + 1);
             f[0] = (1.0f / sc1) * (1.0f / sx); f[1] = (1.0f / sc2) * (1.0f / sh); f[2] = sc1 * sx; f[3] = sc2 * sh;
             f[4] = sx; f[5] = sh; f[6] = 0.f; f[7] = 0.f;
         }
     }
+}
+
+// NT = 2, after mlp_x3_pack_kernel: the image's pre-scaled vectors behind the three slots, from the SAME factors the kernel reads in slots [1] / [2] -
+// b1 2^k1 sx [HP], gamma sx [Cp], beta sx [Cp].  The factors are powers of two, so each product is the exact value the main kernel used to form per token.
+__global__ __launch_bounds__(256) void mlp_x3_prescale_kernel(bf16x8* __restrict__ tail, const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ b1, int Cp, int HP) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= HP + 2 * Cp) return;
+    const float* f = reinterpret_cast<const float*>(tail + 1);
+    float* o = reinterpret_cast<float*>(tail + 3);
+    o[i] = i < HP ? b1[i] * f[2] : (i < HP + Cp ? gamma[i - HP] : beta[i - HP - Cp]) * f[4];
 }
 
 // PatchSplit weights for the SPLIT epilogue of mlp_x3_kernel, from the fp32 fragment stream (Layer::sub_wf, [NT][KK][64] float4): fragment (nt, s, i) -> lane (n, g) holds
@@ -207,12 +247,14 @@ __global__ __launch_bounds__(64 * NW, (mlp_x3_min_waves<CP>())) void mlp_x3_kern
             __builtin_amdgcn_global_load_lds((const void*)(src + c * 64), (__attribute__((address_space(3))) void*)(dst + c * 64), 16, 0, 0);
     };
     issue(0);
-    f32x4 x2sc = {1.f, 1.f, 1.f, 1.f};          // NT = 2: {2^-k1, 2^-k2, 2^k1, 2^k2} of this block's weight image
-    float x2sx = 1.f, x2sh = 1.f;               // NT = 2: power-of-two scales of the LayerNorm output / the GELU output (range rule, split_terms.h); folded into x2sc
-    if constexpr (NT == 2) {
+    f32x4 x2sc = {1.f, 1.f, 1.f, 1.f};          // NT = 2: {2^-k1 / sx, 2^-k2 / sh, 2^k1 sx, 2^k2 sh} of this block's weight image
+    float x2sh = 1.f;                           // NT = 2: power-of-two scale of the GELU output (range rule, split_terms.h)
+    const float* fc1_b = a.b1; const float* ln_g = a.gamma; const float* ln_b = a.beta;
+    if constexpr (NT == 2) {                    // the image's pre-scaled copies: b1 2^k1 sx, gamma sx, beta sx (mlp_x3_prescale_kernel)
         x2sc = *reinterpret_cast<const f32x4*>(wsrc + (size_t)n_pairs_all * CH * 64 + 1);
-        const f32x4 act = *reinterpret_cast<const f32x4*>(wsrc + (size_t)n_pairs_all * CH * 64 + 2);
-        x2sx = act[0]; x2sh = act[1];
+        x2sh = (*reinterpret_cast<const f32x4*>(wsrc + (size_t)n_pairs_all * CH * 64 + 2))[1];
+        fc1_b = reinterpret_cast<const float*>(wsrc + (size_t)n_pairs_all * CH * 64 + 3);
+        ln_g = fc1_b + 16 * a.HT; ln_b = ln_g + CP;
     }
 
     // ---- rows -> k-slot layout of the 32-deep MFMA (lane (row l15, slot group lg) holds channels 32 s + 8 lg .. + 7), LayerNorm in registers, split ----
@@ -245,16 +287,12 @@ __global__ __launch_bounds__(64 * NW, (mlp_x3_min_waves<CP>())) void mlp_x3_kern
         for (int s = 0; s < KS; ++s) {
             const int c0 = 32 * s + 8 * lg;
             f32x4 g0 = zero4(), g1 = zero4(), b0 = zero4(), b1 = zero4();
-            if (c0 < CP) { g0 = ld4(a.gamma + c0); g1 = ld4(a.gamma + c0 + 4); b0 = ld4(a.beta + c0); b1 = ld4(a.beta + c0 + 4); }
+            if (c0 < CP) { g0 = ld4(ln_g + c0); g1 = ld4(ln_g + c0 + 4); b0 = ld4(ln_b + c0); b1 = ld4(ln_b + c0 + 4); }
             float xn[8];
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                xn[e] = (xv[s][e] - mean) * rstd * g0[e] + b0[e];                  // gamma = beta = 0 in the pads -> 0
+                xn[e] = (xv[s][e] - mean) * rstd * g0[e] + b0[e];                  // gamma = beta = 0 in the pads -> 0; NT = 2: gamma sx, beta sx -> xn sx, same rounding
                 xn[4 + e] = (xv[s][4 + e] - mean) * rstd * g1[e] + b1[e];
-            }
-            if constexpr (NT == 2) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) xn[e] *= x2sx;
             }
             bf16x8 t[NT];
             split_rows<NT>(xn, t);
@@ -279,11 +317,9 @@ __global__ __launch_bounds__(64 * NW, (mlp_x3_min_waves<CP>())) void mlp_x3_kern
         return wb;
     };
     for (int p = p0; p < p1; ++p) {
-        const f32x4 bias0 = ld4(a.b1 + 32 * p + 4 * lg), bias1 = ld4(a.b1 + 32 * p + 16 + 4 * lg);
         const bf16x8* wb = nullptr;
-        // ---- fc1: two hidden tiles (independent accumulator chains), the bias rides in the accumulator ----
-        f32x4 h0 = bias0, h1 = bias1;
-        if constexpr (NT == 2) { h0 *= x2sc[2]; h1 *= x2sc[2]; }               // the sums of the scaled weights carry 2^k1: so does the bias (exact)
+        // ---- fc1: two hidden tiles (independent accumulator chains), the bias rides in the accumulator (NT = 2: the image's bias, which already carries 2^k1 sx) ----
+        f32x4 h0 = ld4(fc1_b + 32 * p + 4 * lg), h1 = ld4(fc1_b + 32 * p + 16 + 4 * lg);
 #pragma unroll
         for (int s = 0; s < KS; ++s) {
             if (s % G1 == 0) wb = next_stage();
@@ -307,15 +343,17 @@ __global__ __launch_bounds__(64 * NW, (mlp_x3_min_waves<CP>())) void mlp_x3_kern
 #pragma unroll
         for (int i = 0; i < NT; ++i) hs3[i] = pack8(s0);
 #else
-        if constexpr (NT == 2) { h0 *= x2sc[0]; h1 *= x2sc[0]; }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { hv[e] = gelu_bf(h0[e]); hv[4 + e] = gelu_bf(h1[e]); }
-        if constexpr (NT == 2) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) hv[e] *= x2sh;
-        }
         bf16x8 hs3[NT];
-        split_rows<NT>(hv, hs3);
+        if constexpr (NT == 2) {
+            h0 *= x2sc[0]; h1 *= x2sc[0];           // stays one multiply per value: h 2^-k1 / sx is the variable of gelu_bf's polynomial (header comment)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { hv[e] = gelu_bf(h0[e]); hv[4 + e] = gelu_bf(h1[e]); }
+            split_hidden_x2(hv, x2sh, hs3);         // the range-rule scale of the GELU output is the split's own multiply
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { hv[e] = gelu_bf(h0[e]); hv[4 + e] = gelu_bf(h1[e]); }
+            split_rows<NT>(hv, hs3);
+        }
 #endif
         // ---- fc2: two output tiles per step (no back-to-back MFMAs on one accumulator) ----
         const bf16x8* w2b = SINGLE ? wb + (size_t)(N2 * KS) * 64 : nullptr;

@@ -105,14 +105,18 @@ int mlp_fused(float* x, int M, int C, int Cp, const float* gamma, const float* b
 
 // ---- fused MLP, fp32 operands split into three bf16 terms (fused_mlp_x3.h) ----
 // nt = 3: three bf16 terms per operand (exact split); nt = 2: two fp16 terms + per-matrix power-of-two scales in a 32-byte trailer (fused_mlp_x3.h)
-size_t mlp_x3_bytes(int Cp, int hiddenP, int nt) { return (size_t)(hiddenP / 32) * mlp_x3_frags(Cp, nt) * 1024 + 48; }
+// nt = 2 also carries the pre-scaled fc1 bias [hiddenP] and LayerNorm gamma / beta [Cp] each behind the trailer (mlp_x3_prescale_kernel)
+static size_t mlp_x3_frag_bytes(int Cp, int hiddenP, int nt) { return (size_t)(hiddenP / 32) * mlp_x3_frags(Cp, nt) * 1024; }
+size_t mlp_x3_bytes(int Cp, int hiddenP, int nt) { return mlp_x3_frag_bytes(Cp, hiddenP, nt) + 48 + (nt == 2 ? (size_t)(hiddenP + 2 * Cp) * sizeof(float) : 0); }
 
 int mlp_x3_pack(const float* w1, const float* w2, void* image, int Cp, int hiddenP, hipStream_t s, int nt, const float* gamma, const float* beta, const float* b1, int C) {
     if (Cp % 16 || hiddenP % 32 || (nt != 2 && nt != 3)) return -1;
+    if (nt == 2 && (!gamma || !beta || !b1)) return -1;             // the two-term image holds scaled copies of all three
+    char* tail = reinterpret_cast<char*>(image) + mlp_x3_frag_bytes(Cp, hiddenP, nt);
     const int KS = (Cp + 31) / 32, KK = Cp / 16;
     const long long total = (long long)(hiddenP / 32) * (2 * KS + KK) * 64;
     if (nt == 2) {
-        unsigned* mx = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(image) + mlp_x3_bytes(Cp, hiddenP, nt) - 48);
+        unsigned* mx = reinterpret_cast<unsigned*>(tail);
         if (hipMemsetAsync(mx, 0, 16, s) != hipSuccess) return -1;
         const long long n = (long long)hiddenP * Cp;
         ESCX_LAUNCH(absmax_bits_kernel, dim3((unsigned)std::min<long long>(256, (n + 255) / 256)), dim3(256), 0, s, w1, n, mx);
@@ -120,6 +124,7 @@ int mlp_x3_pack(const float* w1, const float* w2, void* image, int Cp, int hidde
         ESCX_LAUNCH(rownorm2_max_bits_kernel, dim3((unsigned)((hiddenP + 3) / 4)), dim3(256), 0, s, w1, hiddenP, Cp, Cp, mx + 2);      // range rule: bound of the fc1 outputs
     }
     ESCX_LAUNCH(mlp_x3_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, w1, w2, reinterpret_cast<bf16x8*>(image), Cp, hiddenP, KS, KK, nt, gamma, beta, b1, C);
+    if (nt == 2) ESCX_LAUNCH(mlp_x3_prescale_kernel, dim3((unsigned)((hiddenP + 2 * Cp + 255) / 256)), dim3(256), 0, s, reinterpret_cast<bf16x8*>(tail), gamma, beta, b1, Cp, hiddenP);
     return 0;
 }
 

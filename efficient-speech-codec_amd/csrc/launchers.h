@@ -40,7 +40,7 @@ unsigned long long* debug_trace_buffer();      // device buffer set by escx_debu
 // nt: terms per operand - 3 = bf16 (exact split, six cross products), 2 = fp16 with per-matrix power-of-two scales (three cross products); image and kernel must agree
 size_t mlp_x3_bytes(int Cp, int hiddenP, int nt = 3);
 int mlp_x3_pack(const float* w1, const float* w2, void* image, int Cp, int hiddenP, hipStream_t s, int nt = 3, const float* gamma = nullptr, const float* beta = nullptr,
-                const float* b1 = nullptr, int C = 0);      // nt = 2 needs ln2's gamma / beta, b1 and the unpadded width (range rule of split_terms.h)
+                const float* b1 = nullptr, int C = 0);      // nt = 2 needs ln2's gamma / beta, b1 and the unpadded width (range rule of split_terms.h; -1 without them: the image holds their scaled copies)
 struct MlpSplit;
 int mlp_x3(float* x, int M, int C, int Cp, const float* gamma, const float* beta, const float* b1, const float* b2, const void* image, int hiddenP, int nw, int* hs_io, float* partial,
            hipStream_t s, const MlpSplit* split = nullptr, int nt = 3, float* out = nullptr);      // split: PatchSplit in the epilogue, split->wf = image of mlp_x3_split_pack
