@@ -154,6 +154,7 @@ struct escx_handle_s : escx::WsFields {      // the inherited fields are the CUR
     void* dch_x2_buf = nullptr;
     float *dc1_wT = nullptr, *idft_wT = nullptr;     // training: conv5x5 dX weights, transposed inverse-DFT matrix
     float* dft_wT = nullptr;                         // training: transposed DFT matrix ([winP][2Fp]), the STFT adjoint of an input gradient
+    double* dft_w64 = nullptr;                       // rvq+swinT training: the windowed-DFT matrix in fp64, [win][in_dim * Fp] (train.hip ensure_dft64; own allocation)
 
     // ---- training step (train.hip) ----
     std::vector<std::string> flat_keys;          // canonical flat order of the trainable parameters (== required keys)

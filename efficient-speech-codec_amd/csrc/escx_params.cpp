@@ -239,6 +239,7 @@ extern "C" void escx_destroy(escx_handle h) {
     if (h->garena) (void)hipFree(h->garena);
     if (h->grad_seg) (void)hipFree(h->grad_seg);
     if (h->tape.base) (void)hipFree(h->tape.base);
+    if (h->dft_w64) (void)hipFree(h->dft_w64);
     free_train_state(h);
     delete h;
 }
@@ -714,6 +715,7 @@ extern "C" int escx_finalize_params(escx_handle h) {
     for (auto& f : fix) *f.first = reinterpret_cast<float*>(h->wts.base) + f.second;
     h->grad_regions = grads;
     if (h->grad_seg) { (void)hipFree(h->grad_seg); h->grad_seg = nullptr; }      // rebuilt by the next training backward
+    if (h->dft_w64) { ESCX_HIP(hipDeviceSynchronize()); (void)hipFree(h->dft_w64); h->dft_w64 = nullptr; }      // (the window may have been set anew) rebuilt by the next rvq training forward
     h->finalized = true;
     build_flat_layout(h);
     for (Layer& L : h->layers)

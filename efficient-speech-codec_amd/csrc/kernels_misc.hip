@@ -5,6 +5,7 @@
 #include "kernels.h"
 #include "fused_pvq.h"
 #include "fused_prvq.h"
+#include "train_prvq.h"
 #include <atomic>
 #include "launchers.h"
 
@@ -265,6 +266,28 @@ int prvq_fused(const float* enc, const long long* codes_in, int B, int Hq, int W
     } else {
         if (NT == 2) launch_prvq<2, 2, false>(a, s); else launch_prvq<1, 1, false>(a, s);
     }
+    return 0;
+}
+
+// Training form of the same quantiser (train_prvq.h): all R stages, straight-through arithmetic, per-stage loss terms, z_e and the up-projection's operand to the tape.
+template <int NT, int STEPS>
+static void launch_prvq_train(const PrvqTrainArgs& a, hipStream_t s) {
+    constexpr int lds = pvqf_lds_floats<NT>() * (int)sizeof(float);
+    static_assert(lds <= 48 * 1024, "the covered geometries stay within the default dynamic LDS limit");
+    auto kern = prvq_train_fwd_kernel<NT, STEPS>;
+    ESCX_LAUNCH(kern, dim3((a.M + 15) / 16), dim3(64 * PVQF_WAVES), lds, s, a);
+}
+
+int prvq_train_fwd(const float* enc, int B, int Hq, int Wd, int Cp, int ov, const float* wdf, int Np, int Kq, int splits, int bk, const float* cbn, const float* c2,
+                   const float* cbraw, int G, int Ksz, int d, int dt, const float* wup, long long* codes, long long bstride, int S, int R, int freeze, float* ze,
+                   float* zq, float* terms, long long lslot, float loss_scale, int l2norm, float* out, hipStream_t s) {
+    int k_per_z = 0;
+    if (!prvq_geometry(Np, dt, G, Kq, Cp, splits, bk, &k_per_z) || Ksz < 1 || R < 1 || S < 1 || S > R || !codes || !ze || !zq || !terms || !out) return -1;
+    const int Tq = Wd / ov, M = B * Tq;
+    if (M < 1) return 0;
+    PrvqTrainArgs a{enc, wdf, cbn, c2, cbraw, wup, out, codes, bstride, ze, zq, terms, lslot, loss_scale, S, R, freeze,
+                    M, Tq, Hq, Wd, Cp, ov, Kq, k_per_z, splits, G, Ksz, d, l2norm};
+    if (Np / 16 == 2) launch_prvq_train<2, 2>(a, s); else launch_prvq_train<1, 1>(a, s);
     return 0;
 }
 

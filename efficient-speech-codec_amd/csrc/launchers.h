@@ -117,6 +117,11 @@ int prvq_fused(const float* enc, const long long* codes_in, int B, int Hq, int W
                const float* cbn, const float* c2, const float* cbraw, int G, int Ksz, int d, int dt, const float* wup,
                long long* codes, long long bstride, const int* clip_S, int S, int Smax, float* loss, long long lslot, float loss_scale, int l2norm,
                float* out, hipStream_t s);
+// The same quantiser in training mode (train_prvq.h): all R stages run, codes (B, R, G, Tq), straight-through arithmetic, stages >= S masked, terms[i * lslot + g * M + m],
+// z_e and the up-projection's operand to the tape (ze / zq, (M, Np) each), the up-projected operand to `out`.  -1: geometry not covered, nothing launched.
+int prvq_train_fwd(const float* enc, int B, int Hq, int Wd, int Cp, int ov, const float* wdf, int Np, int Kq, int splits, int bk, const float* cbn, const float* c2,
+                   const float* cbraw, int G, int Ksz, int d, int dt, const float* wup, long long* codes, long long bstride, int S, int R, int freeze, float* ze,
+                   float* zq, float* terms, long long lslot, float loss_scale, int l2norm, float* out, hipStream_t s);
 // out = dec + tab[(h, ov * code_g + o)][c] (g = group of element (o, h, c)): the de-quantise + up-projection + un-frame + add of one stream as a table-row add
 void pvq_tab_add(const long long* codes, long long bstride, const float* tab, const float* gq, int G, int Ksz, int B, int Hq, int Wd, int Cp, int ov,
                  const float* dec, float* out, hipStream_t s);

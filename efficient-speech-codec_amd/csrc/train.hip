@@ -43,10 +43,10 @@ struct TrainTape {
     float *spec = nullptr, *pe_pre = nullptr, *tok0 = nullptr, *deemb = nullptr, *rspec = nullptr, *terms = nullptr;
     bool composed = false;                   // the forward ran the folded de-embedding: no fine map (deemb) on the tape
     bool from_feat = false;                  // the forward was given the spectrum (escx_train_forward_feat): an input gradient stops at the spectrum
-    long long* codes = nullptr;              // (B, max_streams, G, Tq)
+    long long* codes = nullptr;              // (B, max_streams, G, Tq); rvq+swinT: (B, num_rvqs, G, Tq)
     std::vector<LayerTape> layers;           // 2n
     std::vector<float*> enc_hs;              // n
-    std::vector<QuantTape> q;                // max_streams
+    std::vector<QuantTape> q;                // max_streams; rvq+swinT: the one bottleneck quantiser (ze = z_e, zup = the up-projection's operand)
     float* post = nullptr;                   // decoder.post_nn output
     size_t fwd_mark = 0;
 };
@@ -379,6 +379,9 @@ int layer_H(escx_handle_s* h, const Shapes& s, int li) {
 
 size_t pad256(size_t nfl) { return (nfl * sizeof(float) + 255) / 256 * 256; }
 
+// code / loss-term slots per clip: every quantiser runs in training mode - ESC's max_streams streams, RVQCodecs' num_rvqs stages (the tiny configuration: 4 against 3)
+inline int code_slots(const escx_handle_s* h) { return h->kind == 1 ? h->num_rvqs : h->cfg.max_streams; }
+
 size_t tape_bytes(escx_handle_s* h, const Shapes& s) {
     const escx_config& c = h->cfg;
     const int n = h->n, B = s.B;
@@ -405,11 +408,12 @@ size_t tape_bytes(escx_handle_s* h, const Shapes& s) {
     size_t zp_max = 0;
     for (const Quant& q : h->quants) {
         add(Mq * q.Nz); add(Mq * q.Nz);                              // ze, zup
-        add((size_t)B * q.Hq * s.W * q.Cp);                          // refined decoder map
-        zp_max = std::max(zp_max, (size_t)pvq_down_splits((int)Mq, q.Kq, q.Cp) * Mq * q.Nz);
+        add((size_t)B * q.Hq * s.W * q.Cp);                          // refined decoder map (rvq+swinT: the decoder's input map)
+        if (!q.rvq) zp_max = std::max(zp_max, (size_t)pvq_down_splits((int)Mq, q.Kq, q.Cp) * Mq * q.Nz);     // (the fused rvq forward keeps its split-K partials in LDS)
+        else zp_max = std::max(zp_max, (size_t)(q.stages + 2) * Mq * q.Nz);          // rvq backward scratch: d z_up, d z_e and one gq per stage
     }
-    add((size_t)c.max_streams * c.group_size * Mq);                  // loss terms
-    add((size_t)B * c.max_streams * c.group_size * s.Tq * 2);        // codes (int64)
+    add((size_t)code_slots(h) * c.group_size * Mq);                  // loss terms
+    add((size_t)B * code_slots(h) * c.group_size * s.Tq * 2);        // codes (int64)
     const int T2 = c.patch_t * s.W, F2 = c.patch_f * s.H0;
     if (!train_deembed_composed(h)) add((size_t)B * T2 * F2 * h->C0p);       // de-embedding fine map (two-convolution form only)
     add((size_t)B * T2 * c.in_dim * h->Fp);                          // rspec
@@ -553,6 +557,53 @@ int quant_fwd(escx_handle_s* h, TrainTape& T, int sid, const float* enc, const f
     return launch_ok("quant_fwd");
 }
 
+// The windowed-DFT matrix of stft_f64_kernel (train_kernels.h): escx_params.cpp's dft_w before its rounding to fp32, [win][in_dim * Fp].  Built once per handle.
+int ensure_dft64(escx_handle_s* h) {
+    if (h->dft_w64) return 0;
+    const escx_config& c = h->cfg;
+    const int win = c.win_length, N = h->n_fft, F = h->F, Fp = h->Fp, Np = c.in_dim * Fp;
+    if (c.in_dim != 2 || win > STF_MAXWIN) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "fp64 STFT: in_dim %d / win_length %d outside the kernel (2, <= %d)", c.in_dim, win, STF_MAXWIN);
+    std::vector<double> tab((size_t)win * Np, 0.0);
+    auto it = h->params.find("ft.window");
+    for (int k = 0; k < win; ++k) {
+        const double w = (it != h->params.end() && (int)it->second.data.size() == win) ? (double)it->second.data[k] : 0.5 - 0.5 * std::cos(2.0 * M_PI * (double)k / (double)win);
+        for (int f = 0; f < F; ++f) {
+            // the quadrant angles exactly: sin(pi) is 1.2e-16 in fp64, not 0, and the power law of ComplexSTFTLoss turns a 1e-16 imaginary part of the DC or
+            // Nyquist bin (exactly 0 from a real FFT) into sign(x) (1e-10)^0.3 = +-1e-3
+            const long long r = (long long)f * (k + h->left) % N;
+            const double ang = 2.0 * M_PI * (double)r / (double)N;
+            const double cs = (4 * r == N || 4 * r == 3LL * N) ? 0.0 : std::cos(ang), sn = (r == 0 || 2 * r == N) ? 0.0 : std::sin(ang);
+            tab[(size_t)k * Np + f] = w * cs;
+            tab[(size_t)k * Np + Fp + f] = -w * sn;
+        }
+    }
+    ESCX_HIP(hipMalloc((void**)&h->dft_w64, tab.size() * sizeof(double)));
+    ESCX_HIP(hipMemcpy(h->dft_w64, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
+    return 0;
+}
+
+// the bottleneck product-residual quantiser of rvq+swinT in training mode (quantization.py:298-335): one launch (train_prvq.h).  T.q[0].out = the decoder's input map
+int rvq_fwd(escx_handle_s* h, TrainTape& T, const float* enc, hipStream_t st) {
+    const escx_config& c = h->cfg;
+    const Quant& q = h->quants[0];
+    const Shapes& s = T.shp;
+    Arena& tp = h->tape;
+    QuantTape& Q = T.q[0];
+    const int B = s.B, W = s.W, Tq = s.Tq, M = B * Tq, G = c.group_size, R = h->num_rvqs;
+    Q.transmit = true; Q.enc = enc; Q.dec = nullptr;
+    Q.ze = tp.take((size_t)M * q.Nz); Q.zup = tp.take((size_t)M * q.Nz);
+    Q.out = tp.take((size_t)B * q.Hq * W * q.Cp);
+    if (!Q.out) ESCX_FAIL(ESCX_ERR_STATE, "training tape too small");
+    const double vec = (double)c.overlap * q.Hq * q.C;
+    int rc = -1;
+    PROF("T.prvq_train", 4.0 * M * vec * q.d + 2.0 * M * R * G * c.codebook_size * q.d, (double)M * vec * 2 * 4,
+         rc = prvq_train_fwd(enc, B, q.Hq, W, q.Cp, c.overlap, q.wdf, q.Nz, q.Kq, pvq_down_splits(M, q.Kq, q.Cp), pvq_down_bk(q.Cp), q.cbn, q.c2, q.cbraw, G,
+                             c.codebook_size, q.d, q.dt, q.wup, T.codes, (long long)R * G * Tq, T.S, R, T.freeze, Q.ze, Q.zup, T.terms, (long long)G * M,
+                             1.0f / ((float)Tq * q.d * G), c.l2norm, Q.out, st));
+    if (rc) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "rvq quantiser: geometry not covered (codebook_dim %d, %d groups)", q.d, G);
+    return launch_ok("rvq_fwd");
+}
+
 int refresh_from_flat(escx_handle_s* h, const float* flat, hipStream_t st) {
     int rc = build_gather_map(h);
     if (rc) return rc;
@@ -638,8 +689,8 @@ int train_forward_impl(escx_handle_s* h, const float* wave, const float* feat, i
     }
     Arena& tp = h->tape;
     tp.used = 0;
-    T.B = B; T.L = L; T.S = freeze ? c.max_streams : S; T.freeze = freeze ? 1 : 0; T.shp = s;      // codecs.py:65: frozen codebooks use every stream
-    const int n = h->n, G = c.group_size, Smax = c.max_streams;
+    const int n = h->n, G = c.group_size, Smax = code_slots(h);
+    T.B = B; T.L = L; T.S = (freeze && h->kind == 0) ? Smax : S; T.freeze = freeze ? 1 : 0; T.shp = s;      // codecs.py:65: frozen codebooks use every stream (ESC.forward only)
     const int T2 = c.patch_t * s.W, out_len = c.hop_length * (T2 - 1);
 
     // STFT -> patch embedding (base.py:29-37, scale.py:42-50)
@@ -650,6 +701,10 @@ int train_forward_impl(escx_handle_s* h, const float* wave, const float* feat, i
     T.codes = reinterpret_cast<long long*>(tp.take((size_t)B * Smax * G * s.Tq * 2));
     if (!T.codes) ESCX_FAIL(ESCX_ERR_STATE, "training tape too small");
     if (feat) pad_rows(feat, T.spec, (long long)B * s.T * c.in_dim, h->F, h->Fp, st);
+    else if (h->kind == 1)          // rvq+swinT: the correctly rounded spectrum (train_kernels.h stft_f64_kernel); ESC's arithmetic stays the fp32-MFMA GEMM below
+        PROF("T.stft_f64", 2.0 * B * s.T * c.win_length * 2 * h->F, ((double)B * L + (double)B * s.T * 2 * h->F) * 4,
+             hipLaunchKernelGGL(stft_f64_kernel, dim3((unsigned)(((long long)B * s.T + STF_FR - 1) / STF_FR)), dim3(256), 0, st, wave, h->dft_w64, T.spec, B, L, s.T,
+                                c.hop_length, h->left - h->n_fft / 2, c.win_length, c.in_dim * h->Fp));
     else
     PROF("T.stft", 2.0 * B * s.T * c.win_length * 2 * h->F, ((double)B * L + (double)B * s.T * 2 * h->F) * 4,
          gemm_frames(wave, B, L, s.T, c.hop_length, h->left - h->n_fft / 2, h->dft_w, c.in_dim * h->Fp, h->winP, T.spec, st));
@@ -668,6 +723,18 @@ int train_forward_impl(escx_handle_s* h, const float* wave, const float* feat, i
         T.enc_hs[i + 1] = T.layers[1 + i].y;
     }
 
+    if (h->kind == 1) {
+        // rvq+swinT (codecs.py:127-148): ONE quantiser step on the bottleneck map, then the plain decoder (base.py:195-203) fed directly - no quantiser further up
+        T.q.assign(1, QuantTape());
+        if ((rc = rvq_fwd(h, T, T.enc_hs[n - 1], st))) return rc;
+        const float* dec = T.q[0].out;
+        int H = s.encH[n - 1];
+        for (int i = 0; i + 1 < n; ++i) {
+            if ((rc = layer_fwd(h, h->layers[n + i], T.layers[n + i], dec, B, H, s.W, st))) return rc;
+            dec = T.layers[n + i].y; H = T.layers[n + i].Hout;
+        }
+        if ((rc = layer_fwd(h, h->layers[2 * n - 1], T.layers[2 * n - 1], dec, B, H, s.W, st))) return rc;
+    } else {
     // cross-scale VQ decoder in training mode (csrvq.py:97-129): every stream is quantised (codes of all max_streams are returned),
     // streams >= num_streams are masked out of the reconstruction and of the losses
     T.q.assign(Smax, QuantTape());
@@ -685,6 +752,7 @@ int train_forward_impl(escx_handle_s* h, const float* wave, const float* feat, i
         dec = T.layers[n + i].y; H = T.layers[n + i].Hout;
     }
     if ((rc = layer_fwd(h, h->layers[2 * n - 1], T.layers[2 * n - 1], dec, B, H, s.W, st))) return rc;
+    }
     T.post = T.layers[2 * n - 1].y;
 
     // De-embedding (scale.py:73-81).  Round 4: the FOLDED 7x7 form of the inference path (composed on the device from the current weights in
@@ -728,6 +796,7 @@ int train_forward_impl(escx_handle_s* h, const float* wave, const float* feat, i
         istft_ola(frames, h->win2, wave_out, B, T2, h->winP, c.win_length, c.hop_length, h->left, h->n_fft / 2, out_len, st);
     }
     // per-clip VQ losses (codebook.py:67-69; quantization.py:57-59,71-72; csrvq.py:42-44): sum over the transmitted streams
+    // (rvq+swinT: quantization.py:187, 319-335 - the slots of the stages >= num_streams, and every slot of the frozen form, hold zeros)
     if (cm_loss) loss_reduce(T.terms, T.S, G, B * s.Tq, s.Tq, cm_loss, st);
     if (cb_loss) loss_reduce(T.terms, T.S, G, B * s.Tq, s.Tq, cb_loss, st);
     ESCX_HIP(hipMemcpyAsync(codes_out, T.codes, (size_t)B * Smax * G * s.Tq * sizeof(long long), hipMemcpyDeviceToDevice, st));
@@ -752,13 +821,14 @@ static int train_forward_entry(escx_handle h, const float* flat_dev, const float
     if ((!wave && !feat) || !codes_out || !wave_out) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null pointer");
     const escx_config& c = h->cfg;
     if (B < 1) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "batch must be positive");
-    if (S < 1 || S > c.max_streams) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "num_streams=%d outside [1, %d]", S, c.max_streams);
+    if (S < 1 || S > code_slots(h)) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "num_streams=%d outside [1, %d]%s", S, code_slots(h), h->kind == 1 ? " (num_rvqs)" : "");
     if (wave && L <= h->n_fft / 2) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "n_samples=%d too short for reflect padding of %d", L, h->n_fft / 2);
     if (h->ws != 4) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "the training step is implemented for window_size=4 (got %d): inference only for other window sizes", h->ws);
     hipStream_t st = (hipStream_t)stream;
     if (flat_dev && (rc = refresh_from_flat(h, flat_dev, st))) return rc;
     if ((rc = build_gather_map(h))) return rc;
     if ((rc = pack_train_mlp_images(h, st))) return rc;         // before the batch parts fork
+    if (h->kind == 1 && wave && (rc = ensure_dft64(h))) return rc;
     TrainRoot& R = *root_of(h);
     R.valid = false;
     ++R.generation;
@@ -786,7 +856,7 @@ static int train_forward_entry(escx_handle h, const float* flat_dev, const float
     }
     Shapes s0;
     if ((rc = make_shapes(h, 1, 1 + L / c.hop_length, &s0))) return rc;
-    const size_t per_codes = (size_t)c.max_streams * c.group_size * s0.Tq;
+    const size_t per_codes = (size_t)code_slots(h) * c.group_size * s0.Tq;
     const size_t per_wave_out = (size_t)c.hop_length * (c.patch_t * s0.W - 1);
     const size_t per_raw = (size_t)s0.T * c.in_dim * h->F, per_recon = (size_t)c.patch_t * s0.W * c.in_dim * h->F;
     for (int p = 0; p <= R.parts; ++p) R.first[p] = (int)((long long)B * p / R.parts);
@@ -811,7 +881,7 @@ static int train_forward_entry(escx_handle h, const float* flat_dev, const float
 
 extern "C" int escx_train_forward(escx_handle h, const float* flat_dev, const float* wave, int B, int L, int S, int freeze, int64_t* codes_out,
                                   float* wave_out, float* raw_feat, float* recon_feat, float* cm_loss, float* cb_loss, void* stream) {
-    if (h && h->kind != 0) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "RVQCodecs training is not implemented (escx_create_rvq handles run encode / decode / eval forward only)");
+    if (h && h->kind != 0) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "RVQCodecs training has entry points of its own: escx_rvq_train_forward / escx_rvq_train_backward (this call serves escx_create handles)");
     if (!wave) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null pointer");
     return train_forward_entry(h, flat_dev, wave, nullptr, B, L, S, freeze, codes_out, wave_out, raw_feat, recon_feat, cm_loss, cb_loss, stream);
 }
@@ -820,10 +890,22 @@ extern "C" int escx_train_forward(escx_handle h, const float* flat_dev, const fl
 extern "C" int escx_train_forward_feat(escx_handle h, const float* flat_dev, const float* feat, int B, int n_frames, int S, int freeze, int64_t* codes_out,
                                        float* wave_out, float* recon_feat, float* cm_loss, float* cb_loss, void* stream) {
     if (!h) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null handle");
-    if (h->kind != 0) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "RVQCodecs training is not implemented (escx_create_rvq handles run encode / decode / eval forward only)");
+    if (h->kind != 0) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "RVQCodecs training has entry points of its own: escx_rvq_train_forward / escx_rvq_train_backward (this call serves escx_create handles)");
     if (!feat) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null pointer");
     if (n_frames < h->cfg.patch_t) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "n_frames=%d shorter than one patch", n_frames);
     return train_forward_entry(h, flat_dev, nullptr, feat, B, h->cfg.hop_length * (n_frames - 1), S, freeze, codes_out, wave_out, nullptr, recon_feat, cm_loss, cb_loss, stream);
+}
+
+// RVQCodecs.forward in training mode (codecs.py:127-167 with quantization.py:167-196, 298-335 and codebook.py:57-75): exactly one of wave_dev (B, n) and
+// feat_dev ((B, n, in_dim, F) frame-major, as escx_train_forward_feat's) is given; n = samples or frames.  codes_dev: (B, num_rvqs, G, T) - every stage runs.
+extern "C" int escx_rvq_train_forward(escx_handle h, const float* flat_dev, const float* wave, const float* feat, int B, int n, int S, int freeze, int64_t* codes_out,
+                                      float* wave_out, float* raw_feat, float* recon_feat, float* cm_loss, float* cb_loss, void* stream) {
+    if (!h) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null handle");
+    if (h->kind != 1) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "escx_rvq_train_forward needs an rvq handle (escx_create_rvq); ESC trains through escx_train_forward");
+    if ((wave != nullptr) == (feat != nullptr)) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "exactly one of wave_dev and feat_dev");
+    if (feat && n < h->cfg.patch_t) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "n_frames=%d shorter than one patch", n);
+    return train_forward_entry(h, flat_dev, wave, feat, B, wave ? n : h->cfg.hop_length * (n - 1), S, freeze, codes_out, wave_out, wave ? raw_feat : nullptr, recon_feat,
+                               cm_loss, cb_loss, stream);
 }
 
 namespace {
@@ -980,6 +1062,48 @@ int quant_bwd(escx_handle_s* h, TrainTape& T, int sid, const float* gref, float*
     return launch_ok("quant_bwd");
 }
 
+// backward of the bottleneck product-residual quantiser of rvq+swinT: gref = gradient of the decoder's input map; accumulates into d_enc (the bottleneck map's
+// gradient).  The GEMMs and their dW launches are quant_bwd's; between them ONE launch replays the residual chain (train_prvq.h), then the deterministic codebook
+// scatter runs once per live stage with the codes and the gradient region offset by stage.  Stages >= S and the frozen form keep the memset's zeros.
+int rvq_bwd(escx_handle_s* h, TrainTape& T, const float* gref, float* d_enc, const float* dcm, const float* dcb, Scratch& sc, hipStream_t st, bool gw) {
+    const escx_config& c = h->cfg;
+    const Quant& q = h->quants[0];
+    const QuantTape& Q = T.q[0];
+    const Shapes& s = T.shp;
+    const int B = s.B, W = s.W, Tq = s.Tq, M = B * Tq, Gr = c.group_size, R = h->num_rvqs;
+    const int live = T.freeze ? 0 : T.S;            // stages with a codebook gradient
+    const long long bstride = (long long)R * Gr * Tq;
+    float* part = sc.take(DW_PART_FLOATS);
+    float* dzup = sc.take((size_t)M * q.Nz);
+    float* dze = sc.take((size_t)M * q.Nz);
+    float* gq = (gw && live) ? sc.take((size_t)live * M * q.Nz) : nullptr;
+    if (!dze || ((gw && live) && !gq)) ESCX_FAIL(ESCX_ERR_STATE, "training tape too small (backward scratch)");
+    int rc = 0;
+    ResidualGatherA gfr{gref, nullptr, q.Hq, W, q.Cp, Tq, c.overlap, M, FastDiv(Tq), FastDiv(q.Cp), FastDiv(q.Hq)};        // framed view of the map gradient
+    // up-projection: out_frames = z_q_m . Wup^T, z_q_m = the operand the forward used (the masked sum, or z_e when frozen)
+    if (gw && (rc = dw_launch(h, gfr, PlainA{Q.zup, q.Nz, M}, M, q.Kq, q.Kup, G(h, q.wup), nullptr, part, st))) return rc;
+    gemm_any(gfr, q.wupT, M, q.Kup, q.Kq, EpiStore{dzup, q.Nz, nullptr}, st, pick_bk(q.Cp));
+    const float scale = 1.0f / ((float)Tq * q.d * Gr);
+    const dim3 bg(blocks_for((long long)M * Gr));
+    if (q.dt == 8) hipLaunchKernelGGL(prvq_train_bwd_kernel<8>, bg, dim3(256), 0, st, Q.ze, T.codes, bstride, q.cbraw, dzup, dcm, dcb, dze, gq, M, Gr, c.codebook_size,
+                                      q.d, q.Nz, Tq, T.S, scale, T.freeze);
+    else if (q.dt == 4) hipLaunchKernelGGL(prvq_train_bwd_kernel<4>, bg, dim3(256), 0, st, Q.ze, T.codes, bstride, q.cbraw, dzup, dcm, dcb, dze, gq, M, Gr, c.codebook_size,
+                                           q.d, q.Nz, Tq, T.S, scale, T.freeze);
+    else ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "rvq quantiser backward: padded codebook_dim %d", q.dt);
+    if (gq) {
+        const dim3 cg(Gr * ((c.codebook_size + CBG_CODES - 1) / CBG_CODES));
+        const size_t set = (size_t)Gr * c.codebook_size * q.dt;      // one stage's codebooks in the packed layout [stage][G][Ksz][dt]
+        for (int i = 0; i < live; ++i)
+            hipLaunchKernelGGL(codebook_grad_kernel<8>, cg, dim3(256), 0, st, T.codes + (long long)i * Gr * Tq, bstride, gq + (size_t)i * M * q.Nz, G(h, q.cbraw) + i * set,
+                               M, Gr, c.codebook_size, q.dt, q.Nz, Tq);
+    }
+    // down-projection: z_e = frames . Wd^T
+    ResidualGatherA rfr{Q.enc, nullptr, q.Hq, W, q.Cp, Tq, c.overlap, M, FastDiv(Tq), FastDiv(q.Cp), FastDiv(q.Hq)};
+    if (gw && (rc = dw_launch(h, PlainA{dze, q.Nz, M}, rfr, M, q.Nz, q.Kq, G(h, q.wd), nullptr, part, st))) return rc;
+    gemm_rows(dze, q.Nz, M, q.wdT, q.Kq, q.Nz, EpiPvqGrad{d_enc, nullptr, q.Hq, W, q.Cp, Tq, c.overlap, FastDiv(Tq), FastDiv(q.Cp), FastDiv(q.Hq)}, st);
+    return launch_ok("rvq_bwd");
+}
+
 void add_inplace(float* dst, const float* src, size_t n, hipStream_t st) {
     hipLaunchKernelGGL(add_inplace_kernel, dim3(blocks_for((long long)(n / 4))), dim3(256), 0, st, dst, src, (long long)(n / 4));
 }
@@ -1007,7 +1131,7 @@ int train_backward_impl(escx_handle_s* h, const float* d_wave, const float* d_re
         ESCX_HIP(hipMemsetAsync(grad_flat, 0, h->flat_total * sizeof(float), st));
     }
     Scratch top(&tp);
-    // gradients of the encoder maps (two consumers each: the next encoder layer and a quantiser)
+    // gradients of the encoder maps (two consumers each: the next encoder layer and a quantiser; rvq+swinT: only the bottleneck map has the second one)
     std::vector<float*> d_enc(n);
     for (int i = 0; i < n; ++i) {
         const size_t nfl = (size_t)B * s.encH[i] * s.W * rup(c.h_dims[i], 16);
@@ -1112,14 +1236,15 @@ int train_backward_impl(escx_handle_s* h, const float* d_wave, const float* d_re
             ESCX_HIP(hipMemcpyAsync(gdec, gcur, nin * sizeof(float), hipMemcpyDeviceToDevice, st));
         }
         // the refined map = dec + residual_q: the +dec path keeps gdec as it is; the quantiser adds to d_enc and subtracts its residual gradient from gdec
-        if (T.q[i + 1].transmit) {           // (every read of the map gradient inside quant_bwd precedes the epilogue that updates it: one buffer serves as both)
+        if (h->kind == 0 && T.q[i + 1].transmit) {           // (every read of the map gradient inside quant_bwd precedes the epilogue that updates it: one buffer serves as both)
             Scratch sc(&tp);
             if ((rc = quant_bwd(h, T, i + 1, gdec, d_enc[n - 1 - i], gdec, d_cm, d_cb, sc, st, gw))) return rc;
         }
     }
-    {   // stream 0: the refined map is residual_q alone (dec = 0.0)
+    {   // stream 0: the refined map is residual_q alone (dec = 0.0); rvq+swinT: the one bottleneck quantiser, whose output IS the decoder's input
         Scratch sc(&tp);
-        if ((rc = quant_bwd(h, T, 0, gdec, d_enc[n - 1], nullptr, d_cm, d_cb, sc, st, gw))) return rc;
+        if (h->kind == 1) { if ((rc = rvq_bwd(h, T, gdec, d_enc[n - 1], d_cm, d_cb, sc, st, gw))) return rc; }
+        else if ((rc = quant_bwd(h, T, 0, gdec, d_enc[n - 1], nullptr, d_cm, d_cb, sc, st, gw))) return rc;
     }
     // ---- encoder ----
     for (int i = n - 2; i >= 0; --i) {
@@ -1228,7 +1353,7 @@ static int train_backward_entry(escx_handle h, const float* d_wave, const float*
 extern "C" int escx_train_backward(escx_handle h, const float* d_wave, const float* d_recon_feat, const float* d_cm, const float* d_cb,
                                    float* grad_flat, void* stream) {
     int rc = check_ready(h); if (rc) return rc;
-    if (h->kind != 0) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "RVQCodecs training is not implemented (escx_create_rvq handles run encode / decode / eval forward only)");
+    if (h->kind != 0) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "RVQCodecs training has entry points of its own: escx_rvq_train_forward / escx_rvq_train_backward (this call serves escx_create handles)");
     if (!grad_flat) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null gradient buffer");
     return train_backward_entry(h, d_wave, d_recon_feat, nullptr, d_cm, d_cb, grad_flat, nullptr, stream);
 }
@@ -1238,7 +1363,16 @@ extern "C" int escx_train_backward(escx_handle h, const float* d_wave, const flo
 extern "C" int escx_train_backward_ex(escx_handle h, const float* d_wave, const float* d_recon_feat, const float* d_raw_feat, const float* d_cm, const float* d_cb,
                                       float* grad_flat, float* d_input, void* stream) {
     int rc = check_ready(h); if (rc) return rc;
-    if (h->kind != 0) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "RVQCodecs training is not implemented (escx_create_rvq handles run encode / decode / eval forward only)");
+    if (h->kind != 0) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "RVQCodecs training has entry points of its own: escx_rvq_train_forward / escx_rvq_train_backward (this call serves escx_create handles)");
+    if (!grad_flat && !d_input) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "neither a gradient buffer nor an input-gradient buffer");
+    return train_backward_entry(h, d_wave, d_recon_feat, d_raw_feat, d_cm, d_cb, grad_flat, d_input, stream);
+}
+
+// Backward of the last escx_rvq_train_forward (the reference's autograd through RVQCodecs.forward_one_step, codecs.py:127-148): null rules of escx_train_backward_ex
+extern "C" int escx_rvq_train_backward(escx_handle h, const float* d_wave, const float* d_recon_feat, const float* d_raw_feat, const float* d_cm, const float* d_cb,
+                                       float* grad_flat, float* d_input, void* stream) {
+    int rc = check_ready(h); if (rc) return rc;
+    if (h->kind != 1) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "escx_rvq_train_backward needs an rvq handle (escx_create_rvq); ESC trains through escx_train_backward");
     if (!grad_flat && !d_input) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "neither a gradient buffer nor an input-gradient buffer");
     return train_backward_entry(h, d_wave, d_recon_feat, d_raw_feat, d_cm, d_cb, grad_flat, d_input, stream);
 }

@@ -1007,6 +1007,49 @@ static __global__ void pvq_train_bwd_kernel(const float* __restrict__ ze, const 
     if (g == 0) for (int c = G * dt; c < ldz; ++c) dze[(size_t)m * ldz + c] = 0.f;
 }
 
+// Quantiser backward of the rvq+swinT codec (the forward and the gradient identities: train_prvq.h).  The residual chain is replayed from z_e and the codes in the
+// forward's exact arithmetic; d z_e = g + 2 s d_cm[b] (r_0 - q_0) (frozen: g), gq_i = 2 s d_cb[b] (q_i - r_i) for the stages i < S, s = 1 / (Tq d G).
+// One thread per (vector m, group g).  ze / dzup / dze: (M, ldz); gq: [S][M][ldz] (nullptr: input-only backward); codes as the forward wrote them.
+template <int DT>
+static __global__ __launch_bounds__(256) void prvq_train_bwd_kernel(const float* __restrict__ ze, const long long* __restrict__ codes, long long bstride,
+                                                             const float* __restrict__ cbraw, const float* __restrict__ dzup, const float* __restrict__ dcm,
+                                                             const float* __restrict__ dcb, float* __restrict__ dze, float* __restrict__ gq, int M, int G, int Ksz,
+                                                             int d, int ldz, int Tq, int S, float loss_scale, int freeze) {
+#pragma clang fp contract(off)
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= M * G) return;
+    const int g = e / M, m = e - g * M;
+    const int b = m / Tq, t = m - b * Tq;
+    const size_t o = (size_t)m * ldz + g * DT;
+    const float wm = (dcm && !freeze) ? 2.0f * loss_scale * dcm[b] : 0.f;
+    const float wb = (dcb && !freeze) ? 2.0f * loss_scale * dcb[b] : 0.f;
+    float r[DT], gz[DT];
+#pragma unroll
+    for (int j = 0; j < DT; ++j) { r[j] = ze[o + j]; gz[j] = dzup[o + j]; }
+    const int live = freeze ? 0 : S;                // stages with a loss term
+    for (int i = 0; i < live; ++i) {
+        long long code = codes[(size_t)b * bstride + ((size_t)i * G + g) * Tq + t];
+        code = code < 0 ? 0 : (code >= Ksz ? Ksz - 1 : code);
+        const float* q = cbraw + (((size_t)i * G + g) * Ksz + (size_t)code) * DT;
+#pragma unroll
+        for (int j = 0; j < DT; ++j) {
+            const float qv = q[j];
+            const float df = r[j] - qv;
+            if (i == 0) gz[j] = (j < d) ? gz[j] + wm * df : 0.f;
+            if (gq) gq[(size_t)i * M * ldz + o + j] = (j < d) ? -wb * df : 0.f;
+            const float dq = qv - r[j];
+            const float z = r[j] + dq;              // the forward's arithmetic: the next residual is r - (r + (q - r))
+            r[j] = r[j] - z;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < DT; ++j) dze[o + j] = (j < d) ? gz[j] : 0.f;
+    if (g == 0) for (int c = G * DT; c < ldz; ++c) {
+        dze[(size_t)m * ldz + c] = 0.f;
+        if (gq) for (int i = 0; i < live; ++i) gq[(size_t)i * M * ldz + (size_t)m * ldz + c] = 0.f;
+    }
+}
+
 // embedding gradient without atomics.  One workgroup per (group, 16 codes): the group's codes are staged once in LDS as int16 (the
 // per-element b / t division happens there, not once per code), then each of the 4 waves takes 4 codes in turn and scans the vectors 64 at a
 // time.  Round 4: the vectors that chose the code are first COLLECTED - ballot + prefix rank into a wave-private LDS list, in increasing vector
@@ -1076,6 +1119,47 @@ static __global__ __launch_bounds__(256) void codebook_grad_kernel(const long lo
         for (int sidx = 1; sidx < SL; ++sidx) tot += __shfl(a, sidx * DTP + j, 64);   // slot order 0, 1, ...: every lane computes the same chain
         const int k = k0 + wave * (CBG_CODES / 4) + c;
         if (k < Ksz && slot == 0 && j < dt) dcb[((size_t)g * Ksz + k) * dt + j] = tot;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// STFT with fp64 accumulation (the rvq+swinT training forward): spec[(b, t)][n] = fp32( sum_k wave[b][reflect(t * hop + off + k)] * W[k][n] ), W the windowed-DFT
+// matrix in fp64 ([win][Np], columns past F zero).  ComplexSTFTLoss's power law |x|^0.3 has an unbounded derivative at the near-empty bins of a harmonic clip, so the
+// RAW spectrum's own rounding decides the fifth digit of that loss: the fp32-MFMA form (gemm_frames) sits 1.6e-7 relative RMS from the fp64 spectrum and moved the loss of
+// such a clip by 1.3e-5; this form returns the correctly rounded fp32 spectrum.  One workgroup per STF_FR frames (samples staged once in LDS as fp64), one thread per
+// spectrum column: the matrix row of a sample is read coalesced and serves all STF_FR frames.
+// ------------------------------------------------------------------------------------------------
+constexpr int STF_FR = 8, STF_MAXWIN = 640;
+static __global__ __launch_bounds__(256) void stft_f64_kernel(const float* __restrict__ wave, const double* __restrict__ W, float* __restrict__ spec, int B, int L, int T,
+                                                              int hop, int off, int win, int Np) {
+    __shared__ double xs[STF_FR][STF_MAXWIN];
+    const long long M = (long long)B * T, m0 = (long long)blockIdx.x * STF_FR;
+    for (int e = threadIdx.x; e < STF_FR * win; e += 256) {
+        const int j = e / win, k = e - j * win;
+        const long long m = m0 + j;
+        double v = 0.0;
+        if (m < M) {
+            const int b = (int)(m / T), t = (int)(m - (long long)b * T);
+            int p = t * hop + off + k;
+            if (p < 0) p = -p;
+            if (p >= L) p = 2 * (L - 1) - p;
+            p = p < 0 ? 0 : (p >= L ? L - 1 : p);        // (a clip shorter than the reflect reach is refused by the entry point; never outside the clip)
+            v = (double)wave[(size_t)b * L + p];
+        }
+        xs[j][k] = v;
+    }
+    __syncthreads();
+    for (int n = threadIdx.x; n < Np; n += 256) {
+        double acc[STF_FR];
+#pragma unroll
+        for (int j = 0; j < STF_FR; ++j) acc[j] = 0.0;
+        for (int k = 0; k < win; ++k) {
+            const double w = W[(size_t)k * Np + n];
+#pragma unroll
+            for (int j = 0; j < STF_FR; ++j) acc[j] += xs[j][k] * w;
+        }
+#pragma unroll
+        for (int j = 0; j < STF_FR; ++j) if (m0 + j < M) spec[(size_t)(m0 + j) * Np + n] = (float)acc[j];
     }
 }
 

@@ -205,6 +205,18 @@ class ESC(nn.Module):
         cc = self._c_config()
         _native.check(lib.escx_create(ctypes.byref(cc), idx, ctypes.byref(hd)))
 
+    # the training step's entry points (`_TrainStep` is shared with RVQCodecs, which overrides these two and `_code_streams`)
+    def _train_forward_call(self, lib, hd, flat, x, feat, B, n, S, freeze, codes, recon, raw_fm, recon_fm, cm, cb, stream):
+        """n = samples of x, or frames of feat when the spectrum is given; every tensor argument is a ctypes pointer (or None)."""
+        if feat is not None:
+            return lib.escx_train_forward_feat(hd, flat, feat, B, n, S, freeze, codes, recon, recon_fm, cm, cb, stream)
+        return lib.escx_train_forward(hd, flat, x, B, n, S, freeze, codes, recon, raw_fm, recon_fm, cm, cb, stream)
+
+    def _train_backward_call(self, lib, hd, d_recon, d_recon_fm, d_raw, d_cm, d_cb, gflat, d_in, with_input, stream):
+        if with_input:
+            return lib.escx_train_backward_ex(hd, d_recon, d_recon_fm, d_raw, d_cm, d_cb, gflat, d_in, stream)
+        return lib.escx_train_backward(hd, d_recon, d_recon_fm, d_cm, d_cb, gflat, stream)
+
     # ---- weight management ------------------------------------------------------------------
     def _apply(self, fn, *a, **k):
         self._dirty = True
@@ -663,22 +675,16 @@ class _TrainStep(torch.autograd.Function):
             raise AssertionError("Time dimension must be multiple of overlap")       # quantization.py:407
         pt = c["patch_size"][1]
         T = 1 + L // model.hop_length
-        codes = torch.empty((B, c["max_streams"], c["group_size"], W // c["overlap"]), dtype=torch.int64, device=dev)
+        codes = torch.empty((B, model._code_streams, c["group_size"], W // c["overlap"]), dtype=torch.int64, device=dev)      # every quantiser runs in training mode
         recon = torch.empty((B, model.hop_length * (pt * W - 1)), dtype=torch.float32, device=dev)
         raw_fm = feat if feat is not None else torch.empty((B, T, model.in_dim, model.in_freq), dtype=torch.float32, device=dev)
         recon_fm = torch.empty((B, pt * W, model.in_dim, model.in_freq), dtype=torch.float32, device=dev)
         cm = torch.empty((B,), dtype=torch.float32, device=dev)
         cb = torch.empty((B,), dtype=torch.float32, device=dev)
+        P = lambda t: ctypes.c_void_p(t.data_ptr())
         with torch.cuda.device(dev):
-            if feat is not None:
-                _native.check(lib.escx_train_forward_feat(hd, ctypes.c_void_p(flat.data_ptr()), ctypes.c_void_p(feat.data_ptr()), B, T, int(S), int(bool(freeze)),
-                                                          ctypes.c_void_p(codes.data_ptr()), ctypes.c_void_p(recon.data_ptr()), ctypes.c_void_p(recon_fm.data_ptr()),
-                                                          ctypes.c_void_p(cm.data_ptr()), ctypes.c_void_p(cb.data_ptr()), model._stream(dev)))
-            else:
-                _native.check(lib.escx_train_forward(hd, ctypes.c_void_p(flat.data_ptr()), ctypes.c_void_p(x.data_ptr()), B, L, int(S), int(bool(freeze)),
-                                                 ctypes.c_void_p(codes.data_ptr()), ctypes.c_void_p(recon.data_ptr()), ctypes.c_void_p(raw_fm.data_ptr()),
-                                                     ctypes.c_void_p(recon_fm.data_ptr()), ctypes.c_void_p(cm.data_ptr()), ctypes.c_void_p(cb.data_ptr()),
-                                                     model._stream(dev)))
+            _native.check(model._train_forward_call(lib, hd, P(flat), P(x), P(feat) if feat is not None else None, B, T if feat is not None else L, int(S), int(bool(freeze)),
+                                                    P(codes), P(recon), P(raw_fm), P(recon_fm), P(cm), P(cb), model._stream(dev)))
         ctx.model, ctx.dev, ctx.idx = model, dev, idx
         ctx.tape_generation = int(lib.escx_train_tape_generation(hd))
         ctx.from_feat = feat is not None
@@ -712,7 +718,7 @@ class _TrainStep(torch.autograd.Function):
         d_recon, d_recon_fm, d_cm, d_cb = prep(d_recon), prep(d_recon_fm), prep(d_cm), prep(d_cb)
         p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
         with torch.cuda.device(dev):
-            _native.check(lib.escx_train_backward(hd, p(d_recon), p(d_recon_fm), p(d_cm), p(d_cb), ctypes.c_void_p(gflat.data_ptr()), model._stream(dev)))
+            _native.check(model._train_backward_call(lib, hd, p(d_recon), p(d_recon_fm), None, p(d_cm), p(d_cb), p(gflat), None, False, model._stream(dev)))
         params = model._named_params()
         if flat_mode:                                   # p.grad are views of st["gflat"]: written in place, nothing for autograd to accumulate
             if st["gfresh"]:
@@ -726,7 +732,7 @@ class _TrainStep(torch.autograd.Function):
 
     @staticmethod
     def _backward_with_input(ctx, lib, hd, want_params, d_recon, d_recon_fm, d_raw, d_cm, d_cb):
-        """escx_train_backward_ex: the input gradient, with the parameter gradients of `backward` when any parameter requires grad."""
+        """escx_train_backward_ex (RVQCodecs: escx_rvq_train_backward): the input gradient, with the parameter gradients of `backward` when any parameter requires grad."""
         model, dev = ctx.model, ctx.dev
         n_params = len(ctx.needs_input_grad) - 5
         st = model._flat[ctx.idx]
@@ -741,7 +747,7 @@ class _TrainStep(torch.autograd.Function):
         d_in = torch.empty(ctx.in_shape, dtype=torch.float32, device=dev)
         p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
         with torch.cuda.device(dev):
-            _native.check(lib.escx_train_backward_ex(hd, p(d_recon), p(d_recon_fm), p(d_raw), p(d_cm), p(d_cb), p(gflat), p(d_in), model._stream(dev)))
+            _native.check(model._train_backward_call(lib, hd, p(d_recon), p(d_recon_fm), p(d_raw), p(d_cm), p(d_cb), p(gflat), p(d_in), True, model._stream(dev)))
         head = (None, None, d_in, None, None) if ctx.from_feat else (None, d_in, None, None, None)
         if not want_params:
             return head + (None,) * n_params
@@ -759,7 +765,8 @@ class _TrainStep(torch.autograd.Function):
 class RVQCodecs(ESC):
     """The rvq+swinT ablation codec (codecs.py:96-181): ESC's Swin encoder and decoder with plain product-residual VQ at the bottleneck
     (quantization.py:292-431) in place of the cross-scale quantisers, MI355X-native execution (fused_prvq.h: one HIP launch per batch part for
-    the whole quantiser).  Inference only: encode, decode and the eval-mode forward, with per-clip num_streams as in ESC; training raises."""
+    the whole quantiser; train_prvq.h: its training form and backward).  encode, decode and the eval-mode forward take per-clip num_streams as in ESC; the
+    training-mode forward is ESC's step (`_TrainStep`: HIP forward, hand-written HIP backward, input gradient, flat gradients) with the one bottleneck quantiser."""
 
     def __init__(self, in_dim: int = 2, in_freq: int = 192, h_dims: list = [45, 72, 96, 144, 192, 384], max_streams: int = 6,
                  backbone: Literal['transformer', 'convolution'] = 'transformer', kernel_size: list = [5, 2], conv_depth: int = 1,
@@ -793,6 +800,12 @@ class RVQCodecs(ESC):
         rc.num_rvqs, rc.codebook_dim = self._rvq["num_rvqs"], self._rvq["codebook_dim"]
         _native.check(lib.escx_create_rvq(ctypes.byref(rc), idx, ctypes.byref(hd)))
 
+    def _train_forward_call(self, lib, hd, flat, x, feat, B, n, S, freeze, codes, recon, raw_fm, recon_fm, cm, cb, stream):
+        return lib.escx_rvq_train_forward(hd, flat, x if feat is None else None, feat, B, n, S, freeze, codes, recon, raw_fm if feat is None else None, recon_fm, cm, cb, stream)
+
+    def _train_backward_call(self, lib, hd, d_recon, d_recon_fm, d_raw, d_cm, d_cb, gflat, d_in, with_input, stream):
+        return lib.escx_rvq_train_backward(hd, d_recon, d_recon_fm, d_raw, d_cm, d_cb, gflat, d_in, stream)
+
     def _streams_arg(self, num_streams):
         """An integer count above num_rvqs gives num_rvqs streams, as the reference's quantize_to_code loop does (quantization.py:230-243);
         a count below 1 is refused.  Per-clip sequences pass through (ESC's checks, bounded by num_rvqs)."""
@@ -813,10 +826,20 @@ class RVQCodecs(ESC):
         return super().encode(x, self._streams_arg(num_streams))
 
     def forward(self, x, x_feat, num_streams, freeze_codebook=False):
-        """codecs.py:129-164 in eval mode: the ESC dict, codes (Bs, min(num_streams, num_rvqs), group_size, T),
-        cm_loss = cb_loss = sum over groups and stages of mse(z_q_i, residual_i).mean([1, 2]) / group_size."""
+        """codecs.py:127-167.  Eval mode: the ESC dict, codes (Bs, min(num_streams, num_rvqs), group_size, T),
+        cm_loss = cb_loss = sum over groups and stages of mse(z_q_i, residual_i).mean([1, 2]) / group_size.
+        Training mode (on a HIP device): differentiable like ESC's; every stage runs, so codes is (Bs, num_rvqs, group_size, T), and the stages
+        >= num_streams are masked out of the reconstruction and the losses (quantization.py:185-187); freeze_codebook as quantization.py:319-321."""
         if self.training:
-            raise NotImplementedError("RVQCodecs training is not implemented in the MI355X build (encode, decode and eval-mode forward only)")
+            S = self._streams_arg(num_streams)
+            if self._is_per_clip(S):
+                raise ValueError("per-clip num_streams is an inference feature: the training step draws one num_streams per batch "
+                                 "(scripts/utils.py:11-25)")
+            t = next((v for v in (x, x_feat) if v is not None and not (isinstance(v, torch.Tensor) and v.is_cuda)), None)
+            if t is not None:
+                raise NotImplementedError("RVQCodecs training is not implemented for CPU tensors: the training step runs on a HIP device only "
+                                          f"(got {getattr(t, 'device', type(t).__name__)}); this package has no CPU implementation of anything")
+            return self.forward_one_step(x, x_feat, S, bool(freeze_codebook))
         if freeze_codebook:
             raise NotImplementedError("RVQCodecs: freeze_codebook is a training option (quantization.py:326-328); not implemented")
         with torch.no_grad():

@@ -4,9 +4,10 @@ trainer_no_adv.py:95-124`) without its experiment plumbing (accelerate, wandb, t
 Per step: sample the number of transmitted streams (quantisation dropout, `scripts/utils.py:11-25`), freeze the codebooks during the
 pre-training phase (`trainer_no_adv.py:99`), training-mode forward, mel + complex-STFT + VQ losses with the config's weights
 (`configs/9kbps_esc_base.yaml:29-33`), backward, clip_grad_norm 0.5, AdamW, learning-rate schedule.  Everything numerical runs in
-libescx (HIP): forward / backward (`esc.ESC` in train mode), losses (`esc.modules`), optimiser (`esc.optim.FlatAdamW`).
+libescx (HIP): forward / backward (`esc.ESC` or `esc.RVQCodecs` in train mode; the stream count is sampled in [1, model.max_streams] for both, as the reference trainer does), losses (`esc.modules`), optimiser (`esc.optim.FlatAdamW`).
 
     python -m scripts.train --synthetic base --steps 20 --batch_size 36                       # synthetic clips, synthetic init
+    python -m scripts.train --synthetic rvq_tiny --clip_samples 1260 --steps 20                # the rvq+swinT ablation (RVQCodecs); with --config: model_name: rvq+swinT
     torchrun --nproc-per-node 8 -m scripts.train --data ./train_wavs --config cfg.yaml        # data parallel: flat-gradient all-reduce
 """
 import argparse
@@ -187,7 +188,7 @@ def _batches(args, device, rank, world):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default=None, help="yaml with model: / loss: blocks (reference layout)")
-    ap.add_argument("--synthetic", default="base", help="without --config: base|large|tiny model block from tests/golden, synthetic init")
+    ap.add_argument("--synthetic", default="base", help="without --config: base|large|tiny (ESC) or rvq_tiny (the rvq+swinT ablation) model block from tests/golden, synthetic init")
     ap.add_argument("--data", default=None, help="folder of 16 kHz wavs (default: synthetic clips)")
     ap.add_argument("--clip_samples", type=int, default=47920)
     ap.add_argument("--batch_size", type=int, default=9)

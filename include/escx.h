@@ -82,8 +82,10 @@ int escx_create(const escx_config* cfg, int device, escx_handle* out);
  * Required keys: the backbone's (encoder.*, decoder.blocks.*, decoder.post_nn.*, decoder.patch_deembed.*) and, per group m and stage i,
  * quantizers.vqs.{m}.proj_down.weight (d, D_m), quantizers.vqs.{m}.proj_up.weight (D_m, d), quantizers.vqs.{m}.vqs.{i}.embedding.weight (K, d).
  * On such a handle escx_encode / escx_decode / escx_forward / escx_forward_feat and the three *_streams calls run the rvq+swinT codec with
- * num_streams (per clip, for *_streams) in [1, num_rvqs]; codes keep the (B, S, G, T) layout.  escx_train_*, escx_pvq_encode and
- * escx_pvq_decode return ESCX_ERR_UNSUPPORTED; the flat-parameter calls (escx_flat_param_*, escx_load_flat_params) work as for ESC. */
+ * num_streams (per clip, for *_streams) in [1, num_rvqs]; codes keep the (B, S, G, T) layout.  The training step has entry points of its own
+ * (escx_rvq_train_forward / escx_rvq_train_backward); escx_train_forward, escx_train_forward_feat, escx_train_backward, escx_train_backward_ex,
+ * escx_pvq_encode and escx_pvq_decode return ESCX_ERR_UNSUPPORTED; the flat-parameter calls (escx_flat_param_*, escx_load_flat_params) and
+ * escx_train_tape_bytes / escx_train_tape_generation work as for ESC. */
 int escx_create_rvq(const escx_rvq_config* cfg, int device, escx_handle* out);
 /* 0 = cross-scale product VQ (escx_create, ESC), 1 = bottleneck product-residual VQ (escx_create_rvq, RVQCodecs); negative for a null handle. */
 int escx_quantizer_kind(escx_handle h);
@@ -244,29 +246,50 @@ int64_t escx_flat_param_total(escx_handle h);
 /* Re-derives every packed layout from the flat buffer.  full == 0: on the device (gather + codebook normalisation; asynchronous),
  * enough for the training step; full != 0: additionally rebuilds the host-folded layouts of the inference path (synchronous). */
 int escx_load_flat_params(escx_handle h, const float* flat_params_dev, int full, void* stream);
-/* ESC.forward in training mode.  flat_params_dev may be NULL (keep the currently packed weights).  codes_dev: (B, max_streams, G, T)
+/* ESC.forward in training mode (ESCX_ERR_UNSUPPORTED on an RVQCodecs handle, whose step is escx_rvq_train_forward).  flat_params_dev may be NULL (keep the currently packed weights).  codes_dev: (B, max_streams, G, T)
  * int64 - every stream is quantised in training mode (csrvq.py:104-113); wave_out (B, hop*(2W-1)); raw_feat (B,T,2,F) and recon_feat
  * (B,2W,2,F) frame-major, optional; cm_loss / cb_loss (B,), optional.  Activations stay on the handle's tape until the backward. */
 int escx_train_forward(escx_handle h, const float* flat_params_dev, const float* wave_dev, int batch, int n_samples, int num_streams,
                        int freeze_codebook, int64_t* codes_dev, float* wave_out_dev, float* raw_feat_dev, float* recon_feat_dev,
                        float* cm_loss_dev, float* cb_loss_dev, void* stream);
 /* The same with a precomputed spectrum instead of the waveform (forward(x, x_feat=...) in training mode, codecs.py:33-34): feat_dev is (B, T, in_dim, F) f32 frame-major,
- * i.e. the reference's x_feat (B,F,T,2) permuted (0,2,3,1); the STFT is skipped, everything downstream (tape, backward) is escx_train_forward's. */
+ * i.e. the reference's x_feat (B,F,T,2) permuted (0,2,3,1); the STFT is skipped, everything downstream (tape, backward) is escx_train_forward's.
+ * ESCX_ERR_UNSUPPORTED on an RVQCodecs handle (escx_rvq_train_forward takes the spectrum there). */
 int escx_train_forward_feat(escx_handle h, const float* flat_params_dev, const float* feat_dev, int batch, int n_frames, int num_streams, int freeze_codebook,
                             int64_t* codes_dev, float* wave_out_dev, float* recon_feat_dev, float* cm_loss_dev, float* cb_loss_dev, void* stream);
 /* Backward of the last escx_train_forward.  Upstream gradients (any may be NULL = zero): d_wave (B, out_len), d_recon_feat (B,2W,2,F),
- * d_cm_loss / d_cb_loss (B,).  grad_flat_dev receives d loss / d parameter in the flat layout (overwritten, not accumulated). */
+ * d_cm_loss / d_cb_loss (B,).  grad_flat_dev receives d loss / d parameter in the flat layout (overwritten, not accumulated).
+ * ESCX_ERR_UNSUPPORTED on an RVQCodecs handle (escx_rvq_train_backward). */
 int escx_train_backward(escx_handle h, const float* d_wave_dev, const float* d_recon_feat_dev, const float* d_cm_loss_dev,
                         const float* d_cb_loss_dev, float* grad_flat_dev, void* stream);
 /* escx_train_backward with the input side (the reference's autograd through spec_transform and the straight-through estimator).
  * d_raw_feat_dev (B,T,2,F), optional: upstream gradient of the forward's raw spectrum output.  d_input_dev, optional: receives d loss / d input,
  * (B, n_samples) after escx_train_forward (patch-embedding dX + d_raw_feat, then the STFT adjoint), (B,T,2,F) after escx_train_forward_feat.
  * grad_flat_dev may be NULL: no parameter gradient, and no launch whose only product is one (a frozen codec in a larger graph).
- * ESCX_ERR_INVALID_ARG when both outputs are NULL; ESCX_ERR_UNSUPPORTED on an RVQCodecs handle. */
+ * ESCX_ERR_INVALID_ARG when both outputs are NULL; ESCX_ERR_UNSUPPORTED on an RVQCodecs handle (escx_rvq_train_backward). */
 int escx_train_backward_ex(escx_handle h, const float* d_wave_dev, const float* d_recon_feat_dev, const float* d_raw_feat_dev,
                            const float* d_cm_loss_dev, const float* d_cb_loss_dev, float* grad_flat_dev, float* d_input_dev, void* stream);
+/* RVQCodecs.forward in training mode (codecs.py:127-167) on an rvq handle: encoder, ONE product-residual quantiser step at the bottleneck
+ * (quantization.py:298-335 ProductResidualVectorQuantize.forward, 167-196 residual_vector_quantization, codebook.py:57-75 straight-through estimator and
+ * losses), the plain decoder (base.py:195-203).  Exactly one of wave_dev (B, n) and feat_dev ((B, n, in_dim, F) frame-major as escx_forward_feat's) is
+ * given, n = samples or frames.  Every one of the num_rvqs stages runs, so codes_dev is (B, num_rvqs, G, T) int64; stages >= num_streams are masked
+ * out of the reconstruction and of the losses (quantization.py:185-187); num_streams in [1, num_rvqs].  freeze_codebook: the up-projection sees
+ * z_e + z_q * 0 and the losses are zero (quantization.py:319-321).  cm_loss = cb_loss = sum over groups and live stages of mse(z_q_i, residual_i)
+ * per clip / groups.  raw_feat_dev is ignored with feat_dev.  Other outputs, the tape, the batch parts and flat_params_dev as escx_train_forward.
+ * ESCX_ERR_UNSUPPORTED on an escx_create handle and for window_size != 4. */
+int escx_rvq_train_forward(escx_handle h, const float* flat_params_dev, const float* wave_dev, const float* feat_dev, int batch, int n_samples_or_frames,
+                           int num_streams, int freeze_codebook, int64_t* codes_dev, float* wave_out_dev, float* raw_feat_dev, float* recon_feat_dev,
+                           float* cm_loss_dev, float* cb_loss_dev, void* stream);
+/* Backward of the last escx_rvq_train_forward: what the reference's autograd gives through RVQCodecs.forward_one_step (codecs.py:127-148).  With
+ * g = d L / d z_q_m from the up-projection: d z_e = g + 2 / (T d G) d_cm[b] (z_e - q_0) (frozen: g); the residual chain carries no gradient
+ * (d r_{i+1} / d r_i = 1 - 1: quantization.py:184 with codebook.py:70); codebook row code_i of a stage i < num_streams receives
+ * 2 / (T d G) d_cb[b] (q_i - r_i) summed over the vectors that chose it, in a fixed order; stages >= num_streams and the frozen form get exact zeros.
+ * Arguments and null rules as escx_train_backward_ex. */
+int escx_rvq_train_backward(escx_handle h, const float* d_wave_dev, const float* d_recon_feat_dev, const float* d_raw_feat_dev,
+                            const float* d_cm_loss_dev, const float* d_cb_loss_dev, float* grad_flat_dev, float* d_input_dev, void* stream);
+/* Bytes held for activation tapes (both kinds of handle). */
 int64_t escx_train_tape_bytes(escx_handle h);
-/* Number of escx_train_forward calls on this handle so far.  The handle holds ONE tape: escx_train_backward consumes the activations of the
+/* Number of training forwards (escx_train_forward*, escx_rvq_train_forward) on this handle so far.  The handle holds ONE tape: escx_train_backward consumes the activations of the
  * LAST forward.  A caller that interleaves several forwards (autograd graphs alive at the same time) records this value after its forward
  * and compares it before its backward; a mismatch means the tape belongs to a later forward (esc/models/codecs.py raises). */
 int64_t escx_train_tape_generation(escx_handle h);
