@@ -8,7 +8,8 @@
 // (base.py:182-214) straight from the signal; DESIGN.md section 13.2.  escx_dac_decode_tape / escx_dac_decode_backward are the decoder with its maps
 // kept in a caller-owned tape and the latent gradient d audio / d z on it (dac_grad_kernels.h); escx_dac_encode_tape /
 // escx_dac_encode_backward are the same for the encoder and the quantiser, with the audio gradient of z, latents and the commitment loss
-// (DESIGN.md section 13.4).
+// (DESIGN.md section 13.4).  escx_dac_decode_backward_params is the decoder's backward with the gradients of its parameters (bias, weight_g, weight_v,
+// alpha) next to d_z, for fine-tuning a decoder (dac_param_grad_kernels.h, gemm_dw_kernel of train_kernels.h).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -20,6 +21,8 @@
 #include "dac_kernels.h"
 #include "dac_x3.h"
 #include "dac_grad_kernels.h"
+#include "train_kernels.h"
+#include "dac_param_grad_kernels.h"
 
 using namespace escx;
 
@@ -71,6 +74,9 @@ struct escx_dac_s {
     // every re-pack of wbuf and set by refresh_wt, as w16_valid is.  Calls that never differentiate pay nothing.
     float* wt = nullptr; bool wt_valid = false;
     float* wte = nullptr; bool wte_valid = false;   // escx_dac_encode_backward: the same for the encoder's layers
+    // escx_dac_decode_backward_params: the slices' partial dW tiles, the staged dW and the bias / alpha partial rows; allocated at the first
+    // parameter backward of the handle, sized from the configuration alone (param_ws_plan)
+    float* pw = nullptr;
 };
 
 namespace {
@@ -436,6 +442,7 @@ extern "C" void escx_dac_destroy(escx_dac d) {
     if (d->w16) (void)hipFree(d->w16);
     if (d->wt) (void)hipFree(d->wt);
     if (d->wte) (void)hipFree(d->wte);
+    if (d->pw) (void)hipFree(d->pw);
     if (d->qoffs_dev) (void)hipFree(d->qoffs_dev);
     if (d->scratch) (void)hipFree(d->scratch);
     if (d->counts) (void)hipFree(d->counts);
@@ -785,6 +792,178 @@ extern "C" int escx_dac_decode_backward(escx_dac d, const float* flat, int64_t v
     }
     bwd_layer(st, Dl[0], nullptr, G, B, p.Ts[0], T, nullptr, nullptr, d_z, d->latent);
     return launch_ok("escx_dac_decode_backward");
+}
+
+// ---- parameter gradients through the decoder, eval mode, padding on (dac.py:24-41, 94-145, 249-266, nn/layers.py:5-33) ----
+namespace {
+
+constexpr int DW_TARGET_WGS = 2048;     // workgroups a dW contraction aims for: 8 per CU of the 256
+constexpr int DW_SLICE_ROWS = 128;      // a slice is a multiple of this many rows: one 32-row chunk for each of gemm_dw_kernel's four waves
+constexpr int COLSUM_BLOCKS = 1024;     // most row ranges of a bias / alpha column sum
+
+// The staged weight gradient of a decoder layer: dW[i][tap * JP + j], i the dimension the weight norm keeps (dac_param_grad_kernels.h)
+struct DwGeom { int I, J, JP, Np, Kp, blocks, smax; };
+DwGeom dw_geom(const DacLayer& l) {
+    DwGeom g{};
+    if (l.kind == 0) { g.I = l.Cout; g.J = l.Cin; g.JP = l.CinP; g.Np = l.Np; g.Kp = l.Kp; }
+    else { g.I = l.Cin; g.J = l.Cout; g.JP = cpad(l.Cout); g.Np = np_t(l); g.Kp = kp_t(l); }
+    g.blocks = ((g.Np + 47) / 48) * ((g.Kp + 47) / 48);
+    g.smax = std::max(1, (DW_TARGET_WGS + g.blocks - 1) / g.blocks);
+    return g;
+}
+// The slice rule: enough slices of M rows to reach DW_TARGET_WGS workgroups, none shorter than DW_SLICE_ROWS, from the geometry alone
+void dw_slices(const DwGeom& g, int M, int* slices, int* mps) {
+    const int s = std::max(1, std::min(g.smax, (M + DW_SLICE_ROWS - 1) / DW_SLICE_ROWS));
+    *mps = ((M + s - 1) / s + DW_SLICE_ROWS - 1) / DW_SLICE_ROWS * DW_SLICE_ROWS;
+    *slices = (M + *mps - 1) / *mps;
+}
+
+// The workspace, in floats, whatever the batch: [partial tiles: smax Np Kp] [staged dW: Np Kp] [column partials: blocks x Cp, fp64]
+struct ParamWs { size_t part = 0, stage = 0, cols = 0; size_t total() const { return part + stage + cols; } };
+ParamWs param_ws_plan(const escx_dac_s* d) {
+    ParamWs w; int cmax = 4;
+    for (const DacLayer& l : d->dec) {
+        const DwGeom g = dw_geom(l);
+        const size_t nk = (size_t)g.Np * g.Kp;
+        w.part = std::max(w.part, pad64((size_t)g.smax * nk));
+        w.stage = std::max(w.stage, pad64(nk));
+        cmax = std::max(cmax, std::max(l.CinP, cpad(l.Cout)));
+    }
+    w.cols = pad64(2 * (size_t)COLSUM_BLOCKS * cmax);
+    return w;
+}
+
+DacConvA rows_of(const float* x, int B, int T, int Cp) {                // the rows (b, t) of a map as a one-tap operand
+    DacConvA a{};
+    a.x = x; a.alpha = nullptr; a.inv = nullptr; a.Tin = T; a.Cp = Cp; a.dCp = FastDiv(Cp);
+    a.Trows = T; a.M = B * T; a.dT = FastDiv(T); a.rs = 1; a.r0 = 0; a.td = 0; a.ntaps = 1;
+    return a;
+}
+
+// sum over the rows of v (M, Cp) [times d snake / d alpha at xs] -> out[0, C)
+void colsum(const escx_dac_s* d, const ParamWs& w, hipStream_t st, const float* v, const float* xs, const DacSnake* sn, long long M, int Cp, int C, float* out) {
+    double* part = reinterpret_cast<double*>(d->pw + w.part + w.stage);          // 256-byte aligned: the regions are multiples of 64 floats
+    const int rows = (int)std::max<long long>(16, (M + COLSUM_BLOCKS - 1) / COLSUM_BLOCKS);
+    const int blocks = (int)((M + rows - 1) / rows);
+    const dim3 grid(blocks, (Cp + 255) / 256);                  // y: 256-column groups (one group when Cp <= 256)
+    if (sn) hipLaunchKernelGGL(dac_colsum_kernel<true>, grid, dim3(256), 0, st, v, xs, (const float*)sn->a, (const float*)sn->inv, M, Cp, rows, part);
+    else hipLaunchKernelGGL(dac_colsum_kernel<false>, grid, dim3(256), 0, st, v, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, M, Cp, rows, part);
+    hipLaunchKernelGGL(dac_reduce_cols_kernel, dim3(nblk(C, 16)), dim3(256), 0, st, (const double*)part, blocks, Cp, C, out);
+}
+
+// bias, weight_g and weight_v gradients of layer l from its output gradient dY (B, Tdy, cpad(Cout)) and its forward operand s (B, Ts, CinP), both
+// plain maps (the Snake already applied to s)
+void param_layer(const escx_dac_s* d, const ParamWs& w, hipStream_t st, const DacLayer& l, const float* dY, int Tdy, const float* s, int Ts, int B,
+                 const float* flat, float* grad) {
+    const DwGeom g = dw_geom(l);
+    const int CoutP = cpad(l.Cout);
+    DacConvA la, lb;
+    if (l.kind == 0) {
+        la = rows_of(dY, B, Tdy, CoutP);
+        lb = rows_of(s, B, Ts, l.CinP);
+        lb.Trows = Tdy; lb.M = B * Tdy; lb.dT = FastDiv(Tdy); lb.rs = l.stride; lb.r0 = -l.pad; lb.td = l.dil; lb.ntaps = l.K;
+    } else {
+        la = rows_of(s, B, Ts, l.CinP);
+        lb = rows_of(dY, B, Tdy, CoutP);
+        lb.Trows = Ts; lb.M = B * Ts; lb.dT = FastDiv(Ts); lb.rs = l.stride; lb.r0 = -l.pad; lb.td = 1; lb.ntaps = l.K;
+    }
+    const int M = la.M;
+    int slices, mps; dw_slices(g, M, &slices, &mps);
+    float* part = d->pw; float* stage = d->pw + w.part;
+    const int nbk = (g.Kp + 47) / 48;
+    hipLaunchKernelGGL((gemm_dw_kernel<DacConvA, DacConvA, false>), dim3(g.blocks, slices), dim3(256), 0, st, la, lb, M, g.Np, g.Kp, nbk, mps, part, (float*)nullptr);
+    const float* dW = part;                                     // one slice: its tile is the sum
+    if (slices > 1) { launch_reduce_partials(part, slices, (long long)g.Np * g.Kp, stage, 0, st); dW = stage; }
+    colsum(d, w, st, dY, nullptr, nullptr, (long long)B * Tdy, CoutP, l.Cout, grad + l.off_b);
+    hipLaunchKernelGGL(dac_wn_bwd_kernel, dim3(g.I), dim3(256), 0, st, dW, flat + l.off_v, flat + l.off_g, grad + l.off_v, grad + l.off_g, g.J, l.K, g.JP, g.Kp);
+}
+
+// bwd_layer for a layer behind a Snake, with v = conv^T(dY) kept in vout (DacGradEpiV): `out` has bwd_layer's bits
+void bwd_layer_v(hipStream_t st, const DacLayer& l, const DacSnake* sn, const float* dY, int B, int Tdy, int Tx, const float* xs, const float* res, float* out,
+                 float* vout) {
+    DacConvA ld{};
+    ld.x = dY; ld.alpha = nullptr; ld.inv = nullptr; ld.Tin = Tdy; ld.Cp = cpad(l.Cout); ld.dCp = FastDiv(ld.Cp);
+    ld.Trows = Tx; ld.M = B * Tx; ld.dT = FastDiv(Tx); ld.ntaps = l.K;
+    if (l.kind == 0) { ld.rs = 1; ld.r0 = l.pad; ld.td = -l.dil; }
+    else { ld.rs = l.stride; ld.r0 = -l.pad; ld.td = 1; }
+    DacGradEpiV ep{};
+    ep.out = out; ep.res = res; ep.xs = xs; ep.alpha = sn->a; ep.inv = sn->inv; ep.vout = vout; ep.Cp = cpad(l.Cin);
+    const int Np = np_t(l), Kp = kp_t(l);
+    const long long tiles = (long long)((ld.M + 127) / 128) * ((Np + 95) / 96);
+    if (tiles >= 512) launch_gemm<128>(ld, l.Wt, ld.M, Np, Kp, ep, st);
+    else launch_gemm<64>(ld, l.Wt, ld.M, Np, Kp, ep, st);
+}
+
+}  // namespace
+
+extern "C" int64_t escx_dac_param_grad_workspace_floats(escx_dac d) { return d ? (int64_t)param_ws_plan(d).total() : 0; }
+
+extern "C" int escx_dac_param_grad_slices(escx_dac d, int B, int T, int layer) {
+    if (!d || B < 1 || T < 1 || layer < 0 || layer >= (int)d->dec.size()) return 0;
+    TapePlan p;
+    if (!tape_plan(d, B, T, &p)) return 0;
+    // rows of the contraction: the output rows of a Conv1d, the input rows of a ConvTranspose1d
+    int Trows;
+    if (layer == 0) Trows = p.Ts[0];
+    else if (layer == (int)d->dec.size() - 1) Trows = p.Lout;
+    else { const int i = (layer - 1) / 7, k = (layer - 1) % 7; Trows = k == 0 ? p.Ts[i] : p.Ts[i + 1]; }
+    int slices, mps; dw_slices(dw_geom(d->dec[layer]), B * Trows, &slices, &mps);
+    return slices;
+}
+
+extern "C" int escx_dac_decode_backward_params(escx_dac d, const float* flat, int64_t version, const float* tape, int64_t tape_floats, const float* z,
+                                               const float* d_audio, int B, int T, float* d_z, float* grad, void* stream) {
+    int rc = check_args(d, flat, B); if (rc) return rc;
+    if (!tape || !d_audio || !z || !grad || T < 1) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "bad argument");
+    TapePlan p;
+    if ((rc = tape_args(d, B, T, (long long)tape_floats, &p))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    long long hdr[5] = {0, 0, 0, 0, 0};                         // as escx_dac_decode_backward: checked before anything of the handle changes
+    ESCX_HIP(hipMemcpyAsync(hdr, tape, sizeof(hdr), hipMemcpyDeviceToHost, st));
+    ESCX_HIP(hipStreamSynchronize(st));
+    if (hdr[0] != DAC_TAPE_MAGIC || hdr[2] != B || hdr[3] != T || hdr[4] != (long long)p.total)
+        ESCX_FAIL(ESCX_ERR_INVALID_ARG, "the buffer is not a tape that escx_dac_decode_tape made for %d x %d frames", B, T);
+    if (hdr[1] != (long long)version)
+        ESCX_FAIL(ESCX_ERR_STATE, "the tape was made with parameter version %lld and the backward is called with %lld: the parameters changed between forward and backward",
+                  hdr[1], (long long)version);
+    if ((long long)B * p.Lout > 0x7fffffffll) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "batch of %d x %d frames: more than 2^31 audio rows in one contraction", B, T);
+    const size_t mf = p.mf;
+    const ParamWs w = param_ws_plan(d);
+    if ((rc = ensure_scratch(d, 4 * mf * sizeof(float)))) return rc;
+    if (!d->pw) ESCX_HIP(hipMalloc((void**)&d->pw, w.total() * sizeof(float)));
+    if ((rc = pack(d, flat, (long long)version, st)) || (rc = refresh_wt(d, st))) return rc;
+    // escx_dac_decode_backward's walk and maps; S holds the Snaked operand of the layer at hand, then the v of its input gradient
+    float* G = d->scratch; float* G2 = G + mf; float* A = G2 + mf; float* S = d->scratch + 3 * mf;
+    auto M = [&](int i) { return tape + p.off[i]; };
+    const DacLayer* Dl = d->dec.data(); const DacSnake* SN = d->dec_sn.data();
+    const int nb = d->cfg.n_decoder_rates;
+    // one layer behind a Snake: its parameter gradients from (dY, snake(xs)), then its input gradient with v kept, then the Snake's alpha gradient
+    auto layer = [&](const DacLayer& l, const DacSnake* sn, const float* dY, int Tdy, int Tx, const float* xs, const float* res, float* out) {
+        const long long n4 = (long long)B * Tx * l.CinP / 4;
+        hipLaunchKernelGGL(dac_snake_map_kernel, dim3(nblk(n4)), dim3(256), 0, st, xs, (const float*)sn->a, (const float*)sn->inv, S, n4, l.CinP / 4);
+        param_layer(d, w, st, l, dY, Tdy, S, Tx, B, flat, grad);
+        bwd_layer_v(st, l, sn, dY, B, Tdy, Tx, xs, res, out, S);
+        colsum(d, w, st, S, xs, sn, (long long)B * Tx, l.CinP, sn->C, grad + sn->off);
+    };
+    const long long n = (long long)B * p.Lout;
+    hipLaunchKernelGGL(dac_tanh_grad_in_kernel, dim3(nblk(n)), dim3(256), 0, st, d_audio, tape + p.audio, A, n);
+    layer(Dl[d->dec.size() - 1], SN + d->dec_sn.size() - 1, A, p.Lout, p.Ts[nb], M(7 * nb), nullptr, G);
+    for (int i = nb - 1; i >= 0; --i) {
+        const DacLayer* Lb = Dl + 1 + i * 7; const DacSnake* Sb = SN + i * 7;
+        const int Tc = p.Ts[i + 1];
+        for (int j = 2; j >= 0; --j) {
+            layer(Lb[2 + 2 * j], &Sb[2 + 2 * j], G, Tc, Tc, M(7 * i + 2 + 2 * j), nullptr, A);
+            layer(Lb[1 + 2 * j], &Sb[1 + 2 * j], A, Tc, Tc, M(7 * i + 1 + 2 * j), G, G);
+        }
+        layer(Lb[0], Sb, G, Tc, p.Ts[i], M(7 * i), nullptr, G2);
+        std::swap(G, G2);
+    }
+    // the first convolution reads the latent itself, staged channels-last as the forward stages it
+    const int Dp = cpad(d->latent);
+    hipLaunchKernelGGL(dac_z_in_kernel, dim3(nblk((long long)B * T * Dp)), dim3(256), 0, st, z, A, B, d->latent, Dp, T);
+    param_layer(d, w, st, Dl[0], G, p.Ts[0], A, T, B, flat, grad);
+    if (d_z) bwd_layer(st, Dl[0], nullptr, G, B, p.Ts[0], T, nullptr, nullptr, d_z, d->latent);
+    return launch_ok("escx_dac_decode_backward_params");
 }
 
 // ---- audio gradient through the encoder and the quantiser, eval mode, padding on (dac.py:209-247, quantize.py:58-70, 173-198) ------

@@ -152,6 +152,9 @@ SIGNATURES = {
     "escx_dac_decode_tape_floats": (c_int64, [c_void_p, c_int, c_int]),
     "escx_dac_decode_tape": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p]),
     "escx_dac_decode_backward": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "escx_dac_decode_backward_params": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "escx_dac_param_grad_workspace_floats": (c_int64, [c_void_p]),
+    "escx_dac_param_grad_slices": (c_int, [c_void_p, c_int, c_int, c_int]),
     "escx_dac_test_grad_math": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
     "escx_dac_encode_tape_floats": (c_int64, [c_void_p, c_int, c_int, c_int]),
     "escx_dac_encode_tape": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, POINTER(c_int32), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

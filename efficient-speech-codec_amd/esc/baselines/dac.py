@@ -152,6 +152,7 @@ class DAC(nn.Module):
         self._handles, self._flat = {}, {}
         self._precision = "fp32"
         self._padding = True
+        self._trainable = None
 
     # ---- native handle and flat parameter buffer (same scheme as esc.models.Discriminator) ----------------------------------------------
     def _version(self) -> int:
@@ -259,6 +260,32 @@ class DAC(nn.Module):
     def precision(self) -> str:
         """The mode in effect: what set_precision chose ("fp32" until then); every live handle is in it."""
         return self._precision
+
+    # ---- fine-tuning the decoder (include/escx.h escx_dac_decode_backward_params) ----------------------------------------------------------------
+    def set_trainable(self, part: Optional[str]) -> "DAC":
+        """Which part of the model `decode` differentiates with respect to its parameters.  None (the default): none, today's behaviour bit for
+        bit.  "decoder": in eval mode, with padding on and gradients enabled, decode(z) delivers through autograd the gradient of every decoder
+        parameter that requires one (and of z if it requires one); the audio is bitwise the plain decode's.  The decoder has no train / eval
+        difference, so the model stays in eval mode; `.train()` still refuses.  The encoder and the quantiser stay frozen: their parameter
+        gradients, quantiser dropout and training mode are not built, so "encoder", "quantizer" and "all" raise NotImplementedError."""
+        if part in ("encoder", "quantizer", "all"):
+            raise NotImplementedError(f"set_trainable({part!r}): only the decoder's parameter gradients are built (set_trainable('decoder')); the "
+                                      "encoder's and the quantiser's parameter gradients, quantiser dropout and training mode are not")
+        if part not in (None, "decoder"):
+            raise ValueError(f"set_trainable({part!r}): expected None or 'decoder'")
+        self._trainable = part
+        return self
+
+    @property
+    def trainable(self) -> Optional[str]:
+        """What set_trainable chose: None or "decoder"."""
+        return self._trainable
+
+    def decoder_parameters(self):
+        """The `decoder.*` parameters in state_dict order: what an optimiser fine-tunes after set_trainable("decoder")."""
+        for key, p in self.named_parameters():
+            if key.startswith("decoder."):
+                yield p
 
     # ---- CodecMixin's padding switch and geometry (base.py:58-123) ----------------------------------------------------------------------
     @property
@@ -504,9 +531,14 @@ class DAC(nn.Module):
     def decode(self, z: torch.Tensor):
         """dac.py:249-266: z (B, D, T) -> audio (B, 1, output_samples(T)).  When gradients are enabled and z requires one, the result carries
         the latent gradient d audio / d z (eval mode, padding on; `_DecodeGrad` below): the same audio bits, computed by escx_dac_decode_tape,
-        which keeps the decoder's maps in a tape on the graph.  The module's parameters get no gradient whatever their requires_grad."""
+        which keeps the decoder's maps in a tape on the graph.  The module's parameters get no gradient whatever their requires_grad, unless
+        set_trainable("decoder") is in effect: then every decoder parameter that requires a gradient gets one (`_DecodeParamGrad`)."""
         if self.training:
             raise NotImplementedError("esc.baselines.DAC is inference only: call .eval() (DAC training is not implemented)")
+        if self._trainable == "decoder" and torch.is_grad_enabled() and isinstance(z, torch.Tensor):
+            params = list(self.decoder_parameters())
+            if any(p.requires_grad for p in params):
+                return _DecodeParamGrad.apply(z, self, *params)
         if torch.is_grad_enabled() and isinstance(z, torch.Tensor) and z.requires_grad:
             return _DecodeGrad.apply(z, self)
         with torch.no_grad():
@@ -792,6 +824,58 @@ class _DecodeGrad(torch.autograd.Function):
             _native.check(lib.escx_dac_decode_backward(hd, ctypes.c_void_p(flat.data_ptr()), ctx.version, ctypes.c_void_p(tape.data_ptr()), tape.numel(),
                                                        ctypes.c_void_p(g.data_ptr()), B, T, ctypes.c_void_p(d_z.data_ptr()), stream))
         return d_z.to(ctx.z_dtype), None
+
+
+class _DecodeParamGrad(torch.autograd.Function):
+    """DAC.decode with the gradients of the decoder's parameters (include/escx.h escx_dac_decode_backward_params), for fine-tuning a decoder on
+    frozen codes or latents after set_trainable("decoder").  forward is `_DecodeGrad`'s: the decode's own launch sequence with its maps kept in a
+    tape on the graph.  backward returns the gradient of every decoder parameter that requires one, and of z if it requires one (bitwise
+    `_DecodeGrad`'s); autograd accumulates them into p.grad.  First order only; fp32 MFMA in both precision modes; no atomics."""
+
+    @staticmethod
+    def forward(ctx, z, model, *params):
+        lib, hd, flat, dev, stream, B, T, n_out = model._decode_args(z)
+        if not model._padding:
+            raise NotImplementedError("the parameter gradients of DAC.decode are implemented with padding on (the chunked path needs no gradients)")
+        zc = z.detach().to(torch.float32).contiguous()
+        floats = int(lib.escx_dac_decode_tape_floats(hd, B, T))
+        if floats < 0:
+            _native.check(floats)
+        if floats < 1:
+            raise RuntimeError(f"libescx gives no tape for a decode of {B} x {T} frames")
+        tape = torch.empty(floats, dtype=torch.float32, device=dev)
+        out = torch.empty(B, 1, n_out, device=dev)
+        version = model._version()
+        with torch.cuda.device(dev):
+            _native.check(lib.escx_dac_decode_tape(hd, ctypes.c_void_p(flat.data_ptr()), version, ctypes.c_void_p(zc.data_ptr()), B, T,
+                                                   ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(tape.data_ptr()), floats, stream))
+        ctx.save_for_backward(tape, zc)
+        ctx.model, ctx.version, ctx.dims, ctx.z_dtype = model, version, (B, T), z.dtype
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_audio):
+        model, (B, T) = ctx.model, ctx.dims
+        tape, zc = ctx.saved_tensors
+        if model._version() != ctx.version:
+            raise RuntimeError("a parameter of the DAC module was changed in place between decode and its backward: the tape was made with the "
+                               "earlier weights (decode again after changing parameters)")
+        lib, hd, flat, dev, stream = model._ctx(tape, "the tape")
+        g = d_audio.to(torch.float32).contiguous()
+        d_z = torch.empty(B, model.latent_dim, T, device=dev) if ctx.needs_input_grad[0] else None
+        grad = torch.empty_like(flat)                        # only the decoder's slots are written, and only they are read below
+        with torch.cuda.device(dev):
+            _native.check(lib.escx_dac_decode_backward_params(hd, ctypes.c_void_p(flat.data_ptr()), ctx.version, ctypes.c_void_p(tape.data_ptr()), tape.numel(),
+                                                              ctypes.c_void_p(zc.data_ptr()), ctypes.c_void_p(g.data_ptr()), B, T,
+                                                              None if d_z is None else ctypes.c_void_p(d_z.data_ptr()), ctypes.c_void_p(grad.data_ptr()),
+                                                              stream))
+        idx = dev.index if dev.index is not None else torch.cuda.current_device()
+        slots = [(off, n) for key, off, n in model._flat[idx]["layout"] if key.startswith("decoder.")]
+        params = list(model.decoder_parameters())
+        # views of the one buffer: the slots are disjoint, so the p.grad that autograd makes of them never alias each other
+        grads = [grad[off:off + n].view(p.shape) if need else None for (off, n), p, need in zip(slots, params, ctx.needs_input_grad[2:])]
+        return (None if d_z is None else d_z.to(ctx.z_dtype), None, *grads)
 
 
 class _EncodeGrad(torch.autograd.Function):

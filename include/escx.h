@@ -492,8 +492,8 @@ int escx_dac_encode_chunks(escx_dac d, const float* flat_params_dev, int64_t par
 /* ---- Latent gradient through the decoder (eval mode, padding on) -------------------------------------------------------------------------------
  * d audio / d z of DAC.decode (baselines/descript/dac/model/dac.py:249-266) for a frozen codec inside a larger autograd graph: the decoder is
  * Decoder.forward (dac.py:115-145) over DecoderBlock (dac.py:94-112: Snake1d, WNConvTranspose1d, three ResidualUnits) and ResidualUnit
- * (dac.py:24-41: x + conv1(snake(conv7(snake(x))))), with Snake1d and the weight-normalised layers of nn/layers.py:9-33.  Parameter gradients, the
- * encoder and the quantiser are not differentiated.  With the handle's padding off every entry point below returns ESCX_ERR_UNSUPPORTED (the
+ * (dac.py:24-41: x + conv1(snake(conv7(snake(x))))), with Snake1d and the weight-normalised layers of nn/layers.py:9-33.  The encoder and the quantiser are not
+ * differentiated here; the decoder's parameter gradients are escx_dac_decode_backward_params below.  With the handle's padding off every entry point below returns ESCX_ERR_UNSUPPORTED (the
  * chunked path needs no gradients).  DESIGN.md section 13.3 has the launch sequence and the tape layout. */
 /* Floats of the activation tape of one padded decode of batch x n_frames (dac.py:249-266): a 64-float header, the input of every convolution
  * that follows a Snake (each DecoderBlock's ConvTranspose input, each ResidualUnit's x and h, dac.py:24-41, 94-112) as channels-last maps, and
@@ -516,6 +516,29 @@ int escx_dac_decode_tape(escx_dac d, const float* flat_params_dev, int64_t param
  * call waits for the stream once. */
 int escx_dac_decode_backward(escx_dac d, const float* flat_params_dev, int64_t params_version, const float* tape_dev, int64_t tape_floats,
                              const float* d_audio_dev, int batch, int n_frames, float* d_z_dev, void* stream);
+/* ---- Parameter gradients through the decoder (eval mode, padding on) ---------------------------------------------------------------------------
+ * The gradient of every decoder parameter of DAC.decode (baselines/descript/dac/model/dac.py:249-266) for the decode that wrote tape_dev, for
+ * fine-tuning a decoder on frozen codes or latents: Decoder.forward (dac.py:115-145) over DecoderBlock (dac.py:94-112) and ResidualUnit
+ * (dac.py:24-41) differentiated with respect to the weight-normalised layers' bias, weight_g and weight_v (nn/layers.py:5-16) and every Snake1d's
+ * alpha (nn/layers.py:19-33).  It walks escx_dac_decode_backward's layers in its order; at each layer, with dY its output gradient and s its forward
+ * operand (the Snaked saved map, zero outside; z for the first convolution):
+ *   Conv1d            dW[co][ci][k] = sum_{b,t} dY(b, t, co) s(b, t - p + k d, ci),   db[co] = sum_{b,t} dY(b, t, co)
+ *   ConvTranspose1d   dW[ci][co][k] = sum_{b,t} s(b, t, ci) dY(b, t st - p + k, co),  db likewise
+ *   Snake1d           d_alpha[c] = sum_{b,t} v(b, t, c) (x sin(2 alpha x) / (alpha + 1e-9) - sin(alpha x)^2 / (alpha + 1e-9)^2),  v = conv^T(dY)
+ *   weight norm       dg = <dW, v> / |v|,  dv = g / |v| (dW - <dW, v> v / |v|^2), the norm over all dimensions but the first
+ * grad_flat_dev has flat_params_dev's layout (escx_dac_param_offset): the slots of every `decoder.*` parameter are OVERWRITTEN and no other float
+ * is touched.  z_dev (B, D, T) is the latent the tape was made from (the tape does not hold it).  d_z_dev may be NULL; when given it is bitwise
+ * what escx_dac_decode_backward writes.  The contractions are fp32 MFMA over row slices whose partial tiles are added in increasing slice order
+ * (no atomics: two calls are bitwise equal), in both precision modes; the slices' tiles live in a handle workspace allocated at the first call
+ * (escx_dac_param_grad_workspace_floats).  Errors are escx_dac_decode_backward's and are found before the handle changes: padding off is
+ * ESCX_ERR_UNSUPPORTED, a foreign or wrong-size tape ESCX_ERR_INVALID_ARG, another params_version ESCX_ERR_STATE with a message naming both, a
+ * NULL grad_flat_dev or z_dev ESCX_ERR_INVALID_ARG.  DESIGN.md section 13.5 has the launch sequence, the workspace and the slice rule. */
+int escx_dac_decode_backward_params(escx_dac d, const float* flat_params_dev, int64_t params_version, const float* tape_dev, int64_t tape_floats,
+                                    const float* z_dev, const float* d_audio_dev, int batch, int n_frames, float* d_z_dev, float* grad_flat_dev, void* stream);
+/* Floats of the handle workspace escx_dac_decode_backward_params allocates at its first call; it depends on the configuration alone. */
+int64_t escx_dac_param_grad_workspace_floats(escx_dac d);
+/* Row slices of the weight-gradient contraction of decoder convolution `layer` (execution order, from 0) for batch x n_frames; 0 on a bad argument. */
+int escx_dac_param_grad_slices(escx_dac d, int batch, int n_frames, int layer);
 /* ---- Audio gradient through the encoder and the quantiser (eval mode, padding on) ---------------------------------------------------------------
  * d (z, latents, commitment_loss) / d audio of DAC.encode (baselines/descript/dac/model/dac.py:209-247) for a frozen codec in the middle of a larger
  * autograd graph: Encoder.forward (dac.py:64-91) over EncoderBlock (dac.py:44-61: three ResidualUnits, Snake1d, strided WNConv1d) and
