@@ -32,10 +32,11 @@ namespace escx {
 // The K = C contractions of a head group's Q, K and V tiles run on v_mfma_f32_16x16x32_bf16 with every fp32 operand split exactly into three bf16
 // terms (six cross products, fp32 accumulation); their outputs land in the same accumulator layout as the fp32 MFMA's, so the 16 x 16 attention
 // itself (scores, softmax, P.V) and the output projection (K = 16 per head group) stay on the fp32 MFMA unchanged.
-// Weight stream of the X3 instantiations: [group][tile][TF][64 lanes][16 B], TF = max(3 KS, KK) fragments per tile; a Q / K / V tile holds its
-// 3 KS split fragments (K-step s, term i) -> lane (row, g): term i of W[row][32 s + 8 g + e]; a projection tile holds its KK fp32 fragments as before.
+// Weight stream of the X3 instantiations: [group][tile][TF][64 lanes][16 B], TF = max(NT KS, KK) fragments per tile (NT = terms per operand: the two-term
+// stream is dense, no piece of it goes unread); a Q / K / V tile holds its NT KS split fragments (K-step s, term i) -> lane (row, g): term i of
+// W[row][32 s + 8 g + e]; a projection tile holds its KK fragments (fp32, or the two-term form described at attn_x3_pack_kernel).
 constexpr int attn_x3_ks(int CP) { return (CP + 31) / 32; }
-constexpr int attn_x3_tf(int CP) { return 3 * attn_x3_ks(CP) > CP / 16 ? 3 * attn_x3_ks(CP) : CP / 16; }
+constexpr int attn_x3_tf(int CP, int NT = 3) { return NT * attn_x3_ks(CP) > CP / 16 ? NT * attn_x3_ks(CP) : CP / 16; }
 __device__ __forceinline__ void attn_split3(const float (&v)[8], bf16x8& t0, bf16x8& t1, bf16x8& t2) {
 #pragma clang fp contract(off)
 #pragma unroll
@@ -48,7 +49,8 @@ __device__ __forceinline__ void attn_split3(const float (&v)[8], bf16x8& t0, bf1
     }
 }
 // builds the X3 stream from the fp32 fragment stream (BlockW::waf): one thread per (group, tile, K-step or projection fragment, lane)
-// NT = 2 (split_terms.h): two fp16 terms per weight, scaled by the power of two of the block's max |w| - the stream then ends with two 16-byte slots,
+// NT = 2 (split_terms.h): two fp16 terms per weight, scaled by the power of two of the block's max |w|, NT KS fragments per Q / K / V or output tile (TF = max(2 KS, KK) per attention tile: the
+// stream carries no unread piece) - the image's allocation then ends with two 16-byte slots (`tail`),
 // [0] bits of max |w| (absmax_bits_kernel over the fp32 fragment stream, before this kernel), [1] {2^-k / sx, 2^k sx, sx, 0} written here: sx = the power-of-two scale of
 // the LayerNorm output that is split against these weights (range rule of split_terms.h; bound from the norm's gamma / beta over n_ln padded channels, C real ones).
 // NT = 2, attention streams (bqkv given): the OUTPUT-PROJECTION tiles are stored in two-term form as well (round 6) - fragment `to` of a projection tile keeps its 1 KiB: lane
@@ -56,7 +58,9 @@ __device__ __forceinline__ void attn_split3(const float (&v)[8], bf16x8& t0, bf1
 // MFMA step whose other four k-slots per lane are zero (fused_attn.h proj_accumulate).  Attention streams carry THREE maxima in slot [0] - max |w| over the Q / K / V tiles
 // (their scale 2^k), over the V tiles alone, over the projection tiles (their own scale 2^kp) - and a third slot: [1] = {2^-k / sx, 2^k sx, sx, so}, [2] = {2^-kp / so};
 // so = the power-of-two scale of the O^T tiles, from |O| <= max |V| <= C max |w_V| B_x + max |b| (a softmax row is a convex combination of V rows).
-__global__ __launch_bounds__(256) void attn_x3_pack_kernel(const f32x4* __restrict__ waf, bf16x8* __restrict__ out, int n_tiles, int TPG, int KK, int KS, int TF, unsigned proj_mask, int NT = 3,
+// `tail`: the trailer's first slot.  The trailer closes the image's ALLOCATION, which has the three-term size for both forms (set_precision re-packs in place), so it
+// does not move with TF: fused_swin.hip attn_x3_trailer / rowgemm_x3_trailer are the one definition, for the packers and (x3_scale) the launchers and kernels.
+__global__ __launch_bounds__(256) void attn_x3_pack_kernel(const f32x4* __restrict__ waf, bf16x8* __restrict__ out, bf16x8* __restrict__ tail, int n_tiles, int TPG, int KK, int KS, int TF, unsigned proj_mask, int NT = 3,
                                                            const float* __restrict__ gamma = nullptr, const float* __restrict__ beta = nullptr, int n_ln = 0, int C = 0,
                                                            const float* __restrict__ bqkv = nullptr, int n_bqkv = 0) {
     const int per_tile = (KS > KK ? KS : KK) * 64;
@@ -69,7 +73,7 @@ __global__ __launch_bounds__(256) void attn_x3_pack_kernel(const f32x4* __restri
         if (f < KK) {
             const f32x4 w = src[f * 64 + lane];
             if (NT == 2 && bqkv) {
-                const float sc = x2_scale(reinterpret_cast<const unsigned*>(out + (size_t)n_tiles * TF * 64)[2]);       // the projection tiles' own scale
+                const float sc = x2_scale(reinterpret_cast<const unsigned*>(tail)[2]);       // the projection tiles' own scale
                 const float v[8] = {w[0], w[1], w[2], w[3], 0.f, 0.f, 0.f, 0.f};
                 bf16x8 t[2];
                 split_terms<2>(v, t, sc);
@@ -94,7 +98,6 @@ __global__ __launch_bounds__(256) void attn_x3_pack_kernel(const f32x4* __restri
         attn_split3(v, t0, t1, t2);
         dst[(f * 3 + 0) * 64 + lane] = t0; dst[(f * 3 + 1) * 64 + lane] = t1; dst[(f * 3 + 2) * 64 + lane] = t2;
     } else {
-        bf16x8* tail = out + (size_t)n_tiles * TF * 64;
         const float sc = x2_scale(*reinterpret_cast<const unsigned*>(tail));
         bf16x8 t[2];
         split_terms<2>(v, t, sc);
@@ -136,7 +139,7 @@ struct AttnArgs {
     // window attention and output projection are ONE launch and nothing is read back (train.hip, layer_fwd).
     float* tape_xn; float* tape_qkv; float* tape_o; int ldq, ldo, hdp, nH;
     const void* x3_wf;          // X3 instantiations: the split weight stream (attn_x3_pack_kernel), else unused
-    const float* x3_scale;      // NT = 2 instantiations: {2^-k / sx, 2^k sx, sx, so | 2^-kp / so} of the block's weight stream (its last 32 bytes; sx / so = scales of the LayerNorm output / of the O^T tiles, split_terms.h)
+    const float* x3_scale;      // NT = 2 instantiations: {2^-k / sx, 2^k sx, sx, so | 2^-kp / so} of the block's weight stream (the last 32 bytes of its allocation; sx / so = scales of the LayerNorm output / of the O^T tiles, split_terms.h)
 };
 
 // Shift mask of one window for this lane's (query l15, keys 4lg..4lg+3): -100 where query and key carry different region labels
@@ -181,8 +184,12 @@ template <int CP, int TMW> constexpr int attn_min_waves() { return (CP * TMW <= 
 // X3 instantiations hold the LayerNorm output as three bf16 terms (1.5x the registers of the fp32 operand): one occupancy step down
 template <int CP, int TMW, bool X3> constexpr int attn_min_waves_x() { return !X3 ? attn_min_waves<CP, TMW>() : ((CP * TMW <= 96) ? 3 : ((CP * TMW <= 160) ? 2 : 1)); }
 
+// An 8-wave workgroup takes SIMD slots in pairs, so a budget for 3 waves holds one workgroup where 4 would hold two.  The two-term one-head-per-tile kernels up to CP = 96
+// fit 128 registers (CP = 96: 130 without the request, 16 bytes of scratch with it); with the dense stream's 48 KiB of LDS two such workgroups fit a CU.
+template <int CP, int MODE, int TMW, int NW, bool X3, int NT> constexpr int attn_min_waves_f() { return (X3 && NT == 2 && NW == 8 && MODE == 0 && TMW == 1 && CP <= 96) ? 4 : attn_min_waves_x<CP, TMW, X3>(); }
+
 template <int CP, int MODE, int UT, int TMW, int NW, bool TAPE = false, bool X3 = false, int NT = 3>
-__global__ __launch_bounds__(64 * NW, (attn_min_waves_x<CP, TMW, X3>())) void attn_fused_kernel(AttnArgs a) {
+__global__ __launch_bounds__(64 * NW, (attn_min_waves_f<CP, MODE, TMW, NW, X3, NT>())) void attn_fused_kernel(AttnArgs a) {
     static_assert(!X3 || !TAPE, "the split-operand form exists for the plain inference instantiations");
     static_assert(NT == 3 || (NT == 2 && X3), "two fp16 terms: the split-operand instantiations");
 #ifdef ESCX_ATTN_PRIO
@@ -193,7 +200,7 @@ __global__ __launch_bounds__(64 * NW, (attn_min_waves_x<CP, TMW, X3>())) void at
     constexpr int NB = (MODE == 2) ? 6 : 3;     // bias rows per group
     static_assert(TPG % UT == 0, "stage size must divide the tiles of a head group");
     constexpr int KS = attn_x3_ks(CP);
-    constexpr int TF = X3 ? attn_x3_tf(CP) : KK;            // fragments (1 KiB) per weight tile in the stream
+    constexpr int TF = X3 ? attn_x3_tf(CP, NT) : KK;            // fragments (1 KiB) per weight tile in the stream
     __shared__ f32x4 wbuf_static[X3 ? 1 : 2 * UT * KK * 64];
     extern __shared__ __attribute__((aligned(16))) f32x4 wbuf_dyn[];      // X3: 2 * UT * TF KiB (above the 64 KiB of static LDS at the wide layers)
     f32x4* const wbuf0 = X3 ? wbuf_dyn : wbuf_static;
@@ -739,7 +746,7 @@ __global__ __launch_bounds__(64 * NW, (attn_min_waves_x<CP, 1, X3>())) void attn
     constexpr int TPG = 4;
     static_assert(TPG % UT == 0, "stage size must divide the tiles of a head group");
     constexpr int KS = attn_x3_ks(CP);
-    constexpr int TF = X3 ? attn_x3_tf(CP) : KK;            // fragments per weight tile in the stream (attn_fused_kernel)
+    constexpr int TF = X3 ? attn_x3_tf(CP, NT) : KK;            // fragments per weight tile in the stream (attn_fused_kernel)
     __shared__ f32x4 wbuf_static[X3 ? 1 : 2 * UT * KK * 64];
     extern __shared__ __attribute__((aligned(16))) f32x4 wbuf_dyn[];
     f32x4* const wbuf0 = X3 ? wbuf_dyn : wbuf_static;

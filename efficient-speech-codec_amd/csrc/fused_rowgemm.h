@@ -28,8 +28,8 @@ struct RowGemmArgs {
     int split, H, W, C2p;       // split != 0: out[(b, 2h+s, w)][c] with n = s*C2p + c ; else out[m][n], row stride 16*NT
     float eps;
     int nt_chunk;               // output tiles per workgroup column: blockIdx.y owns tiles [y * nt_chunk, (y + 1) * nt_chunk)
-    const void* x3_wf;          // rowgemm_x3_kernel: split weight stream [output tile][3 KS fragments] (attn_x3_pack_kernel), else unused
-    const float* x3_scale;      // NT = 2: {2^-k / sx, 2^k sx, sx} of the scaled two-term stream (its last 16 bytes)
+    const void* x3_wf;          // rowgemm_x3_kernel: split weight stream [output tile][3 KS (bf16) or 2 KS (fp16) fragments] (attn_x3_pack_kernel), else unused
+    const float* x3_scale;      // NT = 2: {2^-k / sx, 2^k sx, sx} of the scaled two-term stream (the last 16 bytes of its allocation)
 };
 
 template <int KP, int SEGS, int TM, int NW, int UT>
@@ -146,13 +146,13 @@ __global__ __launch_bounds__(64 * NW) void rowgemm_fused_kernel(RowGemmArgs a) {
 // ------------------------------------------------------------------------------------------------
 // Split-operand form (round 5; arithmetic: fused_mlp_x3.h): the K = SEGS * Cp contraction of PatchMerge / PatchSplit on v_mfma_f32_16x16x32_bf16 with
 // the normalised rows and the weights each split exactly into three bf16 terms (six cross products, fp32 accumulation).  Same gather, same
-// LayerNorm, same stores as rowgemm_fused_kernel; the weight stream is [output tile][3 KS fragments] (attn_x3_pack_kernel with no projection tiles,
-// built from Layer::sub_wf), UT tiles per LDS stage.
+// LayerNorm, same stores as rowgemm_fused_kernel; the weight stream is [output tile][NT KS fragments] (attn_x3_pack_kernel with no projection tiles,
+// built from Layer::sub_wf; NT = terms per operand, 3 bf16 or 2 fp16), UT tiles per LDS stage.
 // ------------------------------------------------------------------------------------------------
-template <int KP, int SEGS, int TM, int NW, int UT, int NT = 3>      // NT = 2: two fp16 terms, three cross products (split_terms.h); the stream keeps its 3 KS fragment slots per tile
+template <int KP, int SEGS, int TM, int NW, int UT, int NT = 3>      // NT = 2: two fp16 terms, three cross products (split_terms.h); its stream is dense, 2 KS fragments per tile
 __global__ __launch_bounds__(64 * NW) void rowgemm_x3_kernel(RowGemmArgs a) {
     ESCX_SET_PRIO_SMALL();
-    constexpr int KS = (KP + 31) / 32, TF = 3 * KS, SEGK = KP / SEGS;
+    constexpr int KS = (KP + 31) / 32, TF = NT * KS, SEGK = KP / SEGS;
     extern __shared__ __attribute__((aligned(16))) bf16x8 rg_wbuf[];            // [2][UT * TF * 64]
     const int lane = threadIdx.x & 63;
     const int l15 = lane & 15, lg = lane >> 4;

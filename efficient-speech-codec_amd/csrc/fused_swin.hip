@@ -204,22 +204,22 @@ template <int KP, int SEGS>
 static int launch_rowgemm(const RowGemmArgs& a, hipStream_t s) {
     if (a.x3_wf) {           // split-operand form (fused_rowgemm.h rowgemm_x3_kernel): the widths of the ESC scale changes
         if constexpr (KP == 96 || KP == 160 || KP == 192 || KP == 288 || KP == 384 || KP == 144 || KP == 80) {
-            constexpr int KSx = (KP + 31) / 32, TFx = 3 * KSx, UTx = 36 / TFx >= 4 ? 4 : (36 / TFx >= 2 ? 2 : 1);
+            constexpr int KSx = (KP + 31) / 32, TFx = 3 * KSx, UTx = 36 / TFx >= 4 ? 4 : (36 / TFx >= 2 ? 2 : 1);          // UT from the three-term tile, for both forms
             constexpr int TMx = KP <= 96 ? 2 : 1, NWx = 4;           // one row tile per wave above K = 96: the three-term operand costs 1.5x the registers of the fp32 one
             auto kern = rowgemm_x3_kernel<KP, SEGS, TMx, NWx, UTx>;
             auto kern2 = rowgemm_x3_kernel<KP, SEGS, TMx, NWx, UTx, 2>;
-            constexpr int lds = 2 * UTx * TFx * 1024;
+            constexpr int lds = 2 * UTx * TFx * 1024, lds2 = 2 * UTx * 2 * KSx * 1024;        // the two-term stream is dense: 2 KS fragments per output tile
             if constexpr (lds > 48 * 1024) {
                 static std::atomic<unsigned> done{0};
                 int dev = 0; (void)hipGetDevice(&dev);
                 const unsigned bit = 1u << (dev & 31);
                 if (!(done.load(std::memory_order_relaxed) & bit)) {
                     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-                    (void)hipFuncSetAttribute((const void*)kern2, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+                    (void)hipFuncSetAttribute((const void*)kern2, hipFuncAttributeMaxDynamicSharedMemorySize, lds2);
                     done.fetch_or(bit, std::memory_order_relaxed);
                 }
             }
-            if (a.x3_scale) ESCX_LAUNCH(kern2, dim3((a.M + 16 * TMx * NWx - 1) / (16 * TMx * NWx), 1), dim3(64 * NWx), lds, s, a);
+            if (a.x3_scale) ESCX_LAUNCH(kern2, dim3((a.M + 16 * TMx * NWx - 1) / (16 * TMx * NWx), 1), dim3(64 * NWx), lds2, s, a);
             else ESCX_LAUNCH(kern, dim3((a.M + 16 * TMx * NWx - 1) / (16 * TMx * NWx), 1), dim3(64 * NWx), lds, s, a);
             return 0;
         }
@@ -239,19 +239,21 @@ static int launch_rowgemm(const RowGemmArgs& a, hipStream_t s) {
     return 0;
 }
 
-// 32-byte trailer: the two-term (nt = 2) form keeps max |w| and its power-of-two scales there (fused_attn.h attn_x3_pack_kernel)
+// 32-byte trailer: the two-term (nt = 2) form keeps max |w| and its power-of-two scales there (fused_attn.h attn_x3_pack_kernel).  The allocation has the
+// three-term size; the two-term image (2 KS fragments per output tile) fills its first two thirds and the trailer stays at the allocation's end.
 size_t rowgemm_x3_bytes(int KP, int Np) { return (size_t)(Np / 16) * 3 * ((KP + 31) / 32) * 1024 + 32; }
+static char* rowgemm_x3_trailer(const void* image, int KP, int Np) { return reinterpret_cast<char*>(const_cast<void*>(image)) + rowgemm_x3_bytes(KP, Np) - 32; }
 int rowgemm_x3_pack(const float* wf, void* image, int KP, int Np, hipStream_t s, int nt, const float* gamma, const float* beta, int C) {
     const int KK = KP / 16, KS = (KP + 31) / 32, NT = Np / 16;
     const long long total = (long long)NT * (KS > KK ? KS : KK) * 64;
     if (nt == 2) {
-        unsigned* mx = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(image) + rowgemm_x3_bytes(KP, Np) - 32);
+        unsigned* mx = reinterpret_cast<unsigned*>(rowgemm_x3_trailer(image, KP, Np));
         (void)hipMemsetAsync(mx, 0, 16, s);
         const long long n = (long long)NT * KK * 64 * 4;
         ESCX_LAUNCH(absmax_bits_kernel, dim3((unsigned)std::min<long long>(256, (n + 255) / 256)), dim3(256), 0, s, wf, n, mx);
     }
     ESCX_LAUNCH(attn_x3_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const f32x4*>(wf), reinterpret_cast<bf16x8*>(image),
-                       NT, 1, KK, KS, 3 * KS, 0u, nt == 2 ? 2 : 3, gamma, beta, KP, C, (const float*)nullptr, 0);
+                       reinterpret_cast<bf16x8*>(rowgemm_x3_trailer(image, KP, Np)), NT, 1, KK, KS, (nt == 2 ? 2 : 3) * KS, 0u, nt == 2 ? 2 : 3, gamma, beta, KP, C, (const float*)nullptr, 0);
     return 0;
 }
 
@@ -261,7 +263,7 @@ int rowgemm_fused(int segs, const float* x, float* out, const float* gamma, cons
     const int KP = segs * Cp;
     RowGemmArgs a{x, out, gamma, beta, reinterpret_cast<const f32x4*>(wf), map, M, rows_per_clip, src_rows_per_clip, C, Cp, Np / 16,
                   split, H, W, C2p, 1e-5f, Np / 16, x3_wf,
-                  (x3_wf && x3_nt == 2) ? reinterpret_cast<const float*>(reinterpret_cast<const char*>(x3_wf) + rowgemm_x3_bytes(KP, Np) - 16) : nullptr};
+                  (x3_wf && x3_nt == 2) ? reinterpret_cast<const float*>(rowgemm_x3_trailer(x3_wf, KP, Np) + 16) : nullptr};
     if (segs == 1) {
         switch (KP) {
             case 16: return launch_rowgemm<16, 1>(a, s);
@@ -343,18 +345,18 @@ static int launch_attn(const AttnArgs& a, hipStream_t s) {
         if (a.x3_wf) {
             auto kern = attn_fused_kernel<CP, MODE, UT, TMW, NW, false, true>;
             auto kern2 = attn_fused_kernel<CP, MODE, UT, TMW, NW, false, true, 2>;        // two fp16 terms (split_terms.h)
-            constexpr int lds = 2 * UT * attn_x3_tf(CP) * 1024;
+            constexpr int lds = 2 * UT * attn_x3_tf(CP) * 1024, lds2 = 2 * UT * attn_x3_tf(CP, 2) * 1024;      // the two-term stream is dense
             if constexpr (lds > 48 * 1024) {
                 static std::atomic<unsigned> done{0};
                 int dev = 0; (void)hipGetDevice(&dev);
                 const unsigned bit = 1u << (dev & 31);
                 if (!(done.load(std::memory_order_relaxed) & bit)) {
                     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-                    (void)hipFuncSetAttribute((const void*)kern2, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+                    (void)hipFuncSetAttribute((const void*)kern2, hipFuncAttributeMaxDynamicSharedMemorySize, lds2);
                     done.fetch_or(bit, std::memory_order_relaxed);
                 }
             }
-            if (a.x3_scale) ESCX_LAUNCH(kern2, dim3(((a.n_windows + per_block - 1) / per_block) * gs), dim3(64 * NW), lds, s, a);
+            if (a.x3_scale) ESCX_LAUNCH(kern2, dim3(((a.n_windows + per_block - 1) / per_block) * gs), dim3(64 * NW), lds2, s, a);
             else ESCX_LAUNCH(kern, dim3(((a.n_windows + per_block - 1) / per_block) * gs), dim3(64 * NW), lds, s, a);
             return 0;
         }
@@ -390,16 +392,16 @@ static int launch_attn_packed(const AttnArgs& a, hipStream_t s) {
         if (a.x3_wf) {
             auto kern = attn_packed_kernel<CP, UT, NW, true>;
             auto kern2 = attn_packed_kernel<CP, UT, NW, true, 2>;
-            constexpr int lds = 2 * UT * attn_x3_tf(CP) * 1024;
+            constexpr int lds = 2 * UT * attn_x3_tf(CP) * 1024, lds2 = 2 * UT * attn_x3_tf(CP, 2) * 1024;
             static std::atomic<unsigned> done{0};
             int dev = 0; (void)hipGetDevice(&dev);
             const unsigned bit = 1u << (dev & 31);
             if (!(done.load(std::memory_order_relaxed) & bit)) {
                 (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-                (void)hipFuncSetAttribute((const void*)kern2, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+                (void)hipFuncSetAttribute((const void*)kern2, hipFuncAttributeMaxDynamicSharedMemorySize, lds2);
                 done.fetch_or(bit, std::memory_order_relaxed);
             }
-            if (a.x3_scale) ESCX_LAUNCH(kern2, dim3(((pairs + NW - 1) / NW) * gs), dim3(64 * NW), lds, s, a);
+            if (a.x3_scale) ESCX_LAUNCH(kern2, dim3(((pairs + NW - 1) / NW) * gs), dim3(64 * NW), lds2, s, a);
             else ESCX_LAUNCH(kern, dim3(((pairs + NW - 1) / NW) * gs), dim3(64 * NW), lds, s, a);
             return 0;
         }
@@ -408,17 +410,20 @@ static int launch_attn_packed(const AttnArgs& a, hipStream_t s) {
     return 0;
 }
 
-size_t attn_x3_bytes(int Cp, int mode, int n_groups) { return (size_t)n_groups * (mode == 2 ? 8 : 4) * attn_x3_tf(Cp) * 1024 + 48; }      // + trailer of the two-term form (three maxima, scales: fused_attn.h attn_x3_pack_kernel)
+// The allocation has the three-term size for both forms (set_precision re-packs in place): the dense two-term image (attn_x3_tf(Cp, 2) fragments per tile)
+// fills its front, and the two-term form's 48-byte trailer (three maxima, scales: fused_attn.h attn_x3_pack_kernel) closes the allocation either way.
+size_t attn_x3_bytes(int Cp, int mode, int n_groups) { return (size_t)n_groups * (mode == 2 ? 8 : 4) * attn_x3_tf(Cp) * 1024 + 48; }
+static char* attn_x3_trailer(const void* image, int Cp, int mode, int n_groups) { return reinterpret_cast<char*>(const_cast<void*>(image)) + attn_x3_bytes(Cp, mode, n_groups) - 48; }
 
 // nt == 2: the two-term fp16 form of the stream (split_terms.h): weights scaled by the power of two of the block's max |w|, scales in the trailer
 int attn_x3_pack(const float* waf, void* image, int Cp, int mode, int n_groups, hipStream_t s, int nt, const float* gamma, const float* beta, int C, const float* bqkv) {
-    const int KK = Cp / 16, KS = attn_x3_ks(Cp), TF = attn_x3_tf(Cp), TPG = mode == 2 ? 8 : 4;
+    const int KK = Cp / 16, KS = attn_x3_ks(Cp), TF = attn_x3_tf(Cp, nt == 2 ? 2 : 3), TPG = mode == 2 ? 8 : 4;
     const unsigned proj_mask = mode == 2 ? ((1u << 5) | (1u << 7)) : (1u << 3);        // stream order [Q, K, V, P] / [Q_lo, K_lo, Q_hi, K_hi, V_lo, P_lo, V_hi, P_hi]
     const int n_tiles = n_groups * TPG;
     (void)hipMemsetAsync(image, 0, attn_x3_bytes(Cp, mode, n_groups), s);
     const long long total = (long long)n_tiles * (KS > KK ? KS : KK) * 64;
     if (nt == 2) {
-        unsigned* mx = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(image) + attn_x3_bytes(Cp, mode, n_groups) - 48);
+        unsigned* mx = reinterpret_cast<unsigned*>(attn_x3_trailer(image, Cp, mode, n_groups));
         const long long n = (long long)n_tiles * KK * 64 * 4;
         const unsigned all = (1u << TPG) - 1, vmask = mode == 2 ? ((1u << 4) | (1u << 6)) : (1u << 2);
         const dim3 grid((unsigned)std::min<long long>(256, (n + 255) / 256));
@@ -427,7 +432,7 @@ int attn_x3_pack(const float* waf, void* image, int Cp, int mode, int n_groups, 
         ESCX_LAUNCH(absmax_tiles_bits_kernel, grid, dim3(256), 0, s, waf, n, KK * 256, TPG, proj_mask, mx + 2);
     }
     ESCX_LAUNCH(attn_x3_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const f32x4*>(waf), reinterpret_cast<bf16x8*>(image),
-                       n_tiles, TPG, KK, KS, TF, proj_mask, nt == 2 ? 2 : 3, gamma, beta, Cp, C, bqkv, n_groups * (mode == 2 ? 6 : 3) * 16);
+                       reinterpret_cast<bf16x8*>(attn_x3_trailer(image, Cp, mode, n_groups)), n_tiles, TPG, KK, KS, TF, proj_mask, nt == 2 ? 2 : 3, gamma, beta, Cp, C, bqkv, n_groups * (mode == 2 ? 6 : 3) * 16);
     return 0;
 }
 
@@ -442,7 +447,7 @@ int attn_fused(const float* src, float* dst, int Cp, int C, int mode, int n_grou
                nWh, nWw, shifted, C, n_groups, scale, 1e-5f, gs, partial, rows, g_mlp_trace,
                tape ? tape->xn : nullptr, tape ? tape->qkv : nullptr, tape ? tape->o : nullptr, tape ? tape->ldq : 0, tape ? tape->ldo : 0,
                tape ? tape->hdp : 0, tape ? tape->nH : 0, tape ? nullptr : x3_wf,
-               (!tape && x3_wf && x3_nt == 2) ? reinterpret_cast<const float*>(reinterpret_cast<const char*>(x3_wf) + attn_x3_bytes(Cp, mode, n_groups) - 32) : nullptr};
+               (!tape && x3_wf && x3_nt == 2) ? reinterpret_cast<const float*>(attn_x3_trailer(x3_wf, Cp, mode, n_groups) + 16) : nullptr};
     if (tape && nw < 0) return ESCX_COMB_UNSUPPORTED;      // the packed H = 2 form has no tape stores
     // H == 2 scale with no padding along W: two half-real windows share one tile (nw < 0 encodes "packing allowed", |nw| waves)
     if (nw < 0) {
