@@ -1,5 +1,5 @@
 // DAC discriminator + GAN losses of the adversarial training step on MI355X (BASELINE configs[4]).
-// Reference: esc/models/discriminator.py:31-221 (MPD, MRD, Discriminator; MSD is unused by every ESC config: rates = []),
+// Reference: esc/models/discriminator.py:31-221 (MPD, MSD, MRD, Discriminator; the ESC configurations use rates = [], i.e. no MSD),
 // esc/modules/loss/gan_loss.py:5-51, scripts/trainer_adv.py:61-107.  fp32 like the reference.
 //
 // One handle = one Discriminator.  Parameters live in a flat fp32 device buffer owned by the caller (reference state_dict order of the
@@ -23,6 +23,7 @@
 #include "disc_kernels.h"
 #include "gemm_bf16.h"
 #include "conv32_halo.h"
+#include "disc_msd_kernels.h"
 
 using namespace escx;
 
@@ -37,13 +38,15 @@ struct DConv {
     size_t off_b = 0, off_g = 0, off_v = 0;
     float *Wf = nullptr, *Wt = nullptr, *bias = nullptr, *scale = nullptr;
     float* Wp = nullptr; size_t wp_floats = 0;      // strided layers: per-residue-class compact dX weights (disc_kernels.h ConvTSP)
+    int groups = 0;                                 // > 0: a grouped 41-tap stride-4 Conv1d of an MSD (disc_msd_kernels.h); Cin, CinP, CinR are then PER GROUP (4)
 };
 struct DSub {
-    int kind, arg;                       // 0: MPD(period), 1: MRD(window length)
-    std::vector<DConv> convs;            // MPD: 5 + post; MRD: nb * 5 (band-major) + post
+    int kind, arg;                       // 0: MPD(period), 1: MRD(window length), 2: MSD(rate)
+    std::vector<DConv> convs;            // MPD: 5 + post; MRD: nb * 5 (band-major) + post; MSD: 6 + post
     std::vector<std::pair<int, int>> bands;
     float *D = nullptr, *DT = nullptr;   // MRD: windowed DFT matrix [2Fq][w] and its transpose
     int Fq = 0;
+    float* taps = nullptr; int ntaps = 1, width = 0;      // MSD: FIR of the resampler (2 * width + rate taps; rate 1: the identity)
 };
 struct FmapShape { int sub, C, Cp, D0, D1, P1, off1; long long base; };     // off1/P1: slice of a concatenated buffer (MRD band tops); base: first fmap of the slice's buffer
 
@@ -76,6 +79,14 @@ DConv make_conv(const std::string& p, int Cin, int Cout, int T0, int T1, int s0,
     return c;
 }
 
+// grouped Conv1d of an MSD: 4 input channels per group, 41 taps, stride 4, padding 20, LeakyReLU.  The packed image is wn_pack_kernel's with Cin = CinP = 4.
+DConv make_gconv(const std::string& p, int Cin, int Cout, int groups) {
+    DConv c; c.prefix = p; c.groups = groups; c.Cin = c.CinP = c.CinR = Cin / groups; c.Cout = c.CoutP = Cout;
+    c.T0 = MSD_TAPS; c.T1 = 1; c.s0 = MSD_STRIDE; c.s1 = 1; c.p0 = MSD_PAD; c.p1 = 0; c.act = 1;
+    c.Kf = MSD_KF; c.Kt = c.T0 * c.CoutP;
+    return c;
+}
+
 int out_dim(int D, int T, int s, int p) { return (D + 2 * p - T) / s + 1; }
 
 // per-sub-discriminator geometry for clips of L samples
@@ -83,7 +94,11 @@ struct SubGeom { int D0, D1; std::vector<int> O0, O1; std::vector<int> bandF; in
 
 SubGeom geometry(const DSub& S, int L) {
     SubGeom g;
-    if (S.kind == 0) {
+    if (S.kind == 2) {
+        g.D0 = L / S.arg; g.D1 = 1;
+        int d0 = g.D0;
+        for (const DConv& c : S.convs) { d0 = out_dim(d0, c.T0, c.s0, c.p0); g.O0.push_back(d0); g.O1.push_back(1); }
+    } else if (S.kind == 0) {
         const int p = S.arg;
         g.D0 = (L + (p - L % p)) / p; g.D1 = p;
         int d0 = g.D0;
@@ -109,7 +124,7 @@ void fmap_shapes(escx_disc_s* d, int L, std::vector<FmapShape>* out) {
     for (size_t si = 0; si < d->subs.size(); ++si) {
         const DSub& S = d->subs[si];
         const SubGeom g = geometry(S, L);
-        if (S.kind == 0) {
+        if (S.kind != 1) {
             for (size_t j = 0; j < S.convs.size(); ++j) out->push_back({(int)si, S.convs[j].Cout, S.convs[j].CoutP, g.O0[j], g.O1[j], g.O1[j], 0, -1});
         } else {
             const int nb = (int)S.bands.size();
@@ -285,6 +300,15 @@ void conv_forward(const TView& x, const DConv& c, const TView& out, int B, hipSt
     conv_gemm(ld, c.Wf, B * out.D0 * out.D1, c.CoutP, c.Kf, EpiConvOut{out, c.bias, c.act, FastDiv(out.D0 * out.D1), FastDiv(out.D1)}, st);
 }
 
+// grouped Conv1d of an MSD (disc_msd_kernels.h): fp32 MFMA in every precision mode
+void gconv_forward(const TView& x, const DConv& c, const TView& out, int B, hipStream_t st) {
+    const int M = B * out.D0, Cin = c.Cin * c.groups;
+    DTrace tr(st, "fwd", c.prefix.c_str(), M, c.Cout, c.Cin * c.T0);
+    const unsigned nb = blk((long long)((M + 15) / 16) * (c.Cout / 16), 4);
+    if (c.Cout / c.groups == 16) hipLaunchKernelGGL(msd_gconv_fwd_kernel<1>, dim3(nb), dim3(256), 0, st, x.p, c.Wf, c.bias, out.p, M, out.D0, x.D0, Cin, c.Cout);
+    else hipLaunchKernelGGL(msd_gconv_fwd_kernel<4>, dim3(nb), dim3(256), 0, st, x.p, c.Wf, c.bias, out.p, M, out.D0, x.D0, Cin, c.Cout);
+}
+
 constexpr size_t DISC_DW_PART = (size_t)48 << 20;          // floats: 192 MB of partial sums (8 slices of the 1024 x 5120 gradient)
 
 // dW partial-sum launch (same scheme as train.hip's dw_launch)
@@ -349,7 +373,12 @@ int disc_dw(const LdA& la, const LdB& lb, int M, int Np, int Kp, float* dW, floa
 // ---------------------------------------------------------------------------------------------------------
 extern "C" int escx_disc_create(const escx_disc_config* cfg, int device, escx_disc* out) {
     if (!cfg || !out) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null argument");
-    if (cfg->n_rates != 0) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "MSD (rates) is not implemented: every ESC configuration uses rates = []");
+    if (cfg->n_rates < 0 || cfg->n_rates > 8) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "n_rates %d: 0 to 8 multi-scale discriminators", cfg->n_rates);
+    for (int i = 0; i < cfg->n_rates; ++i) {
+        if (cfg->rates[i] < 1) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "MSD rate %d: must be at least 1", cfg->rates[i]);
+        if (cfg->sample_rate < 1 || cfg->sample_rate % cfg->rates[i])
+            ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "MSD rate %d does not divide the sample rate %d: the resampler is implemented for integer decimation only", cfg->rates[i], cfg->sample_rate);
+    }
     if (cfg->n_periods < 0 || cfg->n_periods > 8 || cfg->n_ffts < 0 || cfg->n_ffts > 8 || cfg->n_bands < 1 || cfg->n_bands > 8)
         ESCX_FAIL(ESCX_ERR_INVALID_ARG, "bad discriminator configuration");
     escx_disc_s* d = new escx_disc_s();
@@ -362,6 +391,17 @@ extern "C" int escx_disc_create(const escx_disc_config* cfg, int device, escx_di
         const int ch[6] = {1, 32, 128, 512, 1024, 1024};
         for (int j = 0; j < 5; ++j) S.convs.push_back(make_conv(p + "convs." + std::to_string(j) + ".0.", ch[j], ch[j + 1], 5, 1, j < 4 ? 3 : 1, 1, 2, 0, 1));
         S.convs.push_back(make_conv(p + "conv_post.", 1024, 1, 3, 1, 1, 1, 1, 0, 0));
+        d->subs.push_back(S);
+    }
+    for (int i = 0; i < cfg->n_rates; ++i, ++idx) {      // discriminator.py:69-99
+        DSub S; S.kind = 2; S.arg = cfg->rates[i];
+        const std::string p = "discriminators." + std::to_string(idx) + ".";
+        const int ch[6] = {1, 16, 64, 256, 1024, 1024}, grp[5] = {0, 4, 16, 64, 256};
+        S.convs.push_back(make_conv(p + "convs.0.0.", 1, 16, 15, 1, 1, 1, 7, 0, 1));
+        for (int j = 1; j < 5; ++j) S.convs.push_back(make_gconv(p + "convs." + std::to_string(j) + ".0.", ch[j], ch[j + 1], grp[j]));
+        S.convs.push_back(make_conv(p + "convs.5.0.", 1024, 1024, 5, 1, 1, 1, 2, 0, 1));
+        S.convs.push_back(make_conv(p + "conv_post.", 1024, 1, 3, 1, 1, 1, 1, 0, 0));
+        if (S.arg > 1) { S.width = (int)std::ceil(24.0 * S.arg / 0.945); S.ntaps = 2 * S.width + S.arg; }
         d->subs.push_back(S);
     }
     for (int i = 0; i < cfg->n_ffts; ++i, ++idx) {
@@ -390,6 +430,7 @@ extern "C" int escx_disc_create(const escx_disc_config* cfg, int device, escx_di
             wf += pad64((size_t)c.CoutP * c.Kf) + pad64((size_t)c.CinR * c.Kt) + pad64(c.CoutP) + pad64(2 * c.Cout) + pad64(c.wp_floats);
         }
         if (S.kind == 1) wf += 2 * pad64((size_t)2 * S.Fq * S.arg);
+        if (S.kind == 2) wf += pad64(S.ntaps);
     }
     d->total = off;
     hipError_t e = hipSetDevice(device);
@@ -417,6 +458,24 @@ extern "C" int escx_disc_create(const escx_disc_config* cfg, int device, escx_di
             (void)hipMemcpy(S.DT, hT.data(), hT.size() * sizeof(float), hipMemcpyHostToDevice);
         }
     }
+    for (DSub& S : d->subs)
+        if (S.kind == 2) {      // resampler taps: windowed sinc at the cutoff 0.945 / rate, 24 zero crossings, in double, normalised to sum 1
+            std::vector<double> k(S.ntaps, 1.0);
+            if (S.arg > 1) {
+                const double zeros = 24.0, cutoff = 0.945;
+                double sum = 0.0;
+                for (int j = 0; j < S.ntaps; ++j) {
+                    double t = (double)(j - S.width) / S.arg * cutoff;
+                    t = std::min(zeros, std::max(-zeros, t)) * M_PI;
+                    const double c = std::cos(t / zeros / 2.0);
+                    k[j] = (t == 0.0 ? 1.0 : std::sin(t) / t) * c * c; sum += k[j];
+                }
+                for (double& v : k) v /= sum;
+            }
+            std::vector<float> kf(k.begin(), k.end());
+            S.taps = take(S.ntaps);
+            (void)hipMemcpy(S.taps, kf.data(), kf.size() * sizeof(float), hipMemcpyHostToDevice);
+        }
     *out = d;
     return ESCX_OK;
 }
@@ -473,7 +532,7 @@ size_t front_floats(escx_disc_s* d, int B, int L) {
     size_t n = pad64((size_t)B * L) + pad64((size_t)4 * B);
     for (const DSub& S : d->subs) {
         const SubGeom g = geometry(S, L);
-        if (S.kind == 0) n += pad64((size_t)B * g.D0 * g.D1 * 4);
+        if (S.kind != 1) n += pad64((size_t)B * g.D0 * g.D1 * 4);
         else { n += pad64((size_t)B * g.T * 2 * S.Fq); for (int f : g.bandF) n += pad64((size_t)B * g.T * f * 4); }
     }
     return n;
@@ -493,6 +552,10 @@ void build_front(escx_disc_s* d, const float* wave, int B, int L, float* base, s
         if (S.kind == 0) {
             float* in = take((size_t)B * g.D0 * g.D1 * 4);
             hipLaunchKernelGGL(mpd_input_kernel, dim3(blk((long long)B * g.D0 * g.D1)), dim3(256), 0, st, y, in, B, L, g.D0, S.arg);
+            v.push_back(in); specs->push_back(nullptr);
+        } else if (S.kind == 2) {
+            float* in = take((size_t)B * g.D0 * 4);
+            hipLaunchKernelGGL(msd_resample_kernel, dim3(blk((long long)B * g.D0)), dim3(256), 0, st, y, S.taps, in, B, L, g.D0, S.arg, S.width, S.ntaps);
             v.push_back(in); specs->push_back(nullptr);
         } else {
             const int w = S.arg, hop = w / 4;
@@ -520,6 +583,7 @@ extern "C" int escx_disc_forward(escx_disc d, const float* flat_params, int64_t 
     tls_conv_bf16 = d->precision;
     int maxp = 1; for (const DSub& S : d->subs) if (S.kind == 0) maxp = std::max(maxp, S.arg);
     if (L <= maxp + 1) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "clip too short for the reflect padding of the period discriminators");
+    for (const DSub& S : d->subs) if (S.kind == 2 && L < S.arg) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "clip of %d samples: shorter than the MSD rate %d", L, S.arg);
     std::vector<FmapShape> shp; fmap_shapes(d, L, &shp);
     int rc = check_map_sizes(shp, B); if (rc) return rc;
     if ((rc = ensure_scratch(d, front_floats(d, B, L) * sizeof(float)))) return rc;
@@ -536,11 +600,12 @@ extern "C" int escx_disc_forward(escx_disc d, const float* flat_params, int64_t 
         const DSub& S = d->subs[si];
         const SubGeom g = geometry(S, L);
         { const int q = disc_stream_of((int)si, nq); st = q ? d->aux[q - 1] : st0; }
-        if (S.kind == 0) {
+        if (S.kind != 1) {
             TView x{ins[si][0], g.D0, g.D1, g.D1, 4};
             for (size_t j = 0; j < S.convs.size(); ++j, ++fi) {
                 TView o = view_of(fmaps[fi], shp[fi]);
-                conv_forward(x, S.convs[j], o, B, st);
+                if (S.convs[j].groups) gconv_forward(x, S.convs[j], o, B, st);
+                else conv_forward(x, S.convs[j], o, B, st);
                 x = o;
             }
         } else {
@@ -574,6 +639,7 @@ extern "C" int escx_disc_backward(escx_disc d, const float* flat_params, int64_t
     ESCX_HIP(hipSetDevice(d->device));
     hipStream_t st = (hipStream_t)stream;
     tls_conv_bf16 = d->precision;
+    for (const DSub& S : d->subs) if (S.kind == 2 && L < S.arg) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "clip of %d samples: shorter than the MSD rate %d", L, S.arg);
     std::vector<FmapShape> shp; fmap_shapes(d, L, &shp);
     // scratch: front + gradient buffers of every feature-map BUFFER (concatenated buffers once) + input-map gradients + dW staging
     const size_t front = front_floats(d, B, L);
@@ -589,7 +655,7 @@ extern "C" int escx_disc_backward(escx_disc d, const float* flat_params, int64_t
                 else if (f.off1 == 0) gfl += pad64((size_t)B * f.D0 * f.P1 * f.Cp);
                 max_w = std::max(max_w, (size_t)S.convs[j].CoutP * S.convs[j].Kf + S.convs[j].CoutP);
             }
-            if (S.kind == 0) in_g = std::max(in_g, (size_t)B * g.D0 * g.D1 * 4);
+            if (S.kind != 1) in_g = std::max(in_g, (size_t)B * g.D0 * g.D1 * 4);
             else { for (int f : g.bandF) in_g = std::max(in_g, (size_t)B * g.T * f * 4); in_g = std::max(in_g, (size_t)B * g.T * std::max(2 * S.Fq, S.arg)); }
         }
     }
@@ -618,7 +684,7 @@ extern "C" int escx_disc_backward(escx_disc d, const float* flat_params, int64_t
         int f0 = 0;
         for (const DSub& S : d->subs) {
             const int nconv = (int)S.convs.size();
-            if (S.kind == 0) { for (int j = 0; j + 1 < nconv; ++j) fused[f0 + j] = dx_covers(S.convs[j + 1]); }
+            if (S.kind != 1) { for (int j = 0; j + 1 < nconv; ++j) fused[f0 + j] = dx_covers(S.convs[j + 1]); }
             else {
                 const int nb = (int)S.bands.size();
                 for (int b = 0; b < nb; ++b) for (int j = 0; j < 4; ++j) fused[f0 + b * 5 + j] = dx_covers(S.convs[b * 5 + j + 1]);
@@ -708,6 +774,40 @@ extern "C" int escx_disc_backward(escx_disc d, const float* flat_params, int64_t
         return 0;
     };
 
+    // the same for a grouped Conv1d of an MSD (disc_msd_kernels.h); its dX covers every position of the input map exactly once
+    auto glayer_bwd = [&](const DConv& c, const TView& x, const TView& yv, const TView& g, bool g_pre, const TView& gx, bool fin, const float* init,
+                          const float* xact) -> int {
+        const int M = B * yv.D0, Cin = c.Cin * c.groups;
+        if (!g_pre) hipLaunchKernelGGL(leaky_bwd_kernel, dim3(blk((long long)M * yv.Cp / 4)), dim3(256), 0, st, g, yv, (long long)M * yv.Cp / 4, B);
+        if (grad_flat) {
+            DTrace tr(st, "dW", c.prefix.c_str(), M, c.Cout, c.Cin * c.T0);
+            const size_t per = (size_t)c.Cout * MSD_KF + c.Cout;
+            const int tiles = c.Cout / 16;              // a wave per (16 output channels, row slice)
+            int slices = std::max(1, std::min((4096 + tiles - 1) / tiles, (M + 63) / 64));
+            slices = (int)std::max<size_t>(1, std::min<size_t>(slices, DISC_DW_PART / per));
+            const int mps = rup((M + slices - 1) / slices, 8);
+            slices = (M + mps - 1) / mps;
+            float* bpart = part + (size_t)slices * c.Cout * MSD_KF;
+            if (c.Cout / c.groups == 16)
+                hipLaunchKernelGGL(msd_gconv_dw_kernel<1>, dim3(blk(tiles, 4), slices), dim3(256), 0, st, g.p, x.p, part, bpart, M, yv.D0, x.D0, Cin, c.Cout, mps);
+            else
+                hipLaunchKernelGGL(msd_gconv_dw_kernel<4>, dim3(blk(tiles, 4), slices), dim3(256), 0, st, g.p, x.p, part, bpart, M, yv.D0, x.D0, Cin, c.Cout, mps);
+            launch_reduce_partials(part, slices, (long long)c.Cout * MSD_KF, dWs, 0, st);
+            launch_reduce_partials(bpart, slices, (long long)c.Cout, grad_flat + c.off_b, 0, st);
+            hipLaunchKernelGGL(wn_bwd_kernel, dim3(c.Cout), dim3(256), 0, st, dWs, flat_params + c.off_v, c.scale, grad_flat + c.off_v, grad_flat + c.off_g, c.Cin,
+                               c.T0 * c.T1, c.CinP, c.Kf);
+        }
+        {
+            DTrace tr(st, "dX", c.prefix.c_str(), B * x.D0, Cin, c.Cout / c.groups * ((c.T0 + c.s0 - 1) / c.s0));
+            const GradOut go{gx, init, xact, fin ? 1 : 0};
+            const long long mt = ((long long)B * ((x.D0 + MSD_STRIDE - 1) / MSD_STRIDE) + 15) / 16;
+            const dim3 grid(blk(mt * c.groups, 4));
+            if (c.Cout / c.groups == 16) hipLaunchKernelGGL(msd_gconv_dx_kernel<16>, grid, dim3(256), 0, st, g.p, c.Wf, go, B, yv.D0, x.D0, Cin, c.Cout);
+            else hipLaunchKernelGGL(msd_gconv_dx_kernel<4>, grid, dim3(256), 0, st, g.p, c.Wf, go, B, yv.D0, x.D0, Cin, c.Cout);
+        }
+        return 0;
+    };
+
     int fi_end = (int)shp.size();
     for (int si = (int)d->subs.size() - 1; si >= 0; --si) {
         const DSub& S = d->subs[si];
@@ -717,17 +817,22 @@ extern "C" int escx_disc_backward(escx_disc d, const float* flat_params, int64_t
         const int q = disc_stream_of(si, nq);
         st = q ? d->aux[q - 1] : st0;
         gin = gin_q[q]; gspec = gspec_q[q]; gfr = gfr_q[q]; dWs = dWs_q[q]; part = part_q[q]; dy = dy_q[q];
-        if (S.kind == 0) {
+        if (S.kind != 1) {
             for (int j = nconv - 1; j >= 0; --j) {
                 const int fi = f0 + j;
                 TView yv = view_of(fmaps[fi], shp[fi]);
                 TView x = j > 0 ? view_of(fmaps[fi - 1], shp[fi - 1]) : TView{ins[si][0], g.D0, g.D1, g.D1, 4};
-                if (j > 0) {
+                if (S.convs[j].groups) {        // (never the first layer)
+                    if ((rc = glayer_bwd(S.convs[j], x, yv, gv[fi], fused[fi], gv[fi - 1], fused[fi - 1], d_fmaps[fi - 1], S.convs[j - 1].act ? fmaps[fi - 1] : nullptr)))
+                        return rc;
+                } else if (j > 0) {
                     if ((rc = layer_bwd(S.convs[j], x, yv, gv[fi], fused[fi], &gv[fi - 1], nullptr, fused[fi - 1], d_fmaps[fi - 1], S.convs[j - 1].act ? fmaps[fi - 1] : nullptr)))
                         return rc;
                 } else { if ((rc = layer_bwd(S.convs[j], x, yv, gv[fi], fused[fi], nullptr, d_wave ? gin : nullptr, false, nullptr, nullptr))) return rc; }
             }
-            if (d_wave) hipLaunchKernelGGL(mpd_input_bwd_kernel, dim3(blk((long long)B * L)), dim3(256), 0, st, gin, dy, B, L, g.D0, S.arg);
+            if (d_wave && S.kind == 2)
+                hipLaunchKernelGGL(msd_resample_bwd_kernel, dim3(blk((long long)B * L)), dim3(256), 0, st, gin, S.taps, dy, B, L, g.D0, S.arg, S.width, S.ntaps);
+            else if (d_wave) hipLaunchKernelGGL(mpd_input_bwd_kernel, dim3(blk((long long)B * L)), dim3(256), 0, st, gin, dy, B, L, g.D0, S.arg);
         } else {
             const int nb = (int)S.bands.size();
             const int fpost = f0 + nconv - 1, ftop0 = f0 + 4;

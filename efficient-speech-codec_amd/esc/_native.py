@@ -29,7 +29,7 @@ class EscxRvqConfig(Structure):
 
 class EscxDiscConfig(Structure):
     _fields_ = [("sample_rate", c_int32), ("n_rates", c_int32), ("n_periods", c_int32), ("periods", c_int32 * 8), ("n_ffts", c_int32),
-                ("fft_sizes", c_int32 * 8), ("n_bands", c_int32), ("bands", (c_float * 2) * 8)]
+                ("fft_sizes", c_int32 * 8), ("n_bands", c_int32), ("bands", (c_float * 2) * 8), ("rates", c_int32 * 8)]
 
 
 class EscxDacConfig(Structure):

@@ -2,9 +2,11 @@
 
 Same constructor (`rates, periods, fft_sizes, sample_rate, bands`), same parameter names (`discriminators.{i}.convs.{j}.0.{bias,weight_g,
 weight_v}`, `...band_convs.{b}.{j}.0...`, `...conv_post...`: reference checkpoints load with `load_state_dict`), same call:
-`disc(x)` with x (B, 1, L) returns one list of feature maps (B, C, D0, D1) per sub-discriminator, differentiable w.r.t. the parameters and
-the waveform.  The convolutions, weight normalisation, matched-stride STFT and all backward passes run in libescx (csrc/disc.hip); there
-is no PyTorch/CPU implementation here.  MSD (`rates`) is not implemented - no ESC configuration uses it.
+`disc(x)` with x (B, 1, L) returns one list of feature maps per sub-discriminator, (B, C, D0, D1) for the period and spectrogram discriminators
+and (B, C, T) for the multi-scale ones (`rates`), differentiable w.r.t. the parameters and the waveform.  The convolutions, weight
+normalisation, matched-stride STFT, the MSD resampler and all backward passes run in libescx (csrc/disc.hip); there is no PyTorch/CPU
+implementation here.  A rate must divide the sample rate (integer decimation; DESIGN.md 14.1 defines the resampler, which restates the
+reference's audiotools / julius call without being pinned to it).
 """
 from __future__ import annotations
 
@@ -35,13 +37,19 @@ def _default_conv_precision() -> int:
 _DEFAULT_CONV_PRECISION = _default_conv_precision()      # see Discriminator.set_conv_precision
 
 
-def _conv_specs(periods, fft_sizes, n_bands):
-    """(prefix, Cout, Cin, T0, T1) of every convolution in the reference's construction order."""
+def _conv_specs(periods, fft_sizes, n_bands, rates=()):
+    """(prefix, Cout, Cin, T0, T1) of every convolution in the reference's construction order (MPDs, MSDs, MRDs).  T1 = 0 marks a Conv1d (MSD):
+    its weight_v is (Cout, Cin, T0) with Cin the channels PER GROUP."""
     out, idx = [], 0
     for _ in periods:
         p = f"discriminators.{idx}."
         ch = [1, 32, 128, 512, 1024, 1024]
         out += [(f"{p}convs.{j}.0.", ch[j + 1], ch[j], 5, 1) for j in range(5)] + [(f"{p}conv_post.", 1, 1024, 3, 1)]
+        idx += 1
+    for _ in rates:
+        p = f"discriminators.{idx}."
+        out += [(f"{p}convs.0.0.", 16, 1, 15, 0)] + [(f"{p}convs.{j}.0.", c, 4, 41, 0) for j, c in zip(range(1, 5), (64, 256, 1024, 1024))]
+        out += [(f"{p}convs.5.0.", 1024, 1024, 5, 0), (f"{p}conv_post.", 1, 1024, 3, 0)]
         idx += 1
     for _ in fft_sizes:
         p = f"discriminators.{idx}."
@@ -80,15 +88,23 @@ class Discriminator(nn.Module):
     def __init__(self, rates: list = [], periods: list = [2, 3, 5, 7, 11], fft_sizes: list = [2048, 1024, 512], sample_rate: int = 44100,
                  bands: list = BANDS):
         super().__init__()
-        if rates:
-            raise NotImplementedError("MSD (rates) is not implemented in the MI355X build; the ESC configurations use rates=[]")
+        if len(rates) > 8:
+            raise ValueError(f"{len(rates)} rates: at most 8 multi-scale discriminators")
+        for r in rates:
+            if int(r) != r or r < 1:
+                raise ValueError(f"MSD rate {r!r}: a positive integer")
+            if sample_rate % int(r):
+                raise NotImplementedError(f"MSD rate {r} does not divide the sample rate {sample_rate}: the resampler is implemented for integer decimation "
+                                          f"only (a non-dividing rate needs sample_rate // rate filter phases)")
+        rates = [int(r) for r in rates]
         self.cfg = dict(rates=list(rates), periods=list(periods), fft_sizes=list(fft_sizes), sample_rate=sample_rate, bands=[tuple(b) for b in bands])
-        for pfx, cout, cin, t0, t1 in _conv_specs(periods, fft_sizes, len(bands)):
-            fan_in = cin * t0 * t1
+        for pfx, cout, cin, t0, t1 in _conv_specs(periods, fft_sizes, len(bands), rates):
+            shape = (cout, cin, t0, t1) if t1 else (cout, cin, t0)
+            fan_in = cin * t0 * max(t1, 1)
             bound = 1.0 / math.sqrt(fan_in)
-            v = torch.empty(cout, cin, t0, t1).uniform_(-bound, bound)                   # nn.Conv2d default init, then weight_norm: g = ||v||
+            v = torch.empty(*shape).uniform_(-bound, bound)                              # nn.Conv2d / nn.Conv1d default init, then weight_norm: g = ||v||
             _attach(self, pfx + "bias", torch.empty(cout).uniform_(-bound, bound), False)
-            _attach(self, pfx + "weight_g", v.flatten(1).norm(dim=1).view(cout, 1, 1, 1).clone(), False)
+            _attach(self, pfx + "weight_g", v.flatten(1).norm(dim=1).view(cout, *([1] * (len(shape) - 1))).clone(), False)
             _attach(self, pfx + "weight_v", v, False)
         self._handles, self._flat, self._carry = {}, {}, {}
         self._flat_grad_mode = False
@@ -178,7 +194,9 @@ class Discriminator(nn.Module):
         if idx not in self._handles:
             c = self.cfg
             cc = _native.EscxDiscConfig()
-            cc.sample_rate, cc.n_rates, cc.n_periods, cc.n_ffts, cc.n_bands = c["sample_rate"], 0, len(c["periods"]), len(c["fft_sizes"]), len(c["bands"])
+            cc.sample_rate, cc.n_rates, cc.n_periods, cc.n_ffts, cc.n_bands = c["sample_rate"], len(c["rates"]), len(c["periods"]), len(c["fft_sizes"]), len(c["bands"])
+            for i, r in enumerate(c["rates"]):
+                cc.rates[i] = r
             for i, p in enumerate(c["periods"]):
                 cc.periods[i] = p
             for i, w in enumerate(c["fft_sizes"]):
@@ -268,7 +286,8 @@ class Discriminator(nn.Module):
         wave = x[:, 0].to(torch.float32).contiguous()
         bufs = _DiscFn.apply(self, wave, (layout, bool(detach_params), int(grad_clips)), *self.parameters())
         out, bi = [], 0
-        n_sub = len(self.cfg["periods"]) + len(self.cfg["fft_sizes"])
+        n_per, n_msd = len(self.cfg["periods"]), len(self.cfg["rates"])
+        n_sub = n_per + n_msd + len(self.cfg["fft_sizes"])
         per_sub = DiscOutput(FeatureMaps() for _ in range(n_sub))
         per_sub.wave, per_sub.bufs, per_sub.layout = wave.detach(), tuple(b.detach() for b in bufs), layout
         for fm in per_sub:
@@ -281,7 +300,8 @@ class Discriminator(nn.Module):
                 if off1 == 0:
                     cat = bufs[bi]; bi += 1
                 buf = cat
-            per_sub[sub].append(buf[:, :, off1:off1 + D1, :C].permute(0, 3, 1, 2))
+            m = buf[:, :, off1:off1 + D1, :C].permute(0, 3, 1, 2)
+            per_sub[sub].append(m[..., 0] if n_per <= sub < n_per + n_msd else m)         # an MSD's maps are (B, C, T)
             per_sub[sub].entries.append((buf, C, Cp, D0, D1, P1, off1))
         return per_sub
 

@@ -317,16 +317,19 @@ int escx_adamw_step(float* param_flat_dev, const float* grad_flat_dev, float* ex
                     double lr, double beta1, double beta2, double eps, double weight_decay, const float* clip_dev, void* stream);
 
 /* ---- adversarial step: DAC discriminator + GAN losses (BASELINE configs[4]; scripts/trainer_adv.py:61-107) ---------------------------------
- * Reference: esc/models/discriminator.py:31-221 (MPD :31-66, MRD :105-176, Discriminator :179-215; MSD is not used by any ESC config),
- * esc/modules/loss/gan_loss.py:5-51.  Parameters: one flat fp32 device buffer in the order escx_disc_param_*() reports (the reference's
+ * Reference: esc/models/discriminator.py:31-221 (MPD :31-66, MSD :69-99, MRD :105-176, Discriminator :179-215), esc/modules/loss/gan_loss.py:5-51.
+ * Sub-discriminators in the reference's order: one MPD per period, one MSD per rate, one MRD per fft size.  An MSD resamples the pre-processed
+ * waveform to sample_rate / rate (integer decimation by a windowed-sinc FIR, DESIGN.md 14.1: the audiotools / julius resampler of the reference is
+ * restated, not pinned) and its feature maps are (B, C, T) tensors: D1 = P1 = 1, off1 = 0.  Parameters: one flat fp32 device buffer in the order escx_disc_param_*() reports (the reference's
  * named_parameters(): per convolution bias, weight_g, weight_v).  Feature maps are caller-owned channels-last buffers [B][D0][P1][Cp]
  * (escx_disc_fmap_shape); the reference's (B, C, D0, D1) tensor of map i is buffer[:, :, off1 : off1 + D1, :C] permuted (0, 3, 1, 2). */
 typedef struct {
     int32_t sample_rate;                 /* 16000                                                  */
-    int32_t n_rates;                     /* must be 0 (MSD unsupported)                            */
+    int32_t n_rates;                     /* 0 .. 8 multi-scale discriminators, see rates[] below   */
     int32_t n_periods; int32_t periods[8];      /* 2, 3, 5, 7, 11                                  */
     int32_t n_ffts; int32_t fft_sizes[8];       /* 2048, 1024, 512                                 */
     int32_t n_bands; float bands[8][2];         /* (0, .1), (.1, .25), (.25, .5), (.5, .75), (.75, 1) */
+    int32_t rates[8];                    /* read only when n_rates > 0: each >= 1 (else ESCX_ERR_INVALID_ARG) and a divisor of sample_rate (else ESCX_ERR_UNSUPPORTED) */
 } escx_disc_config;
 typedef struct escx_disc_s* escx_disc;
 int escx_disc_create(const escx_disc_config* cfg, int device, escx_disc* out);
