@@ -58,17 +58,28 @@ __device__ __forceinline__ void attn_split3(const float (&v)[8], bf16x8& t0, bf1
 // MFMA step whose other four k-slots per lane are zero (fused_attn.h proj_accumulate).  Attention streams carry THREE maxima in slot [0] - max |w| over the Q / K / V tiles
 // (their scale 2^k), over the V tiles alone, over the projection tiles (their own scale 2^kp) - and a third slot: [1] = {2^-k / sx, 2^k sx, sx, so}, [2] = {2^-kp / so};
 // so = the power-of-two scale of the O^T tiles, from |O| <= max |V| <= C max |w_V| B_x + max |b| (a softmax row is a convex combination of V rows).
+// PAIRED two-term attention streams (`pair`, fused_swin.hip attn_x3_pairing): a head group's 16 dims fill half of the 32-deep fp16 step, so two groups A, B share the projection's
+// MFMAs.  Stream unit = eight tiles [Q_A K_A V_A Q_B K_B V_B P_0 P_1] (pair = 1; pair = 2, the two halves of a MODE 2 group: [Q_lo K_lo Q_hi K_hi V_lo V_hi P_0 P_1]) - the same
+// tile count, bytes and stage structure as two single groups.  P_0 holds output tiles [0, KH), P_1 tiles [KH, KK), KH = ceil(KK / 2) = KS: output tile KH h + j = fragments 2 j (hi terms)
+// and 2 j + 1 (lo terms) of P_h, lane (channel l15, lg) = {A's dims 4 lg .. 4 lg + 3 | B's dims 4 lg .. 4 lg + 3}: all eight k-slots of the lane are real.  Each P tile is
+// self-contained (both terms of its output tiles), so the walk is the same when the two sit in different stages.  No unread piece: a Q / K / V tile is 2 KS = TF fragments,
+// P_0 is 2 KH = 2 KS fragments; only an ODD KK leaves P_1 two fragments short of TF (CP = 80, 144) - the same 2 KiB per two groups that the single
+// form's KK-of-(KK + 1) projection tiles leave.
 // `tail`: the trailer's first slot.  The trailer closes the image's ALLOCATION, which has the three-term size for both forms (set_precision re-packs in place), so it
 // does not move with TF: fused_swin.hip attn_x3_trailer / rowgemm_x3_trailer are the one definition, for the packers and (x3_scale) the launchers and kernels.
 __global__ __launch_bounds__(256) void attn_x3_pack_kernel(const f32x4* __restrict__ waf, bf16x8* __restrict__ out, bf16x8* __restrict__ tail, int n_tiles, int TPG, int KK, int KS, int TF, unsigned proj_mask, int NT = 3,
                                                            const float* __restrict__ gamma = nullptr, const float* __restrict__ beta = nullptr, int n_ln = 0, int C = 0,
-                                                           const float* __restrict__ bqkv = nullptr, int n_bqkv = 0) {
+                                                           const float* __restrict__ bqkv = nullptr, int n_bqkv = 0, int pair = 0) {
     const int per_tile = (KS > KK ? KS : KK) * 64;
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= (long long)n_tiles * per_tile) return;
     const int tile = (int)(idx / per_tile), r = (int)(idx - (long long)tile * per_tile), f = r >> 6, lane = r & 63;
     const f32x4* src = waf + (size_t)tile * KK * 64;
-    bf16x8* dst = out + (size_t)tile * TF * 64;
+    // paired two-term stream: the source tile (group, tt) moves to its slot of the eight-tile unit; `ph` = which eight bytes of a projection operand this source tile fills
+    int dtile = tile, unit = 0, ph = 0;
+    if (pair == 1) { const int grp = tile / TPG, tt = tile % TPG; unit = grp >> 1; ph = grp & 1; dtile = unit * 8 + 3 * ph + tt; }
+    else if (pair == 2) { const int tt = tile % TPG; unit = tile / TPG; ph = tt == 7; dtile = unit * 8 + (tt == 6 ? 5 : tt); }
+    bf16x8* dst = out + (size_t)dtile * TF * 64;
     if ((proj_mask >> (tile % TPG)) & 1) {              // projection tile: fp32 fragments, copied - or (two-term attention stream) split lane by lane
         if (f < KK) {
             const f32x4 w = src[f * 64 + lane];
@@ -78,6 +89,12 @@ __global__ __launch_bounds__(256) void attn_x3_pack_kernel(const f32x4* __restri
                 bf16x8 t[2];
                 split_terms<2>(v, t, sc);
                 const f32x4 hi = __builtin_bit_cast(f32x4, t[0]), lo = __builtin_bit_cast(f32x4, t[1]);
+                if (pair) {
+                    const int KH = (KK + 1) / 2, hf = f >= KH, j = f - hf * KH;             // output tile f = fragments 2 j (hi), 2 j + 1 (lo) of P_hf; 2 KH = 2 KS <= TF
+                    float2* d = reinterpret_cast<float2*>(out + (size_t)(unit * 8 + 6 + hf) * TF * 64);
+                    d[((2 * j) * 64 + lane) * 2 + ph] = float2{hi[0], hi[1]};
+                    d[((2 * j + 1) * 64 + lane) * 2 + ph] = float2{lo[0], lo[1]};
+                } else
                 reinterpret_cast<f32x4*>(dst)[f * 64 + lane] = f32x4{hi[0], hi[1], lo[0], lo[1]};
             } else {
                 reinterpret_cast<f32x4*>(dst)[f * 64 + lane] = w;
@@ -186,11 +203,16 @@ template <int CP, int TMW, bool X3> constexpr int attn_min_waves_x() { return !X
 
 // An 8-wave workgroup takes SIMD slots in pairs, so a budget for 3 waves holds one workgroup where 4 would hold two.  The two-term one-head-per-tile kernels up to CP = 96
 // fit 128 registers (CP = 96: 130 without the request, 16 bytes of scratch with it); with the dense stream's 48 KiB of LDS two such workgroups fit a CU.
-template <int CP, int MODE, int TMW, int NW, bool X3, int NT> constexpr int attn_min_waves_f() { return (X3 && NT == 2 && NW == 8 && MODE == 0 && TMW == 1 && CP <= 96) ? 4 : attn_min_waves_x<CP, TMW, X3>(); }
+// The paired walk (PAIR, attn_x3_pack_kernel) keeps one projection operand instead of two and needs fewer registers in MODE 0 / 2; the two-heads-per-tile form at CP = 96 takes
+// 167 without the request (3 waves) and is asked for 128 like its single form, which fits them unasked.
+template <int CP, int MODE, int TMW, int NW, bool X3, int NT, bool PAIR = false> constexpr int attn_min_waves_f() {
+    return (X3 && NT == 2 && TMW == 1 && CP <= 96 && ((NW == 8 && MODE == 0) || (PAIR && MODE == 1))) ? 4 : attn_min_waves_x<CP, TMW, X3>();
+}
 
-template <int CP, int MODE, int UT, int TMW, int NW, bool TAPE = false, bool X3 = false, int NT = 3>
-__global__ __launch_bounds__(64 * NW, (attn_min_waves_f<CP, MODE, TMW, NW, X3, NT>())) void attn_fused_kernel(AttnArgs a) {
+template <int CP, int MODE, int UT, int TMW, int NW, bool TAPE = false, bool X3 = false, int NT = 3, bool PAIR = false>
+__global__ __launch_bounds__(64 * NW, (attn_min_waves_f<CP, MODE, TMW, NW, X3, NT, PAIR>())) void attn_fused_kernel(AttnArgs a) {
     static_assert(!X3 || !TAPE, "the split-operand form exists for the plain inference instantiations");
+    static_assert(!PAIR || (X3 && NT == 2), "paired head groups: the two-term instantiations (attn_x3_pack_kernel)");
     static_assert(NT == 3 || (NT == 2 && X3), "two fp16 terms: the split-operand instantiations");
 #ifdef ESCX_ATTN_PRIO
     __builtin_amdgcn_s_setprio(ESCX_ATTN_PRIO);     // tuning builds: static wave priority against co-running launches of the other batch part
@@ -527,6 +549,40 @@ __global__ __launch_bounds__(64 * NW, (attn_min_waves_f<CP, MODE, TMW, NW, X3, N
             if constexpr (!X3) { if (to + 1 < KK) ESCX_SGB_MFMA(8 * TMW); else ESCX_SGB_MFMA(4 * TMW); }
         }
     };
+    // Paired two-term projection: the O^T tiles of two head groups (MODE 2: of a group's two halves) fill all eight k-slots of a lane, 4 dims of A and 4 of B, so the three cross
+    // terms per output tile contract 32 real dims - 3 KK MFMAs per pair instead of 6 KK.  Tiles P_0 / P_1 of the stream unit (attn_x3_pack_kernel): output tiles [0, KH) / [KH, KK),
+    // fragments 2 j (hi) and 2 j + 1 (lo).  Same smallest-first order and two-accumulator interleave as the single form.
+    auto proj_pair = [&](const f32x4* oa, const f32x4* ob) {
+        if constexpr (PAIR) {
+            bf16x8 os[TMW][2];
+#pragma unroll
+            for (int t = 0; t < TMW; ++t) {
+                const float v8[8] = {oa[t][0], oa[t][1], oa[t][2], oa[t][3], ob[t][0], ob[t][1], ob[t][2], ob[t][3]};
+                split_terms<2>(v8, os[t], x2_so);
+            }
+            constexpr int KH = (KK + 1) / 2;
+#pragma unroll
+            for (int hf = 0; hf < 2; ++hf) {
+                begin_tile();
+                const bf16x8* tb = reinterpret_cast<const bf16x8*>(wb) + (size_t)(((tile - 1) % UT) * TF) * 64;
+                const int base = hf * KH, n = hf ? KK - KH : KH;
+#pragma unroll
+                for (int j = 0; j < n; j += 2) {
+                    const bool two = j + 1 < n;
+                    const bf16x8 wh = tb[(2 * j) * 64], wl = tb[(2 * j + 1) * 64];
+                    const bf16x8 wnh = tb[(two ? 2 * j + 2 : 2 * j) * 64], wnl = tb[(two ? 2 * j + 3 : 2 * j + 1) * 64];
+                    dma_pinned();
+                    const int to = base + j, tn = two ? to + 1 : to;
+#pragma unroll
+                    for (int t = 0; t < TMW; ++t) { acc[to][t] = mma_x<2>(wh, os[t][1], acc[to][t]); if (two) acc[tn][t] = mma_x<2>(wnh, os[t][1], acc[tn][t]); }
+#pragma unroll
+                    for (int t = 0; t < TMW; ++t) { acc[to][t] = mma_x<2>(wl, os[t][0], acc[to][t]); if (two) acc[tn][t] = mma_x<2>(wnl, os[t][0], acc[tn][t]); }
+#pragma unroll
+                    for (int t = 0; t < TMW; ++t) { acc[to][t] = mma_x<2>(wh, os[t][0], acc[to][t]); if (two) acc[tn][t] = mma_x<2>(wnh, os[t][0], acc[tn][t]); }
+                }
+            }
+        }
+    };
     // Per-group constants (q/k/v biases, relative-position bias rows) are fetched one head group ahead, right behind a stage
     // barrier: they land under a whole group of MFMA work, and the no-op pin behind the next group's first barrier (whose
     // vmcnt(0) has already drained everything) keeps the compiler from waiting at their first use with this stage's DMA in flight.
@@ -567,6 +623,117 @@ __global__ __launch_bounds__(64 * NW, (attn_min_waves_f<CP, MODE, TMW, NW, X3, N
 #pragma unroll
     for (int t = 0; t < TMW; ++t) shmask[t] = window_shift_mask(l15, lg, lastH[t], lastW[t]);
     GroupConst cur = load_consts(g0);
+    if constexpr (PAIR && MODE != 2) {
+        // Paired walk (two-term): groups g, g + 1 share one eight-tile stream unit; A's O^T (4 registers per window) is carried across B's Q / K / V, the
+        // projection runs once per pair.  The per-group constants keep their one-group-ahead prefetch inside a pair.
+        // The group body repeats the single walk's below on purpose: sharing it through a lambda changed the generated code of the fp32, bf16x3 and TAPE instantiations
+        // (registers and spills moved), which this form leaves as they were.  Keep the two in step.
+        for (int g = g0; g < g1; g += 2) {
+            tile = 0;
+            f32x4 op[2][TMW];
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                ESCX_TS(t0)
+                begin_tile();
+                pin_consts(cur);
+                const GroupConst nxt = load_consts(min(g + h + 1, g1 - 1));
+                ESCX_TS(t1)
+                f32x4 q[TMW], k[TMW], vt[TMW], p0[TMW], p1[TMW];
+                gemm_w_rows(q, cur.b[0]);
+#pragma unroll
+                for (int t = 0; t < TMW; ++t) q[t] *= a.scale;
+                begin_tile();
+                gemm_w_rows(k, cur.b[1]);
+                ESCX_TS(t2)
+#pragma unroll
+                for (int t = 0; t < TMW; ++t) {
+                    if constexpr (MODE == 0) {
+                        f32x4 s = zero4();
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) s = __builtin_amdgcn_mfma_f32_16x16x4f32(k[t][r], q[t][r], s, 0, 0, 0);
+                        p0[t] = window_softmax(s, cur.bt0, shmask[t], a.shifted);
+                    } else {
+                        f32x4 sa = zero4(), sb = zero4();
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            sa = __builtin_amdgcn_mfma_f32_16x16x4f32(k[t][r], lg < 2 ? q[t][r] : 0.f, sa, 0, 0, 0);
+                            sb = __builtin_amdgcn_mfma_f32_16x16x4f32(k[t][r], lg < 2 ? 0.f : q[t][r], sb, 0, 0, 0);
+                        }
+                        p0[t] = window_softmax(sa, cur.bt0, shmask[t], a.shifted);
+                        p1[t] = window_softmax(sb, cur.bt1, shmask[t], a.shifted);
+                    }
+                }
+                ESCX_TS(t3)
+                begin_tile();
+                gemm_x_rows(vt, f32x4{cur.bv0, cur.bv0, cur.bv0, cur.bv0});
+                ESCX_TS(t4)
+#pragma unroll
+                for (int t = 0; t < TMW; ++t) {
+                    f32x4 oa = zero4();
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) oa = __builtin_amdgcn_mfma_f32_16x16x4f32(vt[t][r], p0[t][r], oa, 0, 0, 0);
+                    if constexpr (MODE == 1) {
+                        f32x4 ob = zero4();
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) ob = __builtin_amdgcn_mfma_f32_16x16x4f32(vt[t][r], p1[t][r], ob, 0, 0, 0);
+                        op[h][t] = lg < 2 ? oa : ob;
+                    } else {
+                        op[h][t] = oa;
+                    }
+                }
+                ESCX_TS(t5)
+#ifdef ESCX_ATTN_TRACE          // the same six phases as the single walk, summed over both groups of a pair; the projection (tr[5]) once per pair
+                tr[0] += t1 - t0; tr[1] += t2 - t1; tr[2] += t3 - t2; tr[3] += t4 - t3; tr[4] += t5 - t4;
+#endif
+                cur = nxt;
+            }
+            ESCX_TS(t6)
+            proj_pair(op[0], op[1]);
+            ESCX_TS(t7)
+#ifdef ESCX_ATTN_TRACE
+            tr[5] += t7 - t6;
+#endif
+        }
+    } else if constexpr (PAIR) {
+        // MODE 2, stream unit [Q_lo K_lo Q_hi K_hi V_lo V_hi P_0 P_1]: the two halves of one head pair with each other, nothing crosses a group boundary
+        for (int g = g0; g < g1; ++g) {
+            tile = 0;
+            begin_tile();
+            pin_consts(cur);
+            const GroupConst nxt = load_consts(min(g + 1, g1 - 1));
+            f32x4 q[TMW], k[TMW], vt[TMW], s[TMW], p[TMW], op[2][TMW];
+#pragma unroll
+            for (int t = 0; t < TMW; ++t) s[t] = zero4();
+#pragma unroll
+            for (int half = 0; half < 2; ++half) {
+                if (half) begin_tile();
+                gemm_w_rows(q, cur.b[2 * half]);
+#pragma unroll
+                for (int t = 0; t < TMW; ++t) q[t] *= a.scale;
+                begin_tile();
+                gemm_w_rows(k, cur.b[2 * half + 1]);
+#pragma unroll
+                for (int t = 0; t < TMW; ++t)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) s[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(k[t][r], q[t][r], s[t], 0, 0, 0);
+            }
+#pragma unroll
+            for (int t = 0; t < TMW; ++t) p[t] = window_softmax(s[t], cur.bt0, shmask[t], a.shifted);
+#pragma unroll
+            for (int half = 0; half < 2; ++half) {
+                begin_tile();
+                { const float bvh = half ? cur.bv1 : cur.bv0; gemm_x_rows(vt, f32x4{bvh, bvh, bvh, bvh}); }
+#pragma unroll
+                for (int t = 0; t < TMW; ++t) {
+                    op[half][t] = zero4();
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) op[half][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(vt[t][r], p[t][r], op[half][t], 0, 0, 0);
+                }
+            }
+            proj_pair(op[0], op[1]);
+            cur = nxt;
+        }
+    } else
     for (int g = g0; g < g1; ++g) {
         tile = 0;
         ESCX_TS(t0)

@@ -253,7 +253,7 @@ int rowgemm_x3_pack(const float* wf, void* image, int KP, int Np, hipStream_t s,
         ESCX_LAUNCH(absmax_bits_kernel, dim3((unsigned)std::min<long long>(256, (n + 255) / 256)), dim3(256), 0, s, wf, n, mx);
     }
     ESCX_LAUNCH(attn_x3_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const f32x4*>(wf), reinterpret_cast<bf16x8*>(image),
-                       reinterpret_cast<bf16x8*>(rowgemm_x3_trailer(image, KP, Np)), NT, 1, KK, KS, (nt == 2 ? 2 : 3) * KS, 0u, nt == 2 ? 2 : 3, gamma, beta, KP, C, (const float*)nullptr, 0);
+                       reinterpret_cast<bf16x8*>(rowgemm_x3_trailer(image, KP, Np)), NT, 1, KK, KS, (nt == 2 ? 2 : 3) * KS, 0u, nt == 2 ? 2 : 3, gamma, beta, KP, C, (const float*)nullptr, 0, 0);
     return 0;
 }
 
@@ -325,8 +325,18 @@ int deembed7_fused(const float* tok, int B, int H, int W, int Cp, const float* w
 }
 
 // ---- fused window attention --------------------------------------------------------------------
+// Paired head groups of the two-term stream (fused_attn.h attn_x3_pack_kernel): 0 = single groups, 1 = groups (2 i, 2 i + 1) share a stream unit and their projection MFMAs,
+// 2 = the two halves of every MODE 2 group do.  Geometry only - one rule for the packer, the launcher and every batch.  An even group count leaves every workgroup of the
+// head-group split (thirds) whole pairs.  Odd counts (C = 45: 3 groups) stay single; so does C = 384 (packed kernel: at the register limit, not built).
+// attn_x3_fused: the (width, head mapping) pairs that have split-operand instantiations of attn_fused_kernel (the ESC configurations); only those ever read a paired image,
+// so the pairing rule is tied to the same list (everything else runs the float32 kernel on the float32 stream).
+static constexpr bool attn_x3_fused(int Cp, int mode) {
+    return (Cp == 48 && mode == 0) || (Cp == 80 && (mode == 0 || mode == 2)) || (Cp == 96 && mode != 2) || (Cp == 144 && mode != 2) || (Cp == 192 && mode == 1);
+}
+static int attn_x3_pairing(int Cp, int mode, int n_groups) { return (!attn_x3_fused(Cp, mode) || Cp < 80) ? 0 : (mode == 2 ? 2 : (n_groups % 2 == 0 ? 1 : 0)); }
+
 template <int CP, int MODE, int NW>
-static int launch_attn(const AttnArgs& a, hipStream_t s) {
+static int launch_attn(const AttnArgs& a, hipStream_t s, bool pair) {
     constexpr int UT = CP <= 96 ? 4 : (CP <= 192 ? 2 : 1);
     constexpr int TMW = attn_windows_per_wave(CP);
     const int per_block = TMW * NW;
@@ -341,7 +351,7 @@ static int launch_attn(const AttnArgs& a, hipStream_t s) {
         return ESCX_COMB_UNSUPPORTED;
     }
     // split-operand (3 x bf16) Q / K / V projections: the (width, head mapping) pairs of the ESC configurations
-    if constexpr ((CP == 48 && MODE == 0) || (CP == 80 && (MODE == 0 || MODE == 2)) || (CP == 96 && MODE != 2) || (CP == 144 && MODE != 2) || (CP == 192 && MODE == 1)) {
+    if constexpr (attn_x3_fused(CP, MODE)) {
         if (a.x3_wf) {
             auto kern = attn_fused_kernel<CP, MODE, UT, TMW, NW, false, true>;
             auto kern2 = attn_fused_kernel<CP, MODE, UT, TMW, NW, false, true, 2>;        // two fp16 terms (split_terms.h)
@@ -356,6 +366,20 @@ static int launch_attn(const AttnArgs& a, hipStream_t s) {
                     done.fetch_or(bit, std::memory_order_relaxed);
                 }
             }
+            if constexpr (CP >= 80) {
+                if (a.x3_scale && pair) {
+                    auto kern2p = attn_fused_kernel<CP, MODE, UT, TMW, NW, false, true, 2, true>;
+                    if constexpr (lds2 > 48 * 1024) {
+                        static std::atomic<unsigned> donep{0};
+                        int dev = 0; (void)hipGetDevice(&dev);
+                        const unsigned bit = 1u << (dev & 31);
+                        if (!(donep.load(std::memory_order_relaxed) & bit)) { (void)hipFuncSetAttribute((const void*)kern2p, hipFuncAttributeMaxDynamicSharedMemorySize, lds2); donep.fetch_or(bit, std::memory_order_relaxed); }
+                    }
+                    ESCX_LAUNCH(kern2p, dim3(((a.n_windows + per_block - 1) / per_block) * gs), dim3(64 * NW), lds2, s, a);
+                    return 0;
+                }
+            }
+            if (pair) return -1;            // a paired image has no single walk
             if (a.x3_scale) ESCX_LAUNCH(kern2, dim3(((a.n_windows + per_block - 1) / per_block) * gs), dim3(64 * NW), lds2, s, a);
             else ESCX_LAUNCH(kern, dim3(((a.n_windows + per_block - 1) / per_block) * gs), dim3(64 * NW), lds, s, a);
             return 0;
@@ -366,18 +390,18 @@ static int launch_attn(const AttnArgs& a, hipStream_t s) {
 }
 
 template <int CP>
-static int launch_attn_cp(int mode, int nw, const AttnArgs& a, hipStream_t s) {
+static int launch_attn_cp(int mode, int nw, const AttnArgs& a, hipStream_t s, bool pair) {
     if (nw == 8) {
         switch (mode) {
-            case 0: return launch_attn<CP, 0, 8>(a, s);
-            case 1: return launch_attn<CP, 1, 8>(a, s);
-            case 2: return launch_attn<CP, 2, 8>(a, s);
+            case 0: return launch_attn<CP, 0, 8>(a, s, pair);
+            case 1: return launch_attn<CP, 1, 8>(a, s, pair);
+            case 2: return launch_attn<CP, 2, 8>(a, s, pair);
         }
     } else {
         switch (mode) {
-            case 0: return launch_attn<CP, 0, 4>(a, s);
-            case 1: return launch_attn<CP, 1, 4>(a, s);
-            case 2: return launch_attn<CP, 2, 4>(a, s);
+            case 0: return launch_attn<CP, 0, 4>(a, s, pair);
+            case 1: return launch_attn<CP, 1, 4>(a, s, pair);
+            case 2: return launch_attn<CP, 2, 4>(a, s, pair);
         }
     }
     return -1;
@@ -418,7 +442,8 @@ static char* attn_x3_trailer(const void* image, int Cp, int mode, int n_groups) 
 // nt == 2: the two-term fp16 form of the stream (split_terms.h): weights scaled by the power of two of the block's max |w|, scales in the trailer
 int attn_x3_pack(const float* waf, void* image, int Cp, int mode, int n_groups, hipStream_t s, int nt, const float* gamma, const float* beta, int C, const float* bqkv) {
     const int KK = Cp / 16, KS = attn_x3_ks(Cp), TF = attn_x3_tf(Cp, nt == 2 ? 2 : 3), TPG = mode == 2 ? 8 : 4;
-    const unsigned proj_mask = mode == 2 ? ((1u << 5) | (1u << 7)) : (1u << 3);        // stream order [Q, K, V, P] / [Q_lo, K_lo, Q_hi, K_hi, V_lo, P_lo, V_hi, P_hi]
+    const unsigned proj_mask = mode == 2 ? ((1u << 5) | (1u << 7)) : (1u << 3);        // order of the fp32 stream: [Q, K, V, P] / [Q_lo, K_lo, Q_hi, K_hi, V_lo, P_lo, V_hi, P_hi]
+    const int pair = nt == 2 ? attn_x3_pairing(Cp, mode, n_groups) : 0;
     const int n_tiles = n_groups * TPG;
     (void)hipMemsetAsync(image, 0, attn_x3_bytes(Cp, mode, n_groups), s);
     const long long total = (long long)n_tiles * (KS > KK ? KS : KK) * 64;
@@ -432,7 +457,7 @@ int attn_x3_pack(const float* waf, void* image, int Cp, int mode, int n_groups, 
         ESCX_LAUNCH(absmax_tiles_bits_kernel, grid, dim3(256), 0, s, waf, n, KK * 256, TPG, proj_mask, mx + 2);
     }
     ESCX_LAUNCH(attn_x3_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const f32x4*>(waf), reinterpret_cast<bf16x8*>(image),
-                       reinterpret_cast<bf16x8*>(attn_x3_trailer(image, Cp, mode, n_groups)), n_tiles, TPG, KK, KS, TF, proj_mask, nt == 2 ? 2 : 3, gamma, beta, Cp, C, bqkv, n_groups * (mode == 2 ? 6 : 3) * 16);
+                       reinterpret_cast<bf16x8*>(attn_x3_trailer(image, Cp, mode, n_groups)), n_tiles, TPG, KK, KS, TF, proj_mask, nt == 2 ? 2 : 3, gamma, beta, Cp, C, bqkv, n_groups * (mode == 2 ? 6 : 3) * 16, pair);
     return 0;
 }
 
@@ -442,6 +467,8 @@ int attn_fused(const float* src, float* dst, int Cp, int C, int mode, int n_grou
                const AttnTape* tape, const void* x3_wf, int x3_nt) {
     int gs = gs_io ? *gs_io : 1;        // head-group split: same in/out convention as mlp_fused
     if (gs > 1 && (!partial || n_groups % gs)) gs = 1;
+    const int pairing = (!tape && x3_wf && x3_nt == 2) ? attn_x3_pairing(Cp, mode, n_groups) : 0;
+    if (pairing == 1 && (n_groups / gs) % 2) gs = 1;         // a workgroup's share is whole pairs
     if (gs_io) *gs_io = gs;
     AttnArgs a{src, dst, gamma, beta, reinterpret_cast<const f32x4*>(wf), bqkv, bias_tab, bproj, map, slots, tokens, n_windows,
                nWh, nWw, shifted, C, n_groups, scale, 1e-5f, gs, partial, rows, g_mlp_trace,
@@ -459,17 +486,17 @@ int attn_fused(const float* src, float* dst, int Cp, int C, int mode, int n_grou
         }
     }
     switch (Cp) {
-        case 16: return launch_attn_cp<16>(mode, nw, a, s);
-        case 32: return launch_attn_cp<32>(mode, nw, a, s);
-        case 48: return launch_attn_cp<48>(mode, nw, a, s);
-        case 64: return launch_attn_cp<64>(mode, nw, a, s);
-        case 80: return launch_attn_cp<80>(mode, nw, a, s);
-        case 96: return launch_attn_cp<96>(mode, nw, a, s);
-        case 128: return launch_attn_cp<128>(mode, nw, a, s);
-        case 144: return launch_attn_cp<144>(mode, nw, a, s);
-        case 192: return launch_attn_cp<192>(mode, nw, a, s);
-        case 256: return launch_attn_cp<256>(mode, nw, a, s);
-        case 384: return launch_attn_cp<384>(mode, nw, a, s);
+        case 16: return launch_attn_cp<16>(mode, nw, a, s, pairing != 0);
+        case 32: return launch_attn_cp<32>(mode, nw, a, s, pairing != 0);
+        case 48: return launch_attn_cp<48>(mode, nw, a, s, pairing != 0);
+        case 64: return launch_attn_cp<64>(mode, nw, a, s, pairing != 0);
+        case 80: return launch_attn_cp<80>(mode, nw, a, s, pairing != 0);
+        case 96: return launch_attn_cp<96>(mode, nw, a, s, pairing != 0);
+        case 128: return launch_attn_cp<128>(mode, nw, a, s, pairing != 0);
+        case 144: return launch_attn_cp<144>(mode, nw, a, s, pairing != 0);
+        case 192: return launch_attn_cp<192>(mode, nw, a, s, pairing != 0);
+        case 256: return launch_attn_cp<256>(mode, nw, a, s, pairing != 0);
+        case 384: return launch_attn_cp<384>(mode, nw, a, s, pairing != 0);
         default: return -1;
     }
 }
