@@ -74,6 +74,13 @@ struct escx_dac_s {
     // every re-pack of wbuf and set by refresh_wt, as w16_valid is.  Calls that never differentiate pay nothing.
     float* wt = nullptr; bool wt_valid = false;
     float* wte = nullptr; bool wte_valid = false;   // escx_dac_encode_backward: the same for the encoder's layers
+    // escx_dac_set_grad_precision, read at each backward call.  bf16x3: three bf16 planes of the whole transposed image wt[0, wt_floats) (plane p at
+    // wt16 + p * wt_floats) and of wte likewise, allocated at the first backward in that mode and split from whatever fp32 image is current:
+    // wt16_valid / wte16_valid are cleared wherever wt_valid / wte_valid are and set by refresh_wt16.  Handles that never ask for the mode pay nothing.
+    int grad_precision = ESCX_PRECISION_FP32;
+    size_t wt_floats = 0, wte_floats = 0;
+    __bf16* wt16 = nullptr; bool wt16_valid = false;
+    __bf16* wte16 = nullptr; bool wte16_valid = false;
     // escx_dac_decode_backward_params: the slices' partial dW tiles, the staged dW and the bias / alpha partial rows; allocated at the first
     // parameter backward of the handle, sized from the configuration alone (param_ws_plan)
     float* pw = nullptr;
@@ -124,6 +131,7 @@ int conv_out_len(int T, const DacLayer& l, bool padding) {
 int pack(escx_dac_s* d, const float* flat, long long version, hipStream_t st) {
     if (version >= 0 && version == d->packed_version && flat == d->packed_ptr && (int)d->padding == d->packed_padding) return 0;
     d->packed_version = version; d->packed_ptr = flat; d->packed_padding = d->padding; d->w16_valid = false; d->wt_valid = false; d->wte_valid = false;
+    d->wt16_valid = false; d->wte16_valid = false;
     for (auto* L : {&d->enc, &d->dec})
         for (DacLayer& l : *L) {
             if (l.kind == 0)
@@ -442,6 +450,8 @@ extern "C" void escx_dac_destroy(escx_dac d) {
     if (d->w16) (void)hipFree(d->w16);
     if (d->wt) (void)hipFree(d->wt);
     if (d->wte) (void)hipFree(d->wte);
+    if (d->wt16) (void)hipFree(d->wt16);
+    if (d->wte16) (void)hipFree(d->wte16);
     if (d->pw) (void)hipFree(d->pw);
     if (d->qoffs_dev) (void)hipFree(d->qoffs_dev);
     if (d->scratch) (void)hipFree(d->scratch);
@@ -473,6 +483,17 @@ extern "C" int escx_dac_set_precision(escx_dac d, int mode) {
     return ESCX_OK;
 }
 extern "C" int escx_dac_get_precision(escx_dac d) { return d ? d->precision : -1; }
+
+extern "C" int escx_dac_set_grad_precision(escx_dac d, int mode) {
+    if (!d) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null handle");
+    if (mode == ESCX_PRECISION_F16X2)
+        ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "DAC has no f16x2 backward: two fp16 terms need an a-priori bound on every operand (csrc/split_terms.h) and neither "
+                                        "the output gradients nor Snake outputs have one; bf16x3 keeps fp32's exponent range and needs no bound");
+    if (mode != ESCX_PRECISION_FP32 && mode != ESCX_PRECISION_BF16X3) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "DAC grad precision %d: expected fp32 (0) or bf16x3 (3)", mode);
+    d->grad_precision = mode;
+    return ESCX_OK;
+}
+extern "C" int escx_dac_get_grad_precision(escx_dac d) { return d ? d->grad_precision : -1; }
 
 extern "C" int escx_dac_set_padding(escx_dac d, int on) {
     if (!d) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null handle");
@@ -672,6 +693,7 @@ int refresh_wt(escx_dac_s* d, hipStream_t st) {
     if (!d->wt) {
         size_t n = 0;
         for (const DacLayer& l : d->dec) n += pad64((size_t)np_t(l) * kp_t(l));
+        d->wt_floats = n;
         ESCX_HIP(hipMalloc((void**)&d->wt, n * sizeof(float)));
         ESCX_HIP(hipMemsetAsync(d->wt, 0, n * sizeof(float), st));
         size_t cur = 0;
@@ -684,9 +706,37 @@ int refresh_wt(escx_dac_s* d, hipStream_t st) {
     return launch_ok("dac_transpose_weights");
 }
 
+// The three-plane bf16 mirror of a transposed image (wt or wte), for the backward calls that run in bf16x3.  Called after refresh_wt / refresh_wte on
+// the same stream: refresh_w16's scheme, the exact three-term split of whatever fp32 image is current, once per re-pack and once after the mode is
+// first switched on.  The images' pad rows and columns are zeros and split into zeros.
+int refresh_wt16(const escx_dac_s* d, const float* img, size_t floats, __bf16** img16, bool* valid, hipStream_t st) {
+    if (d->grad_precision != ESCX_PRECISION_BF16X3 || *valid) return 0;
+    if (!*img16) ESCX_HIP(hipMalloc((void**)img16, 3 * floats * sizeof(__bf16)));
+    const size_t n4 = floats / 4;
+    hipLaunchKernelGGL(split3_bf16_kernel, dim3((unsigned)std::min<size_t>((n4 + 255) / 256, 4096)), dim3(256), 0, st, img, *img16, n4, floats);
+    *valid = true;
+    return launch_ok("dac_split_transposed_weights");
+}
+
+// What a backward pass needs besides the layer: the stream and, in bf16x3 grad mode, the mirror of the transposed image the layers' Wt point into
+// (w16 == nullptr: fp32 grad mode).  The layers that run on the bf16 matrix cores are the forward's (x3_layer).
+struct GradRun {
+    hipStream_t st; const float* wt; const __bf16* w16; size_t plane;
+    const __bf16* mirror(const DacLayer& l, const float* W) const { return (w16 && x3_layer(l)) ? w16 + (W - wt) : nullptr; }
+};
+
+// The tile rule is launch_conv's: by the layer's tile count (fp32) or launch_dac_x3's, and no output bit depends on it.
+template <class Epi>
+void launch_grad(const GradRun& run, const __bf16* W16, const float* W, const DacConvA& ld, int Np, int Kp, const Epi& ep) {
+    const long long tiles = (long long)((ld.M + 127) / 128) * ((Np + 95) / 96);
+    if (W16) launch_dac_x3(ld, W16, run.plane, ld.M, Np, Kp, ep, run.st);
+    else if (tiles >= 512) launch_gemm<128>(ld, W, ld.M, Np, Kp, ep, run.st);
+    else launch_gemm<64>(ld, W, ld.M, Np, Kp, ep, run.st);
+}
+
 // dX of layer l from dY (B, Tdy, cpad(Cout)):  out (B, Tx, cpad(Cin)) = [res +] conv^T(dY) * snake'(xs), or d_z (B, zD, Tx) when there is no Snake
-// in front (the first convolution).  The tile rule is launch_conv's: by the layer's tile count, and no output bit depends on it.
-void bwd_layer(hipStream_t st, const DacLayer& l, const DacSnake* sn, const float* dY, int B, int Tdy, int Tx, const float* xs, const float* res, float* out,
+// in front (the first convolution).
+void bwd_layer(const GradRun& run, const DacLayer& l, const DacSnake* sn, const float* dY, int B, int Tdy, int Tx, const float* xs, const float* res, float* out,
                int zD = 0) {
     DacConvA ld{};
     ld.x = dY; ld.alpha = nullptr; ld.inv = nullptr; ld.Tin = Tdy; ld.Cp = cpad(l.Cout); ld.dCp = FastDiv(ld.Cp);
@@ -696,10 +746,7 @@ void bwd_layer(hipStream_t st, const DacLayer& l, const DacSnake* sn, const floa
     DacGradEpi ep{};
     ep.out = out; ep.res = res; ep.xs = xs; ep.alpha = sn ? sn->a : nullptr; ep.inv = sn ? sn->inv : nullptr;
     ep.Cp = cpad(l.Cin); ep.D = zD; ep.T = Tx; ep.dT = ld.dT;
-    const int Np = np_t(l), Kp = kp_t(l);
-    const long long tiles = (long long)((ld.M + 127) / 128) * ((Np + 95) / 96);
-    if (tiles >= 512) launch_gemm<128>(ld, l.Wt, ld.M, Np, Kp, ep, st);
-    else launch_gemm<64>(ld, l.Wt, ld.M, Np, Kp, ep, st);
+    launch_grad(run, run.mirror(l, l.Wt), l.Wt, ld, np_t(l), kp_t(l), ep);
 }
 
 int tape_args(escx_dac_s* d, int B, int T, long long tape_floats, TapePlan* p) {
@@ -772,25 +819,26 @@ extern "C" int escx_dac_decode_backward(escx_dac d, const float* flat, int64_t v
                   hdr[1], (long long)version);
     const size_t mf = p.mf;
     if ((rc = ensure_scratch(d, 4 * mf * sizeof(float)))) return rc;
-    if ((rc = pack(d, flat, (long long)version, st)) || (rc = refresh_wt(d, st))) return rc;
+    if ((rc = pack(d, flat, (long long)version, st)) || (rc = refresh_wt(d, st)) || (rc = refresh_wt16(d, d->wt, d->wt_floats, &d->wt16, &d->wt16_valid, st))) return rc;
+    const GradRun run{st, d->wt, d->grad_precision == ESCX_PRECISION_BF16X3 ? d->wt16 : nullptr, d->wt_floats};
     float* G = d->scratch; float* G2 = G + mf; float* A = G2 + mf;
     auto M = [&](int i) { return tape + p.off[i]; };
     const DacLayer* Dl = d->dec.data(); const DacSnake* SN = d->dec_sn.data();
     const int nb = d->cfg.n_decoder_rates;
     const long long n = (long long)B * p.Lout;
     hipLaunchKernelGGL(dac_tanh_grad_in_kernel, dim3(nblk(n)), dim3(256), 0, st, d_audio, tape + p.audio, A, n);
-    bwd_layer(st, Dl[d->dec.size() - 1], SN + d->dec_sn.size() - 1, A, B, p.Lout, p.Ts[nb], M(7 * nb), nullptr, G);
+    bwd_layer(run, Dl[d->dec.size() - 1], SN + d->dec_sn.size() - 1, A, B, p.Lout, p.Ts[nb], M(7 * nb), nullptr, G);
     for (int i = nb - 1; i >= 0; --i) {
         const DacLayer* Lb = Dl + 1 + i * 7; const DacSnake* Sb = SN + i * 7;
         const int Tc = p.Ts[i + 1];
         for (int j = 2; j >= 0; --j) {                      // g_x = g + conv7^T(conv1^T(g) * snake'(h)) * snake'(x), in place in G
-            bwd_layer(st, Lb[2 + 2 * j], &Sb[2 + 2 * j], G, B, Tc, Tc, M(7 * i + 2 + 2 * j), nullptr, A);
-            bwd_layer(st, Lb[1 + 2 * j], &Sb[1 + 2 * j], A, B, Tc, Tc, M(7 * i + 1 + 2 * j), G, G);
+            bwd_layer(run, Lb[2 + 2 * j], &Sb[2 + 2 * j], G, B, Tc, Tc, M(7 * i + 2 + 2 * j), nullptr, A);
+            bwd_layer(run, Lb[1 + 2 * j], &Sb[1 + 2 * j], A, B, Tc, Tc, M(7 * i + 1 + 2 * j), G, G);
         }
-        bwd_layer(st, Lb[0], Sb, G, B, Tc, p.Ts[i], M(7 * i), nullptr, G2);
+        bwd_layer(run, Lb[0], Sb, G, B, Tc, p.Ts[i], M(7 * i), nullptr, G2);
         std::swap(G, G2);
     }
-    bwd_layer(st, Dl[0], nullptr, G, B, p.Ts[0], T, nullptr, nullptr, d_z, d->latent);
+    bwd_layer(run, Dl[0], nullptr, G, B, p.Ts[0], T, nullptr, nullptr, d_z, d->latent);
     return launch_ok("escx_dac_decode_backward");
 }
 
@@ -879,7 +927,7 @@ void param_layer(const escx_dac_s* d, const ParamWs& w, hipStream_t st, const Da
 }
 
 // bwd_layer for a layer behind a Snake, with v = conv^T(dY) kept in vout (DacGradEpiV): `out` has bwd_layer's bits
-void bwd_layer_v(hipStream_t st, const DacLayer& l, const DacSnake* sn, const float* dY, int B, int Tdy, int Tx, const float* xs, const float* res, float* out,
+void bwd_layer_v(const GradRun& run, const DacLayer& l, const DacSnake* sn, const float* dY, int B, int Tdy, int Tx, const float* xs, const float* res, float* out,
                  float* vout) {
     DacConvA ld{};
     ld.x = dY; ld.alpha = nullptr; ld.inv = nullptr; ld.Tin = Tdy; ld.Cp = cpad(l.Cout); ld.dCp = FastDiv(ld.Cp);
@@ -888,10 +936,7 @@ void bwd_layer_v(hipStream_t st, const DacLayer& l, const DacSnake* sn, const fl
     else { ld.rs = l.stride; ld.r0 = -l.pad; ld.td = 1; }
     DacGradEpiV ep{};
     ep.out = out; ep.res = res; ep.xs = xs; ep.alpha = sn->a; ep.inv = sn->inv; ep.vout = vout; ep.Cp = cpad(l.Cin);
-    const int Np = np_t(l), Kp = kp_t(l);
-    const long long tiles = (long long)((ld.M + 127) / 128) * ((Np + 95) / 96);
-    if (tiles >= 512) launch_gemm<128>(ld, l.Wt, ld.M, Np, Kp, ep, st);
-    else launch_gemm<64>(ld, l.Wt, ld.M, Np, Kp, ep, st);
+    launch_grad(run, run.mirror(l, l.Wt), l.Wt, ld, np_t(l), kp_t(l), ep);
 }
 
 }  // namespace
@@ -931,7 +976,8 @@ extern "C" int escx_dac_decode_backward_params(escx_dac d, const float* flat, in
     const ParamWs w = param_ws_plan(d);
     if ((rc = ensure_scratch(d, 4 * mf * sizeof(float)))) return rc;
     if (!d->pw) ESCX_HIP(hipMalloc((void**)&d->pw, w.total() * sizeof(float)));
-    if ((rc = pack(d, flat, (long long)version, st)) || (rc = refresh_wt(d, st))) return rc;
+    if ((rc = pack(d, flat, (long long)version, st)) || (rc = refresh_wt(d, st)) || (rc = refresh_wt16(d, d->wt, d->wt_floats, &d->wt16, &d->wt16_valid, st))) return rc;
+    const GradRun run{st, d->wt, d->grad_precision == ESCX_PRECISION_BF16X3 ? d->wt16 : nullptr, d->wt_floats};
     // escx_dac_decode_backward's walk and maps; S holds the Snaked operand of the layer at hand, then the v of its input gradient
     float* G = d->scratch; float* G2 = G + mf; float* A = G2 + mf; float* S = d->scratch + 3 * mf;
     auto M = [&](int i) { return tape + p.off[i]; };
@@ -942,7 +988,7 @@ extern "C" int escx_dac_decode_backward_params(escx_dac d, const float* flat, in
         const long long n4 = (long long)B * Tx * l.CinP / 4;
         hipLaunchKernelGGL(dac_snake_map_kernel, dim3(nblk(n4)), dim3(256), 0, st, xs, (const float*)sn->a, (const float*)sn->inv, S, n4, l.CinP / 4);
         param_layer(d, w, st, l, dY, Tdy, S, Tx, B, flat, grad);
-        bwd_layer_v(st, l, sn, dY, B, Tdy, Tx, xs, res, out, S);
+        bwd_layer_v(run, l, sn, dY, B, Tdy, Tx, xs, res, out, S);
         colsum(d, w, st, S, xs, sn, (long long)B * Tx, l.CinP, sn->C, grad + sn->off);
     };
     const long long n = (long long)B * p.Lout;
@@ -962,7 +1008,7 @@ extern "C" int escx_dac_decode_backward_params(escx_dac d, const float* flat, in
     const int Dp = cpad(d->latent);
     hipLaunchKernelGGL(dac_z_in_kernel, dim3(nblk((long long)B * T * Dp)), dim3(256), 0, st, z, A, B, d->latent, Dp, T);
     param_layer(d, w, st, Dl[0], G, p.Ts[0], A, T, B, flat, grad);
-    if (d_z) bwd_layer(st, Dl[0], nullptr, G, B, p.Ts[0], T, nullptr, nullptr, d_z, d->latent);
+    if (d_z) bwd_layer(run, Dl[0], nullptr, G, B, p.Ts[0], T, nullptr, nullptr, d_z, d->latent);
     return launch_ok("escx_dac_decode_backward_params");
 }
 
@@ -1018,6 +1064,7 @@ int refresh_wte(escx_dac_s* d, hipStream_t st) {
     if (!d->wte) {
         size_t n = 0;
         for (const DacLayer& l : d->enc) n += wt_floats(l);
+        d->wte_floats = n;
         ESCX_HIP(hipMalloc((void**)&d->wte, n * sizeof(float)));
         ESCX_HIP(hipMemsetAsync(d->wte, 0, n * sizeof(float), st));
         size_t cur = 0;
@@ -1037,7 +1084,7 @@ int refresh_wte(escx_dac_s* d, hipStream_t st) {
 
 // dX of a strided Conv1d (K = 2 stride) from dY (B, Tdy, cpad(Cout)):  out (B, Tx, cpad(Cin)) = conv^T(dY) * snake'(xs), one two-tap GEMM per input
 // phase r (rows t = q s + r).  Every row of out is written by its phase.
-void bwd_strided(hipStream_t st, const DacLayer& l, const DacSnake& sn, const float* dY, int B, int Tdy, int Tx, const float* xs, float* out) {
+void bwd_strided(const GradRun& run, const DacLayer& l, const DacSnake& sn, const float* dY, int B, int Tdy, int Tx, const float* xs, float* out) {
     const int s = l.stride, Np = np_t(l), Kp = kp_ph(l);
     for (int r = 0; r < s && r < Tx; ++r) {
         const int Q = (Tx - r + s - 1) / s;
@@ -1047,9 +1094,7 @@ void bwd_strided(hipStream_t st, const DacLayer& l, const DacSnake& sn, const fl
         DacGradPhaseEpi ep{};
         ep.out = out; ep.xs = xs; ep.alpha = sn.a; ep.inv = sn.inv; ep.Cp = cpad(l.Cin); ep.Trows = Q; ep.Tmap = Tx; ep.os = s; ep.o0 = r; ep.dT = ld.dT;
         const float* W = l.Wt + (size_t)r * Np * Kp;
-        const long long tiles = (long long)((ld.M + 127) / 128) * ((Np + 95) / 96);
-        if (tiles >= 512) launch_gemm<128>(ld, W, ld.M, Np, Kp, ep, st);
-        else launch_gemm<64>(ld, W, ld.M, Np, Kp, ep, st);
+        launch_grad(run, run.mirror(l, W), W, ld, Np, Kp, ep);
     }
 }
 
@@ -1145,7 +1190,8 @@ extern "C" int escx_dac_encode_backward(escx_dac d, const float* flat, int64_t v
                   hdr[1], (long long)version);
     const size_t mf = p.mf;
     if ((rc = ensure_scratch(d, 4 * mf * sizeof(float)))) return rc;
-    if ((rc = pack(d, flat, (long long)version, st)) || (rc = refresh_wte(d, st))) return rc;
+    if ((rc = pack(d, flat, (long long)version, st)) || (rc = refresh_wte(d, st)) || (rc = refresh_wt16(d, d->wte, d->wte_floats, &d->wte16, &d->wte16_valid, st))) return rc;
+    const GradRun run{st, d->wte, d->grad_precision == ESCX_PRECISION_BF16X3 ? d->wte16 : nullptr, d->wte_floats};
     float* G = d->scratch; float* G2 = G + mf; float* A = G2 + mf;
     auto Mp = [&](int i) { return tape + p.off[i]; };
     const DacLayer* E = d->enc.data(); const DacSnake* SN = d->enc_sn.data();
@@ -1155,19 +1201,19 @@ extern "C" int escx_dac_encode_backward(escx_dac d, const float* flat, int64_t v
     qa.latents = tape + p.latents; qa.codes = (const long long*)(tape + p.codes); qa.clip_n = (const int*)(tape + p.counts); qa.out = A;
     qa.M = B * p.Tz; qa.T = p.Tz; qa.D = d->latent; qa.Dp = cpad(d->latent); qa.d = d->cfg.codebook_dim; qa.K = d->cfg.codebook_size; qa.n = p.n; qa.B = B;
     launch_rvq_grad(d->latent, (long long)B * p.Tz, qa, st);
-    bwd_layer(st, E[d->enc.size() - 1], SN + d->enc_sn.size() - 1, A, B, p.Tz, p.Ts[nE], Mp(7 * nE), nullptr, G);
+    bwd_layer(run, E[d->enc.size() - 1], SN + d->enc_sn.size() - 1, A, B, p.Tz, p.Ts[nE], Mp(7 * nE), nullptr, G);
     for (int i = nE - 1; i >= 0; --i) {
         const DacLayer* Lb = E + 1 + i * 7; const DacSnake* Sb = SN + i * 7;
         const int Tc = p.Ts[i];
-        if (phased(Lb[6])) bwd_strided(st, Lb[6], Sb[6], G, B, p.Ts[i + 1], Tc, Mp(7 * i + 6), G2);
-        else bwd_layer(st, Lb[6], &Sb[6], G, B, p.Ts[i + 1], Tc, Mp(7 * i + 6), nullptr, G2);          // a rate of 1: a plain two-tap convolution
+        if (phased(Lb[6])) bwd_strided(run, Lb[6], Sb[6], G, B, p.Ts[i + 1], Tc, Mp(7 * i + 6), G2);
+        else bwd_layer(run, Lb[6], &Sb[6], G, B, p.Ts[i + 1], Tc, Mp(7 * i + 6), nullptr, G2);          // a rate of 1: a plain two-tap convolution
         std::swap(G, G2);
         for (int j = 2; j >= 0; --j) {                      // g_x = g + conv7^T(conv1^T(g) * snake'(h)) * snake'(x), in place in G
-            bwd_layer(st, Lb[2 * j + 1], &Sb[2 * j + 1], G, B, Tc, Tc, Mp(7 * i + 2 * j + 1), nullptr, A);
-            bwd_layer(st, Lb[2 * j], &Sb[2 * j], A, B, Tc, Tc, Mp(7 * i + 2 * j), G, G);
+            bwd_layer(run, Lb[2 * j + 1], &Sb[2 * j + 1], G, B, Tc, Tc, Mp(7 * i + 2 * j + 1), nullptr, A);
+            bwd_layer(run, Lb[2 * j], &Sb[2 * j], A, B, Tc, Tc, Mp(7 * i + 2 * j), G, G);
         }
     }
-    bwd_layer(st, E[0], nullptr, G, B, p.Ts[0], L, nullptr, nullptr, d_audio, 1);
+    bwd_layer(run, E[0], nullptr, G, B, p.Ts[0], L, nullptr, nullptr, d_audio, 1);
     return launch_ok("escx_dac_encode_backward");
 }
 

@@ -10,11 +10,26 @@
 // returns - the Snake value when Snake is on this operand - so they do not depend on where Snake was evaluated.
 // Every output element sees the same sequence of MFMAs whatever the tile shape: K in steps of 32 from 0, per step the cross terms (0,2) (2,0) (1,1) (0,1)
 // (1,0) (0,0) (weight term, activation term).  A row's result therefore does not depend on the batch it is computed in.
+// An epilogue with CHUNKED_K (gemm_engine.h; the backward's DacGradEpi, DacGradEpiV, DacGradPhaseEpi) gets two-level accumulation: the MFMA chain
+// restarts every dac_x3_chunk(Kp) steps of 32 and the chunk's sum is added to a second accumulator, so one output's chain is 6 c MFMAs plus
+// Kp / (32 c) adds instead of 6 Kp / 32 MFMAs (K runs to 12288 in the decoder's backward).  The chunk length comes from Kp alone, so the order of
+// one output's sum is still fixed whatever the tile and the batch.  The chunks alternate in sign: an odd chunk stages the negated activation terms
+// (the split of -v is the negated split of v, so every product is the exact negative) and its sum is subtracted.  On an exactly rounding adder this
+// changes nothing; measured on the MI355X the bf16 MFMA's accumulation errs to one side (a dX element's error had a negative mean as large as its
+// rms, which a column sum over rows - a bias gradient - amplified to 2.1 x the float32 reference's error on DAC-Base), and the alternation makes
+// the one-sided part cancel between neighbouring chunks.  The forward epilogues compile to the kernels they had before the switch.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "gemm_bf16.h"
 
 namespace escx {
+
+// Steps of 32 per chunk of a CHUNKED_K contraction: the largest c in {1, 2, 4, 8} with 6 c^2 <= steps, which keeps the inner chain (6 c MFMAs) no
+// longer than the outer one (steps / c adds).  Kp = 12288: 384 steps, c = 8, 48 + 48.
+__host__ __device__ inline int dac_x3_chunk(int Kp) {
+    const int steps = (Kp + 31) / 32;
+    return steps >= 384 ? 8 : steps >= 96 ? 4 : steps >= 24 ? 2 : 1;
+}
 
 template <int BM, int BN, class Loader, class Epi>
 __global__ __launch_bounds__(256) void dac_x3_kernel(Loader ld, const __bf16* __restrict__ W16, size_t plane, int M, int Np, int Kp, int nblk_n, Epi ep) {
@@ -43,6 +58,18 @@ __global__ __launch_bounds__(256) void dac_x3_kernel(Loader ld, const __bf16* __
     for (int a = 0; a < TN; ++a)
 #pragma unroll
         for (int b = 0; b < TM; ++b) acc[a][b] = zero4();
+    constexpr bool CHUNKED = epi_chunked_k<Epi>::value;
+    [[maybe_unused]] f32x4 tot[CHUNKED ? TN : 1][CHUNKED ? TM : 1];
+    [[maybe_unused]] int left = 0;             // steps until the chunk at hand is closed
+    [[maybe_unused]] int chunk = 0;
+    [[maybe_unused]] float sgn = 1.0f;         // sign of the chunk at hand: +, -, +, ... from k = 0
+    if constexpr (CHUNKED) {
+        chunk = left = dac_x3_chunk(Kp);
+#pragma unroll
+        for (int a = 0; a < TN; ++a)
+#pragma unroll
+            for (int b = 0; b < TM; ++b) tot[a][b] = zero4();
+    }
 
     f32x4 ra[AJ];
     uint4 rw[3 * WJ];
@@ -63,7 +90,9 @@ __global__ __launch_bounds__(256) void dac_x3_kernel(Loader ld, const __bf16* __
 #pragma unroll
         for (int j = 0; j < AJ; ++j) {
             const int i = tid + j * 256;
-            bf16x4 t0, t1, t2; split3_bf16x4(ra[j], t0, t1, t2);
+            f32x4 v = ra[j];
+            if constexpr (CHUNKED) v = v * sgn;
+            bf16x4 t0, t1, t2; split3_bf16x4(v, t0, t1, t2);
             *reinterpret_cast<bf16x4*>(&As[(i / KV) * LD + 4 * (i % KV)]) = t0;
             *reinterpret_cast<bf16x4*>(&As[BM * LD + (i / KV) * LD + 4 * (i % KV)]) = t1;
             *reinterpret_cast<bf16x4*>(&As[2 * BM * LD + (i / KV) * LD + 4 * (i % KV)]) = t2;
@@ -92,7 +121,23 @@ __global__ __launch_bounds__(256) void dac_x3_kernel(Loader ld, const __bf16* __
             ESCX_DX3(0, 2) ESCX_DX3(2, 0) ESCX_DX3(1, 1) ESCX_DX3(0, 1) ESCX_DX3(1, 0) ESCX_DX3(0, 0)
 #undef ESCX_DX3
         }
+        if constexpr (CHUNKED) {
+            if (--left == 0 || k0 + BK >= Kp) {                 // the last chunk may be short
+                left = chunk;
+#pragma unroll
+                for (int a = 0; a < TN; ++a)
+#pragma unroll
+                    for (int b = 0; b < TM; ++b) { tot[a][b] += acc[a][b] * sgn; acc[a][b] = zero4(); }
+                sgn = -sgn;
+            }
+        }
         __syncthreads();
+    }
+    if constexpr (CHUNKED) {
+#pragma unroll
+        for (int a = 0; a < TN; ++a)
+#pragma unroll
+            for (int b = 0; b < TM; ++b) acc[a][b] = tot[a][b];
     }
 #pragma unroll
     for (int b = 0; b < TM; ++b) {
@@ -116,14 +161,19 @@ inline int dac_x3_bn(int Np) {
     return (Np + 127) / 128 * 128 <= (Np + 95) / 96 * 96 ? 128 : 96;
 }
 
+//   CHUNKED_K epilogues  the second accumulator doubles the tile's accumulator registers: 128 x 96 needs 276 VGPRs (one workgroup per CU instead of two)
+//                      and 128 x 128 spills 272 bytes to scratch, so 96- and 128-column tiles always take 64 rows (180 and 204 VGPRs, no scratch) and
+//                      those two instantiations do not exist.
 template <class Loader, class Epi>
 inline void launch_dac_x3(const Loader& ld, const __bf16* W16, size_t plane, int M, int Np, int Kp, const Epi& ep, hipStream_t s) {
+    constexpr bool CHUNKED = epi_chunked_k<Epi>::value;
     const int bn = dac_x3_bn(Np), nbn = (Np + bn - 1) / bn;
-    const bool big = (long long)((M + 127) / 128) * nbn >= 512;
+    const bool big = (long long)((M + 127) / 128) * nbn >= 512 && !(CHUNKED && bn > 64);
     const dim3 grid(((M + (big ? 127 : 63)) / (big ? 128 : 64)) * nbn);
 #define ESCX_DX3_LAUNCH(BM, BN) hipLaunchKernelGGL((dac_x3_kernel<BM, BN, Loader, Epi>), grid, dim3(256), 0, s, ld, W16, plane, M, Np, Kp, nbn, ep)
     if (big) {
-        if (bn == 128) ESCX_DX3_LAUNCH(128, 128); else if (bn == 96) ESCX_DX3_LAUNCH(128, 96); else if (bn == 64) ESCX_DX3_LAUNCH(128, 64); else ESCX_DX3_LAUNCH(128, 32);
+        if constexpr (!CHUNKED) { if (bn == 128) { ESCX_DX3_LAUNCH(128, 128); return; } if (bn == 96) { ESCX_DX3_LAUNCH(128, 96); return; } }
+        if (bn == 64) ESCX_DX3_LAUNCH(128, 64); else ESCX_DX3_LAUNCH(128, 32);
     } else {
         if (bn == 128) ESCX_DX3_LAUNCH(64, 128); else if (bn == 96) ESCX_DX3_LAUNCH(64, 96); else if (bn == 64) ESCX_DX3_LAUNCH(64, 64); else ESCX_DX3_LAUNCH(64, 32);
     }

@@ -142,6 +142,8 @@ SIGNATURES = {
     "escx_dac_get_snake_maps": (c_int, [c_void_p]),
     "escx_dac_set_precision": (c_int, [c_void_p, c_int]),
     "escx_dac_get_precision": (c_int, [c_void_p]),
+    "escx_dac_set_grad_precision": (c_int, [c_void_p, c_int]),
+    "escx_dac_get_grad_precision": (c_int, [c_void_p]),
     "escx_dac_set_padding": (c_int, [c_void_p, c_int]),
     "escx_dac_get_padding": (c_int, [c_void_p]),
     "escx_dac_delay": (c_int, [c_void_p]),

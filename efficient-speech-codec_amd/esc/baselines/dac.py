@@ -151,6 +151,7 @@ class DAC(nn.Module):
         q.from_codes, q.n_codebooks, q.codebook_size, q.codebook_dim = self._from_codes, n_codebooks, codebook_size, [codebook_dim] * n_codebooks
         self._handles, self._flat = {}, {}
         self._precision = "fp32"
+        self._grad_precision = "fp32"
         self._padding = True
         self._trainable = None
 
@@ -200,6 +201,7 @@ class DAC(nn.Module):
             if getattr(self, "_snake_maps", None) is not None:
                 _native.check(lib.escx_dac_set_snake_maps(hd, self._snake_maps))
             _native.check(lib.escx_dac_set_precision(hd, _native.PRECISIONS[self._precision]))
+            _native.check(lib.escx_dac_set_grad_precision(hd, _native.PRECISIONS[self._grad_precision]))
             _native.check(lib.escx_dac_set_padding(hd, int(self._padding)))
         return lib, self._handles[idx]
 
@@ -260,6 +262,29 @@ class DAC(nn.Module):
     def precision(self) -> str:
         """The mode in effect: what set_precision chose ("fp32" until then); every live handle is in it."""
         return self._precision
+
+    # ---- arithmetic of the backward (include/escx.h escx_dac_set_grad_precision) ---------------------------------------------------------------
+    def set_grad_precision(self, mode: str) -> "DAC":
+        """Operand form of the backward of decode / encode / forward, with set_precision's names and independent of it: "fp32" (fp32 MFMA, the
+        default, today's bits) or "bf16x3" (the input gradient of every convolution of the decoder and the encoder on the 16-bit matrix cores:
+        output gradient and transposed weights split exactly into three bf16 terms, six cross products accumulated in fp32 in two levels).  The
+        decoder's weight-gradient contractions and the quantiser's backward are fp32 in both modes.  "f16x2" is refused: two fp16 terms need a
+        bound on every operand, and neither output gradients nor Snake outputs have one.  The mode is read when backward runs, not when the
+        graph was made; forward values never depend on it.  Not part of the reference's surface."""
+        if not isinstance(mode, str) or mode not in _native.PRECISIONS:
+            raise ValueError(f"grad precision {mode!r}: expected one of {sorted(_native.PRECISIONS)}")
+        if mode == "f16x2":
+            raise NotImplementedError("DAC has no f16x2 backward: two fp16 terms need an a-priori bound on every operand (csrc/split_terms.h) and "
+                                      "neither output gradients nor Snake outputs have one; use bf16x3, which keeps fp32's exponent range")
+        self._grad_precision = mode
+        for hd in self._handles.values():
+            _native.check(_native.load().escx_dac_set_grad_precision(hd, _native.PRECISIONS[mode]))
+        return self
+
+    @property
+    def grad_precision(self) -> str:
+        """The backward's mode in effect: what set_grad_precision chose ("fp32" until then); every live handle is in it."""
+        return self._grad_precision
 
     # ---- fine-tuning the decoder (include/escx.h escx_dac_decode_backward_params) ----------------------------------------------------------------
     def set_trainable(self, part: Optional[str]) -> "DAC":
@@ -786,7 +811,8 @@ class DAC(nn.Module):
 class _DecodeGrad(torch.autograd.Function):
     """DAC.decode with the latent gradient (include/escx.h escx_dac_decode_tape / escx_dac_decode_backward): the frozen decoder inside a larger
     autograd graph.  forward is the decode's own launch sequence with the maps the backward needs kept in a tape, a plain tensor saved on the
-    graph, so any number of graphs may be alive at once; backward is first order only and runs on the fp32 MFMA in both precision modes."""
+    graph, so any number of graphs may be alive at once; backward is first order only and runs in the arithmetic of set_grad_precision
+    at the time it is called (fp32 MFMA by default, whatever set_precision says)."""
 
     @staticmethod
     def forward(ctx, z, model):
@@ -830,7 +856,8 @@ class _DecodeParamGrad(torch.autograd.Function):
     """DAC.decode with the gradients of the decoder's parameters (include/escx.h escx_dac_decode_backward_params), for fine-tuning a decoder on
     frozen codes or latents after set_trainable("decoder").  forward is `_DecodeGrad`'s: the decode's own launch sequence with its maps kept in a
     tape on the graph.  backward returns the gradient of every decoder parameter that requires one, and of z if it requires one (bitwise
-    `_DecodeGrad`'s); autograd accumulates them into p.grad.  First order only; fp32 MFMA in both precision modes; no atomics."""
+    `_DecodeGrad`'s); autograd accumulates them into p.grad.  First order only; no atomics.  The input gradients run in
+    set_grad_precision's arithmetic at the time backward is called, the weight-gradient contractions on the fp32 MFMA in every mode."""
 
     @staticmethod
     def forward(ctx, z, model, *params):
@@ -883,7 +910,8 @@ class _EncodeGrad(torch.autograd.Function):
     through the encoder and the quantiser's straight-through estimator (quantize.py:58-70, 173-198).  z, latents and the commitment loss are
     differentiable; the codes are integers and the codebook loss detaches z_e.  forward is the encode's own launch sequence with the maps, latents,
     codes and stage counts the backward needs kept in a tape, a plain tensor saved on the graph; backward is first order only and runs on the
-    fp32 MFMA in both precision modes.  counts: one stage count per clip, or None for n stages everywhere."""
+    The encoder layers' input gradients run in set_grad_precision's arithmetic at the time backward is called (fp32 MFMA by default), the
+    quantiser's backward on the fp32 VALU.  counts: one stage count per clip, or None for n stages everywhere."""
 
     @staticmethod
     def forward(ctx, audio_data, model, n, counts):

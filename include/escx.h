@@ -470,6 +470,24 @@ int escx_dac_get_snake_maps(escx_dac d);
  * The three-term weight image is rebuilt whenever the packed fp32 weights are (params_version, buffer) and when the mode is first switched on. */
 int escx_dac_set_precision(escx_dac d, int mode);
 int escx_dac_get_precision(escx_dac d);
+/* Arithmetic of the backward entry points (escx_dac_decode_backward, escx_dac_decode_backward_params, escx_dac_encode_backward), per handle and
+ * independent of escx_dac_set_precision: all four combinations of forward and backward mode are legal.  The mode is read when a backward entry point
+ * is called, not when the tape was made: a tape is valid under either mode.  escx_set_precision's numbers:
+ *   ESCX_PRECISION_FP32    (default) every contraction of the backward on v_mfma_f32_16x16x4_f32; bitwise what the library computed before this switch existed.
+ *   ESCX_PRECISION_BF16X3  the input gradient (dX) of every convolution of the decoder and of the encoder - the stride-1 layers, the ConvTranspose1d's
+ *                          strided form and the strided Conv1d's two-tap GEMM per input phase - on v_mfma_f32_16x16x32_bf16: the output gradient and the
+ *                          transposed weight image each split EXACTLY into three bf16 terms, six cross products accumulated in fp32 in two levels (the MFMA
+ *                          chain restarts every 1, 2, 4 or 8 steps of 32, by the layer's K alone, and the chunk sums are added in order, with alternating signs so that a
+ *                          one-sided rounding of the matrix core's accumulation cancels: DESIGN.md section 13.3).  The weight terms
+ *                          come from a three-plane bf16 mirror of the transposed images, allocated at the first backward of the handle in this mode and
+ *                          rebuilt on the call's stream whenever the transposed images are (a parameter change).  As in the forward mode the one-channel
+ *                          first and last convolutions stay on the fp32 MFMA.  NOT covered, fp32 in both modes: the weight gradients (dW) of
+ *                          escx_dac_decode_backward_params with their bias / alpha / weight-norm reductions, and the quantiser's backward.
+ *   ESCX_PRECISION_F16X2   ESCX_ERR_UNSUPPORTED: two fp16 terms need an a-priori bound on every operand and neither output gradients nor Snake outputs have one.
+ * Any other value is ESCX_ERR_INVALID_ARG; a refusal leaves the mode as it was.  Forward results never depend on this mode.  In both modes the backward
+ * has no atomics, two calls are bitwise equal, a clip's gradient does not depend on its batch, and a zero cotangent gives an exactly zero gradient. */
+int escx_dac_set_grad_precision(escx_dac d, int mode);
+int escx_dac_get_grad_precision(escx_dac d);
 /* CodecMixin.padding (base.py:58-80), per handle, read at each call; on by default.  Off: every Conv1d and ConvTranspose1d runs with padding 0, as
  * the reference's chunked compress / decompress do (base.py:194-201, 259-260): a Conv1d gives floor((T - dilation (K - 1) - 1) / stride) + 1 rows, a
  * ConvTranspose1d (T + 1) * stride, and a ResidualUnit adds its input cropped by 3 * dilation rows on each side (dac.py:35-40).  escx_dac_num_frames,
@@ -512,8 +530,8 @@ int escx_dac_decode_tape(escx_dac d, const float* flat_params_dev, int64_t param
 /* d_z (B, D, T) = (d audio / d z)^T d_audio for the decode that wrote tape_dev (dac.py:249-266 differentiated; d_audio_dev is (B, samples)):
  * tanh (dac.py:138), then per layer in reverse the transposed convolution of the output gradient times the derivative of the Snake in front of
  * it (nn/layers.py:19-33), the ResidualUnit as g + conv7^T(conv1^T(g) snake'(h)) snake'(x) (dac.py:24-41), the ConvTranspose1d (dac.py:99-105) as
- * one strided convolution.  fp32 MFMA in both precision modes, on transposed images of the packed forward weights (derived at the first backward
- * of a handle and after every parameter change).  No atomics: bitwise deterministic, and a clip's d_z does not depend on its batch.
+ * one strided convolution.  fp32 MFMA or, under escx_dac_set_grad_precision(ESCX_PRECISION_BF16X3), the split-operand form, whatever the forward's
+ * mode; on transposed images of the packed forward weights (derived at the first backward of a handle and after every parameter change).  No atomics: bitwise deterministic, and a clip's d_z does not depend on its batch.
  * params_version must be the version the tape was made with: another one is ESCX_ERR_STATE with a message that says so, and a buffer that is not
  * a tape for (batch, n_frames) is ESCX_ERR_INVALID_ARG; both are found before the handle changes.  The check reads the tape's header back, so the
  * call waits for the stream once. */
@@ -531,8 +549,9 @@ int escx_dac_decode_backward(escx_dac d, const float* flat_params_dev, int64_t p
  *   weight norm       dg = <dW, v> / |v|,  dv = g / |v| (dW - <dW, v> v / |v|^2), the norm over all dimensions but the first
  * grad_flat_dev has flat_params_dev's layout (escx_dac_param_offset): the slots of every `decoder.*` parameter are OVERWRITTEN and no other float
  * is touched.  z_dev (B, D, T) is the latent the tape was made from (the tape does not hold it).  d_z_dev may be NULL; when given it is bitwise
- * what escx_dac_decode_backward writes.  The contractions are fp32 MFMA over row slices whose partial tiles are added in increasing slice order
- * (no atomics: two calls are bitwise equal), in both precision modes; the slices' tiles live in a handle workspace allocated at the first call
+ * what escx_dac_decode_backward writes in the same grad mode.  The weight-gradient contractions are fp32 MFMA over row slices whose partial tiles are
+ * added in increasing slice order (no atomics: two calls are bitwise equal), in both precision modes and both grad modes (escx_dac_set_grad_precision
+ * moves the input gradients that feed them, not the dW contraction); the slices' tiles live in a handle workspace allocated at the first call
  * (escx_dac_param_grad_workspace_floats).  Errors are escx_dac_decode_backward's and are found before the handle changes: padding off is
  * ESCX_ERR_UNSUPPORTED, a foreign or wrong-size tape ESCX_ERR_INVALID_ARG, another params_version ESCX_ERR_STATE with a message naming both, a
  * NULL grad_flat_dev or z_dev ESCX_ERR_INVALID_ARG.  DESIGN.md section 13.5 has the launch sequence, the workspace and the slice rule. */
@@ -568,7 +587,8 @@ int escx_dac_encode_tape(escx_dac d, const float* flat_params_dev, int64_t param
  * 189), g_r += W_in^T e (quantize.py:58, 186); a clip with its own stage count runs that many stages.  Then the encoder (dac.py:64-91 differentiated)
  * in reverse: per layer the transposed convolution of the output gradient times the derivative of the Snake in front of it (nn/layers.py:19-33), the
  * ResidualUnit as g + conv7^T(conv1^T(g) snake'(h)) snake'(x) (dac.py:24-41), the strided convolution (dac.py:55-58) as one two-tap GEMM per input
- * phase, every input row written.  fp32 MFMA in both precision modes; no atomics: bitwise deterministic, and without d_commitment a clip's d_audio
+ * phase, every input row written.  fp32 MFMA, or the split-operand form under escx_dac_set_grad_precision(ESCX_PRECISION_BF16X3) (the quantiser's
+ * backward is fp32 VALU in both), whatever the forward's mode; no atomics: bitwise deterministic, and without d_commitment a clip's d_audio
  * does not depend on its batch.  params_version must be the tape's: another one is ESCX_ERR_STATE with a message naming both; a buffer that is not
  * an encode tape for (batch, n_samples), a decode tape included, or has the wrong size is ESCX_ERR_INVALID_ARG; both are found before the handle
  * changes.  The check reads the tape's header back, so the call waits for the stream once. */
