@@ -9,7 +9,8 @@
 // kept in a caller-owned tape and the latent gradient d audio / d z on it (dac_grad_kernels.h); escx_dac_encode_tape /
 // escx_dac_encode_backward are the same for the encoder and the quantiser, with the audio gradient of z, latents and the commitment loss
 // (DESIGN.md section 13.4).  escx_dac_decode_backward_params is the decoder's backward with the gradients of its parameters (bias, weight_g, weight_v,
-// alpha) next to d_z, for fine-tuning a decoder (dac_param_grad_kernels.h, gemm_dw_kernel of train_kernels.h).
+// alpha) next to d_z, for fine-tuning a decoder (dac_param_grad_kernels.h, gemm_dw_kernel of train_kernels.h);
+// escx_dac_set_param_grad_precision moves its weight-gradient contractions to the split-operand gemm_dw_bf16_kernel<.., 3> of gemm_bf16.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -84,6 +85,10 @@ struct escx_dac_s {
     // escx_dac_decode_backward_params: the slices' partial dW tiles, the staged dW and the bias / alpha partial rows; allocated at the first
     // parameter backward of the handle, sized from the configuration alone (param_ws_plan)
     float* pw = nullptr;
+    // escx_dac_set_param_grad_precision, read at each parameter backward.  bf16x3: the partial tiles of the 128 x 128 split-operand dW contraction
+    // (param_ws16_plan), a second allocation made at the first parameter backward in that mode; the staged dW and the column partials stay in pw.
+    int param_grad_precision = ESCX_PRECISION_FP32;
+    float* pw16 = nullptr;
 };
 
 namespace {
@@ -453,6 +458,7 @@ extern "C" void escx_dac_destroy(escx_dac d) {
     if (d->wt16) (void)hipFree(d->wt16);
     if (d->wte16) (void)hipFree(d->wte16);
     if (d->pw) (void)hipFree(d->pw);
+    if (d->pw16) (void)hipFree(d->pw16);
     if (d->qoffs_dev) (void)hipFree(d->qoffs_dev);
     if (d->scratch) (void)hipFree(d->scratch);
     if (d->counts) (void)hipFree(d->counts);
@@ -494,6 +500,18 @@ extern "C" int escx_dac_set_grad_precision(escx_dac d, int mode) {
     return ESCX_OK;
 }
 extern "C" int escx_dac_get_grad_precision(escx_dac d) { return d ? d->grad_precision : -1; }
+
+extern "C" int escx_dac_set_param_grad_precision(escx_dac d, int mode) {
+    if (!d) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null handle");
+    if (mode == ESCX_PRECISION_F16X2)
+        ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "DAC has no f16x2 weight gradient: two fp16 terms need an a-priori bound on every operand (csrc/split_terms.h) and "
+                                        "neither the output gradients nor Snake outputs have one; bf16x3 keeps fp32's exponent range and needs no bound");
+    if (mode != ESCX_PRECISION_FP32 && mode != ESCX_PRECISION_BF16X3)
+        ESCX_FAIL(ESCX_ERR_INVALID_ARG, "DAC param grad precision %d: expected fp32 (0) or bf16x3 (3)", mode);
+    d->param_grad_precision = mode;
+    return ESCX_OK;
+}
+extern "C" int escx_dac_get_param_grad_precision(escx_dac d) { return d ? d->param_grad_precision : -1; }
 
 extern "C" int escx_dac_set_padding(escx_dac d, int on) {
     if (!d) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null handle");
@@ -866,6 +884,36 @@ void dw_slices(const DwGeom& g, int M, int* slices, int* mps) {
     *slices = (M + *mps - 1) / *mps;
 }
 
+// The same for the split-operand contraction (escx_dac_set_param_grad_precision): gemm_dw_bf16_kernel's 128 x 128 tiles of dW, or
+// dac_dw_x3_kernel's 64 x 128 and 32 x 128 for Np <= 64 and Np <= 32 (dac_x3.h dac_dw_x3_rows).  Which layers take it is a function of the layer's
+// geometry alone: every convolution with more than one input and more than one output channel (x3_layer, the forward's and the input gradients'
+// rule), whatever its (Np, Kp) - a tile's rows and columns behind Np / Kp are staged as zeros and not stored.  The one-channel last convolution
+// keeps the fp32 kernel and the fp32 rule.
+constexpr int DW16_TILE = 128;          // columns of dW per workgroup
+constexpr int DW16_STEP = 32;           // a slice is a multiple of the kernel's row step (one MFMA deep)
+constexpr int DW16_MIN_ROWS = 256;      // no more slices than 256-row pieces of the contraction: a slice's 64 KB partial tile is written and read back
+inline bool dw16_layer(const DacLayer& l) { return x3_layer(l); }
+DwGeom dw16_geom(const DacLayer& l) {
+    DwGeom g = dw_geom(l);
+    const int ta = dac_dw_x3_rows(g.Np);
+    g.blocks = ((g.Np + ta - 1) / ta) * ((g.Kp + DW16_TILE - 1) / DW16_TILE);
+    g.smax = std::max(1, (DW_TARGET_WGS + g.blocks - 1) / g.blocks);
+    return g;
+}
+// Its slice rule: enough slices to reach DW_TARGET_WGS workgroups, none more than M / DW16_MIN_ROWS allows, each a multiple of DW16_STEP rows
+void dw16_slices(const DwGeom& g, int M, int* slices, int* mps) {
+    const int s = std::max(1, std::min(g.smax, (M + DW16_MIN_ROWS - 1) / DW16_MIN_ROWS));
+    *mps = ((M + s - 1) / s + DW16_STEP - 1) / DW16_STEP * DW16_STEP;
+    *slices = (M + *mps - 1) / *mps;
+}
+// Its partial tiles, in floats, whatever the batch: smax Np Kp of the layer that needs most
+size_t param_ws16_plan(const escx_dac_s* d) {
+    size_t part = 0;
+    for (const DacLayer& l : d->dec)
+        if (dw16_layer(l)) { const DwGeom g = dw16_geom(l); part = std::max(part, pad64((size_t)g.smax * g.Np * g.Kp)); }
+    return part;
+}
+
 // The workspace, in floats, whatever the batch: [partial tiles: smax Np Kp] [staged dW: Np Kp] [column partials: blocks x Cp, fp64]
 struct ParamWs { size_t part = 0, stage = 0, cols = 0; size_t total() const { return part + stage + cols; } };
 ParamWs param_ws_plan(const escx_dac_s* d) {
@@ -916,10 +964,18 @@ void param_layer(const escx_dac_s* d, const ParamWs& w, hipStream_t st, const Da
         lb.Trows = Ts; lb.M = B * Ts; lb.dT = FastDiv(Ts); lb.rs = l.stride; lb.r0 = -l.pad; lb.td = 1; lb.ntaps = l.K;
     }
     const int M = la.M;
-    int slices, mps; dw_slices(g, M, &slices, &mps);
+    int slices, mps;
     float* part = d->pw; float* stage = d->pw + w.part;
-    const int nbk = (g.Kp + 47) / 48;
-    hipLaunchKernelGGL((gemm_dw_kernel<DacConvA, DacConvA, false>), dim3(g.blocks, slices), dim3(256), 0, st, la, lb, M, g.Np, g.Kp, nbk, mps, part, (float*)nullptr);
+    if (d->param_grad_precision == ESCX_PRECISION_BF16X3 && dw16_layer(l)) {
+        const DwGeom g16 = dw16_geom(l);
+        dw16_slices(g16, M, &slices, &mps);
+        part = d->pw16;
+        launch_dac_dw_x3(la, lb, M, g.Np, g.Kp, slices, mps, part, st);
+    } else {
+        dw_slices(g, M, &slices, &mps);
+        const int nbk = (g.Kp + 47) / 48;
+        hipLaunchKernelGGL((gemm_dw_kernel<DacConvA, DacConvA, false>), dim3(g.blocks, slices), dim3(256), 0, st, la, lb, M, g.Np, g.Kp, nbk, mps, part, (float*)nullptr);
+    }
     const float* dW = part;                                     // one slice: its tile is the sum
     if (slices > 1) { launch_reduce_partials(part, slices, (long long)g.Np * g.Kp, stage, 0, st); dW = stage; }
     colsum(d, w, st, dY, nullptr, nullptr, (long long)B * Tdy, CoutP, l.Cout, grad + l.off_b);
@@ -941,7 +997,11 @@ void bwd_layer_v(const GradRun& run, const DacLayer& l, const DacSnake* sn, cons
 
 }  // namespace
 
-extern "C" int64_t escx_dac_param_grad_workspace_floats(escx_dac d) { return d ? (int64_t)param_ws_plan(d).total() : 0; }
+extern "C" int64_t escx_dac_param_grad_workspace_floats(escx_dac d) {
+    if (!d) return 0;
+    const bool held16 = d->param_grad_precision == ESCX_PRECISION_BF16X3 && d->pw16;
+    return (int64_t)(param_ws_plan(d).total() + (held16 ? param_ws16_plan(d) : 0));
+}
 
 extern "C" int escx_dac_param_grad_slices(escx_dac d, int B, int T, int layer) {
     if (!d || B < 1 || T < 1 || layer < 0 || layer >= (int)d->dec.size()) return 0;
@@ -952,7 +1012,9 @@ extern "C" int escx_dac_param_grad_slices(escx_dac d, int B, int T, int layer) {
     if (layer == 0) Trows = p.Ts[0];
     else if (layer == (int)d->dec.size() - 1) Trows = p.Lout;
     else { const int i = (layer - 1) / 7, k = (layer - 1) % 7; Trows = k == 0 ? p.Ts[i] : p.Ts[i + 1]; }
-    int slices, mps; dw_slices(dw_geom(d->dec[layer]), B * Trows, &slices, &mps);
+    int slices, mps;
+    if (d->param_grad_precision == ESCX_PRECISION_BF16X3 && dw16_layer(d->dec[layer])) dw16_slices(dw16_geom(d->dec[layer]), B * Trows, &slices, &mps);
+    else dw_slices(dw_geom(d->dec[layer]), B * Trows, &slices, &mps);
     return slices;
 }
 
@@ -976,6 +1038,7 @@ extern "C" int escx_dac_decode_backward_params(escx_dac d, const float* flat, in
     const ParamWs w = param_ws_plan(d);
     if ((rc = ensure_scratch(d, 4 * mf * sizeof(float)))) return rc;
     if (!d->pw) ESCX_HIP(hipMalloc((void**)&d->pw, w.total() * sizeof(float)));
+    if (d->param_grad_precision == ESCX_PRECISION_BF16X3 && !d->pw16) ESCX_HIP(hipMalloc((void**)&d->pw16, param_ws16_plan(d) * sizeof(float)));
     if ((rc = pack(d, flat, (long long)version, st)) || (rc = refresh_wt(d, st)) || (rc = refresh_wt16(d, d->wt, d->wt_floats, &d->wt16, &d->wt16_valid, st))) return rc;
     const GradRun run{st, d->wt, d->grad_precision == ESCX_PRECISION_BF16X3 ? d->wt16 : nullptr, d->wt_floats};
     // escx_dac_decode_backward's walk and maps; S holds the Snaked operand of the layer at hand, then the v of its input gradient

@@ -3,7 +3,8 @@
 // DESIGN.md section 13.5.
 //
 // The weight gradient of every convolution is gemm_dw_kernel of train_kernels.h (fp32 MFMA over row slices, the slices' partial tiles added in
-// increasing order) with DacConvA on both sides, over the layer's output gradient dY and its forward operand s (the Snaked saved map, or the
+// increasing order; under escx_dac_set_param_grad_precision(ESCX_PRECISION_BF16X3) gemm_dw_bf16_kernel<.., 3> of gemm_bf16.h, the same contraction
+// with split operands and 128 x 128 tiles) with DacConvA on both sides, over the layer's output gradient dY and its forward operand s (the Snaked saved map, or the
 // staged latent for the first convolution), both channels-last:
 //   Conv1d (K taps, dilation d, padding p)         rows (b, t) of dY:  A = dY rows (one tap),  B[(b, t)][tap * CinP + ci] = s(b, t - p + tap d, ci)
 //                                                  dW[co][tap * CinP + ci]

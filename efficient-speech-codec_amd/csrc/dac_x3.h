@@ -180,4 +180,103 @@ inline void launch_dac_x3(const Loader& ld, const __bf16* W16, size_t plane, int
 #undef ESCX_DX3_LAUNCH
 }
 
+// ------------------------------------------------------------------------------------------------
+// The split-operand weight gradient of the narrow layers (escx_dac_set_param_grad_precision; dac.hip param_layer): gemm_bf16.h's
+// gemm_dw_bf16_kernel<LdA, LdB, 3> with TA = 32 or 64 rows of dW per workgroup instead of 128, for Np <= 64, where a 128-row tile is at most
+// half full.  dW[n][k] = sum_m A[m][n] B[m][k] over one slice of the rows: one workgroup = a TA x 128 tile, wave w owns the k columns
+// [32 w, 32 w + 32) x all TA n.  The staging is that kernel's - a thread loads rows (m, m + 1) of four columns, splits each value into three
+// bf16 terms and writes [term][column][m] into LDS - with the A side staged by the threads whose four columns lie inside the tile.  Every output
+// sees that kernel's sequence of MFMAs: the rows in steps of 32 from the slice's first, per step the cross terms (0,2) (2,0) (1,1) (0,1) (1,0)
+// (0,0), so for the same slices the two kernels give the same bits.  Rows behind the slice and columns behind Np / Kp are staged as zeros
+// (the loaders' contract, gemm_bf16.h) and not stored.
+// ------------------------------------------------------------------------------------------------
+template <int TA, class LdA, class LdB>
+__global__ __launch_bounds__(256) void dac_dw_x3_kernel(LdA la, LdB lb, int M, int Np, int Kp, int nblk_k, int m_per_slice, float* __restrict__ part) {
+    static_assert(TA == 32 || TA == 64, "rows of dW per workgroup");
+    constexpr int TB = 128, MS = 32, LD = MS + 8, NB = TA / 16;
+    __shared__ __attribute__((aligned(16))) __bf16 At[3 * TA * LD];
+    __shared__ __attribute__((aligned(16))) __bf16 Bt[3 * TB * LD];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, lg = lane >> 4;
+    const int mp = lane & 15, cq = 4 * (4 * wave + (lane >> 4));          // staging role: row pair mp of the step, columns cq .. cq + 3 (B: and + 64)
+    const int bn = blockIdx.x / nblk_k, bk = blockIdx.x - bn * nblk_k;
+    const int n0 = bn * TA, k0 = bk * TB;
+    const int mbeg = blockIdx.y * m_per_slice, mend = min(M, mbeg + m_per_slice);
+    const bool stage_a = cq < TA;               // TA = 64: everybody; TA = 32: waves 0 and 1
+
+    f32x4 acc[2][NB];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < NB; ++b) acc[a][b] = zero4();
+    f32x4 ra[2] = {zero4(), zero4()}, rb[2][2];                         // [row of the pair], [column group][row of the pair]
+    auto fetch = [&](int m0) {
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const int m = m0 + 2 * mp + r;
+            const typename LdB::Ctx cb = lb.make_ctx(m < mend ? m : M);         // rows behind the slice (or the matrix) read as zero
+#pragma unroll
+            for (int j = 0; j < 2; ++j) rb[j][r] = lb.load4(cb, k0 + 64 * j + cq, 0);
+            if (stage_a) { const typename LdA::Ctx ca = la.make_ctx(m < mend ? m : M); ra[r] = la.load4(ca, n0 + cq, 0); }
+        }
+    };
+    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+    auto stage = [](__bf16* img, int rows, int col, int mp2, f32x4 v0, f32x4 v1) {      // rows m, m + 1 of four columns -> three planes of [column][m]
+        bf16x4 t0[3], t1[3];
+        split3_bf16x4(v0, t0[0], t0[1], t0[2]); split3_bf16x4(v1, t1[0], t1[1], t1[2]);
+#pragma unroll
+        for (int p = 0; p < 3; ++p)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                bf16x2 pr; pr[0] = t0[p][e]; pr[1] = t1[p][e];
+                *reinterpret_cast<unsigned*>(&img[p * rows * LD + (col + e) * LD + mp2]) = __builtin_bit_cast(unsigned, pr);
+            }
+    };
+    if (mbeg < mend) fetch(mbeg);
+    for (int m0 = mbeg; m0 < mend; m0 += MS) {
+        if (stage_a) stage(At, TA, cq, 2 * mp, ra[0], ra[1]);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) stage(Bt, TB, 64 * j + cq, 2 * mp, rb[j][0], rb[j][1]);
+        __syncthreads();
+        if (m0 + MS < mend) fetch(m0 + MS);
+        bf16x8 af3[3][NB];
+#pragma unroll
+        for (int p = 0; p < 3; ++p)
+#pragma unroll
+            for (int b = 0; b < NB; ++b) af3[p][b] = *reinterpret_cast<const bf16x8*>(&At[p * TA * LD + (16 * b + l15) * LD + 8 * lg]);
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {
+            bf16x8 wf3[3];
+#pragma unroll
+            for (int p = 0; p < 3; ++p) wf3[p] = *reinterpret_cast<const bf16x8*>(&Bt[p * TB * LD + (32 * wave + 16 * a + l15) * LD + 8 * lg]);
+#define ESCX_DD3(I, J) _Pragma("unroll") for (int b = 0; b < NB; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf3[I], af3[J][b], acc[a][b], 0, 0, 0);
+            ESCX_DD3(0, 2) ESCX_DD3(2, 0) ESCX_DD3(1, 1) ESCX_DD3(0, 1) ESCX_DD3(1, 0) ESCX_DD3(0, 0)
+#undef ESCX_DD3
+        }
+        __syncthreads();
+    }
+    float* pt = part + (size_t)blockIdx.y * Np * Kp;
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        const int n = n0 + 16 * b + l15;
+        if (n >= Np) continue;
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {
+            const int k = k0 + 32 * wave + 16 * a + 4 * lg;
+            if (k < Kp) st4(pt + (size_t)n * Kp + k, acc[a][b]);
+        }
+    }
+}
+
+// Rows of dW per workgroup of the split-operand weight gradient, from Np alone: 32 and 64 where one tile holds all of Np, else gemm_dw_bf16_kernel's 128
+inline int dac_dw_x3_rows(int Np) { return Np <= 32 ? 32 : (Np <= 64 ? 64 : 128); }
+
+template <class LdA, class LdB>
+inline void launch_dac_dw_x3(const LdA& la, const LdB& lb, int M, int Np, int Kp, int slices, int m_per_slice, float* part, hipStream_t s) {
+    const int ta = dac_dw_x3_rows(Np), nbk = (Kp + 127) / 128;
+    const dim3 grid(((Np + ta - 1) / ta) * nbk, slices);
+    if (ta == 32) hipLaunchKernelGGL((dac_dw_x3_kernel<32, LdA, LdB>), grid, dim3(256), 0, s, la, lb, M, Np, Kp, nbk, m_per_slice, part);
+    else if (ta == 64) hipLaunchKernelGGL((dac_dw_x3_kernel<64, LdA, LdB>), grid, dim3(256), 0, s, la, lb, M, Np, Kp, nbk, m_per_slice, part);
+    else hipLaunchKernelGGL((gemm_dw_bf16_kernel<LdA, LdB, 3>), grid, dim3(256), 0, s, la, lb, M, Np, Kp, nbk, m_per_slice, part, (float*)nullptr);
+}
+
 }  // namespace escx

@@ -144,6 +144,8 @@ SIGNATURES = {
     "escx_dac_get_precision": (c_int, [c_void_p]),
     "escx_dac_set_grad_precision": (c_int, [c_void_p, c_int]),
     "escx_dac_get_grad_precision": (c_int, [c_void_p]),
+    "escx_dac_set_param_grad_precision": (c_int, [c_void_p, c_int]),
+    "escx_dac_get_param_grad_precision": (c_int, [c_void_p]),
     "escx_dac_set_padding": (c_int, [c_void_p, c_int]),
     "escx_dac_get_padding": (c_int, [c_void_p]),
     "escx_dac_delay": (c_int, [c_void_p]),

@@ -152,6 +152,7 @@ class DAC(nn.Module):
         self._handles, self._flat = {}, {}
         self._precision = "fp32"
         self._grad_precision = "fp32"
+        self._param_grad_precision = "fp32"
         self._padding = True
         self._trainable = None
 
@@ -202,6 +203,7 @@ class DAC(nn.Module):
                 _native.check(lib.escx_dac_set_snake_maps(hd, self._snake_maps))
             _native.check(lib.escx_dac_set_precision(hd, _native.PRECISIONS[self._precision]))
             _native.check(lib.escx_dac_set_grad_precision(hd, _native.PRECISIONS[self._grad_precision]))
+            _native.check(lib.escx_dac_set_param_grad_precision(hd, _native.PRECISIONS[self._param_grad_precision]))
             _native.check(lib.escx_dac_set_padding(hd, int(self._padding)))
         return lib, self._handles[idx]
 
@@ -268,7 +270,7 @@ class DAC(nn.Module):
         """Operand form of the backward of decode / encode / forward, with set_precision's names and independent of it: "fp32" (fp32 MFMA, the
         default, today's bits) or "bf16x3" (the input gradient of every convolution of the decoder and the encoder on the 16-bit matrix cores:
         output gradient and transposed weights split exactly into three bf16 terms, six cross products accumulated in fp32 in two levels).  The
-        decoder's weight-gradient contractions and the quantiser's backward are fp32 in both modes.  "f16x2" is refused: two fp16 terms need a
+        decoder's weight-gradient contractions (set_param_grad_precision's) and the quantiser's backward (fp32) do not follow this switch.  "f16x2" is refused: two fp16 terms need a
         bound on every operand, and neither output gradients nor Snake outputs have one.  The mode is read when backward runs, not when the
         graph was made; forward values never depend on it.  Not part of the reference's surface."""
         if not isinstance(mode, str) or mode not in _native.PRECISIONS:
@@ -285,6 +287,31 @@ class DAC(nn.Module):
     def grad_precision(self) -> str:
         """The backward's mode in effect: what set_grad_precision chose ("fp32" until then); every live handle is in it."""
         return self._grad_precision
+
+    # ---- arithmetic of the weight gradients (include/escx.h escx_dac_set_param_grad_precision) ------------------------------------------------
+    def set_param_grad_precision(self, mode: str) -> "DAC":
+        """Operand form of the decoder's weight-gradient contractions after set_trainable("decoder"), with set_precision's names and independent
+        of set_precision and set_grad_precision: "fp32" (fp32 MFMA, the default, today's bits) or "bf16x3" (the dW contraction of every decoder
+        convolution with more than one input and more than one output channel on the 16-bit matrix cores: output-gradient rows and Snaked input
+        rows split exactly into three bf16 terms, six cross products accumulated in fp32, the row slices added in increasing order; 128 x 128
+        tiles of dW, 64 or 32 x 128 for layers of at most 64 channels).  The
+        one-channel last convolution, the bias / alpha column sums and the weight norm's backward are the same in both modes, and so are the
+        audio and d_z.  "f16x2" is refused: two fp16 terms need a bound on every operand, and neither output gradients nor Snake outputs have
+        one.  The mode is read when backward runs, not when the graph was made.  Not part of the reference's surface."""
+        if not isinstance(mode, str) or mode not in _native.PRECISIONS:
+            raise ValueError(f"param grad precision {mode!r}: expected one of {sorted(_native.PRECISIONS)}")
+        if mode == "f16x2":
+            raise NotImplementedError("DAC has no f16x2 weight gradient: two fp16 terms need an a-priori bound on every operand (csrc/split_terms.h) "
+                                      "and neither output gradients nor Snake outputs have one; use bf16x3, which keeps fp32's exponent range")
+        self._param_grad_precision = mode
+        for hd in self._handles.values():
+            _native.check(_native.load().escx_dac_set_param_grad_precision(hd, _native.PRECISIONS[mode]))
+        return self
+
+    @property
+    def param_grad_precision(self) -> str:
+        """The weight gradients' mode in effect: what set_param_grad_precision chose ("fp32" until then); every live handle is in it."""
+        return self._param_grad_precision
 
     # ---- fine-tuning the decoder (include/escx.h escx_dac_decode_backward_params) ----------------------------------------------------------------
     def set_trainable(self, part: Optional[str]) -> "DAC":
@@ -857,7 +884,8 @@ class _DecodeParamGrad(torch.autograd.Function):
     frozen codes or latents after set_trainable("decoder").  forward is `_DecodeGrad`'s: the decode's own launch sequence with its maps kept in a
     tape on the graph.  backward returns the gradient of every decoder parameter that requires one, and of z if it requires one (bitwise
     `_DecodeGrad`'s); autograd accumulates them into p.grad.  First order only; no atomics.  The input gradients run in
-    set_grad_precision's arithmetic at the time backward is called, the weight-gradient contractions on the fp32 MFMA in every mode."""
+    set_grad_precision's arithmetic at the time backward is called, the weight-gradient contractions in set_param_grad_precision's (fp32 MFMA
+    by default)."""
 
     @staticmethod
     def forward(ctx, z, model, *params):

@@ -481,8 +481,9 @@ int escx_dac_get_precision(escx_dac d);
  *                          one-sided rounding of the matrix core's accumulation cancels: DESIGN.md section 13.3).  The weight terms
  *                          come from a three-plane bf16 mirror of the transposed images, allocated at the first backward of the handle in this mode and
  *                          rebuilt on the call's stream whenever the transposed images are (a parameter change).  As in the forward mode the one-channel
- *                          first and last convolutions stay on the fp32 MFMA.  NOT covered, fp32 in both modes: the weight gradients (dW) of
- *                          escx_dac_decode_backward_params with their bias / alpha / weight-norm reductions, and the quantiser's backward.
+ *                          first and last convolutions stay on the fp32 MFMA.  NOT covered, the same in both modes: the weight gradients (dW) of
+ *                          escx_dac_decode_backward_params (a switch of their own: escx_dac_set_param_grad_precision) with their bias / alpha /
+ *                          weight-norm reductions, and the quantiser's backward.
  *   ESCX_PRECISION_F16X2   ESCX_ERR_UNSUPPORTED: two fp16 terms need an a-priori bound on every operand and neither output gradients nor Snake outputs have one.
  * Any other value is ESCX_ERR_INVALID_ARG; a refusal leaves the mode as it was.  Forward results never depend on this mode.  In both modes the backward
  * has no atomics, two calls are bitwise equal, a clip's gradient does not depend on its batch, and a zero cotangent gives an exactly zero gradient. */
@@ -551,16 +552,35 @@ int escx_dac_decode_backward(escx_dac d, const float* flat_params_dev, int64_t p
  * is touched.  z_dev (B, D, T) is the latent the tape was made from (the tape does not hold it).  d_z_dev may be NULL; when given it is bitwise
  * what escx_dac_decode_backward writes in the same grad mode.  The weight-gradient contractions are fp32 MFMA over row slices whose partial tiles are
  * added in increasing slice order (no atomics: two calls are bitwise equal), in both precision modes and both grad modes (escx_dac_set_grad_precision
- * moves the input gradients that feed them, not the dW contraction); the slices' tiles live in a handle workspace allocated at the first call
- * (escx_dac_param_grad_workspace_floats).  Errors are escx_dac_decode_backward's and are found before the handle changes: padding off is
+ * moves the input gradients that feed them, not the dW contraction), or the split-operand form under escx_dac_set_param_grad_precision; the slices'
+ * tiles live in a handle workspace allocated at the first call (escx_dac_param_grad_workspace_floats).  Errors are escx_dac_decode_backward's and are found before the handle changes: padding off is
  * ESCX_ERR_UNSUPPORTED, a foreign or wrong-size tape ESCX_ERR_INVALID_ARG, another params_version ESCX_ERR_STATE with a message naming both, a
  * NULL grad_flat_dev or z_dev ESCX_ERR_INVALID_ARG.  DESIGN.md section 13.5 has the launch sequence, the workspace and the slice rule. */
 int escx_dac_decode_backward_params(escx_dac d, const float* flat_params_dev, int64_t params_version, const float* tape_dev, int64_t tape_floats,
                                     const float* z_dev, const float* d_audio_dev, int batch, int n_frames, float* d_z_dev, float* grad_flat_dev, void* stream);
-/* Floats of the handle workspace escx_dac_decode_backward_params allocates at its first call; it depends on the configuration alone. */
+/* Floats of the handle workspace escx_dac_decode_backward_params allocates at its first call; it depends on the configuration alone.  Under
+ * escx_dac_set_param_grad_precision(ESCX_PRECISION_BF16X3) the 128 x 128 tiles' partial region, which is a second allocation made at the first
+ * parameter backward in that mode and sized from the configuration alone, is counted from that backward on; in fp32 mode never. */
 int64_t escx_dac_param_grad_workspace_floats(escx_dac d);
-/* Row slices of the weight-gradient contraction of decoder convolution `layer` (execution order, from 0) for batch x n_frames; 0 on a bad argument. */
+/* Row slices of the weight-gradient contraction of decoder convolution `layer` (execution order, from 0) for batch x n_frames under the current
+ * escx_dac_set_param_grad_precision mode (a layer that stays on the fp32 kernel reports the fp32 rule's count in both); 0 on a bad argument. */
 int escx_dac_param_grad_slices(escx_dac d, int batch, int n_frames, int layer);
+/* Operand form of the weight-gradient (dW) contractions of escx_dac_decode_backward_params (dac.py:24-41, 94-145, 249-266 and nn/layers.py:5-33
+ * differentiated), per handle, independent of escx_dac_set_precision and escx_dac_set_grad_precision and read when the backward runs.
+ *   ESCX_PRECISION_FP32    (default) gemm_dw_kernel on v_mfma_f32_16x16x4_f32 with 48 x 48 tiles: bitwise what the library computed before this switch
+ *                          existed, with the same slices, workspace, launches and allocation time.
+ *   ESCX_PRECISION_BF16X3  the dW contraction of every decoder convolution with more than one input and more than one output channel on
+ *                          v_mfma_f32_16x16x32_bf16 with 128 x 128 tiles of dW (64 x 128 and 32 x 128 where Np <= 64 and Np <= 32): both operands - a Conv1d's output-gradient rows and the im2col rows
+ *                          of its Snaked input, a ConvTranspose1d's Snaked input rows and the strided rows of its output gradient - split EXACTLY into
+ *                          three bf16 terms while they are staged, the six leading cross products accumulated in fp32, the row slices (multiples of
+ *                          32 rows, at least 256 where the contraction has them, counted from the geometry alone) added in increasing order.  The
+ *                          one-channel last convolution stays on the fp32 kernel.  dW keeps its layout, so the weight norm's backward and the bias /
+ *                          alpha column sums (fp64 partials) are the same launches in both modes; d_z and the audio do not depend on the mode.
+ *   ESCX_PRECISION_F16X2   ESCX_ERR_UNSUPPORTED: two fp16 terms need an a-priori bound on every operand and neither output gradients nor Snake outputs have one.
+ * Any other value is ESCX_ERR_INVALID_ARG; a refusal leaves the mode as it was.  In both modes there are no atomics, two calls are bitwise equal and a
+ * gradient that is exactly zero in fp32 mode (a pad channel, a parameter whose output gradient is zero) is exactly zero.  DESIGN.md section 13.5. */
+int escx_dac_set_param_grad_precision(escx_dac d, int mode);
+int escx_dac_get_param_grad_precision(escx_dac d);
 /* ---- Audio gradient through the encoder and the quantiser (eval mode, padding on) ---------------------------------------------------------------
  * d (z, latents, commitment_loss) / d audio of DAC.encode (baselines/descript/dac/model/dac.py:209-247) for a frozen codec in the middle of a larger
  * autograd graph: Encoder.forward (dac.py:64-91) over EncoderBlock (dac.py:44-61: three ResidualUnits, Snake1d, strided WNConv1d) and
