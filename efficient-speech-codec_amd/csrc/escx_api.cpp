@@ -375,7 +375,7 @@ static int ensure_pvq_tables(escx_handle_s* h, hipStream_t st) {
         if (!want || !grab(&L.sub_x3_buf, rowgemm_x3_bytes(KP, Np))) continue;
         if (rowgemm_x3_pack(L.sub_wf, L.sub_x3_buf, KP, Np, st, nt, L.sub_g, L.sub_b, (L.scale == 1 ? 2 : 1) * L.C) == 0) L.sub_x3 = L.sub_x3_buf;
         if (L.scale == 2 && (L.Cp == 80 || L.Cp == 96 || L.Cp == 144) && L.Cp <= x3_max && grab(&L.sub_x3s_buf, mlp_x3_split_bytes(L.Cp, Np)) &&       // PatchSplit folded into the split-operand MLP's epilogue
-            mlp_x3_split_pack(L.sub_wf, L.sub_x3s_buf, L.Cp, Np, st) == 0) L.sub_x3s = L.sub_x3s_buf;
+            mlp_x3_split_pack(L.sub_wf, L.sub_x3s_buf, L.Cp, Np, st, nt, L.sub_g, L.sub_b, L.C) == 0) L.sub_x3s = L.sub_x3s_buf;
     }
     h->pvq_tab_stale = false;
     return launch_ok("derived images");

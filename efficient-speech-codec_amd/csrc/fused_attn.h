@@ -35,6 +35,8 @@ namespace escx {
 // Weight stream of the X3 instantiations: [group][tile][TF][64 lanes][16 B], TF = max(NT KS, KK) fragments per tile (NT = terms per operand: the two-term
 // stream is dense, no piece of it goes unread); a Q / K / V tile holds its NT KS split fragments (K-step s, term i) -> lane (row, g): term i of
 // W[row][32 s + 8 g + e]; a projection tile holds its KK fragments (fp32, or the two-term form described at attn_x3_pack_kernel).
+// Two-term streams of the widths with CP mod 32 == 16 (split_terms.h x2_tail_paired): the last K step of a Q / K / V tile is ONE fragment [w_hi | w_lo], so the tile reads
+// 2 KS - 1 fragments; TF stays max(2 KS, KK) because the paired unit's P_0 tile needs 2 KS, and fragment 2 KS - 1 of a Q / K / V tile is zero and unread.
 constexpr int attn_x3_ks(int CP) { return (CP + 31) / 32; }
 constexpr int attn_x3_tf(int CP, int NT = 3) { return NT * attn_x3_ks(CP) > CP / 16 ? NT * attn_x3_ks(CP) : CP / 16; }
 __device__ __forceinline__ void attn_split3(const float (&v)[8], bf16x8& t0, bf16x8& t1, bf16x8& t2) {
@@ -69,7 +71,7 @@ __device__ __forceinline__ void attn_split3(const float (&v)[8], bf16x8& t0, bf1
 // does not move with TF: fused_swin.hip attn_x3_trailer / rowgemm_x3_trailer are the one definition, for the packers and (x3_scale) the launchers and kernels.
 __global__ __launch_bounds__(256) void attn_x3_pack_kernel(const f32x4* __restrict__ waf, bf16x8* __restrict__ out, bf16x8* __restrict__ tail, int n_tiles, int TPG, int KK, int KS, int TF, unsigned proj_mask, int NT = 3,
                                                            const float* __restrict__ gamma = nullptr, const float* __restrict__ beta = nullptr, int n_ln = 0, int C = 0,
-                                                           const float* __restrict__ bqkv = nullptr, int n_bqkv = 0, int pair = 0) {
+                                                           const float* __restrict__ bqkv = nullptr, int n_bqkv = 0, int pair = 0, int tail_pair = 0) {
     const int per_tile = (KS > KK ? KS : KK) * 64;
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= (long long)n_tiles * per_tile) return;
@@ -104,10 +106,13 @@ __global__ __launch_bounds__(256) void attn_x3_pack_kernel(const f32x4* __restri
     }
     if (f >= KS) return;
     const int l15 = lane & 15, g = lane >> 4;
+    // tail_pair (attention streams of the widths with x2_tail_paired, split_terms.h): the last K step of a Q / K / V tile is ONE fragment [w_hi | w_lo] - lane groups 2, 3 read the
+    // channels of groups 0, 1 and keep their low terms; the tile's fragment 2 KS - 1 stays unwritten and unread (the image is cleared before it is packed)
+    const bool pairf = NT == 2 && tail_pair && f == KS - 1;
     float v[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-        const int kk = 2 * f + (g >> 1), lgs = 2 * (g & 1) + (e >> 2);
+        const int kk = 2 * f + (pairf ? 0 : g >> 1), lgs = 2 * (g & 1) + (e >> 2);
         v[e] = kk < KK ? src[kk * 64 + 16 * lgs + l15][e & 3] : 0.f;
     }
     if (NT == 3) {
@@ -118,7 +123,8 @@ __global__ __launch_bounds__(256) void attn_x3_pack_kernel(const f32x4* __restri
         const float sc = x2_scale(*reinterpret_cast<const unsigned*>(tail));
         bf16x8 t[2];
         split_terms<2>(v, t, sc);
-        dst[(f * 2 + 0) * 64 + lane] = t[0]; dst[(f * 2 + 1) * 64 + lane] = t[1];
+        if (pairf) dst[(f * 2) * 64 + lane] = t[g >> 1];
+        else { dst[(f * 2 + 0) * 64 + lane] = t[0]; dst[(f * 2 + 1) * 64 + lane] = t[1]; }
         if (idx == 0) {
             const float bx = gamma ? ln_out_bound(gamma, beta, n_ln, C) : 0.f;
             const float sx = gamma ? act_pow2_scale(bx) : 1.0f;
@@ -223,6 +229,7 @@ __global__ __launch_bounds__(64 * NW, (attn_min_waves_f<CP, MODE, TMW, NW, X3, N
     static_assert(TPG % UT == 0, "stage size must divide the tiles of a head group");
     constexpr int KS = attn_x3_ks(CP);
     constexpr int TF = X3 ? attn_x3_tf(CP, NT) : KK;            // fragments (1 KiB) per weight tile in the stream
+    constexpr bool TAILA = X3 && x2_tail_paired(CP, NT);        // two-term, CP mod 32 == 16: the last K step of the Q / K / V tiles is the paired one (split_terms.h)
     __shared__ f32x4 wbuf_static[X3 ? 1 : 2 * UT * KK * 64];
     extern __shared__ __attribute__((aligned(16))) f32x4 wbuf_dyn[];      // X3: 2 * UT * TF KiB (above the 64 KiB of static LDS at the wide layers)
     f32x4* const wbuf0 = X3 ? wbuf_dyn : wbuf_static;
@@ -316,6 +323,13 @@ __global__ __launch_bounds__(64 * NW, (attn_min_waves_f<CP, MODE, TMW, NW, X3, N
                 split_terms<NT>(xn, tt);
 #pragma unroll
                 for (int i = 0; i < NT; ++i) xs[t][i][ks] = tt[i];
+            }
+            if constexpr (TAILA) {              // [x_hi | x_hi]: lane groups 2, 3 (zero: pad channels) receive the high terms of groups 0, 1 of their slot; the low terms keep their zeros
+                const f32x4 own = __builtin_bit_cast(f32x4, xs[t][0][KS - 1]);
+                f32x4 dup;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) dup[e] = __shfl_xor(own[e], 32);
+                if (lg >= 2) xs[t][0][KS - 1] = __builtin_bit_cast(bf16x8, dup);
             }
         }
         if constexpr (!X3) {
@@ -443,6 +457,17 @@ __global__ __launch_bounds__(64 * NW, (attn_min_waves_f<CP, MODE, TMW, NW, X3, N
         for (int t = 0; t < TMW; ++t) { out[t] = NT == 2 ? init * x2_up : init; o2[t] = zero4(); }       // NT = 2: the sums carry 2^k, so does the bias (exact)
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
+            if constexpr (TAILA) {
+                if (ks == KS - 1) {             // paired tail: hi.lo on the first chain, hi.hi + lo.hi in one step on the second
+                    const bf16x8 wt = tb[(ks * NT) * 64];
+                    dma_pinned();
+#pragma unroll
+                    for (int t = 0; t < TMW; ++t) out[t] = x_rows ? mma_x<NT>(xs[t][1][ks], wt, out[t]) : mma_x<NT>(wt, xs[t][1][ks], out[t]);
+#pragma unroll
+                    for (int t = 0; t < TMW; ++t) o2[t] = x_rows ? mma_x<NT>(xs[t][0][ks], wt, o2[t]) : mma_x<NT>(wt, xs[t][0][ks], o2[t]);
+                    continue;
+                }
+            }
             bf16x8 w[NT];
 #pragma unroll
             for (int i = 0; i < NT; ++i) w[i] = tb[(ks * NT + i) * 64];

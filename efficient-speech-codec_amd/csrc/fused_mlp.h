@@ -42,6 +42,7 @@ struct MlpArgs {
     const f32x4* sp_wf; const float* sp_gamma; const float* sp_beta; float* sp_out;
     int sp_NT, sp_H, sp_W, sp_C2p;
     const void* x3_w;           // fused_mlp_x3.h: split (3 x bf16) weight image [pair of hidden tiles][fragment][lane][8 bf16], or nullptr
+    const float* sp_scale;      // fused_mlp_x3.h SPLIT, two-term form: {2^-k / sy, 2^k sy, sy} of the split weight image's trailer (mlp_x3_split_pack), else nullptr
 };
 
 template <int CP, int TM>

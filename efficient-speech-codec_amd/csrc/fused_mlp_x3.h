@@ -84,11 +84,13 @@ __device__ __forceinline__ void split_hidden_x2(const float (&v)[8], float scale
 template <int NT> __device__ __forceinline__ void split_hidden_x2(const float (&)[8], float, bf16x8 (&)[NT]) {}     // never called: keeps the NT = 3 instantiations well-formed
 
 constexpr int mlp_x3_ks(int CP) { return (CP + 31) / 32; }
-constexpr int mlp_x3_frags(int CP, int NT = 3) { return 2 * NT * mlp_x3_ks(CP) + NT * (CP / 16); }       // 1 KiB fragments per pair of hidden tiles: fc1 (KS steps x 2 tiles x NT terms), fc2 (KK tiles x NT terms)
+constexpr int mlp_x3_fc1_frags(int CP, int NT = 3) { return 2 * NT * mlp_x3_ks(CP) - (x2_tail_paired(CP, NT) ? 2 : 0); }     // per pair of hidden tiles: KS steps x 2 tiles x NT terms, one fragment per tile in a paired tail
+constexpr int mlp_x3_frags(int CP, int NT = 3) { return mlp_x3_fc1_frags(CP, NT) + NT * (CP / 16); }       // 1 KiB fragments per pair of hidden tiles: fc1, then fc2 (KK tiles x NT terms)
 // LDS staging.  Narrow layers (<= 36 fragments per pair): ONE stage per pair.  Wide layers: fc1 in stages of up to 6 K-steps (36 KiB), fc2 in stages of up to 6 pairs of
-// output tiles (36 KiB); two ring slots of the largest stage.
+// output tiles (36 KiB); two ring slots of the largest stage.  The stage structure is decided on the zero-padded fragment count, so a paired tail shortens a stage and moves no width
+// to another structure (CP = 144 in two-term form stays at two stages per pair).
 constexpr int MLP_X3_STAGE = 36;
-constexpr bool mlp_x3_single(int CP, int NT = 3) { return mlp_x3_frags(CP, NT) <= MLP_X3_STAGE; }
+constexpr bool mlp_x3_single(int CP, int NT = 3) { return 2 * NT * mlp_x3_ks(CP) + NT * (CP / 16) <= MLP_X3_STAGE; }
 constexpr int mlp_x3_gmax(int NT) { return MLP_X3_STAGE / (2 * NT); }               // K-steps (fc1) or output-tile pairs (fc2) per 36 KiB stage: 6 / 9
 constexpr int mlp_x3_g1(int CP, int NT = 3) { return mlp_x3_single(CP, NT) ? mlp_x3_ks(CP) : (mlp_x3_ks(CP) <= mlp_x3_gmax(NT) ? mlp_x3_ks(CP) : mlp_x3_gmax(NT)); }                    // K-steps per fc1 stage
 constexpr int mlp_x3_g2(int CP, int NT = 3) { return mlp_x3_single(CP, NT) ? (CP / 16 + 1) / 2 : ((CP / 16 + 1) / 2 <= mlp_x3_gmax(NT) ? (CP / 16 + 1) / 2 : mlp_x3_gmax(NT)); }           // output-tile pairs per fc2 stage
@@ -100,13 +102,15 @@ constexpr int mlp_x3_stage_frags(int CP, int NT = 3) {
 //   fc1 fragment f = (s * 2 + tt) * 3 + i          -> lane (n, g) holds term i of W1[16 (2p + tt) + n][32 s + 8 g + e], e = 0..7 (zero beyond Cp)
 //   fc2 fragment f = 6 KS + o * 3 + i              -> lane (c, g) holds term i of W2[16 o + c][unit(g, e)], unit = 16 (2p) + 4 g + e for e < 4, 16 (2p + 1) + 4 g + e - 4 otherwise
 // (the k-slot <-> hidden unit map the kernel's two fc1 accumulator tiles dictate).  One thread per (pair, fragment triple, lane).
+// NT = 2 with a paired tail (x2_tail_paired): fc1 fragments of the last K step are f = 4 (KS - 1) + tt, ONE per tile, [w_hi | w_lo]; fc2 starts at mlp_x3_fc1_frags = 4 KS - 2.
 // NT = 2: the image ends with three 16-byte slots - [0] bits of max |w1|, max |w2|, max_row ||w1_row||^2 (absmax_bits_kernel / rownorm2_max_bits_kernel, before this kernel),
 // [1] {2^-k1 / sx, 2^-k2 / sh, 2^k1 sx, 2^k2 sh} and [2] {sx, sh} written here: sx, sh = the power-of-two scales of the LayerNorm output and of the GELU output (split_terms.h
 // range rule; bounds from ln2's gamma / beta, the fc1 row norms and b1).  Behind the slots, written by mlp_x3_prescale_kernel from slot [1] / [2]'s own factors: b1 2^k1 sx [HP],
 // gamma sx [Cp], beta sx [Cp] - what the main kernel loads instead of b1 / gamma / beta (mlp_x3_bytes counts them).
 __global__ __launch_bounds__(256) void mlp_x3_pack_kernel(const float* __restrict__ w1, const float* __restrict__ w2, bf16x8* __restrict__ out, int Cp, int HP, int KS, int KK, int NT,
                                                           const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ b1, int C) {
-    const int CH = 2 * NT * KS + NT * KK, triples = 2 * KS + KK;
+    const bool tail = NT == 2 && Cp % 32 == 16;                 // x2_tail_paired: the last fc1 step is one [w_hi | w_lo] fragment per tile
+    const int F1 = 2 * NT * KS - (tail ? 2 : 0), CH = F1 + NT * KK, triples = 2 * KS + KK;
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     const long long total = (long long)(HP / 32) * triples * 64;
     if (idx >= total) return;
@@ -115,15 +119,17 @@ __global__ __launch_bounds__(256) void mlp_x3_pack_kernel(const float* __restric
     const int n = lane & 15, g = lane >> 4;
     float v[8];
     int fbase;
+    bool pairf = false;                                         // this thread writes a paired tail fragment
     if (t3 < 2 * KS) {
         const int s = t3 >> 1, tt = t3 & 1;
-        fbase = t3 * NT;
+        pairf = tail && s == KS - 1;
+        fbase = pairf ? 2 * NT * (KS - 1) + tt : t3 * NT;
         const float* row = w1 + (size_t)(16 * (2 * p + tt) + n) * Cp;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) { const int k = 32 * s + 8 * g + e; v[e] = k < Cp ? row[k] : 0.f; }
+        for (int e = 0; e < 8; ++e) { const int k = 32 * s + 8 * (pairf ? g & 1 : g) + e; v[e] = k < Cp ? row[k] : 0.f; }      // paired tail: groups 2, 3 read the channels of groups 0, 1
     } else {
         const int o = t3 - 2 * KS;
-        fbase = 2 * NT * KS + o * NT;
+        fbase = F1 + o * NT;
         const float* row = w2 + (size_t)(16 * o + n) * HP;
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = row[16 * (2 * p + (e >> 2)) + 4 * g + (e & 3)];
@@ -139,7 +145,8 @@ __global__ __launch_bounds__(256) void mlp_x3_pack_kernel(const float* __restric
         const float sc1 = x2_scale(mx[0]), sc2 = x2_scale(mx[1]);
         _Float16 h0[8], h1[8];
         split2_f16(v, t3 < 2 * KS ? sc1 : sc2, h0, h1);
-        dst[0] = pack8h(h0); dst[64] = pack8h(h1);
+        if (pairf) dst[0] = g < 2 ? pack8h(h0) : pack8h(h1);
+        else { dst[0] = pack8h(h0); dst[64] = pack8h(h1); }
         if (idx == 0) {
             float gb = 0.f, mb1 = 0.f;
             const float bx = ln_out_bound(gamma, beta, Cp, C, &gb);
@@ -163,9 +170,23 @@ __global__ __launch_bounds__(256) void mlp_x3_prescale_kernel(bf16x8* __restrict
     o[i] = i < HP ? b1[i] * f[2] : (i < HP + Cp ? gamma[i - HP] : beta[i - HP - Cp]) * f[4];
 }
 
+// PatchSplit in the SPLIT epilogue of mlp_x3_kernel: two accumulator tiles of x + mlp(x) are the 8 k-slots per lane of one 32-deep step, KSY = ceil(KK / 2) steps per output tile.
+// ONE rule for the packer, the image size, the LDS stages and the kernel - fragments per output tile:
+//   NT = 3: 3 KSY (three bf16 terms per step; an odd KK leaves the upper four k-slots of the last step zero);
+//   NT = 2: 2 KSY (hi, lo fp16 terms per step), and with an odd KK the last step is PAIRED (mlp_x3_split_tail): ONE fragment whose real slots e < 4 hold the hi terms and whose
+//           formerly-zero slots e >= 4 hold the lo terms of the same channels.  Against the activations [y_hi | y_hi] one MFMA gives hi.hi + lo.hi, against [y_lo | 0] hi.lo:
+//           two MFMAs and one fragment where the zero-padded step took three and two.
+constexpr int mlp_x3_split_ksy(int CP) { return (CP / 16 + 1) / 2; }
+constexpr bool mlp_x3_split_tail(int CP, int NT) { return x2_tail_paired(CP, NT); }           // KK odd <=> CP mod 32 == 16
+constexpr int mlp_x3_split_tfy(int CP, int NT) { return NT * mlp_x3_split_ksy(CP) - (mlp_x3_split_tail(CP, NT) ? 1 : 0); }
+
 // PatchSplit weights for the SPLIT epilogue of mlp_x3_kernel, from the fp32 fragment stream (Layer::sub_wf, [NT][KK][64] float4): fragment (nt, s, i) -> lane (n, g) holds
 // term i of W[16 nt + n][16 (2 s + (e >> 2)) + 4 g + (e & 3)], e = 0..7 - the k-slot <-> channel map of the epilogue (two accumulator tiles = one K step).
-__global__ __launch_bounds__(256) void mlp_x3_split_pack_kernel(const f32x4* __restrict__ wf, bf16x8* __restrict__ out, int NT, int KK) {
+// terms = 2 (split_terms.h): fp16 terms of w 2^k, TFY = mlp_x3_split_tfy fragments per output tile (the paired tail fragment above when KK is odd).  `tail` = the trailer that
+// closes the image's allocation (fused_swin.hip mlp_x3_split_trailer): slot [0] bits of max |w| (absmax_bits_kernel, before this kernel), slot [1] {2^-k / sy, 2^k sy, sy, 0}
+// written here, sy = the power-of-two scale of the PatchSplit norm's output (range rule; bound from its gamma / beta over Cp padded channels, C real ones) - rowgemm_x3_pack's trailer.
+__global__ __launch_bounds__(256) void mlp_x3_split_pack_kernel(const f32x4* __restrict__ wf, bf16x8* __restrict__ out, int NT, int KK, int terms, int TFY, bf16x8* __restrict__ tail,
+                                                                const float* __restrict__ gamma, const float* __restrict__ beta, int Cp, int C) {
     const int KSY = (KK + 1) / 2;
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= (long long)NT * KSY * 64) return;
@@ -174,10 +195,27 @@ __global__ __launch_bounds__(256) void mlp_x3_split_pack_kernel(const f32x4* __r
     float v[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) { const int kk = 2 * s + (e >> 2); v[e] = kk < KK ? wf[((size_t)nt * KK + kk) * 64 + 16 * g + l15][e & 3] : 0.f; }
-    __bf16 s0[8], s1[8], s2[8];
-    split3_bf16(v, s0, s1, s2);
-    bf16x8* dst = out + ((size_t)(nt * KSY + s) * 3) * 64 + lane;
-    dst[0] = pack8(s0); dst[64] = pack8(s1); dst[128] = pack8(s2);
+    if (terms == 3) {
+        __bf16 s0[8], s1[8], s2[8];
+        split3_bf16(v, s0, s1, s2);
+        bf16x8* dst = out + ((size_t)(nt * KSY + s) * 3) * 64 + lane;
+        dst[0] = pack8(s0); dst[64] = pack8(s1); dst[128] = pack8(s2);
+        return;
+    }
+    const float sc = x2_scale(*reinterpret_cast<const unsigned*>(tail));
+    bf16x8 t[2];
+    split_terms<2>(v, t, sc);
+    bf16x8* dst = out + ((size_t)nt * TFY + 2 * s) * 64 + lane;
+    if (TFY < 2 * KSY && s == KSY - 1) {          // paired tail: [w_hi | w_lo] of the last, half-empty step
+        const half8 hi = __builtin_bit_cast(half8, t[0]), lo = __builtin_bit_cast(half8, t[1]);
+        dst[0] = __builtin_bit_cast(bf16x8, half8{hi[0], hi[1], hi[2], hi[3], lo[0], lo[1], lo[2], lo[3]});
+    } else {
+        dst[0] = t[0]; dst[64] = t[1];
+    }
+    if (idx == 0) {
+        const float sy = act_pow2_scale(ln_out_bound(gamma, beta, Cp, C));
+        float* o = reinterpret_cast<float*>(tail + 1); o[0] = (1.0f / sc) * (1.0f / sy); o[1] = sc * sy; o[2] = sy; o[3] = 0.f;
+    }
 }
 
 // Timing-only ablations for tagged builds (-DESCX_X3_ABL=bits; results are wrong by construction, profiles/r5_mlp_x3_ablation.txt): 1 = one cross term instead of six,
@@ -209,6 +247,8 @@ __global__ __launch_bounds__(64 * NW, (mlp_x3_min_waves<CP>())) void mlp_x3_kern
     constexpr int NSP = SINGLE ? 1 : NS1 + NS2;                                   // stages per pair
     constexpr int SF = mlp_x3_stage_frags(CP, NT);                               // ring slot size in fragments
     constexpr int N2 = 2 * NT;
+    constexpr bool TAIL1 = x2_tail_paired(CP, NT);                               // the last fc1 step is the paired one: two fragments instead of N2
+    constexpr int F1 = mlp_x3_fc1_frags(CP, NT);
     extern __shared__ __attribute__((aligned(16))) bf16x8 x3_wbuf[];             // [2][SF * 64]
     const int lane = threadIdx.x & 63;
     const int l15 = lane & 15, lg = lane >> 4;
@@ -229,11 +269,11 @@ __global__ __launch_bounds__(64 * NW, (mlp_x3_min_waves<CP>())) void mlp_x3_kern
     // stage g (global counter over the pairs this workgroup walks): its fragments and where they start inside the pair's image
     auto stage_off = [&](int k) -> int {        // k = stage index inside a pair
         if (SINGLE) return 0;
-        return k < NS1 ? N2 * G1 * k : N2 * KS + N2 * G2 * (k - NS1);
+        return k < NS1 ? N2 * G1 * k : F1 + N2 * G2 * (k - NS1);
     };
     auto stage_cnt = [&](int k) -> int {
         if (SINGLE) return CH;
-        if (k < NS1) return N2 * (k + 1 < NS1 ? G1 : KS - G1 * (NS1 - 1));
+        if (k < NS1) return k + 1 < NS1 ? N2 * G1 : F1 - N2 * G1 * (NS1 - 1);
         const int pairs_before = G2 * (k - NS1), tiles = min(KK - 2 * pairs_before, 2 * G2);
         return NT * tiles;
     };
@@ -299,6 +339,13 @@ __global__ __launch_bounds__(64 * NW, (mlp_x3_min_waves<CP>())) void mlp_x3_kern
 #pragma unroll
             for (int i = 0; i < NT; ++i) xs[i][s] = t[i];
         }
+        if constexpr (TAIL1) {                  // [x_hi | x_hi]: lane groups 2, 3 (zero: pad channels) receive the high terms of groups 0, 1 of their row; the low terms keep their zeros
+            const f32x4 own = __builtin_bit_cast(f32x4, xs[0][KS - 1]);
+            f32x4 dup;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) dup[e] = __shfl_xor(own[e], 32);
+            if (lg >= 2) xs[0][KS - 1] = __builtin_bit_cast(bf16x8, dup);
+        }
     }
 
     f32x4 acc[KK];
@@ -324,6 +371,14 @@ __global__ __launch_bounds__(64 * NW, (mlp_x3_min_waves<CP>())) void mlp_x3_kern
         for (int s = 0; s < KS; ++s) {
             if (s % G1 == 0) wb = next_stage();
             const bf16x8* wf = wb + (size_t)((s % G1) * N2) * 64;
+            if constexpr (TAIL1) {
+                if (s == KS - 1) {              // paired tail: hi.lo, then hi.hi + lo.hi in one step
+                    const bf16x8 t0 = wf[0], t1 = wf[64];
+                    h0 = mma_x<NT>(t0, xs[1][s], h0); h1 = mma_x<NT>(t1, xs[1][s], h1);
+                    h0 = mma_x<NT>(t0, xs[0][s], h0); h1 = mma_x<NT>(t1, xs[0][s], h1);
+                    continue;
+                }
+            }
             bf16x8 w0[NT], w1[NT];
 #pragma unroll
             for (int i = 0; i < NT; ++i) { w0[i] = wf[i * 64]; w1[i] = wf[(NT + i) * 64]; }
@@ -356,7 +411,7 @@ __global__ __launch_bounds__(64 * NW, (mlp_x3_min_waves<CP>())) void mlp_x3_kern
         }
 #endif
         // ---- fc2: two output tiles per step (no back-to-back MFMAs on one accumulator) ----
-        const bf16x8* w2b = SINGLE ? wb + (size_t)(N2 * KS) * 64 : nullptr;
+        const bf16x8* w2b = SINGLE ? wb + (size_t)F1 * 64 : nullptr;
 #pragma unroll
         for (int op = 0; op < NOP; ++op) {
             if (!SINGLE && op % G2 == 0) w2b = next_stage();
@@ -376,7 +431,8 @@ __global__ __launch_bounds__(64 * NW, (mlp_x3_min_waves<CP>())) void mlp_x3_kern
     }
 
     if constexpr (SPLIT) {
-        constexpr int KSY = (KK + 1) / 2, TFY = 3 * KSY, UTY = SF / TFY;           // fragments per output tile of the split weights, output tiles per LDS stage
+        constexpr int KSY = mlp_x3_split_ksy(CP), TFY = mlp_x3_split_tfy(CP, NT), UTY = SF / TFY;      // fragments per output tile of the split weights, output tiles per LDS stage
+        constexpr bool YTAIL = mlp_x3_split_tail(CP, NT);                          // NT = 2, odd KK: the last step is the paired one
         static_assert(UTY >= 1, "one output tile of the split weights must fit a ring slot");
         const bf16x8* ssrc = reinterpret_cast<const bf16x8*>(a.sp_wf);
         const int n_st = (a.sp_NT + UTY - 1) / UTY;
@@ -408,7 +464,9 @@ __global__ __launch_bounds__(64 * NW, (mlp_x3_min_waves<CP>())) void mlp_x3_kern
             for (int e = 0; e < 4; ++e) { const float d = acc[o][e] - smean; v += d * d; }
         v = sum_groups(v) - (float)(CP - a.C) * smean * smean;
         const float srstd = 1.0f / sqrtf(v / (float)a.C + a.eps);
-        bf16x8 ys[3][KSY];
+        bf16x8 ys[NT][KSY];
+        float y2dn = 1.f, y2sy = 1.f;           // NT = 2: 2^-k / sy of the scaled split weights, sy = the power-of-two scale of this norm's output (range rule)
+        if constexpr (NT == 2) { y2dn = a.sp_scale[0]; y2sy = a.sp_scale[2]; }
 #pragma unroll
         for (int sy = 0; sy < KSY; ++sy) {
             float yn[8];
@@ -424,9 +482,19 @@ __global__ __launch_bounds__(64 * NW, (mlp_x3_min_waves<CP>())) void mlp_x3_kern
                     for (int e = 0; e < 4; ++e) yn[4 * hlf + e] = 0.f;
                 }
             }
-            __bf16 t0[8], t1[8], t2[8];
-            split3_bf16(yn, t0, t1, t2);
-            ys[0][sy] = pack8(t0); ys[1][sy] = pack8(t1); ys[2][sy] = pack8(t2);
+            if constexpr (NT == 2) {
+                bf16x8 t[2];
+                split_terms<2>(yn, t, y2sy);
+                if (YTAIL && sy == KSY - 1) {   // paired tail: the high terms fill their own zero slots, [y_hi | y_hi]; the low terms keep theirs, [y_lo | 0]
+                    const half8 hi = __builtin_bit_cast(half8, t[0]);
+                    t[0] = __builtin_bit_cast(bf16x8, half8{hi[0], hi[1], hi[2], hi[3], hi[0], hi[1], hi[2], hi[3]});
+                }
+                ys[0][sy] = t[0]; ys[1][sy] = t[1];
+            } else {
+                __bf16 t0[8], t1[8], t2[8];
+                split3_bf16(yn, t0, t1, t2);
+                ys[0][sy] = pack8(t0); ys[1][sy] = pack8(t1); ys[2][sy] = pack8(t2);
+            }
         }
         size_t ob0 = 0, ob1 = 0;
         if (live) {
@@ -443,6 +511,18 @@ __global__ __launch_bounds__(64 * NW, (mlp_x3_min_waves<CP>())) void mlp_x3_kern
             const int nt_end = min(a.sp_NT, (st + 1) * UTY);
             for (int nt = st * UTY; nt < nt_end; ++nt, wbs += TFY * 64) {
                 f32x4 o0 = zero4(), o1 = zero4();
+                if constexpr (NT == 2) {        // three products per full step in ESCX_X2_TERMS order on the two accumulators, two in the paired tail (smallest first)
+#pragma unroll
+                    for (int sy = 0; sy < KSY; ++sy) {
+                        const bf16x8 w0 = wbs[(2 * sy) * 64];
+                        if (YTAIL && sy == KSY - 1) {
+                            o0 = mma_x<2>(w0, ys[1][sy], o0); o1 = mma_x<2>(w0, ys[0][sy], o1);
+                        } else {
+                            const bf16x8 w1 = wbs[(2 * sy + 1) * 64];
+                            o0 = mma_x<2>(w0, ys[1][sy], o0); o1 = mma_x<2>(w1, ys[0][sy], o1); o0 = mma_x<2>(w0, ys[0][sy], o0);
+                        }
+                    }
+                } else {
 #pragma unroll
                 for (int sy = 0; sy < KSY; ++sy) {
                     bf16x8 w[3];
@@ -452,9 +532,12 @@ __global__ __launch_bounds__(64 * NW, (mlp_x3_min_waves<CP>())) void mlp_x3_kern
                     o0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[1], ys[1][sy], o0, 0, 0, 0); o1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[0], ys[1][sy], o1, 0, 0, 0);
                     o0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[1], ys[0][sy], o0, 0, 0, 0); o1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[0], ys[0][sy], o1, 0, 0, 0);
                 }
+                }
                 if (live) {
                     const int n = 16 * nt + 4 * lg, s2 = n / a.sp_C2p;
-                    st4(a.sp_out + (s2 ? ob1 : ob0) + (n - s2 * a.sp_C2p), o0 + o1);
+                    f32x4 ov = o0 + o1;
+                    if constexpr (NT == 2) ov *= y2dn;          // back from 2^k sy, once per output tile (exact)
+                    st4(a.sp_out + (s2 ? ob1 : ob0) + (n - s2 * a.sp_C2p), ov);
                 }
             }
         }

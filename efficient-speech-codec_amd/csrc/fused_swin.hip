@@ -143,11 +143,23 @@ static void launch_mlp_x3(const MlpArgs& a, hipStream_t s) {
 }
 
 
-size_t mlp_x3_split_bytes(int Cp, int Np) { return (size_t)(Np / 16) * 3 * ((Cp / 16 + 1) / 2) * 1024; }
-int mlp_x3_split_pack(const float* wf, void* image, int Cp, int Np, hipStream_t s) {
+// 32-byte trailer as rowgemm_x3_bytes: the allocation has the three-term size for both forms (set_precision re-packs in place); the two-term image (mlp_x3_split_tfy fragments
+// per output tile) fills its head and the trailer {bits of max |w|}, {2^-k / sy, 2^k sy, sy, 0} stays at the allocation's end.  mlp_x3_split_trailer is the one definition.
+size_t mlp_x3_split_bytes(int Cp, int Np) { return (size_t)(Np / 16) * mlp_x3_split_tfy(Cp, 3) * 1024 + 32; }
+static char* mlp_x3_split_trailer(const void* image, int Cp, int Np) { return reinterpret_cast<char*>(const_cast<void*>(image)) + mlp_x3_split_bytes(Cp, Np) - 32; }
+int mlp_x3_split_pack(const float* wf, void* image, int Cp, int Np, hipStream_t s, int nt, const float* gamma, const float* beta, int C) {
+    if (nt != 2 && nt != 3) return -1;
+    if (nt == 2 && (!gamma || !beta)) return -1;                    // the range rule needs the PatchSplit norm
     const int KK = Cp / 16, NT = Np / 16;
     const long long total = (long long)NT * ((KK + 1) / 2) * 64;
-    ESCX_LAUNCH(mlp_x3_split_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const f32x4*>(wf), reinterpret_cast<bf16x8*>(image), NT, KK);
+    char* tail = mlp_x3_split_trailer(image, Cp, Np);
+    if (nt == 2) {
+        if (hipMemsetAsync(tail, 0, 16, s) != hipSuccess) return -1;
+        const long long n = (long long)NT * KK * 64 * 4;
+        ESCX_LAUNCH(absmax_bits_kernel, dim3((unsigned)std::min<long long>(256, (n + 255) / 256)), dim3(256), 0, s, wf, n, reinterpret_cast<unsigned*>(tail));
+    }
+    ESCX_LAUNCH(mlp_x3_split_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const f32x4*>(wf), reinterpret_cast<bf16x8*>(image), NT, KK,
+                nt, mlp_x3_split_tfy(Cp, nt), reinterpret_cast<bf16x8*>(tail), gamma, beta, Cp, C);
     return 0;
 }
 
@@ -176,6 +188,7 @@ int mlp_x3(float* x, int M, int C, int Cp, const float* gamma, const float* beta
         a.x = x; a.gamma = gamma; a.beta = beta; a.b1 = b1; a.b2 = b2; a.M = M; a.C = C; a.HT = hiddenP / 16; a.eps = 1e-5f; a.HS = 1; a.x3_w = image;
         a.sp_wf = reinterpret_cast<const f32x4*>(split->wf); a.sp_gamma = split->gamma; a.sp_beta = split->beta; a.sp_out = split->out;
         a.sp_NT = split->NT; a.sp_H = split->H; a.sp_W = split->W; a.sp_C2p = split->C2p;
+        if (nt == 2) a.sp_scale = reinterpret_cast<const float*>(mlp_x3_split_trailer(split->wf, Cp, 16 * split->NT) + 16);
         switch (Cp) {
 #define ESCX_X3S_CASE(CPV) case CPV: if (nt == 2) { if (nw == 8) launch_mlp_x3_split<CPV, 8, 2>(a, s); else launch_mlp_x3_split<CPV, 4, 2>(a, s); } \
                            else { if (nw == 8) launch_mlp_x3_split<CPV, 8>(a, s); else launch_mlp_x3_split<CPV, 4>(a, s); } return 0;
@@ -253,7 +266,7 @@ int rowgemm_x3_pack(const float* wf, void* image, int KP, int Np, hipStream_t s,
         ESCX_LAUNCH(absmax_bits_kernel, dim3((unsigned)std::min<long long>(256, (n + 255) / 256)), dim3(256), 0, s, wf, n, mx);
     }
     ESCX_LAUNCH(attn_x3_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const f32x4*>(wf), reinterpret_cast<bf16x8*>(image),
-                       reinterpret_cast<bf16x8*>(rowgemm_x3_trailer(image, KP, Np)), NT, 1, KK, KS, (nt == 2 ? 2 : 3) * KS, 0u, nt == 2 ? 2 : 3, gamma, beta, KP, C, (const float*)nullptr, 0, 0);
+                       reinterpret_cast<bf16x8*>(rowgemm_x3_trailer(image, KP, Np)), NT, 1, KK, KS, (nt == 2 ? 2 : 3) * KS, 0u, nt == 2 ? 2 : 3, gamma, beta, KP, C, (const float*)nullptr, 0, 0, 0);         // no paired tail: rowgemm_x3_kernel keeps the zero-padded last step
     return 0;
 }
 
@@ -457,7 +470,8 @@ int attn_x3_pack(const float* waf, void* image, int Cp, int mode, int n_groups, 
         ESCX_LAUNCH(absmax_tiles_bits_kernel, grid, dim3(256), 0, s, waf, n, KK * 256, TPG, proj_mask, mx + 2);
     }
     ESCX_LAUNCH(attn_x3_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const f32x4*>(waf), reinterpret_cast<bf16x8*>(image),
-                       reinterpret_cast<bf16x8*>(attn_x3_trailer(image, Cp, mode, n_groups)), n_tiles, TPG, KK, KS, TF, proj_mask, nt == 2 ? 2 : 3, gamma, beta, Cp, C, bqkv, n_groups * (mode == 2 ? 6 : 3) * 16, pair);
+                       reinterpret_cast<bf16x8*>(attn_x3_trailer(image, Cp, mode, n_groups)), n_tiles, TPG, KK, KS, TF, proj_mask, nt == 2 ? 2 : 3, gamma, beta, Cp, C, bqkv, n_groups * (mode == 2 ? 6 : 3) * 16, pair,
+                       x2_tail_paired(Cp, nt) ? 1 : 0);          // the paired tail step of the Q / K / V tiles (split_terms.h)
     return 0;
 }
 

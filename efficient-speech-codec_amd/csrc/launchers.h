@@ -45,7 +45,7 @@ struct MlpSplit;
 int mlp_x3(float* x, int M, int C, int Cp, const float* gamma, const float* beta, const float* b1, const float* b2, const void* image, int hiddenP, int nw, int* hs_io, float* partial,
            hipStream_t s, const MlpSplit* split = nullptr, int nt = 3, float* out = nullptr);      // split: PatchSplit in the epilogue, split->wf = image of mlp_x3_split_pack
 size_t mlp_x3_split_bytes(int Cp, int Np);
-int mlp_x3_split_pack(const float* wf, void* image, int Cp, int Np, hipStream_t s);
+int mlp_x3_split_pack(const float* wf, void* image, int Cp, int Np, hipStream_t s, int nt = 3, const float* gamma = nullptr, const float* beta = nullptr, int C = 0);   // nt terms as mlp_x3_pack; gamma / beta over Cp channels, C real ones: the PatchSplit norm (nt = 2 range rule)
 void rows_combine(float* dst, const float* src, const float* partial, const float* bias, long long M, int Cp, int n, hipStream_t s);
 
 // LN + linear for PatchMerge (segs = 2, map gives the two source rows) / PatchSplit (segs = 1, split = 1: pixel-shuffled store)

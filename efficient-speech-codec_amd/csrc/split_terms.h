@@ -101,4 +101,12 @@ static __global__ __launch_bounds__(256) void rownorm2_max_bits_kernel(const flo
 // the cross terms (weight term i, activation term j), smallest first
 #define ESCX_X2_TERMS(M) M(0, 1) M(1, 0) M(0, 0)
 
+// PAIRED TAIL STEP of the two-term form (the one rule; the packers, launchers and kernels of fused_mlp_x3.h and fused_attn.h derive from it).  CP mod 32 == 16: the last 32-deep step of a K = C contraction has 16 real
+// channels and 16 zero k-slots on both operands, in each of the three cross products.  The slots are filled with another cross term instead: the tail step has ONE weight
+// fragment per output tile, [w_hi | w_lo] - lane groups 0, 1 hold the high terms of channels 32 s + 8 g + e as before, groups 2, 3 the LOW terms of the same channels
+// (group g holds channels 32 s + 8 (g - 2) + e) - and the activations' high-term tail fragment carries a copy of its own real slots in groups 2, 3, [x_hi | x_hi], made once per
+// row tile; the low-term tail fragment keeps its zeros, [x_lo | 0].  Then mma(tailW, [x_lo | 0]) = hi.lo and mma(tailW, [x_hi | x_hi]) = hi.hi + lo.hi: two matrix steps and one
+// fragment where the zero-padded step took three and two, smallest term first as in ESCX_X2_TERMS.  Every width with the tail takes it (register table: DESIGN.md section 10 item 19).
+constexpr bool x2_tail_paired(int CP, int NT) { return NT == 2 && CP % 32 == 16; }
+
 }  // namespace escx
