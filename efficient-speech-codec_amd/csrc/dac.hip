@@ -11,6 +11,8 @@
 // (DESIGN.md section 13.4).  escx_dac_decode_backward_params is the decoder's backward with the gradients of its parameters (bias, weight_g, weight_v,
 // alpha) next to d_z, for fine-tuning a decoder (dac_param_grad_kernels.h, gemm_dw_kernel of train_kernels.h);
 // escx_dac_set_param_grad_precision moves its weight-gradient contractions to the split-operand gemm_dw_bf16_kernel<.., 3> of gemm_bf16.h.
+// escx_dac_encode_lengths / escx_dac_from_codes_lengths / escx_dac_decode_lengths are encode, from_codes and decode for a batch with one length per
+// clip (padding on): per-clip length tables in the loader and the epilogue, every clip bitwise its own call.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -71,6 +73,7 @@ struct escx_dac_s {
     // call in that mode; w16_valid is cleared by every re-pack of the fp32 image and set by refresh_w16, so the image can never be older than wbuf.
     __bf16* w16 = nullptr; size_t conv_floats = 0; bool w16_valid = false;
     int* counts = nullptr; size_t counts_cap = 0;   // per-clip stage counts / snapshot stages of the _ex calls, uploaded on the call's stream
+    std::vector<int32_t> len_host;                  // the _lengths calls: the host image of their length tables, alive while the upload is in flight
     // escx_dac_decode_backward: the decoder's transposed weight images, allocated (zeroed) at the first backward of the handle; wt_valid is cleared by
     // every re-pack of wbuf and set by refresh_wt, as w16_valid is.  Calls that never differentiate pay nothing.
     float* wt = nullptr; bool wt_valid = false;
@@ -186,8 +189,8 @@ struct Run { int snake_maps; float* tmp; hipStream_t st; const float* wbuf; cons
 // The cropped skip of a ResidualUnit without padding: res has Tres rows per clip and is read `off` rows in (DacEpiCrop)
 struct Crop { int Tres, off; };
 
-template <class Epi>
-void launch_conv(const Run& run, const DacLayer& l, const __bf16* W16, const float* W, const DacConvA& ld, const Epi& ep) {
+template <class Ld, class Epi>
+void launch_conv(const Run& run, const DacLayer& l, const __bf16* W16, const float* W, const Ld& ld, const Epi& ep) {
     const long long tiles = (long long)((ld.M + 127) / 128) * ((l.Np + 95) / 96);
     if (W16) launch_dac_x3(ld, W16, run.plane, ld.M, l.Np, l.Kp, ep, run.st);
     else if (tiles >= 512) launch_gemm<128>(ld, W, ld.M, l.Np, l.Kp, ep, run.st);
@@ -673,6 +676,211 @@ extern "C" int escx_dac_decode(escx_dac d, const float* flat, int64_t version, c
     }
     run_layer(run, ESCX_DAC_SNAKE_LAST, Dl[d->dec.size() - 1], SN + d->dec_sn.size() - 1, x, B, T, audio, Lout, nullptr, 1);
     return launch_ok("escx_dac_decode");
+}
+
+// ---- mixed-length batches: per-clip lengths in encode, from_codes and decode (padding on; dac.py:209-323) ------------------
+namespace {
+
+// run_layer for a batch with per-clip lengths: the padded maps' rows per clip (Tin, Tout) and the device tables of the clips' own rows in them.
+// The launches are run_layer's - the same tile rule on the padded row count, and no output bit depends on it - with DacConvALen / DacEpiLen.
+void run_layer_len(const Run& run, int cls, const DacLayer& l, const DacSnake* sn, const float* x, int B, int Tin, const int* tin, float* out, int Tout,
+                   const int* tout, const float* res, int tanh_out) {
+    const hipStream_t st = run.st;
+    if (sn && ((run.snake_maps >> cls) & 1)) {                  // over the padded map: the rows past a clip's length are stale values nobody reads
+        const long long n4 = (long long)B * Tin * l.CinP / 4;
+        hipLaunchKernelGGL(dac_snake_map_kernel, dim3(nblk(n4)), dim3(256), 0, st, x, sn->a, sn->inv, run.tmp, n4, l.CinP / 4);
+        x = run.tmp; sn = nullptr;
+    }
+    const int phases = l.kind ? l.stride : 1;
+    const __bf16* W16 = (run.w16 && x3_layer(l)) ? run.w16 + (l.W - run.wbuf) : nullptr;
+    for (int r = 0; r < phases; ++r) {
+        DacConvALen ld{};
+        ld.x = x; ld.alpha = sn ? sn->a : nullptr; ld.inv = sn ? sn->inv : nullptr; ld.tin = tin; ld.tout = tout; ld.Tin = Tin; ld.Cp = l.CinP;
+        ld.dCp = FastDiv(l.CinP); ld.keep_dead = tanh_out;
+        DacEpiLen ep{};
+        ep.out = out; ep.res = res; ep.tout = tout; ep.Cp = tanh_out ? 4 : cpad(l.Cout); ep.Tmap = Tout; ep.tanh_out = tanh_out; ep.bias = l.bias;
+        if (l.kind == 0) {
+            ld.Trows = Tout; ld.rs = l.stride; ld.r0 = -l.pad; ld.td = l.dil; ld.ntaps = l.K; ld.os = 1; ld.o0 = 0;
+            ld.M = B * Tout; ld.dT = FastDiv(Tout);
+            ep.os = 1; ep.o0 = 0; ep.Trows = Tout; ep.dT = ld.dT;
+            launch_conv(run, l, W16, l.W, ld, ep);
+        } else {
+            const int s = l.stride, Q = r < Tout ? (Tout - r + s - 1) / s : 0;
+            if (Q == 0) continue;
+            ld.Trows = Q; ld.rs = 1; ld.r0 = (r + l.pad) / s; ld.td = -1; ld.ntaps = 2; ld.os = s; ld.o0 = r;
+            ld.M = B * Q; ld.dT = FastDiv(Q);
+            ep.os = s; ep.o0 = r; ep.Trows = Q; ep.dT = ld.dT;
+            launch_conv(run, l, W16 ? W16 + (size_t)r * l.Np * l.Kp : nullptr, l.W + (size_t)r * l.Np * l.Kp, ld, ep);
+        }
+    }
+}
+
+// ResidualUnit in place (padding on: the length is kept)
+void run_res_len(const Run& run, const DacLayer* L, const DacSnake* S, float* x, float* h, int B, int T, const int* tl) {
+    run_layer_len(run, ESCX_DAC_SNAKE_RES7, L[0], &S[0], x, B, T, tl, h, T, tl, nullptr, 0);
+    run_layer_len(run, ESCX_DAC_SNAKE_RES1, L[1], &S[1], h, B, T, tl, x, T, tl, x, 0);
+}
+
+// Per-clip rows at every resolution level of the encoder (level 0: samples; one more level per strided convolution) or the decoder (level 0: latent
+// frames; one more per ConvTranspose1d), from conv_out_len per clip: tab[level * B + b].  With the padding on the stride-1 layers keep the length, so
+// one table per level serves every layer of it.  false when clip *bad gives no row at some layer.
+bool level_table(const escx_dac_s* d, bool decoder, const int32_t* len0, int B, std::vector<int32_t>* tab, int* bad) {
+    const std::vector<DacLayer>& V = decoder ? d->dec : d->enc;
+    const int levels = 1 + (decoder ? d->cfg.n_decoder_rates : d->cfg.n_encoder_rates);
+    tab->assign((size_t)levels * B, 0);
+    for (int b = 0; b < B; ++b) {
+        int T = len0[b], lv = 0;
+        (*tab)[b] = T;
+        for (const DacLayer& l : V) {
+            const int T2 = conv_out_len(T, l, true);
+            if (T2 < 1) { *bad = b; return false; }
+            if (l.kind == 1 || l.stride > 1) (*tab)[(size_t)(++lv) * B + b] = T2;
+            else if (T2 != T) { *bad = b; return false; }       // never with the padding on
+            T = T2;
+        }
+    }
+    return true;
+}
+
+int check_lengths(const escx_dac_s* d, const int32_t* len, int B, int hi, const char* what) {
+    if (!d->padding) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "per-clip %s need the padding on (escx_dac_set_padding)", what);
+    if (!len) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null %s", what);
+    for (int b = 0; b < B; ++b)
+        if (len[b] < 1 || len[b] > hi) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "%s[%d]=%d outside [1, %d]", what, b, len[b], hi);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int escx_dac_encode_lengths(escx_dac d, const float* flat, int64_t version, const float* audio, int B, int Lmax, const int32_t* lengths, int pad_multiple,
+                                       int n_q, const int32_t* clip_n, float* z, int64_t* codes, float* latents, float* losses, void* stream) {
+    int rc = check_args(d, flat, B); if (rc) return rc;
+    if (!audio || !z || !codes || !latents || !losses || n_q < 1 || Lmax < 1 || pad_multiple < 1) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "bad argument");
+    if ((rc = check_lengths(d, lengths, B, Lmax, "lengths"))) return rc;
+    if (clip_n && n_q > d->cfg.n_codebooks) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "%d code slots above the %d codebooks", n_q, d->cfg.n_codebooks);
+    const int n = std::min(n_q, d->cfg.n_codebooks);
+    if (clip_n && (rc = check_clip_counts(d, clip_n, B, n))) return rc;
+    // the clips' lengths as the encoder sees them: right-padded with zeros to a multiple of pad_multiple (DAC.preprocess, dac.py:198-207)
+    std::vector<int32_t> padded(B), tab;
+    int Lmap = 0;
+    for (int b = 0; b < B; ++b) {
+        const long long p = ((long long)lengths[b] + pad_multiple - 1) / pad_multiple * pad_multiple;
+        if (p > 0x7fffffffll) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "lengths[%d]=%d padded to a multiple of %d overflows", b, lengths[b], pad_multiple);
+        padded[b] = (int32_t)p; Lmap = std::max(Lmap, padded[b]);
+    }
+    int bad = 0;
+    if (!level_table(d, false, padded.data(), B, &tab, &bad))
+        ESCX_FAIL(ESCX_ERR_INVALID_ARG, "lengths[%d]=%d samples give no latent frame (the hop is %d)", bad, lengths[bad], d->hop);
+    size_t mf = 0;
+    const int Tz = enc_walk(d, true, B, Lmap, &mf);
+    if (Tz < 1) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "%d samples give no latent frame (the hop is %d)", Lmap, d->hop);
+    if ((unsigned long long)mf >= (1ull << 32)) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "batch of %d x %d samples: a feature map above 2^32 elements", B, Lmap);
+    hipStream_t st = (hipStream_t)stream;
+    const size_t M = (size_t)B * Tz;
+    const size_t lossf = pad64((size_t)n * M) + pad64((size_t)n * B);
+    if ((rc = ensure_scratch(d, (4 * mf + lossf) * sizeof(float)))) return rc;
+    // one upload: the lengths as given (what is read of the audio), the level tables, the stage counts
+    const int nE = d->cfg.n_encoder_rates;
+    std::vector<int32_t>& host = d->len_host;
+    host.assign(lengths, lengths + B);
+    host.insert(host.end(), tab.begin(), tab.end());
+    if (clip_n) host.insert(host.end(), clip_n, clip_n + B);
+    const int* dev; if ((rc = upload_counts(d, host.data(), (int)host.size(), &dev, st))) return rc;
+    const int* lv = dev + B;                                    // lv + i * B: level i
+    if ((rc = pack(d, flat, (long long)version, st)) || (rc = refresh_w16(d, st))) return rc;
+    float* x = d->scratch; float* y = x + mf; float* h = y + mf; float* lossb = h + mf + mf;
+    const Run run{d->snake_maps, h + mf, st, d->wbuf, d->precision == ESCX_PRECISION_BF16X3 ? d->w16 : nullptr, d->conv_floats, true};
+    hipLaunchKernelGGL(dac_wave_in_len_kernel, dim3(nblk((long long)B * Lmap)), dim3(256), 0, st, audio, h, (long long)B * Lmap, Lmax, Lmap, dev);
+    const DacLayer* E = d->enc.data(); const DacSnake* SN = d->enc_sn.data();
+    int T = Lmap;
+    run_layer_len(run, ESCX_DAC_SNAKE_LAST, E[0], nullptr, h, B, T, lv, x, T, lv, nullptr, 0);
+    for (int i = 0; i < nE; ++i) {
+        const DacLayer* Lb = E + 1 + i * 7; const DacSnake* Sb = SN + i * 7;
+        const int* tl = lv + (size_t)i * B;
+        for (int j = 0; j < 3; ++j) run_res_len(run, Lb + 2 * j, Sb + 2 * j, x, h, B, T, tl);
+        const int T2 = conv_out_len(T, Lb[6], true);
+        run_layer_len(run, ESCX_DAC_SNAKE_DOWN, Lb[6], Sb + 6, x, B, T, tl, y, T2, tl + B, nullptr, 0);
+        std::swap(x, y); T = T2;
+    }
+    const int* tz = lv + (size_t)nE * B;
+    run_layer_len(run, ESCX_DAC_SNAKE_LAST, E[d->enc.size() - 1], SN + d->enc_sn.size() - 1, x, B, T, tz, y, T, tz, nullptr, 0);
+    DacQArgs qa{};
+    qa.t = d->qt; qa.zmap = y; qa.z = z; qa.codes = (long long*)codes; qa.latents = latents; qa.loss = lossb;
+    qa.M = (int)M; qa.T = T; qa.D = d->latent; qa.Dp = cpad(d->latent); qa.d = d->cfg.codebook_dim; qa.K = d->cfg.codebook_size; qa.n = n;
+    qa.frame_len = tz;
+    if (clip_n) { qa.clip_n = tz + B; launch_rvq<false, DAC_Q_LEN | DAC_Q_CLIPS>(d->latent, (long long)M, qa, st); }
+    else launch_rvq<false, DAC_Q_LEN | DAC_Q_PLAIN>(d->latent, (long long)M, qa, st);
+    hipLaunchKernelGGL(dac_loss_len_kernel, dim3(1), dim3(256), 0, st, lossb, lossb + pad64((size_t)n * M), losses, B, T, n, d->cfg.codebook_dim, tz);
+    return launch_ok("escx_dac_encode_lengths");
+}
+
+extern "C" int escx_dac_from_codes_lengths(escx_dac d, const float* flat, int64_t version, const int64_t* codes, int B, int n, int Tmax, const int32_t* frame_lengths,
+                                           const int32_t* clip_n, float* z, float* zp, void* stream) {
+    int rc = check_args(d, flat, B); if (rc) return rc;
+    if (!codes || !z || !zp || Tmax < 1 || n < 1 || n > d->cfg.n_codebooks) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "bad argument (codes of %d codebooks, %d frames)", n, Tmax);
+    if ((rc = check_lengths(d, frame_lengths, B, Tmax, "frame_lengths"))) return rc;
+    if (clip_n && (rc = check_clip_counts(d, clip_n, B, n))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    std::vector<int32_t>& host = d->len_host;
+    host.assign(frame_lengths, frame_lengths + B);
+    if (clip_n) host.insert(host.end(), clip_n, clip_n + B);
+    const int* dev; if ((rc = upload_counts(d, host.data(), (int)host.size(), &dev, st))) return rc;
+    if ((rc = pack(d, flat, (long long)version, st))) return rc;
+    DacQArgs qa{};
+    qa.t = d->qt; qa.codes_in = (const long long*)codes; qa.z = z; qa.latents = zp;
+    qa.M = B * Tmax; qa.T = Tmax; qa.D = d->latent; qa.Dp = cpad(d->latent); qa.d = d->cfg.codebook_dim; qa.K = d->cfg.codebook_size; qa.n = n;
+    qa.frame_len = dev;
+    if (clip_n) { qa.clip_n = dev + B; launch_rvq<true, DAC_Q_LEN | DAC_Q_CLIPS>(d->latent, (long long)B * Tmax, qa, st); }
+    else launch_rvq<true, DAC_Q_LEN | DAC_Q_PLAIN>(d->latent, (long long)B * Tmax, qa, st);
+    return launch_ok("escx_dac_from_codes_lengths");
+}
+
+extern "C" int escx_dac_decode_lengths(escx_dac d, const float* flat, int64_t version, const float* z, int B, int Tmax, const int32_t* frame_lengths,
+                                       const int32_t* sample_caps, float* audio, void* stream) {
+    int rc = check_args(d, flat, B); if (rc) return rc;
+    if (!z || !audio || Tmax < 1) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "bad argument");
+    if ((rc = check_lengths(d, frame_lengths, B, Tmax, "frame_lengths"))) return rc;
+    std::vector<int32_t> tab;
+    int bad = 0;
+    if (!level_table(d, true, frame_lengths, B, &tab, &bad))
+        ESCX_FAIL(ESCX_ERR_INVALID_ARG, "frame_lengths[%d]=%d latent frames decode to no sample", bad, frame_lengths[bad]);
+    hipStream_t st = (hipStream_t)stream;
+    size_t mf = 0;
+    const int Lout = dec_walk(d, true, B, Tmax, &mf);
+    if (Lout < 1) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "%d latent frames decode to no sample", Tmax);
+    if ((unsigned long long)mf >= (1ull << 32)) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "batch of %d x %d frames: a feature map above 2^32 elements", B, Tmax);
+    // the audio's own table: a clip's decoded samples, cut at sample_caps[b] when given (DAC.forward trims to the input length, dac.py:316)
+    const int nD = d->cfg.n_decoder_rates;
+    for (int b = 0; b < B; ++b) {
+        int v = tab[(size_t)nD * B + b];
+        if (sample_caps) {
+            if (sample_caps[b] < 1) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "sample_caps[%d]=%d below 1", b, sample_caps[b]);
+            v = std::min(v, (int)sample_caps[b]);
+        }
+        tab.push_back(v);
+    }
+    if ((rc = ensure_scratch(d, 4 * mf * sizeof(float)))) return rc;
+    d->len_host = tab;
+    const int* lv; if ((rc = upload_counts(d, d->len_host.data(), (int)d->len_host.size(), &lv, st))) return rc;
+    if ((rc = pack(d, flat, (long long)version, st)) || (rc = refresh_w16(d, st))) return rc;
+    float* x = d->scratch; float* y = x + mf; float* h = y + mf;
+    const Run run{d->snake_maps, h + mf, st, d->wbuf, d->precision == ESCX_PRECISION_BF16X3 ? d->w16 : nullptr, d->conv_floats, true};
+    const int Dp = cpad(d->latent);
+    hipLaunchKernelGGL(dac_z_in_len_kernel, dim3(nblk((long long)B * Tmax * Dp)), dim3(256), 0, st, z, h, B, d->latent, Dp, Tmax, lv);
+    const DacLayer* Dl = d->dec.data(); const DacSnake* SN = d->dec_sn.data();
+    int T = Tmax;
+    run_layer_len(run, ESCX_DAC_SNAKE_LAST, Dl[0], nullptr, h, B, T, lv, x, T, lv, nullptr, 0);
+    for (int i = 0; i < nD; ++i) {
+        const DacLayer* Lb = Dl + 1 + i * 7; const DacSnake* Sb = SN + i * 7;
+        const int* tl = lv + (size_t)i * B;
+        const int T2 = conv_out_len(T, Lb[0], true);
+        run_layer_len(run, ESCX_DAC_SNAKE_UP, Lb[0], Sb, x, B, T, tl, y, T2, tl + B, nullptr, 0);
+        std::swap(x, y); T = T2;
+        for (int j = 0; j < 3; ++j) run_res_len(run, Lb + 1 + 2 * j, Sb + 1 + 2 * j, x, h, B, T, tl + B);
+    }
+    run_layer_len(run, ESCX_DAC_SNAKE_LAST, Dl[d->dec.size() - 1], SN + d->dec_sn.size() - 1, x, B, T, lv + (size_t)nD * B, audio, Lout, lv + (size_t)(nD + 1) * B,
+                  nullptr, 1);
+    return launch_ok("escx_dac_decode_lengths");
 }
 
 // ---- latent gradient through the decoder, eval mode, padding on (dac.py:249-266) -----------------------------------------

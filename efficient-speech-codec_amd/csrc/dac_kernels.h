@@ -8,6 +8,7 @@
 //              (p is the padding in effect: the layer's own, or 0 for every layer when the handle's padding is off)
 //   DacEpi     out(b, t * os + o0, n..n+3) = [res +] (v + bias)   or   audio(b, t) = tanh(v + bias) for the one-channel last layer
 //   DacEpiCrop out(b, t, n..n+3) = res(b, t + off, n..n+3) + (v + bias): the ResidualUnit's cropped skip when the padding is off
+//   DacConvALen / DacEpiLen: the same two for a batch with per-clip lengths (a table of rows per clip instead of one Tin / Tout); DESIGN.md section 13.6
 // Snake (nn/layers.py:19-24) is applied to the operand while it is staged: x + inv * sin(alpha * x)^2 with inv = 1 / (alpha + 1e-9) derived
 // once per parameter version, in the reference's operation order, with the accurate sinf and no contraction into fma.
 #pragma once
@@ -80,6 +81,68 @@ struct DacEpiCrop {
         v += ld4(bias + n);
         v = ld4(res + ((size_t)b * Tres + t + off) * Cp + n) + v;
         st4(out + ((size_t)b * Trows + t) * Cp + n, v);
+    }
+};
+
+// Mixed-length batches (escx_dac_encode_lengths / escx_dac_decode_lengths; padding on): the maps keep their padded (B, Tmax, Cp) layout and clip b
+// owns the rows t < tin[b] of the input map and t_out < tout[b] of the output map.  A row of the GEMM is live when its output row
+// t_out = t * os + o0 lies inside its clip (os = 1, o0 = 0 for a Conv1d; os = stride, o0 = phase for a ConvTranspose1d phase GEMM, whose rows per clip
+// Q_b = ceil((tout[b] - phase) / stride) are exactly the t with t * os + o0 < tout[b]).  A live row zero-fills outside [0, tin[b]): what DacConvA does
+// for that clip alone with Tin = tin[b], tap for tap, so a live row sees the operands, and the MFMA sequence, of the call on its clip alone.  A dead
+// row is staged as zeros and never stored; the rows past a clip's length hold stale scratch that no loader reads.  Types of their own: DacConvA and
+// DacEpi, and with them every kernel of the uniform paths, stay what they are.
+struct DacConvALen {
+    static constexpr bool SKIPS_DEAD_TILES = true;             // gemm_engine.h: a workgroup without a live row returns before its first load
+    const float* x; const float* alpha; const float* inv;      // alpha == nullptr: no Snake on this operand
+    const int* tin; const int* tout;                           // [B] rows of clip b in the input map / in the layer's output map
+    int Tin, Cp, Trows, rs, r0, td, ntaps, M, os, o0;          // Tin, Trows: the padded maps' rows per clip
+    int keep_dead;                                             // the tanh layer: its epilogue zeroes the audio past a clip's length, so no tile is skipped
+    FastDiv dT, dCp;
+    struct Ctx { int tb, tin; unsigned base; };                // tin == 0: a dead row (or one behind M); every tap then fails the bounds test
+    __device__ __forceinline__ Ctx make_ctx(int m) const {
+        Ctx c; c.tb = 0; c.tin = 0; c.base = 0;
+        if (m < M) {
+            const int b = dT.div(m); const int t = m - b * Trows;
+            if (t * os + o0 < tout[b]) { c.tb = t * rs + r0; c.tin = tin[b]; c.base = (unsigned)b * (unsigned)Tin * (unsigned)Cp; }
+        }
+        return c;
+    }
+    __device__ __forceinline__ int row_live(const Ctx& c) const { return c.tin | keep_dead; }
+    __device__ __forceinline__ f32x4 load4(const Ctx& c, int k0, int kin) const {
+        const int k = k0 + kin;                 // Cp is a multiple of 4: the four values share one tap
+        const int tap = dCp.div(k), cc = k - tap * Cp;
+        const int ti = c.tb + tap * td;
+        if (tap >= ntaps || (unsigned)ti >= (unsigned)c.tin) return zero4();
+        f32x4 v = ld4(x + c.base + (unsigned)ti * (unsigned)Cp + (unsigned)cc);
+        if (alpha) {
+            const f32x4 a = ld4(alpha + cc), r = ld4(inv + cc);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = dac_snake(v[e], a[e], r[e]);
+        }
+        return v;
+    }
+};
+
+// DacEpi for the live rows only; the one-channel tanh layer writes 0 to the audio past a clip's length (its launch keeps the dead tiles).
+struct DacEpiLen {
+    float* out; const float* bias; const float* res;           // res may alias out (same element read then written by one lane)
+    const int* tout;                                           // [B] rows of clip b in the output map
+    int Cp, Trows, Tmap, os, o0, tanh_out; FastDiv dT;
+    __device__ __forceinline__ void store(int m, int n, f32x4 v, int) const {
+#pragma clang fp contract(off)
+        if (n >= Cp) return;
+        const int b = dT.div(m), t = m - b * Trows;
+        const int to = t * os + o0;
+        const bool live = to < tout[b];
+        if (tanh_out) {                                         // one output channel: audio (B, Tmap)
+            if (n == 0) out[(size_t)b * Tmap + to] = live ? tanhf(v[0] + bias[0]) : 0.f;
+            return;
+        }
+        if (!live) return;
+        v += ld4(bias + n);
+        const size_t idx = ((size_t)b * Tmap + to) * Cp + n;
+        if (res) v = ld4(res + idx) + v;
+        st4(out + idx, v);
     }
 };
 
@@ -201,9 +264,12 @@ __global__ void dac_qtables_kernel(const float* __restrict__ flat, const long lo
 //                masked mean.  FROM_CODES never reads those slots and writes zero z_p there.
 //   DAC_Q_SNAPS  after stage i with i + 1 == snap_n[r] the running sum goes to zsnap[r] (B, D, T) with the store pattern of the final z:
 //                the same registers at the same point of the same sum as a call that stops at n = snap_n[r].
+//   DAC_Q_LEN    a flag on top of DAC_Q_PLAIN or DAC_Q_CLIPS (EXT = DAC_Q_LEN | DAC_Q_CLIPS): frame_len[b] frames of clip b.  A row at or past its
+//                clip's length is a row with zero stages: nothing of it is read (not zmap, not codes_in), z and latents / z_p get 0 and codes -1
+//                in every slot.  Without the flag the kernels are what they were, name and instructions.
 // ------------------------------------------------------------------------------------------------
 constexpr int DAC_DMAX = 8;
-constexpr int DAC_Q_PLAIN = 0, DAC_Q_CLIPS = 1, DAC_Q_SNAPS = 2;
+constexpr int DAC_Q_PLAIN = 0, DAC_Q_CLIPS = 1, DAC_Q_SNAPS = 2, DAC_Q_LEN = 4;
 
 struct DacQArgs {
     DacQTables t;
@@ -218,6 +284,7 @@ struct DacQArgs {
     const int* snap_n;              // DAC_Q_SNAPS: [n_snaps] strictly increasing stage counts in [1, n]
     float* zsnap;                   // DAC_Q_SNAPS: (n_snaps, B, D, T)
     int n_snaps;
+    const int* frame_len;           // DAC_Q_LEN: [B] frames per clip, each in [1, T]
 };
 
 __device__ __forceinline__ float wave_sum(float v) {
@@ -226,23 +293,29 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
-template <int J, bool FROM_CODES, int EXT = DAC_Q_PLAIN>
+template <int J, bool FROM_CODES, int EXT_ = DAC_Q_PLAIN>
 __global__ __launch_bounds__(256) void dac_rvq_kernel(DacQArgs a) {
 #pragma clang fp contract(off)
+    constexpr int EXT = EXT_ & ~DAC_Q_LEN;
+    constexpr bool LEN = (EXT_ & DAC_Q_LEN) != 0;
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= a.M) return;                                     // wave-uniform
     const int b = row / a.T, t = row - b * a.T;
     const int D = a.D, d = a.d, K = a.K;
+    [[maybe_unused]] bool live = true;                          // wave-uniform
+    if constexpr (LEN) live = t < a.frame_len[b];
     float zq[J], res[J];
 #pragma unroll
     for (int j = 0; j < J; ++j) {
         const int c = lane + 64 * j;
         zq[j] = 0.f;
-        res[j] = (!FROM_CODES && c < D) ? a.zmap[((size_t)b * a.T + t) * a.Dp + c] : 0.f;
+        if constexpr (LEN) res[j] = (!FROM_CODES && c < D && live) ? a.zmap[((size_t)b * a.T + t) * a.Dp + c] : 0.f;
+        else res[j] = (!FROM_CODES && c < D) ? a.zmap[((size_t)b * a.T + t) * a.Dp + c] : 0.f;
     }
     int nb = a.n;                                               // stages of this row
     if constexpr (EXT == DAC_Q_CLIPS) nb = max(0, min(a.clip_n[b], a.n));
+    if constexpr (LEN) nb = live ? nb : 0;
     [[maybe_unused]] int snap = 0;
     for (int i = 0; i < nb; ++i) {
         float q[DAC_DMAX];
@@ -320,8 +393,8 @@ __global__ __launch_bounds__(256) void dac_rvq_kernel(DacQArgs a) {
             }
         }
     }
-    if constexpr (EXT == DAC_Q_CLIPS) {
-        for (int i = nb; i < a.n; ++i) {                                        // the slots past this clip's count
+    if constexpr (EXT == DAC_Q_CLIPS || LEN) {
+        for (int i = nb; i < a.n; ++i) {                                        // the slots past this clip's count (LEN: every slot of a dead row)
             if (lane < d) a.latents[((size_t)b * a.n * d + (size_t)i * d + lane) * a.T + t] = 0.f;
             if constexpr (!FROM_CODES) if (lane == 0) { a.codes[((size_t)b * a.n + i) * a.T + t] = -1; a.loss[(size_t)i * a.M + row] = 0.f; }
         }
@@ -340,6 +413,28 @@ __global__ __launch_bounds__(256) void dac_loss_kernel(const float* __restrict__
         float s = 0.f;
         for (int t = 0; t < T; ++t) s += loss[(size_t)p * T + t];
         perclip[p] = s / (float)(d * T);
+    }
+    __threadfence_block();
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    float tot = 0.f;
+    for (int i = 0; i < n; ++i) {
+        float mb = 0.f;
+        for (int b = 0; b < B; ++b) mb += perclip[i * B + b];
+        tot += mb / (float)B;
+    }
+    out[0] = tot; out[1] = tot;
+}
+
+// dac_loss_kernel for a batch with per-clip lengths: clip b's mean runs over its own frames t < tl[b], in the order and with the divisor of the call
+// on that clip alone; the slots of the rows past them are never read.
+__global__ __launch_bounds__(256) void dac_loss_len_kernel(const float* __restrict__ loss, float* __restrict__ perclip, float* __restrict__ out, int B, int T, int n,
+                                                           int d, const int* __restrict__ tl) {
+    for (int p = threadIdx.x; p < n * B; p += 256) {
+        const int Tb = tl[p % B];
+        float s = 0.f;
+        for (int t = 0; t < Tb; ++t) s += loss[(size_t)p * T + t];
+        perclip[p] = s / (float)(d * Tb);
     }
     __threadfence_block();
     __syncthreads();
@@ -379,6 +474,15 @@ __global__ void dac_wave_in_kernel(const float* __restrict__ x, float* __restric
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) st4(out + 4 * i, f32x4{x[i], 0.f, 0.f, 0.f});
 }
+// Mixed-length batch: (B, 1, Lsrc) audio -> (B, Lmap, 4) map; sample s of clip b is read only for s < len[b] and staged as 0 from there on (the clip's
+// right-pad to a multiple of the hop, dac.py:198-207, and everything behind it: nothing at or past a clip's length is read, whatever it holds)
+__global__ void dac_wave_in_len_kernel(const float* __restrict__ x, float* __restrict__ out, long long n, int Lsrc, int Lmap, const int* __restrict__ len) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int b = (int)(i / Lmap), s = (int)(i - (long long)b * Lmap);
+    const float v = s < len[b] ? x[(size_t)b * Lsrc + s] : 0.f;
+    st4(out + 4 * i, f32x4{v, 0.f, 0.f, 0.f});
+}
 // Chunked compress (base.py:197, 206-208) without the host's copies: the (rows * n_chunks, n_samples, 4) map of overlapping windows straight from
 // the (rows, n_signal) signal.  Sample j of chunk c of row r is signal[r][c * hop + j - lead], zero outside [0, n_signal): the reference's
 // zero_pad(delay, delay), its slice [c hop, c hop + n_samples) and the right zero-pad of a short last slice, with lead = delay.
@@ -398,6 +502,13 @@ __global__ void dac_z_in_kernel(const float* __restrict__ z, float* __restrict__
     if (i >= (long long)B * T * Dp) return;
     const int c = (int)(i % Dp); const long long bt = i / Dp; const int t = (int)(bt % T), b = (int)(bt / T);
     out[i] = c < D ? z[((size_t)b * D + c) * T + t] : 0.f;
+}
+// dac_z_in_kernel for a mixed-length batch: frame t of clip b is read only for t < tl[b] and staged as 0 from there on
+__global__ void dac_z_in_len_kernel(const float* __restrict__ z, float* __restrict__ out, int B, int D, int Dp, int T, const int* __restrict__ tl) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long long)B * T * Dp) return;
+    const int c = (int)(i % Dp); const long long bt = i / Dp; const int t = (int)(bt % T), b = (int)(bt / T);
+    out[i] = (c < D && t < tl[b]) ? z[((size_t)b * D + c) * T + t] : 0.f;
 }
 
 }  // namespace escx

@@ -52,6 +52,12 @@ __global__ __launch_bounds__(256) void dac_x3_kernel(Loader ld, const __bf16* __
     typename Loader::Ctx ctx[AJ];
 #pragma unroll
     for (int j = 0; j < AJ; ++j) ctx[j] = ld.make_ctx(m0 + (tid + j * 256) / KV);
+    if constexpr (loader_skips_dead<Loader>::value) {      // gemm_engine.h: a tile of rows past their clips' lengths has nothing to compute
+        int live = 0;
+#pragma unroll
+        for (int j = 0; j < AJ; ++j) live |= ld.row_live(ctx[j]);
+        if (!__syncthreads_or(live)) return;
+    }
 
     f32x4 acc[TN][TM];
 #pragma unroll

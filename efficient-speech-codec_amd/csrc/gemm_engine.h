@@ -49,6 +49,13 @@ template <class E> struct epi_is_rowwise<E, std::enable_if_t<E::ROWWISE>> : std:
 template <class E, class = void> struct epi_chunked_k : std::false_type {};
 template <class E> struct epi_chunked_k<E, std::enable_if_t<E::CHUNKED_K>> : std::true_type {};
 
+// A loader with `static constexpr bool SKIPS_DEAD_TILES = true` marks rows whose output nobody stores (the rows past a clip's own length in a
+// mixed-length batch, dac_kernels.h DacConvALen): row_live(ctx) tells whether the row of a make_ctx() is one that is stored.  A workgroup whose
+// rows are all dead returns before its first load.  Every other loader never has a dead tile and compiles to the kernel it had before this
+// switch existed.
+template <class L, class = void> struct loader_skips_dead : std::false_type {};
+template <class L> struct loader_skips_dead<L, std::enable_if_t<L::SKIPS_DEAD_TILES>> : std::true_type {};
+
 template <int BM, int BN, int BK, class Loader, class Epi>
 __global__ __launch_bounds__(256) void gemm_kernel(Loader ld, const float* __restrict__ Wt, int M, int Np,
                                                    int Kp, int k_per_z, Epi ep) {
@@ -80,6 +87,12 @@ __global__ __launch_bounds__(256) void gemm_kernel(Loader ld, const float* __res
     for (int j = 0; j < AJ; ++j) {
         const int i = tid + j * 256;
         ctx[j] = ld.make_ctx(m0 + (i < A4 ? i / KV : 0));
+    }
+    if constexpr (loader_skips_dead<Loader>::value) {      // the threads' rows cover the tile: block-uniform
+        int live = 0;
+#pragma unroll
+        for (int j = 0; j < AJ; ++j) live |= ld.row_live(ctx[j]);
+        if (!__syncthreads_or(live)) return;
     }
 
     f32x4 acc[TN][TM];

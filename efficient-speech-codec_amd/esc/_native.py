@@ -138,6 +138,11 @@ SIGNATURES = {
     "escx_dac_from_codes": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "escx_dac_from_codes_ex": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, POINTER(c_int32), c_void_p, c_void_p, c_void_p]),
     "escx_dac_decode": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "escx_dac_encode_lengths": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, POINTER(c_int32), c_int, c_int, POINTER(c_int32), c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_void_p]),
+    "escx_dac_from_codes_lengths": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, POINTER(c_int32), POINTER(c_int32), c_void_p, c_void_p,
+                                            c_void_p]),
+    "escx_dac_decode_lengths": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, POINTER(c_int32), POINTER(c_int32), c_void_p, c_void_p]),
     "escx_dac_set_snake_maps": (c_int, [c_void_p, c_int]),
     "escx_dac_get_snake_maps": (c_int, [c_void_p]),
     "escx_dac_set_precision": (c_int, [c_void_p, c_int]),

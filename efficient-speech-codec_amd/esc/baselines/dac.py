@@ -7,6 +7,9 @@ libescx (csrc/dac.hip); there is no PyTorch/CPU implementation here.  Inference 
 frozen codec can sit inside a larger autograd graph (eval mode, padding on, input gradients only): `decode(z)` is differentiable in `z`
 (`_DecodeGrad`), `encode(x)` in `x` through the encoder and the straight-through quantiser (`_EncodeGrad`), and `forward(x)` chains the two.
 
+Mixed-length batches (not part of the reference's surface): `encode` / `forward` take `lengths`, `decode` / `quantizer.from_codes` take
+`frame_lengths`, one entry per clip; every clip's results are bitwise those of the call on that clip alone.
+
 `DACFile`, `DAC.padding`, `DAC.compress` and `DAC.decompress` are CodecMixin's (reference baselines/descript/dac/model/base.py:15-294): files of any
 length in overlapping windows on padding-free convolutions, all windows of a file as one batch.
 """
@@ -490,6 +493,92 @@ class DAC(nn.Module):
             raise ValueError(f"encode_sweep's n_quantizers {vals} repeat a count once clamped to the {self.n_codebooks} codebooks")
         return out
 
+    # ---- mixed-length batches: one length per clip (include/escx.h escx_dac_encode_lengths and its two neighbours) --------------------------
+    def _clip_lengths(self, lengths, batch: int, hi: int, what: str) -> List[int]:
+        """Per-clip lengths: `batch` integers in [1, hi], read with the helper (and the messages) of the per-clip codebook counts."""
+        vals = self._int_entries(lengths, what)
+        if len(vals) != batch:
+            raise ValueError(f"{what} has {len(vals)} entries for a batch of {batch}")
+        for b, v in enumerate(vals):
+            if v < 1 or v > hi:
+                raise ValueError(f"{what}[{b}] = {v} outside [1, {hi}]")
+        return vals
+
+    def _refuse_lengths(self, what: str, grad: bool):
+        """The calls per-clip lengths do not cover, refused before anything is launched."""
+        if not self._padding:
+            raise NotImplementedError(f"{what} needs padding = True: with the padding off every clip loses the receptive field at both ends and "
+                                      "the chunked path batches equal windows already")
+        if grad:
+            raise NotImplementedError(f"{what} is not implemented on the gradient paths (an input that requires grad, or set_trainable('decoder') "
+                                      "with a parameter that requires grad): call it under torch.no_grad() or differentiate clip by clip")
+
+    def _decoder_trains(self) -> bool:
+        return self._trainable == "decoder" and torch.is_grad_enabled() and any(p.requires_grad for p in self.decoder_parameters())
+
+    def frame_lengths(self, lengths) -> torch.Tensor:
+        """num_frames of every entry of `lengths` (a sequence or 1-D integer tensor of sample counts): a 1-D int64 CPU tensor."""
+        return torch.tensor([self.num_frames(v) for v in self._int_entries(lengths, "lengths")], dtype=torch.int64)
+
+    def output_lengths(self, frame_lengths) -> torch.Tensor:
+        """output_samples of every entry of `frame_lengths`: a 1-D int64 CPU tensor."""
+        return torch.tensor([self.output_samples(v) for v in self._int_entries(frame_lengths, "frame_lengths")], dtype=torch.int64)
+
+    def _check_encode_lengths(self, audio_data, lengths, pad_multiple: int):
+        """(lengths, frames per clip) of an encode with per-clip lengths; every clip must give a frame once padded to a multiple of pad_multiple."""
+        if not isinstance(audio_data, torch.Tensor) or audio_data.dim() != 3 or audio_data.shape[1] != 1:
+            raise ValueError(f"audio_data must be (B, 1, L), got {tuple(getattr(audio_data, 'shape', ()))}")
+        B, _, L = audio_data.shape
+        lens = self._clip_lengths(lengths, B, L, "lengths")
+        frames = [self.num_frames(-(-v // pad_multiple) * pad_multiple) for v in lens]
+        for b, (v, t) in enumerate(zip(lens, frames)):
+            if t < 1:
+                raise ValueError(f"lengths[{b}] = {v} samples are shorter than one hop ({self.hop_length}): the encoder gives no frame for clip {b}")
+        return lens, frames
+
+    @torch.no_grad()
+    def _encode_lengths(self, audio_data: torch.Tensor, lens: List[int], frames: List[int], n_quantizers, pad_multiple: int):
+        """encode of clips of their own lengths (include/escx.h escx_dac_encode_lengths), each right-padded with staged zeros to a multiple of
+        pad_multiple."""
+        counts = self._clip_counts(n_quantizers, audio_data.shape[0]) if self._is_per_clip(n_quantizers) else None
+        n = self._n_quantizers(n_quantizers) if counts is None else max(counts)
+        lib, hd, flat, dev, stream = self._ctx(audio_data, "audio_data")
+        B, _, L = audio_data.shape
+        T = max(frames)
+        x = audio_data.to(torch.float32).contiguous()
+        z = torch.empty(B, self.latent_dim, T, device=dev)
+        codes = torch.empty(B, n, T, dtype=torch.int64, device=dev)
+        latents = torch.empty(B, n * self.codebook_dim, T, device=dev)
+        losses = torch.empty(2, device=dev)
+        cn = (ctypes.c_int32 * B)(*counts) if counts is not None else None
+        with torch.cuda.device(dev):
+            _native.check(lib.escx_dac_encode_lengths(hd, ctypes.c_void_p(flat.data_ptr()), self._version(), ctypes.c_void_p(x.data_ptr()), B, L,
+                                                      (ctypes.c_int32 * B)(*lens), pad_multiple, n, cn, ctypes.c_void_p(z.data_ptr()),
+                                                      ctypes.c_void_p(codes.data_ptr()), ctypes.c_void_p(latents.data_ptr()),
+                                                      ctypes.c_void_p(losses.data_ptr()), stream))
+        return z, codes, latents, losses[0], losses[1]
+
+    def _check_frame_lengths(self, t: torch.Tensor, frame_lengths, what: str) -> List[int]:
+        if not isinstance(t, torch.Tensor) or t.dim() != 3:
+            raise ValueError(f"{what} must be 3-D, got {tuple(getattr(t, 'shape', ()))}")
+        fl = self._clip_lengths(frame_lengths, t.shape[0], t.shape[-1], "frame_lengths")
+        for b, v in enumerate(fl):
+            if self.output_samples(v) < 1:
+                raise ValueError(f"frame_lengths[{b}] = {v} latent frames decode to no sample for clip {b}")
+        return fl
+
+    @torch.no_grad()
+    def _decode_lengths(self, z: torch.Tensor, fl: List[int], caps: Optional[List[int]] = None):
+        """decode of clips of their own frame counts (include/escx.h escx_dac_decode_lengths); caps: cut clip b's audio at caps[b] samples."""
+        lib, hd, flat, dev, stream, B, T, n_out = self._decode_args(z)
+        zc = z.to(torch.float32).contiguous()
+        out = torch.empty(B, 1, n_out, device=dev)
+        with torch.cuda.device(dev):
+            _native.check(lib.escx_dac_decode_lengths(hd, ctypes.c_void_p(flat.data_ptr()), self._version(), ctypes.c_void_p(zc.data_ptr()), B, T,
+                                                      (ctypes.c_int32 * B)(*fl), None if caps is None else (ctypes.c_int32 * B)(*caps),
+                                                      ctypes.c_void_p(out.data_ptr()), stream))
+        return out
+
     def _audio_shape(self, audio_data):
         if audio_data.dim() != 3 or audio_data.shape[1] != 1:
             raise ValueError(f"audio_data must be (B, 1, L), got {tuple(audio_data.shape)}")
@@ -518,12 +607,15 @@ class DAC(nn.Module):
         return z, codes, latents, losses[0], losses[1]
 
     @torch.no_grad()
-    def encode_sweep(self, audio_data: torch.Tensor, n_quantizers: Sequence[int]):
+    def encode_sweep(self, audio_data: torch.Tensor, n_quantizers: Sequence[int], lengths=None):
         """One encode for a whole bitrate sweep: (zs (R, B, D, T), codes (B, n_max, T), latents (B, n_max d, T)) with zs[r] bitwise the z of
         encode(audio_data, n_quantizers[r]) and codes / latents those of the largest count (the codes are prefix codes; the quantiser stores its
         running sum, quantize.py:185, after each requested stage: include/escx.h escx_dac_encode_ex, snap_n).  Not part of the reference's surface."""
         if self.training:
             raise NotImplementedError("esc.baselines.DAC is inference only: call .eval() (DAC training is not implemented)")
+        if lengths is not None:
+            raise NotImplementedError("encode_sweep takes no per-clip lengths: the snapshots are built for uniform batches (use encode with lengths, "
+                                      "one call per bitrate)")
         ns = self._sweep_counts(n_quantizers)
         lib, hd, flat, dev, stream = self._ctx(audio_data, "audio_data")
         B, L, T = self._audio_shape(audio_data)
@@ -541,15 +633,27 @@ class DAC(nn.Module):
                                                  ctypes.c_void_p(losses.data_ptr()), ctypes.c_void_p(zs.data_ptr()), stream))
         return zs, codes, latents
 
-    def encode(self, audio_data: torch.Tensor, n_quantizers: Union[int, Sequence[int], torch.Tensor] = None):
+    def encode(self, audio_data: torch.Tensor, n_quantizers: Union[int, Sequence[int], torch.Tensor] = None, lengths=None):
         """dac.py:209-247: (z (B, D, T), codes (B, n, T) int64, latents (B, n d, T), commitment_loss, codebook_loss).  n_quantizers may also be
         one count per clip (a sequence or 1-D integer tensor of B entries, the per-item mask of quantize.py:181-190): n = max(counts), codes hold
         -1 and latents 0 past a clip's count, the losses are the reference's masked means.  When gradients are enabled and audio_data requires
         one, z, latents and commitment_loss carry the audio gradient of the reference's eval-mode autograd (straight-through quantiser,
         quantize.py:58-70; eval mode, padding on; `_EncodeGrad` below): the same bits, computed by escx_dac_encode_tape, which keeps the
-        encoder's maps in a tape on the graph.  The module's parameters get no gradient whatever their requires_grad."""
+        encoder's maps in a tape on the graph.  The module's parameters get no gradient whatever their requires_grad.
+
+        lengths (a sequence or 1-D integer tensor, one sample count in [1, L] per clip; not part of the reference's surface) makes the batch a
+        mixed-length one: clip b's results are bitwise those of encode(audio_data[b:b+1, :, :lengths[b]]) alone, nothing at or past a clip's
+        length is read, and the tuple comes at Tmax = num_frames(max(lengths)) with z and latents 0 and codes -1 at frames >=
+        num_frames(lengths[b]).  The losses are the means over the clips of the single-clip calls' losses.  Combines with per-clip
+        n_quantizers; padding on, no gradients."""
         if self.training:
             raise NotImplementedError("esc.baselines.DAC is inference only: call .eval() (DAC training is not implemented)")
+        if lengths is not None:
+            self._refuse_lengths("encode with lengths", torch.is_grad_enabled() and isinstance(audio_data, torch.Tensor) and audio_data.requires_grad)
+            lens, frames = self._check_encode_lengths(audio_data, lengths, 1)
+            if self._is_per_clip(n_quantizers):
+                self._clip_counts(n_quantizers, audio_data.shape[0])
+            return self._encode_lengths(audio_data, lens, frames, n_quantizers, 1)
         if torch.is_grad_enabled() and isinstance(audio_data, torch.Tensor) and audio_data.requires_grad:
             counts = self._clip_counts(n_quantizers, audio_data.shape[0]) if self._is_per_clip(n_quantizers) else None
             return _EncodeGrad.apply(audio_data, self, self._n_quantizers(n_quantizers) if counts is None else max(counts), counts)
@@ -580,13 +684,22 @@ class DAC(nn.Module):
                                               ctypes.c_void_p(losses.data_ptr()), stream))
         return z, codes, latents, losses[0], losses[1]
 
-    def decode(self, z: torch.Tensor):
+    def decode(self, z: torch.Tensor, frame_lengths=None):
         """dac.py:249-266: z (B, D, T) -> audio (B, 1, output_samples(T)).  When gradients are enabled and z requires one, the result carries
         the latent gradient d audio / d z (eval mode, padding on; `_DecodeGrad` below): the same audio bits, computed by escx_dac_decode_tape,
         which keeps the decoder's maps in a tape on the graph.  The module's parameters get no gradient whatever their requires_grad, unless
-        set_trainable("decoder") is in effect: then every decoder parameter that requires a gradient gets one (`_DecodeParamGrad`)."""
+        set_trainable("decoder") is in effect: then every decoder parameter that requires a gradient gets one (`_DecodeParamGrad`).
+
+        frame_lengths (one frame count in [1, T] per clip; not part of the reference's surface): clip b of the (B, 1, output_samples(T)) result is
+        bitwise decode(z[b:b+1, :, :frame_lengths[b]]) and 0 from sample output_samples(frame_lengths[b]) on; the frames at or past a clip's
+        count are not read.  Padding on, no gradients."""
         if self.training:
             raise NotImplementedError("esc.baselines.DAC is inference only: call .eval() (DAC training is not implemented)")
+        if frame_lengths is not None:
+            self._refuse_lengths("decode with frame_lengths",
+                                 (torch.is_grad_enabled() and isinstance(z, torch.Tensor) and z.requires_grad) or self._decoder_trains())
+            fl = self._check_frame_lengths(z, frame_lengths, "z")
+            return self._decode_lengths(z, fl)
         if self._trainable == "decoder" and torch.is_grad_enabled() and isinstance(z, torch.Tensor):
             params = list(self.decoder_parameters())
             if any(p.requires_grad for p in params):
@@ -619,10 +732,20 @@ class DAC(nn.Module):
         return out
 
     @torch.no_grad()
-    def _from_codes(self, codes: torch.Tensor, n_quantizers: Union[Sequence[int], torch.Tensor] = None):
+    def _from_codes(self, codes: torch.Tensor, n_quantizers: Union[Sequence[int], torch.Tensor] = None, frame_lengths=None):
         """ResidualVectorQuantize.from_codes: (z_q (B, D, T), z_p (B, n d, T), codes); `model.quantizer.from_codes` is this method.  With
         n_quantizers (one count per clip, as encode takes them) clip b sums its first n_b codebooks and the slots past its count are ignored,
-        whatever they hold (encode's per-clip form writes -1 there); z_p is 0 in them."""
+        whatever they hold (encode's per-clip form writes -1 there); z_p is 0 in them.  With frame_lengths (one frame count per clip, as decode
+        takes them) the slots at frames >= frame_lengths[b] are neither read nor range-checked (encode with lengths writes -1 there) and z_q and
+        z_p are 0 there."""
+        fl = None
+        if frame_lengths is not None:
+            if self.training:
+                raise NotImplementedError("esc.baselines.DAC is inference only: call .eval() (DAC training is not implemented)")
+            self._refuse_lengths("from_codes with frame_lengths", False)
+            if not isinstance(codes, torch.Tensor) or codes.dim() != 3:
+                raise ValueError(f"codes must be (B, n <= {self.n_codebooks}, T), got {tuple(getattr(codes, 'shape', ()))}")
+            fl = self._clip_lengths(frame_lengths, codes.shape[0], codes.shape[-1], "frame_lengths")
         counts = None
         if n_quantizers is not None:
             if self.training:
@@ -636,15 +759,23 @@ class DAC(nn.Module):
         if counts is not None and max(counts) > n:
             raise ValueError(f"per-clip n_quantizers up to {max(counts)} for codes of {n} codebooks")
         used = c
-        if counts is not None:                                   # the range check covers the slots that are read
-            live = torch.arange(n, device=dev)[None, :, None] < torch.tensor(counts, device=dev)[:, None, None]
+        if counts is not None or fl is not None:                 # the range check covers the slots that are read
+            live = torch.ones(1, 1, 1, dtype=torch.bool, device=dev)
+            if counts is not None:
+                live = live & (torch.arange(n, device=dev)[None, :, None] < torch.tensor(counts, device=dev)[:, None, None])
+            if fl is not None:
+                live = live & (torch.arange(T, device=dev)[None, None, :] < torch.tensor(fl, device=dev)[:, None, None])
             used = c[live.expand_as(c)]
         if used.numel() and (int(used.min()) < 0 or int(used.max()) >= self.codebook_size):
             raise IndexError(f"codes outside [0, {self.codebook_size}): F.embedding of the reference raises here")
         z = torch.empty(B, self.latent_dim, T, device=dev)
         zp = torch.empty(B, n * self.codebook_dim, T, device=dev)
         with torch.cuda.device(dev):
-            if counts is None:
+            if fl is not None:
+                _native.check(lib.escx_dac_from_codes_lengths(hd, ctypes.c_void_p(flat.data_ptr()), self._version(), ctypes.c_void_p(c.data_ptr()), B, n, T,
+                                                              (ctypes.c_int32 * B)(*fl), None if counts is None else (ctypes.c_int32 * B)(*counts),
+                                                              ctypes.c_void_p(z.data_ptr()), ctypes.c_void_p(zp.data_ptr()), stream))
+            elif counts is None:
                 _native.check(lib.escx_dac_from_codes(hd, ctypes.c_void_p(flat.data_ptr()), self._version(), ctypes.c_void_p(c.data_ptr()), B, n, T,
                                                       ctypes.c_void_p(z.data_ptr()), ctypes.c_void_p(zp.data_ptr()), stream))
             else:
@@ -652,11 +783,28 @@ class DAC(nn.Module):
                                                          (ctypes.c_int32 * B)(*counts), ctypes.c_void_p(z.data_ptr()), ctypes.c_void_p(zp.data_ptr()), stream))
         return z, zp, codes
 
-    def forward(self, audio_data: torch.Tensor, sample_rate: int = None, n_quantizers: Union[int, Sequence[int], torch.Tensor] = None):
+    def forward(self, audio_data: torch.Tensor, sample_rate: int = None, n_quantizers: Union[int, Sequence[int], torch.Tensor] = None, lengths=None):
         """dac.py:268-323 in eval mode: right-pad to a multiple of the hop, encode, decode, trim the audio to the input length.  n_quantizers
-        may be one count per clip, as in encode."""
+        may be one count per clip, as in encode.  lengths (one sample count in [1, L] per clip): every clip goes through the reference's
+        preprocess on its own - the samples from lengths[b] up to the next multiple of the hop are staged as zeros, not read - then encode and
+        decode; out["audio"][b, :, :lengths[b]] is bitwise forward(audio_data[b:b+1, :, :lengths[b]])["audio"] and 0 from there on, and the
+        dict gains "frame_lengths" (1-D int64 on the CPU: the frames of every clip in z, codes and latents)."""
         if self.training:
             raise NotImplementedError("esc.baselines.DAC is inference only: call .eval() (DAC training is not implemented)")
+        if lengths is not None:
+            hop = self.hop_length
+            self._refuse_lengths("forward with lengths",
+                                 (torch.is_grad_enabled() and isinstance(audio_data, torch.Tensor) and audio_data.requires_grad) or self._decoder_trains())
+            lens, frames = self._check_encode_lengths(audio_data, lengths, hop)
+            if self._is_per_clip(n_quantizers):
+                n_quantizers = self._clip_counts(n_quantizers, audio_data.shape[0])
+            if sample_rate is not None and sample_rate != self.sample_rate:
+                raise AssertionError(f"sample_rate {sample_rate} != the model's {self.sample_rate}")
+            _check_device(audio_data, "audio_data")
+            z, codes, latents, cm, cb = self._encode_lengths(audio_data, lens, frames, n_quantizers, hop)
+            audio = self._decode_lengths(z, frames, lens)
+            return {"audio": audio[..., :audio_data.shape[-1]], "z": z, "codes": codes, "latents": latents, "vq/commitment_loss": cm,
+                    "vq/codebook_loss": cb, "frame_lengths": torch.tensor(frames, dtype=torch.int64)}
         if self._is_per_clip(n_quantizers):
             n_quantizers = self._clip_counts(n_quantizers, audio_data.shape[0])
         _check_device(audio_data, "audio_data")
@@ -710,7 +858,7 @@ class DAC(nn.Module):
 
     @torch.no_grad()
     def compress(self, audio: torch.Tensor, sample_rate: int = None, win_duration: Optional[float] = 1.0, n_quantizers: int = None, input_db=None,
-                 chunks_per_pass: int = None) -> DACFile:
+                 chunks_per_pass: int = None, lengths=None) -> DACFile:
         """CodecMixin.compress (base.py:125-233) for a tensor `audio` of shape (nt,), (channels, nt) or (batch, channels, nt) on the device.
         A signal of at most win_duration seconds is one padded pass.  A longer one is encoded with `padding` off in windows of
         n_samples = ceil(int(win_duration * sr) / hop_length) * hop_length samples that start every get_output_length(n_samples) samples of the
@@ -722,6 +870,9 @@ class DAC(nn.Module):
         Out of scope, because they are audiotools.AudioSignal's work and audiotools is not a dependency: resampling (a sample_rate other than
         the model's raises ValueError), loudness measurement and normalisation (input_db is stored in the file as given and not applied) and
         peak limiting.  The caller hands in the signal the reference would encode after those steps."""
+        if lengths is not None:
+            raise NotImplementedError("compress takes no per-clip lengths: a DACFile holds one original_length for all its rows (compress signals of "
+                                      "different lengths one by one, or tokenise them with encode and lengths)")
         if self.training:
             raise NotImplementedError("esc.baselines.DAC is inference only: call .eval() (DAC training is not implemented)")
         if sample_rate is not None and sample_rate != self.sample_rate:

@@ -447,6 +447,31 @@ int escx_dac_from_codes_ex(escx_dac d, const float* flat_params_dev, int64_t par
                            const int32_t* clip_n, float* z_dev, float* zp_dev, void* stream);
 /* DAC.decode (dac.py:249-266): z (B, D, T) -> audio (B, escx_dac_output_samples(T)). */
 int escx_dac_decode(escx_dac d, const float* flat_params_dev, int64_t params_version, const float* z_dev, int batch, int n_frames, float* audio_dev, void* stream);
+/* ---- Mixed-length batches: per-clip lengths (dac.py:209-323; padding on) -------------------------------------------------
+ * The three entry points below take one length per clip as a HOST int32 array, copied with the tables derived from it (conv_out_len per clip and
+ * resolution level) to a handle-owned device buffer on the call's stream.  Clip b's results are bitwise those of the uniform entry point on that
+ * clip alone, in fp32 and in bf16x3; nothing at or past a clip's length is read, whatever it holds; everything at or past a clip's length in an
+ * output is a fixed filler (0, codes -1).  A null array, batch < 1, an entry outside its range, a clip that gives no frame or no sample (the
+ * message names the clip) and a handle with the padding off are ESCX_ERR_INVALID_ARG before anything is launched, and leave the handle usable. */
+/* DAC.encode (dac.py:209-247) of audio (B, row_samples) with lengths[b] in [1, row_samples] samples of clip b.  Each clip is first right-padded with
+ * zeros to a multiple of pad_multiple (1: as it is; the hop: DAC.preprocess, dac.py:198-207) - staged, not read: the audio tensor need not hold
+ * those samples.  With Lp_b that padded length, T_b = escx_dac_num_frames(Lp_b) and Tmax = escx_dac_num_frames(max_b Lp_b), the outputs are those
+ * of escx_dac_encode_ex at n_frames = Tmax: z (B, D, Tmax), codes (B, n_quantizers, Tmax), latents (B, n_quantizers * codebook_dim, Tmax), with z
+ * and latents 0 and codes -1 at frames >= T_b.  losses[0..1] = sum_i mean_b([i < clip_n[b]] * loss_ib), loss_ib the mean over clip b's own T_b
+ * frames: the mean over the clips of the single-clip calls' losses (quantize.py:189-190).  clip_n (HOST array or NULL) is escx_dac_encode_ex's. */
+int escx_dac_encode_lengths(escx_dac d, const float* flat_params_dev, int64_t params_version, const float* audio_dev, int batch, int row_samples,
+                            const int32_t* lengths, int pad_multiple, int n_quantizers, const int32_t* clip_n, float* z_dev, int64_t* codes_dev,
+                            float* latents_dev, float* losses_dev, void* stream);
+/* ResidualVectorQuantize.from_codes (quantize.py:200-220) of codes (B, n_codes, n_frames) with frame_lengths[b] in [1, n_frames] frames of clip b:
+ * the slots at frames >= frame_lengths[b] are never read, whatever they hold (escx_dac_encode_lengths writes -1 there), and z_q and z_p are 0 there.
+ * clip_n (HOST array or NULL) is escx_dac_from_codes_ex's. */
+int escx_dac_from_codes_lengths(escx_dac d, const float* flat_params_dev, int64_t params_version, const int64_t* codes_dev, int batch, int n_codes, int n_frames,
+                                const int32_t* frame_lengths, const int32_t* clip_n, float* z_dev, float* zp_dev, void* stream);
+/* DAC.decode (dac.py:249-266) of z (B, D, n_frames) with frame_lengths[b] in [1, n_frames] frames of clip b: audio (B, escx_dac_output_samples(n_frames)),
+ * clip b bitwise escx_dac_decode of its own frame_lengths[b] frames and 0 from sample escx_dac_output_samples(frame_lengths[b]) on.  sample_caps (HOST
+ * array or NULL) cuts clip b's audio at min(that, sample_caps[b]) samples, 0 from there on: the trim to the input length of DAC.forward (dac.py:316). */
+int escx_dac_decode_lengths(escx_dac d, const float* flat_params_dev, int64_t params_version, const float* z_dev, int batch, int n_frames,
+                            const int32_t* frame_lengths, const int32_t* sample_caps, float* audio_dev, void* stream);
 /* Where Snake (nn/layers.py:19-24) is evaluated, per layer class: bit set = written once per element into a Snaked copy of the map that the
  * convolution then reads; bit clear = applied to the operand while the convolution stages it (once per tap and per output-column tile).  Both
  * give bitwise the same results; the default is the faster per class on MI355X.  A/B switch, not a numerics setting. */
