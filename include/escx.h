@@ -302,7 +302,8 @@ int escx_stft_loss_ex(const float* raw_feat_dev, const float* recon_feat_dev, in
                       float* d_recon_feat_dev, float* d_raw_feat_dev, void* stream);
 /* MelSpectrogramLoss (generator_loss.py:37-74; 7 resolutions, windows 32..2048, hop = window/4, HTK mel filterbanks of 5..320 bins,
  * L1 on the mel magnitudes + L1 on log10(clamp(mel)^2)): per-clip loss (B,) and, optionally, d loss_b / d recon_wave (B,L).
- * Runs on the current device; the DFT / filterbank matrices are built once per device. */
+ * Runs on the current device; the DFT / filterbank matrices are built once per device (and rebuilt when sample_rate changes).
+ * sample_rate: even rates only are verified (the reference fixes 16000): at an odd rate the filterbank's top edge (sr / 2.0) and the bin grid (sr / 2) differ. */
 int escx_mel_loss(const float* raw_wave_dev, const float* recon_wave_dev, int batch, int n_samples, int sample_rate, float* loss_dev,
                   float* d_recon_wave_dev, void* stream);
 /* The same with d loss_b / d raw_wave (B,L) as well (d_raw_wave_dev optional; the recon side is computed exactly as escx_mel_loss does). */
