@@ -11,6 +11,8 @@
 // (DESIGN.md section 13.4).  escx_dac_decode_backward_params is the decoder's backward with the gradients of its parameters (bias, weight_g, weight_v,
 // alpha) next to d_z, for fine-tuning a decoder (dac_param_grad_kernels.h, gemm_dw_kernel of train_kernels.h);
 // escx_dac_set_param_grad_precision moves its weight-gradient contractions to the split-operand gemm_dw_bf16_kernel<.., 3> of gemm_bf16.h.
+// escx_dac_encode_backward_params is the encoder's and the quantiser's backward with the gradients of their parameters (the codebooks included) next
+// to d_audio, for fine-tuning the whole baseline (dac_param_grad_kernels.h).
 // escx_dac_encode_lengths / escx_dac_from_codes_lengths / escx_dac_decode_lengths are encode, from_codes and decode for a batch with one length per
 // clip (padding on): per-clip length tables in the loader and the epilogue, every clip bitwise its own call.
 #include <hip/hip_runtime.h>
@@ -92,6 +94,9 @@ struct escx_dac_s {
     // (param_ws16_plan), a second allocation made at the first parameter backward in that mode; the staged dW and the column partials stay in pw.
     int param_grad_precision = ESCX_PRECISION_FP32;
     float* pw16 = nullptr;
+    // escx_dac_encode_backward_params: the same two workspaces for the encoder's layers and the quantiser's projections, allocated at the first
+    // encode parameter backward of the handle (in that mode), sized from the configuration alone (enc_param_ws_plan)
+    float* pwe = nullptr; float* pwe16 = nullptr;
 };
 
 namespace {
@@ -462,6 +467,8 @@ extern "C" void escx_dac_destroy(escx_dac d) {
     if (d->wte16) (void)hipFree(d->wte16);
     if (d->pw) (void)hipFree(d->pw);
     if (d->pw16) (void)hipFree(d->pw16);
+    if (d->pwe) (void)hipFree(d->pwe);
+    if (d->pwe16) (void)hipFree(d->pwe16);
     if (d->qoffs_dev) (void)hipFree(d->qoffs_dev);
     if (d->scratch) (void)hipFree(d->scratch);
     if (d->counts) (void)hipFree(d->counts);
@@ -1115,25 +1122,32 @@ void dw16_slices(const DwGeom& g, int M, int* slices, int* mps) {
     *slices = (M + *mps - 1) / *mps;
 }
 // Its partial tiles, in floats, whatever the batch: smax Np Kp of the layer that needs most
-size_t param_ws16_plan(const escx_dac_s* d) {
+size_t param_ws16_plan(const std::vector<DacLayer>& layers) {
     size_t part = 0;
-    for (const DacLayer& l : d->dec)
+    for (const DacLayer& l : layers)
         if (dw16_layer(l)) { const DwGeom g = dw16_geom(l); part = std::max(part, pad64((size_t)g.smax * g.Np * g.Kp)); }
     return part;
 }
+size_t param_ws16_plan(const escx_dac_s* d) { return param_ws16_plan(d->dec); }
 
-// The workspace, in floats, whatever the batch: [partial tiles: smax Np Kp] [staged dW: Np Kp] [column partials: blocks x Cp, fp64]
-struct ParamWs { size_t part = 0, stage = 0, cols = 0; size_t total() const { return part + stage + cols; } };
+// The workspace, in floats, whatever the batch: [partial tiles: smax Np Kp] [staged dW: Np Kp] [column partials: blocks x Cp, fp64].  pw / pw16:
+// the allocations a pass works in (the decoder's, or the encoder's and the quantiser's own).
+struct ParamWs {
+    size_t part = 0, stage = 0, cols = 0; int cmax = 4;
+    float* pw = nullptr; float* pw16 = nullptr;
+    size_t total() const { return part + stage + cols; }
+};
+void param_ws_take(ParamWs& w, const DacLayer& l) {
+    const DwGeom g = dw_geom(l);
+    const size_t nk = (size_t)g.Np * g.Kp;
+    w.part = std::max(w.part, pad64((size_t)g.smax * nk));
+    w.stage = std::max(w.stage, pad64(nk));
+    w.cmax = std::max(w.cmax, std::max(l.CinP, cpad(l.Cout)));
+    w.cols = pad64(2 * (size_t)COLSUM_BLOCKS * w.cmax);
+}
 ParamWs param_ws_plan(const escx_dac_s* d) {
-    ParamWs w; int cmax = 4;
-    for (const DacLayer& l : d->dec) {
-        const DwGeom g = dw_geom(l);
-        const size_t nk = (size_t)g.Np * g.Kp;
-        w.part = std::max(w.part, pad64((size_t)g.smax * nk));
-        w.stage = std::max(w.stage, pad64(nk));
-        cmax = std::max(cmax, std::max(l.CinP, cpad(l.Cout)));
-    }
-    w.cols = pad64(2 * (size_t)COLSUM_BLOCKS * cmax);
+    ParamWs w;
+    for (const DacLayer& l : d->dec) param_ws_take(w, l);
     return w;
 }
 
@@ -1146,7 +1160,7 @@ DacConvA rows_of(const float* x, int B, int T, int Cp) {                // the r
 
 // sum over the rows of v (M, Cp) [times d snake / d alpha at xs] -> out[0, C)
 void colsum(const escx_dac_s* d, const ParamWs& w, hipStream_t st, const float* v, const float* xs, const DacSnake* sn, long long M, int Cp, int C, float* out) {
-    double* part = reinterpret_cast<double*>(d->pw + w.part + w.stage);          // 256-byte aligned: the regions are multiples of 64 floats
+    double* part = reinterpret_cast<double*>(w.pw + w.part + w.stage);           // 256-byte aligned: the regions are multiples of 64 floats
     const int rows = (int)std::max<long long>(16, (M + COLSUM_BLOCKS - 1) / COLSUM_BLOCKS);
     const int blocks = (int)((M + rows - 1) / rows);
     const dim3 grid(blocks, (Cp + 255) / 256);                  // y: 256-column groups (one group when Cp <= 256)
@@ -1156,9 +1170,10 @@ void colsum(const escx_dac_s* d, const ParamWs& w, hipStream_t st, const float* 
 }
 
 // bias, weight_g and weight_v gradients of layer l from its output gradient dY (B, Tdy, cpad(Cout)) and its forward operand s (B, Ts, CinP), both
-// plain maps (the Snake already applied to s)
+// plain maps (the Snake already applied to s).  split_ok false: the contraction stays on the fp32 MFMA whatever the switch says (the quantiser's
+// projections).
 void param_layer(const escx_dac_s* d, const ParamWs& w, hipStream_t st, const DacLayer& l, const float* dY, int Tdy, const float* s, int Ts, int B,
-                 const float* flat, float* grad) {
+                 const float* flat, float* grad, bool split_ok = true) {
     const DwGeom g = dw_geom(l);
     const int CoutP = cpad(l.Cout);
     DacConvA la, lb;
@@ -1173,11 +1188,11 @@ void param_layer(const escx_dac_s* d, const ParamWs& w, hipStream_t st, const Da
     }
     const int M = la.M;
     int slices, mps;
-    float* part = d->pw; float* stage = d->pw + w.part;
-    if (d->param_grad_precision == ESCX_PRECISION_BF16X3 && dw16_layer(l)) {
+    float* part = w.pw; float* stage = w.pw + w.part;
+    if (split_ok && d->param_grad_precision == ESCX_PRECISION_BF16X3 && dw16_layer(l)) {
         const DwGeom g16 = dw16_geom(l);
         dw16_slices(g16, M, &slices, &mps);
-        part = d->pw16;
+        part = w.pw16;
         launch_dac_dw_x3(la, lb, M, g.Np, g.Kp, slices, mps, part, st);
     } else {
         dw_slices(g, M, &slices, &mps);
@@ -1203,12 +1218,30 @@ void bwd_layer_v(const GradRun& run, const DacLayer& l, const DacSnake* sn, cons
     launch_grad(run, run.mirror(l, l.Wt), l.Wt, ld, np_t(l), kp_t(l), ep);
 }
 
+// The quantiser's projections of stage i as 1 x 1 convolutions with their slots of the flat layout: in_proj (D -> d), out_proj (d -> D)
+DacLayer q_layer(const escx_dac_s* d, int i, bool out_proj) {
+    DacLayer l = out_proj ? make_layer(0, d->cfg.codebook_dim, d->latent, 1, 1, 0, 1) : make_layer(0, d->latent, d->cfg.codebook_dim, 1, 1, 0, 1);
+    const long long* o = d->qoffs.data() + 6 * (size_t)i + (out_proj ? 3 : 0);
+    l.off_b = (size_t)o[0]; l.off_g = (size_t)o[1]; l.off_v = (size_t)o[2];
+    return l;
+}
+// The encode parameter backward's own workspace: param_ws_plan over the encoder's layers and the quantiser's two projections
+ParamWs enc_param_ws_plan(const escx_dac_s* d) {
+    ParamWs w;
+    for (const DacLayer& l : d->enc) param_ws_take(w, l);
+    param_ws_take(w, q_layer(d, 0, false));
+    param_ws_take(w, q_layer(d, 0, true));
+    return w;
+}
+
 }  // namespace
 
 extern "C" int64_t escx_dac_param_grad_workspace_floats(escx_dac d) {
     if (!d) return 0;
     const bool held16 = d->param_grad_precision == ESCX_PRECISION_BF16X3 && d->pw16;
-    return (int64_t)(param_ws_plan(d).total() + (held16 ? param_ws16_plan(d) : 0));
+    const bool helde16 = d->param_grad_precision == ESCX_PRECISION_BF16X3 && d->pwe16;
+    return (int64_t)(param_ws_plan(d).total() + (held16 ? param_ws16_plan(d) : 0) + (d->pwe ? enc_param_ws_plan(d).total() : 0) +
+                     (helde16 ? param_ws16_plan(d->enc) : 0));
 }
 
 extern "C" int escx_dac_param_grad_slices(escx_dac d, int B, int T, int layer) {
@@ -1243,10 +1276,11 @@ extern "C" int escx_dac_decode_backward_params(escx_dac d, const float* flat, in
                   hdr[1], (long long)version);
     if ((long long)B * p.Lout > 0x7fffffffll) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "batch of %d x %d frames: more than 2^31 audio rows in one contraction", B, T);
     const size_t mf = p.mf;
-    const ParamWs w = param_ws_plan(d);
+    ParamWs w = param_ws_plan(d);
     if ((rc = ensure_scratch(d, 4 * mf * sizeof(float)))) return rc;
     if (!d->pw) ESCX_HIP(hipMalloc((void**)&d->pw, w.total() * sizeof(float)));
     if (d->param_grad_precision == ESCX_PRECISION_BF16X3 && !d->pw16) ESCX_HIP(hipMalloc((void**)&d->pw16, param_ws16_plan(d) * sizeof(float)));
+    w.pw = d->pw; w.pw16 = d->pw16;
     if ((rc = pack(d, flat, (long long)version, st)) || (rc = refresh_wt(d, st)) || (rc = refresh_wt16(d, d->wt, d->wt_floats, &d->wt16, &d->wt16_valid, st))) return rc;
     const GradRun run{st, d->wt, d->grad_precision == ESCX_PRECISION_BF16X3 ? d->wt16 : nullptr, d->wt_floats};
     // escx_dac_decode_backward's walk and maps; S holds the Snaked operand of the layer at hand, then the v of its input gradient
@@ -1486,6 +1520,163 @@ extern "C" int escx_dac_encode_backward(escx_dac d, const float* flat, int64_t v
     }
     bwd_layer(run, E[0], nullptr, G, B, p.Ts[0], L, nullptr, nullptr, d_audio, 1);
     return launch_ok("escx_dac_encode_backward");
+}
+
+// ---- parameter gradients through the encoder and the quantiser, eval mode, padding on (dac.py:24-91, quantize.py:58-70, 173-198,
+// nn/layers.py:5-33) ------------------------------------------------------------------------------------------------------
+namespace {
+
+// bwd_strided with v = conv^T(dY) kept in vout (DacGradPhaseEpiV): `out` has bwd_strided's bits
+void bwd_strided_v(const GradRun& run, const DacLayer& l, const DacSnake& sn, const float* dY, int B, int Tdy, int Tx, const float* xs, float* out, float* vout) {
+    const int s = l.stride, Np = np_t(l), Kp = kp_ph(l);
+    for (int r = 0; r < s && r < Tx; ++r) {
+        const int Q = (Tx - r + s - 1) / s;
+        DacConvA ld{};
+        ld.x = dY; ld.alpha = nullptr; ld.inv = nullptr; ld.Tin = Tdy; ld.Cp = cpad(l.Cout); ld.dCp = FastDiv(ld.Cp);
+        ld.Trows = Q; ld.M = B * Q; ld.dT = FastDiv(Q); ld.ntaps = 2; ld.rs = 1; ld.r0 = (r + l.pad) / s; ld.td = -1;
+        DacGradPhaseEpiV ep{};
+        ep.out = out; ep.xs = xs; ep.alpha = sn.a; ep.inv = sn.inv; ep.vout = vout; ep.Cp = cpad(l.Cin); ep.Trows = Q; ep.Tmap = Tx; ep.os = s; ep.o0 = r;
+        ep.dT = ld.dT;
+        const float* W = l.Wt + (size_t)r * Np * Kp;
+        launch_grad(run, run.mirror(l, W), W, ld, Np, Kp, ep);
+    }
+}
+
+void launch_rvq_param_rows(int latent, long long M, const DacQParamArgs& qa, hipStream_t st) {
+    const int J = (latent + 63) / 64;
+    const dim3 g(nblk(M, 4)), blk(256);
+    if (J <= 1) hipLaunchKernelGGL((dac_rvq_param_rows_kernel<1>), g, blk, 0, st, qa);
+    else if (J <= 2) hipLaunchKernelGGL((dac_rvq_param_rows_kernel<2>), g, blk, 0, st, qa);
+    else if (J <= 4) hipLaunchKernelGGL((dac_rvq_param_rows_kernel<4>), g, blk, 0, st, qa);
+    else if (J <= 8) hipLaunchKernelGGL((dac_rvq_param_rows_kernel<8>), g, blk, 0, st, qa);
+    else hipLaunchKernelGGL((dac_rvq_param_rows_kernel<16>), g, blk, 0, st, qa);
+}
+
+// Output rows per clip of encoder layer `layer` (every one a Conv1d: the rows of its dW contraction)
+int enc_layer_rows(const escx_dac_s* d, const EncTapePlan& p, int layer) {
+    if (layer == 0) return p.Ts[0];
+    if (layer == (int)d->enc.size() - 1) return p.Tz;
+    const int i = (layer - 1) / 7, k = (layer - 1) % 7;
+    return k == 6 ? p.Ts[i + 1] : p.Ts[i];
+}
+
+}  // namespace
+
+extern "C" int escx_dac_encode_param_grad_slices(escx_dac d, int B, int L, int layer) {
+    if (!d || B < 1 || L < 1 || layer < 0 || layer >= (int)d->enc.size() || !d->padding) return 0;
+    EncTapePlan p;
+    if (!enc_tape_plan(d, B, L, 1, &p)) return 0;
+    const DacLayer& l = d->enc[layer];
+    int slices, mps;
+    if (d->param_grad_precision == ESCX_PRECISION_BF16X3 && dw16_layer(l)) dw16_slices(dw16_geom(l), B * enc_layer_rows(d, p, layer), &slices, &mps);
+    else dw_slices(dw_geom(l), B * enc_layer_rows(d, p, layer), &slices, &mps);
+    return slices;
+}
+
+extern "C" int escx_dac_encode_backward_params(escx_dac d, const float* flat, int64_t version, const float* tape, int64_t tape_floats, const float* audio,
+                                               const float* d_z, const float* d_latents, const float* d_commitment, const float* d_codebook, int B, int L,
+                                               int parts, float* d_audio, float* grad, void* stream) {
+    int rc = check_args(d, flat, B); if (rc) return rc;
+    if (!tape || !audio || !grad || L < 1 || tape_floats < DAC_TAPE_HEADER) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "bad argument");
+    if (parts < 1 || parts > 3) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "parts %d: expected 1 (encoder), 2 (quantiser) or 3 (both)", parts);
+    if (!d->padding) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "%s", ENC_GRAD_PADDING);
+    if ((rc = check_phased(d))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    long long hdr[6] = {0, 0, 0, 0, 0, 0};                      // as escx_dac_encode_backward: checked before anything of the handle changes
+    ESCX_HIP(hipMemcpyAsync(hdr, tape, sizeof(hdr), hipMemcpyDeviceToHost, st));
+    ESCX_HIP(hipStreamSynchronize(st));
+    EncTapePlan p;
+    if (hdr[0] != DAC_ENC_TAPE_MAGIC || hdr[2] != B || hdr[3] != L || hdr[4] != (long long)tape_floats || hdr[5] < 1 || hdr[5] > d->cfg.n_codebooks ||
+        !enc_tape_plan(d, B, L, (int)hdr[5], &p) || (long long)p.total != (long long)tape_floats)
+        ESCX_FAIL(ESCX_ERR_INVALID_ARG, "the buffer of %lld floats is not a tape that escx_dac_encode_tape made for %d x %d samples", (long long)tape_floats, B, L);
+    if ((unsigned long long)p.mf >= (1ull << 32)) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "batch of %d x %d samples: a feature map above 2^32 elements", B, L);
+    if (hdr[1] != (long long)version)
+        ESCX_FAIL(ESCX_ERR_STATE, "the tape was made with parameter version %lld and the backward is called with %lld: the parameters changed between forward and backward",
+                  hdr[1], (long long)version);
+    if ((long long)B * L > 0x7fffffffll) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "batch of %d x %d samples: more than 2^31 audio rows in one contraction", B, L);
+    const bool enc = parts & 1, qnt = parts & 2;
+    const bool walk = enc || d_audio;                           // the encoder's layers are walked for their parameters or for the audio gradient
+    const size_t mf = p.mf, M = (size_t)B * p.Tz;
+    const int D = d->latent, Dp = cpad(D), dd = d->cfg.codebook_dim, dp = cpad(dd), S = d->cfg.n_codebooks, K = d->cfg.codebook_size, n = p.n;
+    const size_t qrow = pad64(M * dp);
+    ParamWs w = enc_param_ws_plan(d);
+    if ((rc = ensure_scratch(d, (5 * mf + 2 * qrow) * sizeof(float)))) return rc;
+    if (!d->pwe) ESCX_HIP(hipMalloc((void**)&d->pwe, w.total() * sizeof(float)));
+    if (d->param_grad_precision == ESCX_PRECISION_BF16X3 && !d->pwe16) ESCX_HIP(hipMalloc((void**)&d->pwe16, std::max<size_t>(64, param_ws16_plan(d->enc)) * sizeof(float)));
+    w.pw = d->pwe; w.pw16 = d->pwe16;
+    if ((rc = pack(d, flat, (long long)version, st)) || (rc = refresh_wte(d, st)) || (rc = refresh_wt16(d, d->wte, d->wte_floats, &d->wte16, &d->wte16_valid, st))) return rc;
+    if (qnt && (rc = refresh_w16(d, st))) return rc;
+    const GradRun run{st, d->wte, d->grad_precision == ESCX_PRECISION_BF16X3 ? d->wte16 : nullptr, d->wte_floats};
+    // escx_dac_encode_backward's maps; Sm holds the Snaked operand of the layer at hand, then the v of its input gradient
+    float* G = d->scratch; float* G2 = G + mf; float* A = G2 + mf; float* Sm = d->scratch + 3 * mf;
+    auto Mp = [&](int i) { return tape + p.off[i]; };
+    const DacLayer* E = d->enc.data(); const DacSnake* SN = d->enc_sn.data();
+    const int nE = d->cfg.n_encoder_rates;
+    const float* lat = tape + p.latents; const long long* codes = (const long long*)(tape + p.codes); const int* counts = (const int*)(tape + p.counts);
+    if (walk) {                                                 // d_z_enc, the dY of the encoder's last convolution: escx_dac_encode_backward's launch
+        DacQGradArgs qa{};
+        qa.win = d->qt.win; qa.wout = d->qt.wout; qa.cbraw = d->qt.cbraw; qa.g_z = d_z; qa.g_lat = d_latents; qa.g_cm = d_commitment;
+        qa.latents = lat; qa.codes = codes; qa.clip_n = counts; qa.out = A;
+        qa.M = (int)M; qa.T = p.Tz; qa.D = D; qa.Dp = Dp; qa.d = dd; qa.K = K; qa.n = n; qa.B = B;
+        launch_rvq_grad(D, (long long)M, qa, st);
+    }
+    if (qnt) {
+        // z_enc: the encoder's last convolution again from the last taped map, the forward's launch (the tape does not hold the quantiser's input)
+        float* zmap = d->scratch + 4 * mf; float* Em = d->scratch + 5 * mf; float* Qm = Em + qrow;
+        float* gr = G; float* U = G2; float* R = Sm;
+        const Run frun{d->snake_maps, Sm, st, d->wbuf, d->precision == ESCX_PRECISION_BF16X3 ? d->w16 : nullptr, d->conv_floats, true};
+        run_layer(frun, ESCX_DAC_SNAKE_LAST, E[d->enc.size() - 1], SN + d->enc_sn.size() - 1, Mp(7 * nE), B, p.Ts[nE], zmap, p.Tz, nullptr, 0);
+        ESCX_HIP(hipMemsetAsync(gr, 0, M * Dp * sizeof(float), st));
+        DacQParamArgs qp{};
+        qp.win = d->qt.win; qp.wout = d->qt.wout; qp.bout = d->qt.bout; qp.cbraw = d->qt.cbraw; qp.g_z = d_z; qp.g_lat = d_latents; qp.g_cm = d_commitment;
+        qp.latents = lat; qp.codes = codes; qp.clip_n = counts; qp.zmap = zmap; qp.gr = gr; qp.U = U; qp.R = R; qp.E = Em; qp.Q = Qm;
+        qp.M = (int)M; qp.T = p.Tz; qp.D = D; qp.Dp = Dp; qp.d = dd; qp.dp = dp; qp.K = K; qp.n = n; qp.B = B;
+        for (int i = n - 1; i >= 0; --i) {
+            qp.stage = i;
+            launch_rvq_param_rows(D, (long long)M, qp, st);
+            param_layer(d, w, st, q_layer(d, i, true), U, p.Tz, Qm, p.Tz, B, flat, grad, false);
+            param_layer(d, w, st, q_layer(d, i, false), Em, p.Tz, R, p.Tz, B, flat, grad, false);
+        }
+        hipLaunchKernelGGL(dac_codebook_grad_kernel, dim3(nblk((long long)n * K, 4)), dim3(256), 0, st, (const float*)d->qt.cbraw, lat, codes, counts, d_codebook,
+                           (const long long*)(d->qoffs_dev + 6 * (size_t)S), (int)M, p.Tz, dd, K, n, B, grad);
+        if (n < S) {                                            // the stages no clip ran: a stage's seven tensors are consecutive, and so are the stages
+            const size_t lo = (size_t)d->qoffs[6 * (size_t)n], hi = (size_t)d->qoffs[6 * (size_t)S + S - 1] + (size_t)K * dd;
+            ESCX_HIP(hipMemsetAsync(grad + lo, 0, (hi - lo) * sizeof(float), st));
+        }
+    }
+    if (!walk) return launch_ok("escx_dac_encode_backward_params");
+    // one layer behind a Snake.  With the encoder chosen: its parameter gradients from (dY, snake(xs)), its input gradient with v kept, the Snake's
+    // alpha gradient; otherwise escx_dac_encode_backward's launch.  `out` has the same bits either way.
+    auto layer = [&](const DacLayer& l, const DacSnake* sn, const float* dY, int Tdy, int Tx, const float* xs, const float* res, float* out) {
+        if (!enc) {
+            if (phased(l)) bwd_strided(run, l, *sn, dY, B, Tdy, Tx, xs, out);
+            else bwd_layer(run, l, sn, dY, B, Tdy, Tx, xs, res, out);
+            return;
+        }
+        const long long n4 = (long long)B * Tx * l.CinP / 4;
+        hipLaunchKernelGGL(dac_snake_map_kernel, dim3(nblk(n4)), dim3(256), 0, st, xs, (const float*)sn->a, (const float*)sn->inv, Sm, n4, l.CinP / 4);
+        param_layer(d, w, st, l, dY, Tdy, Sm, Tx, B, flat, grad);
+        if (phased(l)) bwd_strided_v(run, l, *sn, dY, B, Tdy, Tx, xs, out, Sm);
+        else bwd_layer_v(run, l, sn, dY, B, Tdy, Tx, xs, res, out, Sm);
+        colsum(d, w, st, Sm, xs, sn, (long long)B * Tx, l.CinP, sn->C, grad + sn->off);
+    };
+    layer(E[d->enc.size() - 1], SN + d->enc_sn.size() - 1, A, p.Tz, p.Ts[nE], Mp(7 * nE), nullptr, G);
+    for (int i = nE - 1; i >= 0; --i) {
+        const DacLayer* Lb = E + 1 + i * 7; const DacSnake* Sb = SN + i * 7;
+        const int Tc = p.Ts[i];
+        layer(Lb[6], &Sb[6], G, p.Ts[i + 1], Tc, Mp(7 * i + 6), nullptr, G2);
+        std::swap(G, G2);
+        for (int j = 2; j >= 0; --j) {
+            layer(Lb[2 * j + 1], &Sb[2 * j + 1], G, Tc, Tc, Mp(7 * i + 2 * j + 1), nullptr, A);
+            layer(Lb[2 * j], &Sb[2 * j], A, Tc, Tc, Mp(7 * i + 2 * j), G, G);
+        }
+    }
+    if (enc) {                                                  // the first convolution reads the audio itself, staged as the forward stages it; no Snake in front
+        hipLaunchKernelGGL(dac_wave_in_kernel, dim3(nblk((long long)B * L)), dim3(256), 0, st, audio, A, (long long)B * L);
+        param_layer(d, w, st, E[0], G, p.Ts[0], A, L, B, flat, grad);
+    }
+    if (d_audio) bwd_layer(run, E[0], nullptr, G, B, p.Ts[0], L, nullptr, nullptr, d_audio, 1);
+    return launch_ok("escx_dac_encode_backward_params");
 }
 
 extern "C" int escx_dac_test_grad_math(const float* x, const float* alpha, float* out, int64_t n, int mode, void* stream) {

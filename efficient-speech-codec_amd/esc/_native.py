@@ -169,6 +169,9 @@ SIGNATURES = {
     "escx_dac_encode_tape": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, POINTER(c_int32), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_int64, c_void_p]),
     "escx_dac_encode_backward": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "escx_dac_encode_backward_params": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                                c_void_p, c_void_p, c_void_p]),
+    "escx_dac_encode_param_grad_slices": (c_int, [c_void_p, c_int, c_int, c_int]),
     "escx_set_rccl_library": (c_int, [c_char_p]),
     "escx_allgather_codes": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p]),
 }

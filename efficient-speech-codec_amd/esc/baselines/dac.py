@@ -6,6 +6,9 @@ Same constructor keywords, same state_dict keys and shapes (`*.weight_g`, `*.wei
 libescx (csrc/dac.hip); there is no PyTorch/CPU implementation here.  Inference only: training mode raises NotImplementedError.  The
 frozen codec can sit inside a larger autograd graph (eval mode, padding on, input gradients only): `decode(z)` is differentiable in `z`
 (`_DecodeGrad`), `encode(x)` in `x` through the encoder and the straight-through quantiser (`_EncodeGrad`), and `forward(x)` chains the two.
+Fine-tuning (still eval mode): `set_trainable("decoder")` gives `decode` the decoder's parameter gradients (`_DecodeParamGrad`),
+`set_encode_trainable("encoder" | "quantizer" | "both")` gives `encode` the encoder's and the quantiser's (`_EncodeParamGrad`), and with both
+`forward(x)` delivers the gradient of every parameter of the model.
 
 Mixed-length batches (not part of the reference's surface): `encode` / `forward` take `lengths`, `decode` / `quantizer.from_codes` take
 `frame_lengths`, one entry per clip; every clip's results are bitwise those of the call on that clip alone.
@@ -16,6 +19,7 @@ length in overlapping windows on padding-free convolutions, all windows of a fil
 from __future__ import annotations
 
 import ctypes
+import functools
 import math
 from dataclasses import dataclass
 from pathlib import Path
@@ -27,6 +31,8 @@ import torch.nn as nn
 
 from .. import _native
 from ..models.codecs import _attach
+
+_ENCODE_PARTS = {"encoder": 1, "quantizer": 2, "both": 3}       # set_encode_trainable -> escx_dac_encode_backward_params' `parts`
 
 
 def _param_specs(enc_dim, enc_rates, latent, dec_dim, dec_rates, n_cb, cb_size, cb_dim):
@@ -110,6 +116,21 @@ class DACFile:
         return cls(codes=torch.from_numpy(artifacts["codes"].astype(np.int64)), **meta)
 
 
+def _no_grad_frozen(what: str):
+    """torch.no_grad() for a method that has no gradient path, which refuses when set_encode_trainable would have made one expected: the switch
+    on, gradients enabled and a parameter of the chosen part requiring one."""
+    def deco(fn):
+        @functools.wraps(fn)
+        def wrapped(self, *args, **kwargs):
+            if self._encoder_trains():
+                raise NotImplementedError(f"{what} has no parameter gradients (set_encode_trainable({self._encode_trainable!r}) is in effect and a "
+                                          "parameter requires grad): call it under torch.no_grad(), or train through encode / forward")
+            with torch.no_grad():
+                return fn(self, *args, **kwargs)
+        return wrapped
+    return deco
+
+
 def _check_device(x: torch.Tensor, what: str):
     if not x.is_cuda:
         raise RuntimeError(f"esc.baselines.DAC runs on the HIP device only: {what} is on {x.device}")
@@ -158,6 +179,7 @@ class DAC(nn.Module):
         self._param_grad_precision = "fp32"
         self._padding = True
         self._trainable = None
+        self._encode_trainable = None
 
     # ---- native handle and flat parameter buffer (same scheme as esc.models.Discriminator) ----------------------------------------------
     def _version(self) -> int:
@@ -321,11 +343,12 @@ class DAC(nn.Module):
         """Which part of the model `decode` differentiates with respect to its parameters.  None (the default): none, today's behaviour bit for
         bit.  "decoder": in eval mode, with padding on and gradients enabled, decode(z) delivers through autograd the gradient of every decoder
         parameter that requires one (and of z if it requires one); the audio is bitwise the plain decode's.  The decoder has no train / eval
-        difference, so the model stays in eval mode; `.train()` still refuses.  The encoder and the quantiser stay frozen: their parameter
-        gradients, quantiser dropout and training mode are not built, so "encoder", "quantizer" and "all" raise NotImplementedError."""
+        difference, so the model stays in eval mode; `.train()` still refuses.  This is `decode`'s switch: the encoder's and the quantiser's
+        parameters are `encode`'s and have their own, set_encode_trainable, so "encoder", "quantizer" and "all" raise NotImplementedError here."""
         if part in ("encoder", "quantizer", "all"):
-            raise NotImplementedError(f"set_trainable({part!r}): only the decoder's parameter gradients are built (set_trainable('decoder')); the "
-                                      "encoder's and the quantiser's parameter gradients, quantiser dropout and training mode are not")
+            raise NotImplementedError(f"set_trainable({part!r}): this is decode's switch and takes None or 'decoder'; the encoder's and the quantiser's "
+                                      "parameter gradients are encode's: set_encode_trainable('encoder' | 'quantizer' | 'both'), next to "
+                                      "set_trainable('decoder') for the whole model (quantiser dropout and training mode are not built)")
         if part not in (None, "decoder"):
             raise ValueError(f"set_trainable({part!r}): expected None or 'decoder'")
         self._trainable = part
@@ -341,6 +364,46 @@ class DAC(nn.Module):
         for key, p in self.named_parameters():
             if key.startswith("decoder."):
                 yield p
+
+    # ---- fine-tuning the encoder and the quantiser (include/escx.h escx_dac_encode_backward_params) ----------------------------------------------
+    def set_encode_trainable(self, part: Optional[str]) -> "DAC":
+        """Which part of the model `encode` differentiates with respect to its parameters, independent of set_trainable.  None (the default):
+        none, today's behaviour bit for bit.  "encoder", "quantizer" or "both": in eval mode, with padding on and gradients enabled,
+        encode(x, n_quantizers) delivers through autograd the gradient of every parameter of the chosen part that requires one (and of x if it
+        requires one, bitwise the frozen path's); the forward values are bitwise the plain encode's.  With the quantiser chosen the codebook loss
+        is differentiable with respect to the codebooks.  A quantiser stage that no clip of the call runs gets no gradient (None), as under
+        torch autograd of the reference.  With set_trainable("decoder") next to "both", forward(x) delivers the gradient of every parameter of
+        the model.  The model stays in eval mode; `.train()` still refuses, and quantiser dropout is per-clip n_quantizers sampled by the caller.
+        Anything else raises ValueError and leaves the switch as it was.  Never touches a device."""
+        if not (part is None or (isinstance(part, str) and part in _ENCODE_PARTS)):
+            raise ValueError(f"set_encode_trainable({part!r}): expected None, 'encoder', 'quantizer' or 'both'")
+        self._encode_trainable = part
+        return self
+
+    @property
+    def encode_trainable(self) -> Optional[str]:
+        """What set_encode_trainable chose: None, "encoder", "quantizer" or "both"."""
+        return self._encode_trainable
+
+    def encoder_parameters(self):
+        """The `encoder.*` parameters in state_dict order."""
+        for key, p in self.named_parameters():
+            if key.startswith("encoder."):
+                yield p
+
+    def quantizer_parameters(self):
+        """The `quantizer.*` parameters in state_dict order (per stage: in_proj, out_proj, codebook)."""
+        for key, p in self.named_parameters():
+            if key.startswith("quantizer."):
+                yield p
+
+    def _encode_named(self):
+        """[(key, parameter)] of the part set_encode_trainable chose, in state_dict order."""
+        prefixes = {"encoder": ("encoder.",), "quantizer": ("quantizer.",), "both": ("encoder.", "quantizer.")}[self._encode_trainable]
+        return [(k, p) for k, p in self.named_parameters() if k.startswith(prefixes)]
+
+    def _encoder_trains(self) -> bool:
+        return self._encode_trainable is not None and torch.is_grad_enabled() and any(p.requires_grad for _, p in self._encode_named())
 
     # ---- CodecMixin's padding switch and geometry (base.py:58-123) ----------------------------------------------------------------------
     @property
@@ -510,8 +573,8 @@ class DAC(nn.Module):
             raise NotImplementedError(f"{what} needs padding = True: with the padding off every clip loses the receptive field at both ends and "
                                       "the chunked path batches equal windows already")
         if grad:
-            raise NotImplementedError(f"{what} is not implemented on the gradient paths (an input that requires grad, or set_trainable('decoder') "
-                                      "with a parameter that requires grad): call it under torch.no_grad() or differentiate clip by clip")
+            raise NotImplementedError(f"{what} is not implemented on the gradient paths (an input that requires grad, or set_trainable('decoder') / "
+                                      "set_encode_trainable with a parameter that requires grad): call it under torch.no_grad() or differentiate clip by clip")
 
     def _decoder_trains(self) -> bool:
         return self._trainable == "decoder" and torch.is_grad_enabled() and any(p.requires_grad for p in self.decoder_parameters())
@@ -606,7 +669,7 @@ class DAC(nn.Module):
                                                  ctypes.c_void_p(losses.data_ptr()), None, stream))
         return z, codes, latents, losses[0], losses[1]
 
-    @torch.no_grad()
+    @_no_grad_frozen("encode_sweep")
     def encode_sweep(self, audio_data: torch.Tensor, n_quantizers: Sequence[int], lengths=None):
         """One encode for a whole bitrate sweep: (zs (R, B, D, T), codes (B, n_max, T), latents (B, n_max d, T)) with zs[r] bitwise the z of
         encode(audio_data, n_quantizers[r]) and codes / latents those of the largest count (the codes are prefix codes; the quantiser stores its
@@ -639,7 +702,9 @@ class DAC(nn.Module):
         -1 and latents 0 past a clip's count, the losses are the reference's masked means.  When gradients are enabled and audio_data requires
         one, z, latents and commitment_loss carry the audio gradient of the reference's eval-mode autograd (straight-through quantiser,
         quantize.py:58-70; eval mode, padding on; `_EncodeGrad` below): the same bits, computed by escx_dac_encode_tape, which keeps the
-        encoder's maps in a tape on the graph.  The module's parameters get no gradient whatever their requires_grad.
+        encoder's maps in a tape on the graph.  The module's parameters get no gradient whatever their requires_grad, unless
+        set_encode_trainable is in effect: then every parameter of the chosen part that requires a gradient gets one, x may or may not
+        require one, and with the quantiser chosen codebook_loss is differentiable in the codebooks (`_EncodeParamGrad`).
 
         lengths (a sequence or 1-D integer tensor, one sample count in [1, L] per clip; not part of the reference's surface) makes the batch a
         mixed-length one: clip b's results are bitwise those of encode(audio_data[b:b+1, :, :lengths[b]]) alone, nothing at or past a clip's
@@ -649,11 +714,17 @@ class DAC(nn.Module):
         if self.training:
             raise NotImplementedError("esc.baselines.DAC is inference only: call .eval() (DAC training is not implemented)")
         if lengths is not None:
-            self._refuse_lengths("encode with lengths", torch.is_grad_enabled() and isinstance(audio_data, torch.Tensor) and audio_data.requires_grad)
+            self._refuse_lengths("encode with lengths",
+                                 (torch.is_grad_enabled() and isinstance(audio_data, torch.Tensor) and audio_data.requires_grad) or self._encoder_trains())
             lens, frames = self._check_encode_lengths(audio_data, lengths, 1)
             if self._is_per_clip(n_quantizers):
                 self._clip_counts(n_quantizers, audio_data.shape[0])
             return self._encode_lengths(audio_data, lens, frames, n_quantizers, 1)
+        if isinstance(audio_data, torch.Tensor) and self._encoder_trains():
+            counts = self._clip_counts(n_quantizers, audio_data.shape[0]) if self._is_per_clip(n_quantizers) else None
+            named = self._encode_named()
+            return _EncodeParamGrad.apply(audio_data, self, self._n_quantizers(n_quantizers) if counts is None else max(counts), counts,
+                                          tuple(k for k, _ in named), *[p for _, p in named])
         if torch.is_grad_enabled() and isinstance(audio_data, torch.Tensor) and audio_data.requires_grad:
             counts = self._clip_counts(n_quantizers, audio_data.shape[0]) if self._is_per_clip(n_quantizers) else None
             return _EncodeGrad.apply(audio_data, self, self._n_quantizers(n_quantizers) if counts is None else max(counts), counts)
@@ -794,7 +865,8 @@ class DAC(nn.Module):
         if lengths is not None:
             hop = self.hop_length
             self._refuse_lengths("forward with lengths",
-                                 (torch.is_grad_enabled() and isinstance(audio_data, torch.Tensor) and audio_data.requires_grad) or self._decoder_trains())
+                                 (torch.is_grad_enabled() and isinstance(audio_data, torch.Tensor) and audio_data.requires_grad) or self._decoder_trains()
+                                 or self._encoder_trains())
             lens, frames = self._check_encode_lengths(audio_data, lengths, hop)
             if self._is_per_clip(n_quantizers):
                 n_quantizers = self._clip_counts(n_quantizers, audio_data.shape[0])
@@ -856,7 +928,7 @@ class DAC(nn.Module):
         return {"padding": False, "n_samples": n_samples, "hop": hop, "starts": list(range(0, nt, hop)), "chunk_length": frames,
                 "delay": self.get_delay()}
 
-    @torch.no_grad()
+    @_no_grad_frozen("compress")
     def compress(self, audio: torch.Tensor, sample_rate: int = None, win_duration: Optional[float] = 1.0, n_quantizers: int = None, input_db=None,
                  chunks_per_pass: int = None, lengths=None) -> DACFile:
         """CodecMixin.compress (base.py:125-233) for a tensor `audio` of shape (nt,), (channels, nt) or (batch, channels, nt) on the device.
@@ -1138,3 +1210,77 @@ class _EncodeGrad(torch.autograd.Function):
             _native.check(lib.escx_dac_encode_backward(hd, ctypes.c_void_p(flat.data_ptr()), ctx.version, ctypes.c_void_p(tape.data_ptr()), tape.numel(),
                                                        ptr[0], ptr[1], ptr[2], B, L, ctypes.c_void_p(d_audio.data_ptr()), stream))
         return d_audio.to(ctx.x_dtype), None, None, None
+
+
+class _EncodeParamGrad(torch.autograd.Function):
+    """DAC.encode with the gradients of the encoder's and / or the quantiser's parameters (include/escx.h escx_dac_encode_backward_params), for
+    fine-tuning after set_encode_trainable.  forward is `_EncodeGrad`'s: the encode's own launch sequence with its maps kept in a tape on the
+    graph; the audio is saved next to it (the tape does not hold it).  backward returns the gradient of every parameter of the chosen part that
+    requires one and whose quantiser stage the call ran, and of the audio if it requires one (bitwise `_EncodeGrad`'s); autograd accumulates
+    them into p.grad.  With the quantiser chosen the codebook loss carries the codebooks' gradient.  First order only; no atomics.  The input
+    gradients run in set_grad_precision's arithmetic at the time backward is called, the encoder's weight-gradient contractions in
+    set_param_grad_precision's, the quantiser's kernels in fp32.  keys: the names of `params`, in state_dict order."""
+
+    @staticmethod
+    def forward(ctx, audio_data, model, n, counts, keys, *params):
+        lib, hd, flat, dev, stream = model._ctx(audio_data, "audio_data")
+        if not model._padding:
+            raise NotImplementedError("the parameter gradients of DAC.encode are implemented with padding on (the chunked path needs no gradients)")
+        B, L, T = model._audio_shape(audio_data)
+        x = audio_data.detach().to(torch.float32).contiguous()
+        floats = int(lib.escx_dac_encode_tape_floats(hd, B, L, n))
+        if floats < 0:
+            _native.check(floats)
+        if floats < 1:
+            raise RuntimeError(f"libescx gives no tape for an encode of {B} x {L} samples")
+        tape = torch.empty(floats, dtype=torch.float32, device=dev)
+        z = torch.empty(B, model.latent_dim, T, device=dev)
+        codes = torch.empty(B, n, T, dtype=torch.int64, device=dev)
+        latents = torch.empty(B, n * model.codebook_dim, T, device=dev)
+        losses = torch.empty(2, device=dev)
+        version = model._version()
+        cn = (ctypes.c_int32 * B)(*counts) if counts is not None else None
+        with torch.cuda.device(dev):
+            _native.check(lib.escx_dac_encode_tape(hd, ctypes.c_void_p(flat.data_ptr()), version, ctypes.c_void_p(x.data_ptr()), B, L, n, cn,
+                                                   ctypes.c_void_p(z.data_ptr()), ctypes.c_void_p(codes.data_ptr()), ctypes.c_void_p(latents.data_ptr()),
+                                                   ctypes.c_void_p(losses.data_ptr()), ctypes.c_void_p(tape.data_ptr()), floats, stream))
+        cm, cb = losses[0].clone(), losses[1].clone()
+        ctx.save_for_backward(tape, x)
+        ctx.model, ctx.version, ctx.dims, ctx.x_dtype = model, version, (B, L), audio_data.dtype
+        ctx.keys, ctx.stages, ctx.parts = keys, n, _ENCODE_PARTS[model._encode_trainable]
+        if ctx.parts & 2:
+            ctx.mark_non_differentiable(codes)               # the codebook loss is differentiable in the codebooks
+        else:
+            ctx.mark_non_differentiable(codes, cb)
+        ctx.set_materialize_grads(False)                     # an output the loss does not use hands None to backward: a NULL cotangent, not a map of zeros
+        return z, codes, latents, cm, cb
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_z, _d_codes, d_latents, d_cm, d_cb):
+        model, (B, L) = ctx.model, ctx.dims
+        tape, x = ctx.saved_tensors
+        if model._version() != ctx.version:
+            raise RuntimeError("a parameter of the DAC module was changed in place between encode and its backward: the tape was made with the "
+                               "earlier weights (encode again after changing parameters)")
+        lib, hd, flat, dev, stream = model._ctx(tape, "the tape")
+        gs = [None if g is None else g.to(device=dev, dtype=torch.float32).contiguous() for g in (d_z, d_latents, d_cm, d_cb if ctx.parts & 2 else None)]
+        ptr = [None if g is None else ctypes.c_void_p(g.data_ptr()) for g in gs]
+        d_audio = torch.empty(B, 1, L, device=dev) if ctx.needs_input_grad[0] else None
+        grad = torch.empty_like(flat)                        # only the chosen part's slots are written, and only they are read below
+        with torch.cuda.device(dev):
+            _native.check(lib.escx_dac_encode_backward_params(hd, ctypes.c_void_p(flat.data_ptr()), ctx.version, ctypes.c_void_p(tape.data_ptr()), tape.numel(),
+                                                              ctypes.c_void_p(x.data_ptr()), ptr[0], ptr[1], ptr[2], ptr[3], B, L, ctx.parts,
+                                                              None if d_audio is None else ctypes.c_void_p(d_audio.data_ptr()), ctypes.c_void_p(grad.data_ptr()),
+                                                              stream))
+        idx = dev.index if dev.index is not None else torch.cuda.current_device()
+        slots = {key: (off, cnt) for key, off, cnt in model._flat[idx]["layout"]}
+        named = dict(model.named_parameters())
+        grads = []
+        for key, need in zip(ctx.keys, ctx.needs_input_grad[5:]):
+            # a quantiser stage the call did not run is not on the reference's graph: None, not the zeros the library wrote
+            unused = key.startswith("quantizer.quantizers.") and int(key.split(".")[2]) >= ctx.stages
+            off, cnt = slots[key]
+            # views of the one buffer: the slots are disjoint, so the p.grad that autograd makes of them never alias each other
+            grads.append(grad[off:off + cnt].view(named[key].shape) if need and not unused else None)
+        return (None if d_audio is None else d_audio.to(ctx.x_dtype), None, None, None, None, *grads)

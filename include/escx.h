@@ -640,6 +640,41 @@ int escx_dac_encode_tape(escx_dac d, const float* flat_params_dev, int64_t param
  * changes.  The check reads the tape's header back, so the call waits for the stream once. */
 int escx_dac_encode_backward(escx_dac d, const float* flat_params_dev, int64_t params_version, const float* tape_dev, int64_t tape_floats, const float* d_z_dev,
                              const float* d_latents_dev, const float* d_commitment_dev, int batch, int n_samples, float* d_audio_dev, void* stream);
+/* ---- Parameter gradients through the encoder and the quantiser (eval mode, padding on) ----------------------------------------------------------
+ * The gradient of every encoder parameter (bit 0 of `parts`) and every quantiser parameter (bit 1) of DAC.encode (dac.py:209-247) for the encode
+ * that wrote tape_dev, for fine-tuning the whole baseline: Encoder.forward (dac.py:64-91) over EncoderBlock (dac.py:44-61) and ResidualUnit
+ * (dac.py:24-41), and ResidualVectorQuantize.forward in eval mode (nn/quantize.py:173-198) over VectorQuantize.forward (nn/quantize.py:58-70),
+ * differentiated with respect to the weight-normalised layers' bias, weight_g and weight_v (nn/layers.py:5-16), every Snake1d's alpha
+ * (nn/layers.py:19-33) and the codebooks.  The cotangents are escx_dac_encode_backward's d_z, d_latents and d_commitment plus the DEVICE scalar
+ * d_codebook on the codebook loss; each may be NULL (zero).
+ * Quantiser, per latent row (b, t) and stage i < n_b in reverse, with r_0 = z_enc, z_e_i = W_in_i r_i + b_in_i, q_i = C_i[code_i],
+ * r_{i+1} = r_i - (W_out_i q_i + b_out_i), u_i the cotangent of z_q_i and e_i the cotangent of z_e_i as escx_dac_encode_backward forms them:
+ *   dW_out_i = sum_rows u_i q_i^T        db_out_i = sum_rows u_i                                  (quantize.py:58, 69)
+ *   dW_in_i  = sum_rows e_i r_i^T        db_in_i  = sum_rows e_i                                  (quantize.py:58, 186)
+ *   dC_i[c]  = d_codebook * 2 / (batch * codebook_dim * T) * sum_{rows with code_i = c, i < n_b} (q_i - z_e_i)      (quantize.py:62, 66, 189)
+ * then the weight norm's backward on both projections (nn/layers.py:5-10, K = 1).  u_i and r_i are formed per row, one launch per stage, never as
+ * differences of sums over rows; a code's rows are added in increasing row order and a code no row chose gets exactly zero.  The quantiser's
+ * kernels are fp32 in every mode.  z_e_i is the tape's latents; z_enc, which the tape does not hold, is the encoder's last convolution run again
+ * from the last taped map (one layer, the forward's launch in the forward's current escx_dac_set_precision mode); audio_dev (B, n_samples) is the
+ * audio the tape was made from (the tape does not hold it either).
+ * Encoder: escx_dac_encode_backward's walk in its order with its maps; at each layer escx_dac_decode_backward_params' formulas for Conv1d (the strided
+ * convolution reads s(b, t st - p + k, ci)), Snake1d (v = conv^T(dY) kept by the per-phase GEMMs too) and the weight norm; the first convolution
+ * contracts against the staged audio.  escx_dac_set_grad_precision and escx_dac_set_param_grad_precision are honoured by the decoder path's geometry
+ * rules; column sums and the weight norm's dot products accumulate in fp64.
+ * grad_flat_dev has flat_params_dev's layout: the slots of every `encoder.*` parameter (bit 0) and every `quantizer.*` parameter (bit 1) are
+ * OVERWRITTEN - the quantiser stages at or past the tape's stage count with zeros - and no other float is touched.  d_audio_dev may be NULL; when
+ * given it is bitwise what escx_dac_encode_backward writes in the same grad mode.  No atomics: two calls are bitwise equal.  Errors are
+ * escx_dac_encode_backward's, plus ESCX_ERR_INVALID_ARG for a NULL grad_flat_dev or audio_dev and for parts outside 1..3; all are found before the
+ * handle changes.  DESIGN.md section 13.7 has the launch sequence and the workspace. */
+int escx_dac_encode_backward_params(escx_dac d, const float* flat_params_dev, int64_t params_version, const float* tape_dev, int64_t tape_floats,
+                                    const float* audio_dev, const float* d_z_dev, const float* d_latents_dev, const float* d_commitment_dev,
+                                    const float* d_codebook_dev, int batch, int n_samples, int parts, float* d_audio_dev, float* grad_flat_dev, void* stream);
+/* Row slices of the weight-gradient contraction of encoder convolution `layer` (execution order, from 0) for batch x n_samples under the current
+ * escx_dac_set_param_grad_precision mode, the encoder's analogue of escx_dac_param_grad_slices; 0 on a bad argument or with the padding off.
+ * escx_dac_param_grad_workspace_floats counts the encoder's and the quantiser's own workspace (the same three regions, sized over the encoder's
+ * layers and the two projections from the configuration alone) from the first escx_dac_encode_backward_params of the handle on, and its
+ * split-operand partial region from the first such call in that mode on. */
+int escx_dac_encode_param_grad_slices(escx_dac d, int batch, int n_samples, int layer);
 /* Test hook: the kernels' Snake (mode 0: x + sin(alpha x)^2 / (alpha + 1e-9), nn/layers.py:19-24) or tanh (mode 1) over n device values. */
 int escx_dac_test_math(const float* x_dev, const float* alpha_dev, float* out_dev, int64_t n, int mode, void* stream);
 /* Test hook of the backward of DAC.decode (dac.py:249-266): the kernels' Snake derivative (mode 0: 1 + alpha sin(2 alpha x) / (alpha + 1e-9), the
