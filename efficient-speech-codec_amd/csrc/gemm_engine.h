@@ -564,4 +564,15 @@ inline void launch_gemm(const Loader& ld, const float* Wt, int M, int Np, int Kp
     }
 }
 
+// The tile rule of the training-side row GEMMs (train.hip gemm_any, dac_loss.hip): 128-row tiles halve the weight traffic per output row, 64 when the grid
+// would not fill the chip (same rule as gemm_swin.hip); K steps of 16 keep the workgroup's LDS image small (more resident workgroups: 98.0 -> 96.1 ms per
+// ESC training step over the engine's default steps).
+template <class Loader, class Epi>
+inline void launch_gemm_rows(const Loader& ld, const float* Wt, int M, int Np, int Kp, const Epi& ep, hipStream_t s, int force_bk = 0) {
+    const long long tiles128 = (long long)((M + 127) / 128) * ((Np + 95) / 96);
+    if (!force_bk && Kp % 16 == 0) force_bk = 16;
+    if (tiles128 >= 512) launch_gemm<128>(ld, Wt, M, Np, Kp, ep, s, 1, force_bk);
+    else launch_gemm<64>(ld, Wt, M, Np, Kp, ep, s, 1, force_bk);
+}
+
 }  // namespace escx

@@ -114,12 +114,7 @@ void gemm_any(const Ld& ld, const float* W, int M, int Np, int Kp, const Epi& ep
     if constexpr (std::is_same<Ld, PlainA>::value && !epi_is_rowwise<Epi>::value) {
         if (train_x3() && train_x3_shape(Np, Kp)) { launch_gemm_x3(PlainG{ld.A, ld.lda, ld.M, Kp}, W, M, Np, Kp, ep, st); return; }
     }
-    // 128-row tiles halve the weight traffic per output row; 64 when the grid would not fill the chip (same rule as gemm_swin.hip)
-    const long long tiles128 = (long long)((M + 127) / 128) * ((Np + 95) / 96);
-    // K steps of 16 keep the workgroup's LDS image small (more resident workgroups): 98.0 -> 96.1 ms/step over the engine's default steps
-    if (!force_bk && Kp % 16 == 0) force_bk = 16;
-    if (tiles128 >= 512) launch_gemm<128>(ld, W, M, Np, Kp, ep, st, 1, force_bk);
-    else launch_gemm<64>(ld, W, M, Np, Kp, ep, st, 1, force_bk);
+    launch_gemm_rows(ld, W, M, Np, Kp, ep, st, force_bk);        // gemm_engine.h: the 128 / 64-row tile rule and the K step of 16
 }
 template <class Epi>
 void gemm_rows(const float* A, int lda, int M, const float* W, int Np, int Kp, const Epi& ep, hipStream_t st) {

@@ -32,6 +32,12 @@ class EscxDiscConfig(Structure):
                 ("fft_sizes", c_int32 * 8), ("n_bands", c_int32), ("bands", (c_float * 2) * 8), ("rates", c_int32 * 8)]
 
 
+class EscxSpecLossConfig(Structure):
+    """include/escx.h escx_spec_loss_config: one MelSpectrogramLoss / MultiScaleSTFTLoss of the DAC baseline."""
+    _fields_ = [("n_scales", c_int32), ("window", c_int32 * 16), ("n_mels", c_int32 * 16), ("filterbank", c_void_p * 16), ("clamp_eps", c_float), ("pow", c_float),
+                ("mag_weight", c_float), ("log_weight", c_float)]
+
+
 class EscxDacConfig(Structure):
     """include/escx.h escx_dac_config: the DAC baseline codec."""
     _fields_ = [("encoder_dim", c_int32), ("n_encoder_rates", c_int32), ("encoder_rates", c_int32 * 8), ("latent_dim", c_int32),
@@ -172,6 +178,12 @@ SIGNATURES = {
     "escx_dac_encode_backward_params": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                                 c_void_p, c_void_p, c_void_p]),
     "escx_dac_encode_param_grad_slices": (c_int, [c_void_p, c_int, c_int, c_int]),
+    "escx_spec_loss_create": (c_int, [POINTER(EscxSpecLossConfig), c_int, POINTER(c_void_p)]),
+    "escx_spec_loss_destroy": (None, [c_void_p]),
+    "escx_spec_loss_workspace_floats": (c_int64, [c_void_p, c_int, c_int, c_int, c_int]),
+    "escx_spec_loss_eval": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "escx_wave_l1": (c_int, [c_void_p, c_void_p, c_int64, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "escx_sisdr": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     "escx_set_rccl_library": (c_int, [c_char_p]),
     "escx_allgather_codes": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p]),
 }

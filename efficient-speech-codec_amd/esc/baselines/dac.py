@@ -503,6 +503,17 @@ class DAC(nn.Module):
         right_pad = math.ceil(length / self.hop_length) * self.hop_length - length
         return nn.functional.pad(audio_data, (0, right_pad))
 
+    def sample_n_quantizers(self, batch: int, generator: Optional[torch.Generator] = None) -> List[int]:
+        """The reference's training-mode quantiser dropout (nn/quantize.py:166-171) as per-clip counts for encode / forward: the first
+        int(batch * quantizer_dropout) clips get randint(1, n_codebooks + 1), the rest all n_codebooks.  One draw per clip of the batch, as the
+        reference makes them (on the CPU; `generator` seeds it)."""
+        batch = int(batch)
+        if batch < 1:
+            raise ValueError(f"batch must be at least 1, got {batch}")
+        dropout = torch.randint(1, self.n_codebooks + 1, (batch,), generator=generator)
+        n_dropout = int(batch * self.quantizer_dropout)
+        return [int(v) for v in dropout[:n_dropout].tolist()] + [self.n_codebooks] * (batch - n_dropout)
+
     def _n_quantizers(self, n_quantizers):
         if n_quantizers is None:
             return self.n_codebooks

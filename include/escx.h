@@ -681,6 +681,50 @@ int escx_dac_test_math(const float* x_dev, const float* alpha_dev, float* out_de
  * derivative of nn/layers.py:19-24) or the tanh derivative from the output (mode 1: 1 - y^2 of y = x_dev, dac.py:138) over n device values. */
 int escx_dac_test_grad_math(const float* x_dev, const float* alpha_dev, float* out_dev, int64_t n, int mode, void* stream);
 
+/* ---- Training losses of the DAC baseline (baselines/descript/dac/nn/loss.py:11-327) ----------------------------------------
+ * MelSpectrogramLoss and MultiScaleSTFTLoss are one handle type.  A scale is a window (hop = window / 4, periodic hann, center = True with reflect
+ * padding, as audiotools' STFT) and either a filterbank of n_mels rows over the window / 2 + 1 bins (row-major (n_mels, window / 2 + 1) fp32 HOST data,
+ * copied at create: the caller computes it, so fmin / fmax / the mel scale cost nothing here) or n_mels = 0: no filterbank, the STFT loss.  The loss is
+ *   sum over scales of  log_weight * mean |log10(clamp(x, clamp_eps)^pow) - log10(clamp(y, clamp_eps)^pow)|  +  mag_weight * mean |x - y|
+ * with x / y the (mel) magnitudes of the estimate / the reference and the means over clips, frames and bins (nn.L1Loss).  A zero weight skips its term.
+ * The handle owns its DFT and filterbank matrices; several handles may be alive at once and do not see each other.  ESC's own mel loss (HTK filterbanks,
+ * per-clip values, one table per device) is a different loss with its own entry points above.
+ * Spectra of the scales without a filterbank are accumulated in fp64 (the log term's 1 / |S| amplifies the rounding of near-empty bins).
+ * Debugging knob: with ESCX_SPEC_LOSS_F32=1 in the environment when a handle is CREATED, that handle computes those spectra with the fp32 framing GEMM of
+ * the filterbank scales instead (values within 2e-7, gradients up to 7.9 times float32 torch eager's error against float64: DESIGN.md 15.1 is measured
+ * with it).  Not for training runs. */
+#define ESCX_SPEC_LOSS_MAX_SCALES 16
+typedef struct {
+    int32_t n_scales;                                        /* 1 .. ESCX_SPEC_LOSS_MAX_SCALES                     */
+    int32_t window[ESCX_SPEC_LOSS_MAX_SCALES];               /* positive multiples of 4, at most 4096              */
+    int32_t n_mels[ESCX_SPEC_LOSS_MAX_SCALES];               /* 0 = no filterbank                                  */
+    const float* filterbank[ESCX_SPEC_LOSS_MAX_SCALES];      /* host, (n_mels, window / 2 + 1); ignored for n_mels = 0 */
+    float clamp_eps;                                         /* 1e-5                                               */
+    float pow;                                               /* 2.0 (the 16 kHz yml: 1.0)                          */
+    float mag_weight;                                        /* 1.0 (the 16 kHz yml: 0.0)                          */
+    float log_weight;                                        /* 1.0                                                */
+} escx_spec_loss_config;
+typedef struct escx_spec_loss_s* escx_spec_loss;
+/* ESCX_ERR_INVALID_ARG: null pointers, n_scales out of range, a window that is not a positive multiple of 4, n_mels < 0, a missing filterbank,
+ * clamp_eps or pow not positive; ESCX_ERR_UNSUPPORTED: a window above 4096. */
+int escx_spec_loss_create(const escx_spec_loss_config* cfg, int device, escx_spec_loss* out);
+void escx_spec_loss_destroy(escx_spec_loss h);
+/* Floats of per-stream scratch one evaluation of (batch, n_samples) uses (grow-only, shared by the handles of a stream); -1 on a bad argument. */
+int64_t escx_spec_loss_workspace_floats(escx_spec_loss h, int batch, int n_samples, int want_d_est, int want_d_ref);
+/* loss_dev[0] = the loss of est (B, L) against ref (B, L); d_est_dev / d_ref_dev (B, L), each optional, receive d loss / d est and d loss / d ref.  A NULL
+ * gradient pointer launches nothing for that side and does not change the other side's bits.  Every argument is checked before the first launch
+ * (ESCX_ERR_INVALID_ARG: null handle / signal / loss pointer, batch < 1, n_samples <= largest window / 2, another current device than the handle's).
+ * No atomics, fixed summation order: two calls are bitwise equal. */
+int escx_spec_loss_eval(escx_spec_loss h, const float* est_dev, const float* ref_dev, int batch, int n_samples, float* loss_dev, float* d_est_dev,
+                        float* d_ref_dev, void* stream);
+/* L1Loss (loss.py:11-48) over n values: loss_dev[0] = scale * sum |est - ref| (scale = 1 / n is the mean), d_est = scale * sign(est - ref) with
+ * sign(0) = 0, d_ref = -d_est; both gradients optional. */
+int escx_wave_l1(const float* est_dev, const float* ref_dev, int64_t n, float scale, float* loss_dev, float* d_est_dev, float* d_ref_dev, void* stream);
+/* SISDRLoss (loss.py:51-139), per clip in fp64 on the fp32 samples: loss_dev (B,) and the optional unit gradients (B, L) w.r.t. the references (the
+ * reference class's FIRST argument) and the estimates.  has_clip_min = 0: no clip_min; below clip_min the value is clip_min and the gradient zero. */
+int escx_sisdr(const float* references_dev, const float* estimates_dev, int batch, int64_t n_samples, int scaling, int zero_mean, int has_clip_min,
+               float clip_min, float* loss_dev, float* d_references_dev, float* d_estimates_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
