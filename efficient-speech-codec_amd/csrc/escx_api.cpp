@@ -173,11 +173,44 @@ static int run_layer(escx_handle_s* h, const Layer& L, const float* x_in, float*
     for (size_t j = 0; j < L.blocks.size(); ++j) {
         const BlockW& bw = L.blocks[j];
         const int shift = (j % 2 == 0) ? 0 : ws / 2;                          // attention.py:29
-        const int* map;
-        if ((rc = get_map(h, H, W, shift, &map))) return rc;
+        const int* map = nullptr;
+        if (!h->len && (rc = get_map(h, H, W, shift, &map))) return rc;
         const std::string tag = h->prof ? "[C=" + std::to_string(L.C) + "]" : std::string();
         const double dM = M, dMs = Ms, dC = L.C, f4 = sizeof(float);
         bool attn_done = false;
+        if (h->len) {
+            // Mixed-length batch (W = Wmax): the general fused kernel on the batch-wide table of the clips' own windows (fused_attn.h LEN).  The head-group split
+            // follows the padded map's tokens per clip (H * Wmax) and the waves per workgroup change no arithmetic, so a clip's result depends on Wmax and
+            // the mode only.  The packed half-window kernel has no length form (the general kernel runs at H == 2); a width without a fused mode runs the unfused sequence below.
+            LenMap lm;
+            if ((rc = get_len_map(h, *h->len, H, shift, &lm))) return rc;
+            int frc = -1;
+            if (h->use_fused && h->use_fused_attn && L.attn_mode >= 0) {
+                const double dW = 16.0 * lm.n_windows;
+                const int nw = (L.Cp > 192 || (L.Cp == 192 && bw.x3a)) ? 4 : pick_nw(lm.n_windows, attn_windows_per_wave(L.Cp), attn_cap(L.Cp, attn_windows_per_wave(L.Cp)));
+                int gs = attn_gs_for(h, tokens, L.n_groups, L.hiddenP, L.Cp);
+                PROF("attn_fused_len" + tag, 2 * dW * dC * 4 * dC + 4 * dW * 16 * dC, 2 * dW * dC * f4,
+                     frc = attn_fused(src, cur, L.Cp, L.C, L.attn_mode, L.n_groups, bw.ln1_g, bw.ln1_b, bw.waf, bw.baf, bw.bias_tab_f, bw.bproj,
+                                      lm.dev, 0, 0, lm.n_windows, 1, lm.n_windows, shift > 0, 1.0f / std::sqrt((float)L.hd), nw, &gs, h->hid, M, st, nullptr, bw.x3a, x3_nt(h), true));
+                if (frc == 0 && gs > 1)
+                    PROF("attn_combine" + tag, 0, (gs + 2) * dM * L.Cp * f4, rows_combine(cur, src, h->hid, bw.bproj, M, L.Cp, gs, st));
+            }
+            if (frc != 0) {         // no fused mode for this width (or the fused kernels are switched off): the unfused sequence on the same table, flags to the attention core
+                if (h->prof && !h->prof_recs.empty() && h->use_fused && h->use_fused_attn && L.attn_mode >= 0) h->prof_recs.pop_back();
+                const int Msl = 16 * lm.n_windows;
+                const double dW = Msl;
+                PROF("ln1_gather" + tag, 0, 2 * dW * dC * f4, ln_rows(1, src, h->xn, bw.ln1_g, bw.ln1_b, lm.dev, Msl, 0, Msl, L.C, L.Cp, st));
+                PROF("gemm_qkv" + tag, 2 * dW * dC * 3 * dC, (dW * 4 * dC + 3 * dC * dC) * f4,
+                     gemm_qkv(h->xn, L.Cp, Msl, bw.wqkv, L.Nqkv, L.Cp, h->qkv, bw.bqkv, L.nH * L.hdp, 1.0f / std::sqrt((float)L.hd), st));
+                int arc = 0;
+                PROF("window_attn_len" + tag, 4 * dW * 16 * dC, dW * 4 * dC * f4,
+                     arc = window_attention_len(h->qkv, bw.bias_tab, h->obuf, lm.n_windows, L.nH, L.hdp, L.Nqkv, L.Ko, lm.dev + 16 * lm.n_windows, shift > 0, st));
+                if (arc) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "head_dim %d unsupported by the attention kernel", L.hd);
+                PROF("gemm_proj" + tag, 2 * dW * dC * dC, (3 * dW * dC + dC * dC) * f4,
+                     gemm_proj_scatter(h->obuf, L.Ko, Msl, bw.wproj, L.Cp, L.Ko, cur, src, bw.bproj, lm.dev, Msl, 0, st));
+            }
+            attn_done = true;
+        } else
         if (h->use_fused && h->use_fused_attn && L.attn_mode >= 0) {
             int frc = 0;
             int nw = (L.Cp > 192 || (L.Cp == 192 && bw.x3a)) ? 4 : pick_nw(Ms / 16, attn_windows_per_wave(L.Cp), attn_cap(L.Cp, attn_windows_per_wave(L.Cp)));    // 8 waves cap the kernel at 256 VGPRs: spills above C = 192
@@ -286,6 +319,11 @@ static int run_layer(escx_handle_s* h, const Layer& L, const float* x_in, float*
 }
 
 static int run_stft(escx_handle_s* h, const float* wave, int B, int L, int T, float* spec, hipStream_t st) {
+    if (h->len) {       // mixed-length batch: L = row stride of `wave`; clip b reflects about its own last sample and the frames past 1 + L_b / hop are not computed
+        PROF("stft_dft_gemm_len", 2.0 * B * T * h->cfg.win_length * 2 * h->F, ((double)B * L + (double)B * T * 2 * h->F) * 4,
+             gemm_frames_len(wave, h->len->d_L, B, L, T, h->cfg.hop_length, h->left - h->n_fft / 2, h->dft_w, h->cfg.in_dim * h->Fp, h->winP, spec, st));
+        return launch_ok("stft");
+    }
     PROF("stft_dft_gemm", 2.0 * B * T * h->cfg.win_length * 2 * h->F, ((double)B * L + (double)B * T * 2 * h->F) * 4,
          gemm_frames(wave, B, L, T, h->cfg.hop_length, h->left - h->n_fft / 2, h->dft_w, h->cfg.in_dim * h->Fp, h->winP, spec, st));
     return launch_ok("stft");
@@ -392,6 +430,13 @@ extern "C" int escx_set_precision(escx_handle h, int mode) {
 }
 extern "C" int escx_get_precision(escx_handle h) { return h ? h->prec : ESCX_ERR_INVALID_ARG; }
 
+// scale of the per-vector loss terms: mse over (Tq, d) per group, mean over groups.  A mixed-length batch divides by the clip's own frame count in its
+// reduction (loss_reduce_len_kernel), so the terms carry 1 / (d G) only.
+static float pvq_loss_scale(const escx_handle_s* h, const Quant& q, int Tq) {
+    if (h->len) return 1.0f / ((float)q.d * h->cfg.group_size);
+    return 1.0f / ((float)Tq * q.d * h->cfg.group_size);
+}
+
 static int run_pvq_encode(escx_handle_s* h, const Quant& q, const float* enc, const float* dec, int B, int W, long long* codes,
                           long long bstride, float* loss, hipStream_t st) {
     const escx_config& c = h->cfg;
@@ -404,7 +449,7 @@ static int run_pvq_encode(escx_handle_s* h, const Quant& q, const float* enc, co
     int src_rc = 0;
     PROF("pvq_search", 2.0 * M * c.group_size * c.codebook_size * q.d, ((double)c.group_size * c.codebook_size * q.d + (double)M * c.group_size * q.d) * 4,
          src_rc = pvq_search(h->zpart, splits, M, q.Nz, q.cbn, q.c2, q.cbraw, c.group_size, c.codebook_size, q.d, q.dt, Tq, codes, bstride,
-                             loss, 1.0f / ((float)Tq * q.d * c.group_size), c.l2norm, st));
+                             loss, pvq_loss_scale(h, q, Tq), c.l2norm, st));
     if (src_rc) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "codebook_dim %d unsupported by the search kernel", q.d);
     return launch_ok("pvq_encode");
 }
@@ -444,7 +489,7 @@ static int run_pvq_quantize(escx_handle_s* h, const Quant& q, const float* enc, 
         PROF(out ? "pvq_fused" : "pvq_fused_codes", 2.0 * M * vec * q.d * (out ? 2 : 1) + 2.0 * M * c.group_size * c.codebook_size * q.d,
              (double)M * vec * ((dec ? 2 : 1) + (out ? (dec ? 2 : 1) : 0)) * 4,
              frc = pvq_fused(enc, dec, B, q.Hq, W, q.Cp, c.overlap, q.wdf, q.Nz, q.Kq, pvq_down_splits(M, q.Kq, q.Cp), pvq_down_bk(q.Cp), q.cbn, q.c2, q.cbraw,
-                             c.group_size, c.codebook_size, q.d, q.dt, q.wup, q.tab, q.gq, out, codes, bstride, loss, 1.0f / ((float)Tq * q.d * c.group_size), c.l2norm, st));
+                             c.group_size, c.codebook_size, q.d, q.dt, q.wup, q.tab, q.gq, out, codes, bstride, loss, pvq_loss_scale(h, q, Tq), c.l2norm, st));
         if (frc == 0) return launch_ok("pvq_quantize");
         if (h->prof && !h->prof_recs.empty()) h->prof_recs.pop_back();
     }
@@ -457,6 +502,25 @@ static int run_pvq_quantize(escx_handle_s* h, const Quant& q, const float* enc, 
 static int run_deembed(escx_handle_s* h, const float* tok, int B, int W, float* rspec, hipStream_t st) {   // scale.py:73-81
     const escx_config& c = h->cfg;
     const int H0 = c.in_freq / c.patch_f;
+    if (h->len) {
+        // Mixed-length batch: the convolutions zero-pad at the clip's own W_b.  The dead columns of the input are stored as zeros, the composed 7x7 runs on the
+        // padded maps as it is (its interior form is exact up to column W_b - 2), and the border pass recomputes the clip's own last column with the variants.
+        if (h->deembed_two_stage || c.in_dim * h->Q > 16) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "mixed-length batches run the composed de-embedding only (in_dim * patch area <= 16, ESCX_DEEMBED_TWO_STAGE unset)");
+        const double tk = (double)B * H0 * W;
+        PROF("deembed_zero_dead", 0, tk * h->C0p * 4, zero_dead_cols(const_cast<float*>(tok), h->len->d_W, B, H0, W, h->C0p, st));
+        int hrc = -1;
+        if (h->deembed_halo)
+            PROF("deembed_composed7x7", 2.0 * tk * 49 * h->C0 * c.in_dim * h->Q, (tk * h->C0 + tk * c.in_dim * h->Q) * 4,
+                 hrc = deembed7_fused(tok, B, H0, W, h->C0p, h->dch_w, h->dcc_b, rspec, c.patch_f, c.patch_t, c.in_dim, h->Fp, st, h->dch_x2));
+        if (hrc != 0)
+        PROF("deembed_composed7x7", 2.0 * tk * 49 * h->C0 * c.in_dim * h->Q, (tk * h->C0 + tk * c.in_dim * h->Q) * 4,
+             gemm_deembed_composed(tok, B, H0, W, h->C0p, h->dcc_w, rspec, h->dcc_b, c.patch_f, c.patch_t, c.in_dim, h->Fp, st));
+        int brc = 0;
+        PROF("deembed_border_len", 0, 0,
+             brc = deembed_border_len(tok, h->dcv_w, h->dcv_b, rspec, h->len->d_W, B, H0, W, h->C0, h->C0p, c.patch_f, c.patch_t, c.in_dim, h->Fp, st));
+        if (brc != 0) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "mixed-length batches: no border kernel for %d de-embedding outputs", c.in_dim * h->Q);
+        return launch_ok("patch_deembed");
+    }
     if (!h->deembed_two_stage && c.in_dim * h->Q <= 16) {
         const double tk = (double)B * H0 * W;
         int hrc = -1;
@@ -483,6 +547,11 @@ static int run_istft(escx_handle_s* h, const float* rspec, int B, int T2, float*
     const escx_config& c = h->cfg;
     PROF("istft_idft_gemm", 2.0 * B * T2 * c.win_length * 2 * h->F, (double)B * T2 * (2 * h->F + c.win_length) * 4,
          gemm_store(rspec, c.in_dim * h->Fp, B * T2, h->idft_w, h->winP, c.in_dim * h->Fp, h->frames, h->winP, nullptr, st));
+    if (h->len) {       // mixed-length batch: each clip overlap-adds its own patch_t * W_b frames; zeros past hop * (patch_t * W_b - 1)
+        PROF("istft_overlap_add_len", 0, (double)B * T2 * c.win_length * 4 + (double)B * c.hop_length * (T2 - 1) * 4,
+             istft_ola_len(h->frames, h->win2, wave, h->len->d_W, c.patch_t, B, T2, h->winP, c.win_length, c.hop_length, h->left, h->n_fft / 2, c.hop_length * (T2 - 1), st));
+        return launch_ok("istft");
+    }
     PROF("istft_overlap_add", 0, (double)B * T2 * c.win_length * 4 + (double)B * c.hop_length * (T2 - 1) * 4,
          istft_ola(h->frames, h->win2, wave, B, T2, h->winP, c.win_length, c.hop_length, h->left, h->n_fft / 2, c.hop_length * (T2 - 1), st));
     return launch_ok("istft");
@@ -908,6 +977,165 @@ extern "C" int escx_forward_streams(escx_handle h, const float* wave, const floa
     if (recon_feat) PROF("mix_scatter", 0, 2.0 * B * rec_row * 4, rows_permute(recon_ws, recon_feat, maps + B, B, rec_row, st));
     if (cm_loss) PROF("mix_scatter", 0, 8.0 * B, rows_permute(loss_ws, cm_loss, maps + B, B, 1, st));
     return launch_ok("forward_streams");
+}
+
+// ------------------------------------------------------------------------------------------------
+// Mixed-length batches: escx_encode_lengths / escx_decode_lengths / escx_forward_lengths (include/escx.h).  Clip b has L_b samples, i.e. W_b latent
+// columns, and gets what the plain call on x[b, :L_b] alone computes: the batch keeps the padded layout (B, H * Wmax, Cp), every row-wise kernel runs on
+// it unchanged, and the stages that are coupled along time (STFT framing, window attention, de-embedding borders, overlap-add, loss reduction) read the
+// per-clip tables (len_kernels.h, fused_attn.h LEN).  The batch runs as ONE part on the caller's stream, and every variant choice is made from Wmax and the
+// precision mode - never from B or the other lengths - so that a clip's result is a function of its own samples, L_b, Wmax, num_streams and the mode.
+// ------------------------------------------------------------------------------------------------
+namespace {
+struct LenGuard {                   // the context is visible to the launch sequences for the duration of the call only
+    escx_handle_s* h;
+    LenGuard(escx_handle_s* h_, const LenCtx* c) : h(h_) { h->len = c; }
+    ~LenGuard() { h->len = nullptr; }
+};
+}  // namespace
+
+static int len_common_checks(escx_handle_s* h, int B, const int32_t* v, const char* what) {
+    if (h->kind == 1) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "mixed-length batches are not implemented for the rvq+swinT codec (RVQCodecs)");
+    if (h->ws != 4) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "mixed-length batches are implemented for window_size 4 only (this model: %d)", h->ws);
+    if (!v) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null %s pointer", what);
+    if (B < 1) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "batch=%d: the per-clip %s need at least one clip", B, what);
+    return 0;
+}
+
+// samples per clip -> latent widths; every L_b in (n_fft / 2, Lx], every W_b a multiple of `overlap`
+static int plan_lengths(escx_handle_s* h, int B, int Lx, const int32_t* lengths, LenCtx* lc, int* Lmax) {
+    const escx_config& c = h->cfg;
+    lc->B = B; lc->W.assign(B, 0); lc->Wmax = 0; *Lmax = 0;
+    for (int b = 0; b < B; ++b) {
+        const int L = lengths[b];
+        if (L <= h->n_fft / 2 || L > Lx) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "lengths[%d]=%d outside (%d, %d] (reflect padding of %d, row length %d)", b, L, h->n_fft / 2, Lx, h->n_fft / 2, Lx);
+        const int W = frames_of(h, L) / c.patch_t;
+        if (W < 1 || W % c.overlap) ESCX_FAIL(ESCX_ERR_ASSERT, "Time dimension must be multiple of overlap (clip %d: %d samples give %d latent frames)", b, L, W);
+        lc->W[b] = W; lc->Wmax = std::max(lc->Wmax, W); *Lmax = std::max(*Lmax, L);
+    }
+    return 0;
+}
+
+// uploads [W_b | L_b] into the staging buffer (after `extra` bytes of other staging the caller asked for through mb)
+static int upload_lengths(escx_handle_s* h, MixBufs& mb, LenCtx* lc, const int32_t* lengths, hipStream_t st) {
+    int32_t* tab = nullptr;
+    mb.add(&tab, (size_t)2 * lc->B);
+    int rc = mix_alloc(h, mb); if (rc) return rc;
+    ESCX_HIP(hipMemcpyAsync(tab, lc->W.data(), (size_t)lc->B * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    lc->d_W = tab;
+    if (lengths) { ESCX_HIP(hipMemcpyAsync(tab + lc->B, lengths, (size_t)lc->B * sizeof(int32_t), hipMemcpyHostToDevice, st)); lc->d_L = tab + lc->B; }
+    return 0;
+}
+
+extern "C" int escx_encode_lengths(escx_handle h, const float* wave, int B, int Lx, const int32_t* lengths, int S, int64_t* codes, int* fh, int* fw, void* stream) {
+    int rc = check_ready(h); if (rc) return rc;
+    if ((rc = len_common_checks(h, B, lengths, "lengths"))) return rc;
+    if (!wave || !codes) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null pointer");
+    const escx_config& c = h->cfg;
+    if (S < 1 || S > c.max_streams) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "num_streams=%d outside [1, %d]", S, c.max_streams);
+    LenCtx lc; int Lmax = 0;
+    if ((rc = plan_lengths(h, B, Lx, lengths, &lc, &Lmax))) return rc;
+    Shapes s; if ((rc = ensure_ws(h, B, frames_of(h, Lmax), &s, B))) return rc;
+    if (h->sets[0].shp.B < B || h->sets[0].shp.T < s.T) ESCX_FAIL(ESCX_ERR_STATE, "workspace set holds %d clips of %d frames, the batch needs %d of %d", h->sets[0].shp.B, h->sets[0].shp.T, B, s.T);
+    hipStream_t st = (hipStream_t)stream;
+    MixBufs mb; if ((rc = upload_lengths(h, mb, &lc, lengths, st))) return rc;
+    if ((rc = ensure_pvq_tables(h, st))) return rc;
+    use_set(h, 0);
+    LenGuard guard(h, &lc);
+    if ((rc = run_stft(h, wave, B, Lx, s.T, h->spec, st))) return rc;
+    if ((rc = run_encoder(h, s, st))) return rc;
+    if ((rc = run_csvq_encode(h, s, S, (long long*)codes, st))) return rc;
+    PROF("codes_mask_len", 0, 8.0 * B * S * c.group_size * s.Tq, codes_mask_len((const long long*)codes, (long long*)codes, lc.d_W, c.overlap, B, S * c.group_size, s.Tq, -1, st));
+    if ((rc = launch_ok("encode_lengths"))) return rc;
+    if (fh) *fh = s.encH[h->n - 1];
+    if (fw) *fw = s.W;
+    return ESCX_OK;
+}
+
+// widths per clip for decode: each a positive multiple of `overlap`, at most fw
+static int plan_widths(escx_handle_s* h, int B, int fw, const int32_t* widths, LenCtx* lc) {
+    lc->B = B; lc->W.assign(widths, widths + B); lc->Wmax = fw;
+    for (int b = 0; b < B; ++b) {
+        if (widths[b] < 1 || widths[b] > fw) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "frame_lengths[%d]=%d outside [1, %d]", b, widths[b], fw);
+        if (widths[b] % h->cfg.overlap) ESCX_FAIL(ESCX_ERR_ASSERT, "Time dimension must be multiple of overlap (clip %d: %d latent frames)", b, widths[b]);
+    }
+    return 0;
+}
+
+extern "C" int escx_decode_lengths(escx_handle h, const int64_t* codes, int B, int S, const int32_t* widths, int fh, int fw, float* wave_out, float* recon_feat,
+                                   void* stream) {
+    int rc = check_infer_ready(h); if (rc) return rc;
+    if ((rc = len_common_checks(h, B, widths, "frame_lengths"))) return rc;
+    if (!codes || !wave_out) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null pointer");
+    const escx_config& c = h->cfg;
+    if (S < 1 || S > c.max_streams) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "codes.size(1)=%d outside [1, %d]", S, c.max_streams);
+    if (fw < 1 || fw % c.overlap) ESCX_FAIL(ESCX_ERR_ASSERT, "Time dimension must be multiple of overlap");
+    LenCtx lc;
+    if ((rc = plan_widths(h, B, fw, widths, &lc))) return rc;
+    Shapes s; if ((rc = ensure_ws(h, B, frames_for_width(h, fw), &s, B))) return rc;
+    if (h->sets[0].shp.B < B || h->sets[0].shp.T < s.T) ESCX_FAIL(ESCX_ERR_STATE, "workspace set holds %d clips of %d frames, the batch needs %d of %d", h->sets[0].shp.B, h->sets[0].shp.T, B, s.T);
+    if (s.W != fw || s.encH[h->n - 1] != fh) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "feat_shape (%d,%d) does not match the model (%d,%d)", fh, fw, s.encH[h->n - 1], s.W);
+    const int T2 = c.patch_t * fw, Tq = fw / c.overlap;
+    hipStream_t st = (hipStream_t)stream;
+    long long* codes_ws = nullptr;
+    MixBufs mb; mb.add(&codes_ws, (size_t)B * S * c.group_size * Tq);
+    if ((rc = upload_lengths(h, mb, &lc, nullptr, st))) return rc;
+    if ((rc = ensure_pvq_tables(h, st))) return rc;
+    use_set(h, 0);
+    LenGuard guard(h, &lc);
+    // the clip's own code frames are copied; the slots past them are not read (the copy holds code 0 there, which feeds dead tokens only)
+    PROF("codes_mask_len", 0, 16.0 * B * S * c.group_size * Tq, codes_mask_len((const long long*)codes, codes_ws, lc.d_W, c.overlap, B, S * c.group_size, Tq, 0, st));
+    if ((rc = run_csvq_decode(h, codes_ws, B, S, fh, fw, h->rspec, st))) return rc;
+    if ((rc = run_istft(h, h->rspec, B, T2, wave_out, st))) return rc;
+    if (recon_feat) PROF("unpad_len", 0, 2.0 * B * T2 * c.in_dim * h->F * 4, unpad_rows_len(h->rspec, recon_feat, lc.d_W, 1, c.patch_t, c.hop_length, B, T2, c.in_dim, h->F, h->Fp, st));
+    return launch_ok("decode_lengths");
+}
+
+// codecs.py:30-66 in eval mode on a mixed-length batch (forward_impl is the uniform form): raw_feat (B, Tmax, in_dim, F) with Tmax = 1 + max(L_b) / hop
+extern "C" int escx_forward_lengths(escx_handle h, const float* wave, int B, int Lx, const int32_t* lengths, int S, int64_t* codes, float* wave_out,
+                                    float* raw_feat, float* recon_feat, float* cm_loss, void* stream) {
+    int rc = check_infer_ready(h); if (rc) return rc;
+    if ((rc = len_common_checks(h, B, lengths, "lengths"))) return rc;
+    if (!wave || !codes || !wave_out) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null pointer");
+    const escx_config& c = h->cfg;
+    if (S < 1 || S > c.max_streams) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "num_streams=%d outside [1, %d]", S, c.max_streams);
+    LenCtx lc; int Lmax = 0;
+    if ((rc = plan_lengths(h, B, Lx, lengths, &lc, &Lmax))) return rc;
+    Shapes s; if ((rc = ensure_ws(h, B, frames_of(h, Lmax), &s, B))) return rc;
+    if (h->sets[0].shp.B < B || h->sets[0].shp.T < s.T) ESCX_FAIL(ESCX_ERR_STATE, "workspace set holds %d clips of %d frames, the batch needs %d of %d", h->sets[0].shp.B, h->sets[0].shp.T, B, s.T);
+    hipStream_t st = (hipStream_t)stream;
+    MixBufs mb; if ((rc = upload_lengths(h, mb, &lc, lengths, st))) return rc;
+    if ((rc = ensure_pvq_tables(h, st))) return rc;
+    use_set(h, 0);
+    LenGuard guard(h, &lc);
+    const int n = h->n, G = c.group_size;
+    const long long bstride = (long long)S * G * s.Tq, sstride = (long long)G * s.Tq;
+    const int T2 = c.patch_t * s.W;
+    long long* cd = (long long*)codes;
+    if ((rc = run_stft(h, wave, B, Lx, s.T, h->spec, st))) return rc;
+    if (raw_feat) PROF("unpad_len", 0, 2.0 * B * s.T * c.in_dim * h->F * 4, unpad_rows_len(h->spec, raw_feat, lc.d_L, 0, c.patch_t, c.hop_length, B, s.T, c.in_dim, h->F, h->Fp, st));
+    if ((rc = run_encoder(h, s, st))) return rc;
+    const size_t lslot = (size_t)G * B * s.Tq;
+    float* loss = cm_loss ? h->loss_terms : nullptr;
+    int n_slots = 1;
+    int H = s.encH[n - 1], Hn;
+    float* dec = h->decA; float* other = h->decB;
+    if ((rc = run_pvq_quantize(h, h->quants[0], h->enc_hs[n - 1], nullptr, B, s.W, cd, bstride, loss, dec, st))) return rc;
+    for (int i = 0; i + 1 < n; ++i) {
+        if (i < S - 1) {
+            if ((rc = run_pvq_quantize(h, h->quants[i + 1], h->enc_hs[n - 1 - i], dec, B, s.W, cd + (i + 1) * sstride, bstride, loss ? loss + (size_t)(i + 1) * lslot : nullptr, dec, st))) return rc;
+            n_slots = i + 2;
+        }
+        if ((rc = run_layer(h, h->layers[n + i], dec, other, B, H, s.W, &Hn, st))) return rc;
+        std::swap(dec, other); H = Hn;
+    }
+    if ((rc = run_layer(h, h->layers[2 * n - 1], dec, other, B, H, s.W, &Hn, st))) return rc;
+    if ((rc = run_deembed(h, other, B, s.W, h->rspec, st))) return rc;
+    if ((rc = run_istft(h, h->rspec, B, T2, wave_out, st))) return rc;
+    if (recon_feat) PROF("unpad_len", 0, 2.0 * B * T2 * c.in_dim * h->F * 4, unpad_rows_len(h->rspec, recon_feat, lc.d_W, 1, c.patch_t, c.hop_length, B, T2, c.in_dim, h->F, h->Fp, st));
+    if (cm_loss) PROF("loss_reduce_len", 0, (double)n_slots * lslot * 4, loss_reduce_len(loss, lc.d_W, c.overlap, n_slots, G, B, s.Tq, cm_loss, st));
+    PROF("codes_mask_len", 0, 8.0 * B * bstride, codes_mask_len(cd, cd, lc.d_W, c.overlap, B, S * G, s.Tq, -1, st));
+    return launch_ok("forward_lengths");
 }
 
 // ------------------------------------------------------------------------------------------------

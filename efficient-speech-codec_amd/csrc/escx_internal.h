@@ -95,10 +95,21 @@ struct WsFields {                    // one workspace: every scratch buffer of t
     size_t zpart_cap = 0;
 };
 
+// Mixed-length batch in flight (escx_encode_lengths / escx_decode_lengths / escx_forward_lengths): clip b owns the first W[b] latent columns of the padded
+// (B, H * Wmax, Cp) maps.  The launch sequences read it through escx_handle_s::len (null in every other call, which then runs exactly as before).
+struct LenCtx {
+    int B = 0, Wmax = 0;
+    std::vector<int32_t> W;          // host: latent width per clip (the cache key of the attention tables)
+    const int* d_W = nullptr;        // device copies: latent widths, sample counts (null in decode)
+    const int* d_L = nullptr;
+};
+struct LenMap { int* dev = nullptr; int n_windows = 0; };     // [n_windows][16] slot -> absolute token row | [n_windows] flags (fused_attn.h LEN)
+
 }  // namespace escx
 
 struct escx_handle_s;
 namespace escx {
+int get_len_map(escx_handle_s* h, const LenCtx& lc, int H, int shift, LenMap* out);     // cached by (widths, Wmax, H, shift); trimmed with the other maps
 int make_shapes(escx_handle_s* h, int B, int T, Shapes* out);
 int check_infer_ready(escx_handle_s* h);     // check_ready + the folded inference layouts are current (see escx_api.cpp)
 void free_train_state(escx_handle_s* h);     // train.hip: deletes the TrainTape bookkeeping object
@@ -189,6 +200,9 @@ struct escx_handle_s : escx::WsFields {      // the inherited fields are the CUR
 
     // index maps (device), keyed by (H, W, shift) ; shift = -1 -> merge map
     std::map<std::tuple<int, int, int>, int*> maps;
+    // mixed-length batches: the call's context (null outside escx_*_lengths) and the batch-wide attention tables, keyed by ([W_b..., Wmax], H, shift)
+    const escx::LenCtx* len = nullptr;
+    std::map<std::pair<std::vector<int32_t>, std::pair<int, int>>, escx::LenMap> len_maps;
 
     // per-launch HIP-event profiler (escx_profile_*); off by default
     bool prof = false, prof_isolated = false;

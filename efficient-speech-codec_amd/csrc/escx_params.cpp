@@ -228,6 +228,7 @@ extern "C" void escx_destroy(escx_handle h) {
     }
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
     for (auto& kv : h->maps) (void)hipFree(kv.second);
+    for (auto& kv : h->len_maps) (void)hipFree(kv.second.dev);
     if (h->coll_buf) (void)hipFree(h->coll_buf);
     if (h->mix_buf) (void)hipFree(h->mix_buf);
     for (Quant& q : h->quants) if (q.tab) (void)hipFree(q.tab);
@@ -834,6 +835,37 @@ int escx::get_map(escx_handle_s* h, int H, int W, int shift, const int** out) {
     return 0;
 }
 
+// The attention tables of a mixed-length batch (fused_attn.h LEN): get_map's arithmetic clip by clip - the roll runs over the clip's OWN padded width
+// rup(W_b, ws), slots outside its W_b columns are -1, token rows are absolute with row stride Wmax - and one flag word per window: bit 0 = last window
+// row, bit 1 = last window column of its clip (attention.py:56-75: the regions of the shift mask).  Windows past a clip's padded width are not listed.
+int escx::get_len_map(escx_handle_s* h, const LenCtx& lc, int H, int shift, LenMap* out) {
+    std::vector<int32_t> kv(lc.W); kv.push_back(lc.Wmax);
+    auto key = std::make_pair(std::move(kv), std::make_pair(H, shift));
+    auto it = h->len_maps.find(key);
+    if (it != h->len_maps.end()) { *out = it->second; return 0; }
+    const int ws = h->ws, Hp = rup(H, ws), nWh = Hp / ws;
+    int nwin = 0;
+    for (int b = 0; b < lc.B; ++b) nwin += nWh * (rup(lc.W[b], ws) / ws);
+    std::vector<int> m((size_t)nwin * (ws * ws + 1));
+    int win = 0;
+    for (int b = 0; b < lc.B; ++b) {
+        const int Wb = lc.W[b], Wp = rup(Wb, ws), nWw = Wp / ws;
+        for (int wh = 0; wh < nWh; ++wh) for (int ww = 0; ww < nWw; ++ww, ++win) {
+            for (int i = 0; i < ws; ++i) for (int j = 0; j < ws; ++j) {
+                const int sh = (wh * ws + i + shift) % Hp, sw = (ww * ws + j + shift) % Wp;       // roll(-shift) over the clip's padded map
+                m[(size_t)win * ws * ws + i * ws + j] = (sh < H && sw < Wb) ? (b * H + sh) * lc.Wmax + sw : -1;
+            }
+            m[(size_t)nwin * ws * ws + win] = (wh == nWh - 1 ? 1 : 0) | (ww == nWw - 1 ? 2 : 0);
+        }
+    }
+    LenMap lm; lm.n_windows = nwin;
+    ESCX_HIP(hipMalloc((void**)&lm.dev, m.size() * sizeof(int)));
+    ESCX_HIP(hipMemcpy(lm.dev, m.data(), m.size() * sizeof(int), hipMemcpyHostToDevice));
+    h->len_maps[key] = lm;
+    *out = lm;
+    return 0;
+}
+
 extern "C" int64_t escx_workspace_bytes(escx_handle h) {
     int64_t t = 0;
     if (h) for (auto& S : h->sets) t += (int64_t)S.ws.cap;
@@ -890,7 +922,9 @@ static int reserve_frames(escx_handle_s* h, int Btotal, int T, int set_clips_min
         if ((rc = get_map(h, H, s.W, h->ws / 2, &dummy))) return rc;
         if (Ly.scale == 1 && (rc = get_map(h, H, s.W, -1, &dummy))) return rc;
     }
-    if (ws_fits(h, Btotal, T)) return ESCX_OK;
+    bool holds_min = true;          // a caller that runs the whole batch on one set (set_clips_min) needs that many clips per set, not one pass's
+    for (int i = 0; i < sets && set_clips_min; ++i) holds_min = holds_min && h->sets[i].ws.base && h->sets[i].shp.B >= set_clips_min;
+    if (ws_fits(h, Btotal, T) && holds_min) return ESCX_OK;
     // grow only: keep the largest batch and clip length seen so far, so that callers alternating between shapes do not thrash
     if (h->sets[0].ws.base && !(set_clips_min || sets_min)) {
         const int Bs = std::max(B, h->sets[0].shp.B), ns = std::max(sets, h->n_sets), Tt = std::max(T, h->sets[0].shp.T);
@@ -980,10 +1014,12 @@ extern "C" int escx_reserve(escx_handle h, int B, int L) {
 // Called at the start of every entry point, i.e. when no launch sequence of this handle holds a map pointer on the host side.  Dropping every
 // map needs the kernels that read them to have finished.
 static int trim_maps(escx_handle_s* h) {
-    if (h->maps.size() < 768) return 0;
+    if (h->maps.size() < 768 && h->len_maps.size() < 256) return 0;      // a mixed-length batch adds one table per (lengths, H, shift): ~20 per distinct batch
     ESCX_HIP(hipDeviceSynchronize());
     for (auto& kv : h->maps) (void)hipFree(kv.second);
     h->maps.clear();
+    for (auto& kv : h->len_maps) (void)hipFree(kv.second.dev);
+    h->len_maps.clear();
     return 0;
 }
 

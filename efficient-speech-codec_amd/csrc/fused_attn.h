@@ -215,9 +215,14 @@ template <int CP, int MODE, int TMW, int NW, bool X3, int NT, bool PAIR = false>
     return (X3 && NT == 2 && TMW == 1 && CP <= 96 && ((NW == 8 && MODE == 0) || (PAIR && MODE == 1))) ? 4 : attn_min_waves_x<CP, TMW, X3>();
 }
 
-template <int CP, int MODE, int UT, int TMW, int NW, bool TAPE = false, bool X3 = false, int NT = 3, bool PAIR = false>
+// LEN instantiations (mixed-length batches, len_kernels.h): `map` is a BATCH-WIDE table - [n_windows][16] window slot -> absolute token row (or -1) of the
+// live windows of every clip, followed by [n_windows] flags (bit 0: last window row, bit 1: last window column OF ITS CLIP, which is where the shift mask
+// sits) - so a window needs no clip index, `tokens` is unused and windows that hold no token of their clip are not in the table at all.  Everything after
+// the gather is the plain instantiation's code.
+template <int CP, int MODE, int UT, int TMW, int NW, bool TAPE = false, bool X3 = false, int NT = 3, bool PAIR = false, bool LEN = false>
 __global__ __launch_bounds__(64 * NW, (attn_min_waves_f<CP, MODE, TMW, NW, X3, NT, PAIR>())) void attn_fused_kernel(AttnArgs a) {
     static_assert(!X3 || !TAPE, "the split-operand form exists for the plain inference instantiations");
+    static_assert(!LEN || !TAPE, "the length tables exist for the inference instantiations");
     static_assert(!PAIR || (X3 && NT == 2), "paired head groups: the two-term instantiations (attn_x3_pack_kernel)");
     static_assert(NT == 3 || (NT == 2 && X3), "two fp16 terms: the split-operand instantiations");
 #ifdef ESCX_ATTN_PRIO
@@ -275,6 +280,13 @@ __global__ __launch_bounds__(64 * NW, (attn_min_waves_f<CP, MODE, TMW, NW, X3, N
     for (int t = 0; t < TMW; ++t) {
         const int win = win0 + t;
         tok[t] = -1; lastH[t] = false; lastW[t] = false;
+        if constexpr (LEN) {
+            if (win < a.n_windows) {
+                const int fl = a.map[a.n_windows * 16 + win];
+                lastH[t] = (fl & 1) != 0; lastW[t] = (fl & 2) != 0;
+                tok[t] = a.map[win * 16 + l15];
+            }
+        } else
         if (win < a.n_windows) {
             const int b = win / nW, wloc = win - b * nW;
             const int wh = wloc / a.nWw, ww = wloc - wh * a.nWw;

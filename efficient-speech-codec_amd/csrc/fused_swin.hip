@@ -348,13 +348,15 @@ static constexpr bool attn_x3_fused(int Cp, int mode) {
 }
 static int attn_x3_pairing(int Cp, int mode, int n_groups) { return (!attn_x3_fused(Cp, mode) || Cp < 80) ? 0 : (mode == 2 ? 2 : (n_groups % 2 == 0 ? 1 : 0)); }
 
-template <int CP, int MODE, int NW>
+// LEN: the length-table instantiations (fused_attn.h; mixed-length batches).  Same rules, same register budgets, same streams as the plain ones.
+template <int CP, int MODE, int NW, bool LEN = false>
 static int launch_attn(const AttnArgs& a, hipStream_t s, bool pair) {
     constexpr int UT = CP <= 96 ? 4 : (CP <= 192 ? 2 : 1);
     constexpr int TMW = attn_windows_per_wave(CP);
     const int per_block = TMW * NW;
     const int gs = a.GS > 1 ? a.GS : 1;
-    if (a.tape_qkv) {               // training forward (TAPE instantiations for the memory-bound widths; the deep scales keep their GEMMs)
+    if (a.tape_qkv) {
+        if constexpr (LEN) return ESCX_COMB_UNSUPPORTED;               // training forward (TAPE instantiations for the memory-bound widths; the deep scales keep their GEMMs)
         if constexpr (CP == 16 || CP == 48 || CP == 80 || CP == 96) {      // C = 144 / 192 measured: no gain over their GEMM sequence (62.5 vs 62.3-62.6 ms per step)
             if (gs == 1) {
                 ESCX_LAUNCH((attn_fused_kernel<CP, MODE, UT, TMW, NW, true>), dim3((a.n_windows + per_block - 1) / per_block), dim3(64 * NW), 0, s, a);
@@ -366,8 +368,8 @@ static int launch_attn(const AttnArgs& a, hipStream_t s, bool pair) {
     // split-operand (3 x bf16) Q / K / V projections: the (width, head mapping) pairs of the ESC configurations
     if constexpr (attn_x3_fused(CP, MODE)) {
         if (a.x3_wf) {
-            auto kern = attn_fused_kernel<CP, MODE, UT, TMW, NW, false, true>;
-            auto kern2 = attn_fused_kernel<CP, MODE, UT, TMW, NW, false, true, 2>;        // two fp16 terms (split_terms.h)
+            auto kern = attn_fused_kernel<CP, MODE, UT, TMW, NW, false, true, 3, false, LEN>;
+            auto kern2 = attn_fused_kernel<CP, MODE, UT, TMW, NW, false, true, 2, false, LEN>;        // two fp16 terms (split_terms.h)
             constexpr int lds = 2 * UT * attn_x3_tf(CP) * 1024, lds2 = 2 * UT * attn_x3_tf(CP, 2) * 1024;      // the two-term stream is dense
             if constexpr (lds > 48 * 1024) {
                 static std::atomic<unsigned> done{0};
@@ -381,7 +383,7 @@ static int launch_attn(const AttnArgs& a, hipStream_t s, bool pair) {
             }
             if constexpr (CP >= 80) {
                 if (a.x3_scale && pair) {
-                    auto kern2p = attn_fused_kernel<CP, MODE, UT, TMW, NW, false, true, 2, true>;
+                    auto kern2p = attn_fused_kernel<CP, MODE, UT, TMW, NW, false, true, 2, true, LEN>;
                     if constexpr (lds2 > 48 * 1024) {
                         static std::atomic<unsigned> donep{0};
                         int dev = 0; (void)hipGetDevice(&dev);
@@ -398,23 +400,23 @@ static int launch_attn(const AttnArgs& a, hipStream_t s, bool pair) {
             return 0;
         }
     }
-    ESCX_LAUNCH((attn_fused_kernel<CP, MODE, UT, TMW, NW>), dim3(((a.n_windows + per_block - 1) / per_block) * gs), dim3(64 * NW), 0, s, a);
+    ESCX_LAUNCH((attn_fused_kernel<CP, MODE, UT, TMW, NW, false, false, 3, false, LEN>), dim3(((a.n_windows + per_block - 1) / per_block) * gs), dim3(64 * NW), 0, s, a);
     return 0;
 }
 
-template <int CP>
+template <int CP, bool LEN = false>
 static int launch_attn_cp(int mode, int nw, const AttnArgs& a, hipStream_t s, bool pair) {
     if (nw == 8) {
         switch (mode) {
-            case 0: return launch_attn<CP, 0, 8>(a, s, pair);
-            case 1: return launch_attn<CP, 1, 8>(a, s, pair);
-            case 2: return launch_attn<CP, 2, 8>(a, s, pair);
+            case 0: return launch_attn<CP, 0, 8, LEN>(a, s, pair);
+            case 1: return launch_attn<CP, 1, 8, LEN>(a, s, pair);
+            case 2: return launch_attn<CP, 2, 8, LEN>(a, s, pair);
         }
     } else {
         switch (mode) {
-            case 0: return launch_attn<CP, 0, 4>(a, s, pair);
-            case 1: return launch_attn<CP, 1, 4>(a, s, pair);
-            case 2: return launch_attn<CP, 2, 4>(a, s, pair);
+            case 0: return launch_attn<CP, 0, 4, LEN>(a, s, pair);
+            case 1: return launch_attn<CP, 1, 4, LEN>(a, s, pair);
+            case 2: return launch_attn<CP, 2, 4, LEN>(a, s, pair);
         }
     }
     return -1;
@@ -478,7 +480,7 @@ int attn_x3_pack(const float* waf, void* image, int Cp, int mode, int n_groups, 
 int attn_fused(const float* src, float* dst, int Cp, int C, int mode, int n_groups, const float* gamma, const float* beta,
                const float* wf, const float* bqkv, const float* bias_tab, const float* bproj, const int* map, int slots, int tokens,
                int n_windows, int nWh, int nWw, int shifted, float scale, int nw, int* gs_io, float* partial, int rows, hipStream_t s,
-               const AttnTape* tape, const void* x3_wf, int x3_nt) {
+               const AttnTape* tape, const void* x3_wf, int x3_nt, bool len_tables) {
     int gs = gs_io ? *gs_io : 1;        // head-group split: same in/out convention as mlp_fused
     if (gs > 1 && (!partial || n_groups % gs)) gs = 1;
     const int pairing = (!tape && x3_wf && x3_nt == 2) ? attn_x3_pairing(Cp, mode, n_groups) : 0;
@@ -490,6 +492,23 @@ int attn_fused(const float* src, float* dst, int Cp, int C, int mode, int n_grou
                tape ? tape->hdp : 0, tape ? tape->nH : 0, tape ? nullptr : x3_wf,
                (!tape && x3_wf && x3_nt == 2) ? reinterpret_cast<const float*>(attn_x3_trailer(x3_wf, Cp, mode, n_groups) + 16) : nullptr};
     if (tape && nw < 0) return ESCX_COMB_UNSUPPORTED;      // the packed H = 2 form has no tape stores
+    if (len_tables) {       // mixed-length batches: `map` = batch-wide slot table + per-window flags (fused_attn.h LEN); the widths of the ESC configurations; general kernel only
+        if (tape || nw < 0) return ESCX_COMB_UNSUPPORTED;
+        switch (Cp) {
+            case 16: return launch_attn_cp<16, true>(mode, nw, a, s, pairing != 0);
+            case 32: return launch_attn_cp<32, true>(mode, nw, a, s, pairing != 0);
+            case 48: return launch_attn_cp<48, true>(mode, nw, a, s, pairing != 0);
+            case 64: return launch_attn_cp<64, true>(mode, nw, a, s, pairing != 0);
+            case 80: return launch_attn_cp<80, true>(mode, nw, a, s, pairing != 0);
+            case 96: return launch_attn_cp<96, true>(mode, nw, a, s, pairing != 0);
+            case 128: return launch_attn_cp<128, true>(mode, nw, a, s, pairing != 0);
+            case 144: return launch_attn_cp<144, true>(mode, nw, a, s, pairing != 0);
+            case 192: return launch_attn_cp<192, true>(mode, nw, a, s, pairing != 0);
+            case 256: return launch_attn_cp<256, true>(mode, nw, a, s, pairing != 0);
+            case 384: return launch_attn_cp<384, true>(mode, nw, a, s, pairing != 0);
+            default: return -1;
+        }
+    }
     // H == 2 scale with no padding along W: two half-real windows share one tile (nw < 0 encodes "packing allowed", |nw| waves)
     if (nw < 0) {
         nw = -nw;

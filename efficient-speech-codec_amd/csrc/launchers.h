@@ -67,7 +67,8 @@ int attn_fused(const float* src, float* dst, int Cp, int C, int mode, int n_grou
                const float* wf, const float* bqkv, const float* bias_tab, const float* bproj, const int* map, int slots, int tokens,
                int n_windows, int nWh, int nWw, int shifted, float scale, int nw, int* gs_io, float* partial, int rows, hipStream_t s,
                const struct AttnTape* tape = nullptr,
-               const void* x3_wf = nullptr, int x3_nt = 3);     // split weight stream of this block (attn_x3_pack, x3_nt terms: 3 = bf16, 2 = fp16 + scales), nullptr = fp32 MFMA
+               const void* x3_wf = nullptr, int x3_nt = 3,      // split weight stream of this block (attn_x3_pack, x3_nt terms: 3 = bf16, 2 = fp16 + scales), nullptr = fp32 MFMA
+               bool len_tables = false);    // mixed-length batches: map = [n_windows][16] absolute token rows + [n_windows] flags (fused_attn.h LEN), nWh * nWw >= n_windows, tokens unused
 size_t attn_x3_bytes(int Cp, int mode, int n_groups);
 int attn_x3_pack(const float* waf, void* image, int Cp, int mode, int n_groups, hipStream_t s, int nt = 3, const float* gamma = nullptr, const float* beta = nullptr, int C = 0, const float* bqkv = nullptr);   // norm1's gamma / beta and the tile biases (nt == 2: range rule; the output projection in two-term form too)
 // training forward: the fused attention also writes what the backward reads (fused_attn.h, TAPE); returns ESCX_COMB_UNSUPPORTED when the width has
@@ -145,6 +146,18 @@ void codes_permute(const long long* src, long long src_stride, long long* dst, c
 void loss_reduce_streams(const float* terms, long long lslot, const int* S, int cap, const int* slot_clips, int G, int Tq, int B, float* out, hipStream_t s);
 void codes_pack10_streams(const long long* in, unsigned char* out, const long long* off, int B, long long clip_stride, long long n, hipStream_t s);
 void codes_unpack10_streams(const unsigned char* in, long long* out, const long long* off, int B, long long clip_stride, hipStream_t s);
+// mixed-length batches of ESC (len_kernels.h / len_kernels.hip): len = per-clip sample counts, wlen = per-clip latent widths, both on the device
+void gemm_frames_len(const float* wave, const int* len, int B, int L, int T, int hop, int off, const float* W, int Np, int Kp, float* out, hipStream_t s);
+int window_attention_len(const float* qkv, const float* bias, float* out, int total_windows, int nH, int hdp, int ldq, int ldo, const int* flags, int shifted,
+                         hipStream_t s);      // window_attention with the per-window flags of the batch-wide table; -1: head_dim not instantiated
+void zero_dead_cols(float* x, const int* wlen, int B, int H, int W, int Cp, hipStream_t s);
+int deembed_border_len(const float* x, const float* wv, const float* bv, float* out, const int* wlen, int B, int H, int W, int C, int Cp, int pf, int pt,
+                       int in_dim, int Fp, hipStream_t s);
+void istft_ola_len(const float* frames, const float* win2, float* wave, const int* wlen, int pt, int B, int T, int ldf, int win, int hop, int left, int half,
+                   int out_len, hipStream_t s);
+void loss_reduce_len(const float* terms, const int* wlen, int ov, int n_slots, int G, int B, int Tq, float* out, hipStream_t s);
+void codes_mask_len(const long long* src, long long* dst, const int* wlen, int ov, int B, int rows, int Tq, long long fill, hipStream_t s);
+void unpad_rows_len(const float* src, float* dst, const int* len, int per_w, int pt, int hop, int B, int T, int segs, int C, int Cp, hipStream_t s);
 void codes_narrow(const long long* in, short* out, long long n, hipStream_t s);
 void codes_widen(const short* in, long long* out, long long n, hipStream_t s);
 

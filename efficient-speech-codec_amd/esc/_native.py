@@ -68,6 +68,9 @@ SIGNATURES = {
     "escx_encode_streams": (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(c_int32), c_void_p, POINTER(c_int), POINTER(c_int), c_void_p]),
     "escx_decode_streams": (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(c_int32), c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "escx_forward_streams": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(c_int32), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "escx_encode_lengths": (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(c_int32), c_int, c_void_p, POINTER(c_int), POINTER(c_int), c_void_p]),
+    "escx_decode_lengths": (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(c_int32), c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "escx_forward_lengths": (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(c_int32), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "escx_num_frames": (c_int, [c_void_p, c_int]),
     "escx_output_samples": (c_int, [c_void_p, c_int]),
     "escx_spec_transform": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),

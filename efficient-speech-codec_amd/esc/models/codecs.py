@@ -470,15 +470,86 @@ class ESC(nn.Module):
                 raise ValueError(f"num_streams[{b}]={v} outside [1, {self._code_streams}]")
         return out
 
+    # ---- mixed-length batches (include/escx.h escx_encode_lengths) ----------------------------------------
+    _supports_lengths = True            # RVQCodecs: False
+
+    def frame_lengths(self, lengths) -> List[int]:
+        """Latent frames W_b of clips of `lengths` samples: latent_shape(L_b)[1]."""
+        return [self.latent_shape(int(L))[1] for L in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths)]
+
+    def output_lengths(self, frame_lengths) -> List[int]:
+        """Samples decode returns for clips of `frame_lengths` latent frames: hop * (patch_t * W_b - 1)."""
+        pt = self.cfg["patch_size"][1]
+        return [self.hop_length * (pt * int(W) - 1) for W in (frame_lengths.tolist() if isinstance(frame_lengths, torch.Tensor) else frame_lengths)]
+
+    def _check_lengths_call(self, what: str, num_streams=None, x_feat=None):
+        """The refusals of a call with per-clip lengths (none of them needs a device)."""
+        if not self._supports_lengths:
+            raise NotImplementedError(f"{type(self).__name__}: {what} (mixed-length batches) is implemented for ESC (csvq+swinT) only, not for RVQCodecs")
+        if self.cfg["window_size"] != 4:
+            raise NotImplementedError(f"{what} (mixed-length batches) is implemented for window_size 4 only (this model: {self.cfg['window_size']})")
+        if self.training:
+            raise ValueError(f"{what} (mixed-length batches) is an inference feature: call model.eval() first; the training step takes equal-length clips")
+        if num_streams is not None and self._is_per_clip(num_streams):
+            raise NotImplementedError(f"{what} together with per-clip num_streams is not implemented: a mixed-length batch takes one num_streams")
+        if x_feat is not None:
+            raise NotImplementedError(f"{what} together with x_feat is not implemented: a mixed-length batch starts from the waveform")
+
+    @staticmethod
+    def _int_list(values, what: str, B: int) -> List[int]:
+        """A sequence or 1-D integer tensor of B integers -> list; anything else is a ValueError."""
+        if isinstance(values, (str, bytes)) or values is None:
+            raise ValueError(f"{what} must be a sequence or a 1-D integer tensor of {B} values (got {values!r})")
+        if isinstance(values, torch.Tensor):
+            if values.dim() != 1 or values.dtype.is_floating_point or values.dtype.is_complex or values.dtype == torch.bool:
+                raise ValueError(f"{what} must be a 1-D integer tensor (got {values.dtype}, {values.dim()}-D)")
+            vals = values.tolist()
+        else:
+            if int(getattr(values, "ndim", 1)) != 1:
+                raise ValueError(f"{what} must be one-dimensional")
+            try:
+                vals = list(values)
+            except TypeError:
+                raise ValueError(f"{what} must be a sequence or a 1-D integer tensor of {B} values (got {values!r})") from None
+        out = []
+        for v in vals:
+            if isinstance(v, (bool, float)):
+                raise ValueError(f"{what} must be integers (got {v!r})")
+            try:
+                out.append(operator.index(v))
+            except TypeError:
+                raise ValueError(f"{what} must be integers (got {v!r})") from None
+        if len(out) != B:
+            raise ValueError(f"{what} has {len(out)} entries for a batch of {B} clips")
+        return out
+
+    def _sample_lengths(self, lengths, B: int, Lx: int) -> Tuple[List[int], List[int]]:
+        """Per-clip sample counts -> (lengths, latent widths); n_fft // 2 < L_b <= Lx, and every W_b a multiple of `overlap` (the single-clip call's assertion)."""
+        vals = self._int_list(lengths, "lengths", B)
+        half = self.in_freq - 1                         # n_fft // 2 with n_fft = 2 (in_freq - 1): the reflect padding of torch.stft(center=True)
+        for b, L in enumerate(vals):
+            if not half < L <= Lx:
+                raise ValueError(f"lengths[{b}]={L} outside ({half}, {Lx}]: a clip is longer than the reflect padding and no longer than x.shape[1]")
+        widths = [self.latent_shape(L)[1] for L in vals]
+        for b, W in enumerate(widths):
+            if W < 1 or W % self.cfg["overlap"] != 0:
+                raise AssertionError(f"Time dimension must be multiple of overlap (clip {b}: {vals[b]} samples give {W} latent frames)")       # quantization.py:407
+        return vals, widths
+
     # ---- public API (codecs.py:48-94) ---------------------------------------------------------
     @torch.no_grad()
-    def encode(self, x: torch.Tensor, num_streams=6):
+    def encode(self, x: torch.Tensor, num_streams=6, lengths=None):
         """(Bs, L) waveform -> codes (Bs, num_streams, group_size, W/overlap) int64, feat_shape (H, W).
         `num_streams` may also be a length-Bs sequence or 1-D integer tensor of per-clip counts (a mixed-bitrate batch): the codes are then
         (Bs, max(num_streams), group_size, W/overlap) with -1 in the slots past each clip's own count, and clip b's codes equal those of
-        encode(x[b:b+1], num_streams[b])."""
+        encode(x[b:b+1], num_streams[b]).
+        `lengths` (a length-Bs sequence or 1-D integer tensor of sample counts, n_fft // 2 < L_b <= L) makes the batch a mixed-length one: clip b is
+        x[b, :L_b] (what is stored past it is not read) and gets the codes of encode(x[b:b+1, :L_b], num_streams); codes are
+        (Bs, num_streams, group_size, Wmax/overlap) with Wmax = max(frame_lengths(lengths)) and -1 at the frames >= W_b/overlap, feat_shape (H, Wmax)."""
         if x.dim() != 2:
             raise ValueError("x must have shape (Bs, L)")
+        if lengths is not None:
+            return self._encode_lengths(x, num_streams, lengths)
         streams = self._per_clip_streams(num_streams, x.shape[0])
         self._need_gpu(x, "x")
         if streams is not None:
@@ -499,6 +570,24 @@ class ESC(nn.Module):
                                           ctypes.byref(fw), self._stream(x.device)))
         return codes, (fh.value, fw.value)
 
+    def _encode_lengths(self, x: torch.Tensor, num_streams, lengths):
+        self._check_lengths_call("encode(lengths=...)", num_streams)
+        B, Lx = x.shape
+        vals, widths = self._sample_lengths(lengths, B, Lx)
+        self._need_gpu(x, "x")
+        x = x.to(torch.float32).contiguous()
+        H = self.latent_shape(Lx)[0]
+        Wmax = max(widths, default=0)
+        codes = torch.empty((B, int(num_streams), self.cfg["group_size"], Wmax // self.cfg["overlap"]), dtype=torch.int64, device=x.device)
+        if B == 0:
+            return codes, (H, Wmax)
+        lib, hd = self._handle(x.device)
+        fh, fw = ctypes.c_int(), ctypes.c_int()
+        with torch.cuda.device(x.device):
+            _native.check(lib.escx_encode_lengths(hd, x.data_ptr(), B, Lx, (ctypes.c_int32 * B)(*vals), int(num_streams), codes.data_ptr(),
+                                                  ctypes.byref(fh), ctypes.byref(fw), self._stream(x.device)))
+        return codes, (fh.value, fw.value)
+
     def _encode_streams(self, x: torch.Tensor, streams: List[int]):
         x = x.to(torch.float32).contiguous()
         B, L = x.shape
@@ -517,12 +606,17 @@ class ESC(nn.Module):
         return codes, (fh.value, fw.value)
 
     @torch.no_grad()
-    def decode(self, codes: torch.Tensor, feat_shape=(2, 1000), return_feat: bool = False, num_streams=None):
+    def decode(self, codes: torch.Tensor, feat_shape=(2, 1000), return_feat: bool = False, num_streams=None, frame_lengths=None):
         """codes (Bs, num_streams, group_size, *) + feat_shape (H, W) -> waveform (Bs, hop*(2W-1)).
         num_streams=None: every clip carries codes.size(1) streams.  A length-Bs sequence / 1-D integer tensor gives each clip its own
-        count (at most codes.size(1)); the slots at or past it are never read."""
+        count (at most codes.size(1)); the slots at or past it are never read.
+        frame_lengths (a length-Bs sequence / 1-D integer tensor of latent widths W_b, multiples of `overlap`, at most W): a mixed-length batch - clip b
+        is decoded from its own W_b/overlap code frames (the others are never read) as decode(codes[b:b+1, :, :, :W_b/overlap], (H, W_b)) would; its
+        audio is exactly 0 from output_lengths(frame_lengths)[b] on, and the spectrum of return_feat=True is zero past patch_t * W_b frames."""
         if codes.dim() != 4:
             raise ValueError("codes must have shape (Bs, num_streams, group_size, T)")
+        if frame_lengths is not None:
+            return self._decode_lengths(codes, feat_shape, return_feat, num_streams, frame_lengths)
         streams = None
         if num_streams is not None:
             if not self._is_per_clip(num_streams):
@@ -553,9 +647,64 @@ class ESC(nn.Module):
             return out, feat.permute(0, 2, 3, 1)
         return out
 
-    def forward_one_step(self, x, x_feat=None, num_streams=6, freeze_codebook=False):
+    def _decode_lengths(self, codes, feat_shape, return_feat, num_streams, frame_lengths):
+        self._check_lengths_call("decode(frame_lengths=...)", num_streams)
+        if num_streams is not None:
+            raise ValueError("decode(num_streams=...) takes per-clip counts (a sequence or 1-D tensor); a uniform count is codes.size(1)")
+        B, S, G, Tq = codes.shape
+        H, W = int(feat_shape[0]), int(feat_shape[1])
+        ov, pt = self.cfg["overlap"], self.cfg["patch_size"][1]
+        if G != self.cfg["group_size"] or Tq * ov != W:
+            raise ValueError(f"codes shape {tuple(codes.shape)} does not match feat_shape {(H, W)}")
+        widths = self._int_list(frame_lengths, "frame_lengths", B)
+        for b, Wb in enumerate(widths):
+            if not 1 <= Wb <= W:
+                raise ValueError(f"frame_lengths[{b}]={Wb} outside [1, {W}] (feat_shape[1])")
+            if Wb % ov != 0:
+                raise AssertionError(f"Time dimension must be multiple of overlap (clip {b}: {Wb} latent frames)")
+        self._need_gpu(codes, "codes")
+        codes = codes.to(torch.int64).contiguous()
+        out = torch.empty((B, self.hop_length * (pt * W - 1)), dtype=torch.float32, device=codes.device)
+        feat = torch.empty((B, pt * W, self.in_dim, self.in_freq), dtype=torch.float32, device=codes.device) if return_feat else None
+        if B > 0:
+            lib, hd = self._handle(codes.device)
+            with torch.cuda.device(codes.device):
+                _native.check(lib.escx_decode_lengths(hd, codes.data_ptr(), B, S, (ctypes.c_int32 * B)(*widths), H, W, out.data_ptr(),
+                                                      feat.data_ptr() if return_feat else None, self._stream(codes.device)))
+        return (out, feat.permute(0, 2, 3, 1)) if return_feat else out
+
+    def _forward_lengths(self, x, x_feat, num_streams, lengths):
+        """Eval forward of a mixed-length batch (escx_forward_lengths): the composition of encode(lengths=...) and decode(frame_lengths=...).  raw_feat is
+        (Bs, 2, F, Tmax) with Tmax = 1 + max(lengths) // hop and zeros past a clip's own frames; cm_loss / cb_loss are means over a clip's own frames."""
+        self._check_lengths_call("forward(lengths=...)", num_streams, x_feat)
+        if x.dim() != 2:
+            raise ValueError("x must have shape (Bs, L)")
+        B, Lx = x.shape
+        vals, widths = self._sample_lengths(lengths, B, Lx)
+        self._need_gpu(x, "x")
+        xin = x.to(torch.float32).contiguous()
+        dev = xin.device
+        S, pt, ov = int(num_streams), self.cfg["patch_size"][1], self.cfg["overlap"]
+        Wmax = max(widths, default=0)
+        T = 1 + max(vals, default=0) // self.hop_length
+        codes = torch.empty((B, S, self.cfg["group_size"], Wmax // ov), dtype=torch.int64, device=dev)
+        recon = torch.empty((B, max(self.hop_length * (pt * Wmax - 1), 0)), dtype=torch.float32, device=dev)
+        raw_feat = torch.empty((B, T, self.in_dim, self.in_freq), dtype=torch.float32, device=dev)
+        recon_feat = torch.empty((B, pt * Wmax, self.in_dim, self.in_freq), dtype=torch.float32, device=dev)
+        cm = torch.empty((B,), dtype=torch.float32, device=dev)
+        if B > 0:
+            lib, hd = self._handle(dev)
+            with torch.cuda.device(dev):
+                _native.check(lib.escx_forward_lengths(hd, xin.data_ptr(), B, Lx, (ctypes.c_int32 * B)(*vals), S, codes.data_ptr(), recon.data_ptr(),
+                                                       raw_feat.data_ptr(), recon_feat.data_ptr(), cm.data_ptr(), self._stream(dev)))
+        return {"cm_loss": cm, "cb_loss": cm.clone(), "raw_audio": x, "recon_audio": recon,
+                "raw_feat": raw_feat.permute(0, 2, 3, 1), "recon_feat": recon_feat.permute(0, 2, 3, 1), "codes": codes}
+
+    def forward_one_step(self, x, x_feat=None, num_streams=6, freeze_codebook=False, lengths=None):
         if not self.training and freeze_codebook:
             raise ValueError("``freeze_vq`` must be set False during inference")       # quantization.py:43-44
+        if lengths is not None:
+            return self._forward_lengths(x, x_feat, num_streams, lengths)
         if self.training:
             if self._is_per_clip(num_streams):
                 raise ValueError("per-clip num_streams is an inference feature: the training step draws one num_streams per batch "
@@ -643,10 +792,14 @@ class ESC(nn.Module):
         return {"cm_loss": cm, "cb_loss": cb, "raw_audio": x, "recon_audio": recon,
                 "raw_feat": raw_fm.permute(0, 2, 3, 1), "recon_feat": recon_fm.permute(0, 2, 3, 1), "codes": codes}
 
-    def forward(self, x, x_feat, num_streams, freeze_codebook=False):
+    def forward(self, x, x_feat, num_streams, freeze_codebook=False, lengths=None):
         """codecs.py:48-66: dict with cm_loss, cb_loss, raw_audio, recon_audio, raw_feat (Bs,2,F,T), recon_feat (Bs,2,F,T'), codes.
-        Eval mode: inference path, no autograd graph.  Training mode: differentiable (HIP forward + hand-written HIP backward)."""
+        Eval mode: inference path, no autograd graph.  Training mode: differentiable (HIP forward + hand-written HIP backward).
+        lengths (eval mode only): per-clip sample counts of a mixed-length batch, as in encode; see _forward_lengths."""
         num_streams = self.max_streams if freeze_codebook else num_streams
+        if lengths is not None:
+            with torch.no_grad():
+                return self.forward_one_step(x, x_feat, num_streams, freeze_codebook, lengths)
         if self.training:
             return self.forward_one_step(x, x_feat, num_streams, freeze_codebook)
         with torch.no_grad():
@@ -794,6 +947,8 @@ class RVQCodecs(ESC):
     def _code_streams(self) -> int:
         return self._rvq["num_rvqs"]
 
+    _supports_lengths = False           # mixed-length batches: ESC only
+
     def _create_handle(self, lib, idx: int, hd: ctypes.c_void_p):
         rc = _native.EscxRvqConfig()
         rc.base = self._c_config()
@@ -820,16 +975,20 @@ class RVQCodecs(ESC):
         return min(S, self._rvq["num_rvqs"])
 
     @torch.no_grad()
-    def encode(self, x: torch.Tensor, num_streams=6):
+    def encode(self, x: torch.Tensor, num_streams=6, lengths=None):
         """(Bs, L) waveform -> codes (Bs, min(num_streams, num_rvqs), group_size, W/overlap) int64, feat_shape (H, W) (codecs.py:166-171).
-        Per-clip counts as in ESC.encode (each in [1, num_rvqs])."""
+        Per-clip counts as in ESC.encode (each in [1, num_rvqs]).  lengths: NotImplementedError (mixed-length batches are ESC's)."""
+        if lengths is not None:
+            self._check_lengths_call("encode(lengths=...)")
         return super().encode(x, self._streams_arg(num_streams))
 
-    def forward(self, x, x_feat, num_streams, freeze_codebook=False):
+    def forward(self, x, x_feat, num_streams, freeze_codebook=False, lengths=None):
         """codecs.py:127-167.  Eval mode: the ESC dict, codes (Bs, min(num_streams, num_rvqs), group_size, T),
         cm_loss = cb_loss = sum over groups and stages of mse(z_q_i, residual_i).mean([1, 2]) / group_size.
         Training mode (on a HIP device): differentiable like ESC's; every stage runs, so codes is (Bs, num_rvqs, group_size, T), and the stages
         >= num_streams are masked out of the reconstruction and the losses (quantization.py:185-187); freeze_codebook as quantization.py:319-321."""
+        if lengths is not None:
+            self._check_lengths_call("forward(lengths=...)")
         if self.training:
             S = self._streams_arg(num_streams)
             if self._is_per_clip(S):

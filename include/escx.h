@@ -169,6 +169,28 @@ int escx_decode_streams(escx_handle h, const int64_t* codes_dev, int batch, int 
  * cm_loss[b] sums only clip b's own streams. */
 int escx_forward_streams(escx_handle h, const float* wave_dev, const float* feat_dev, int batch, int n_samples_or_frames, const int32_t* streams,
                          int64_t* codes_dev, float* wave_out_dev, float* raw_feat_dev, float* recon_feat_dev, float* cm_loss_dev, void* stream);
+/* Mixed-length batches (csvq+swinT handles, window_size 4): the same three calls with a length PER CLIP.  wave_dev is (B, row_len) f32; `lengths` is a HOST
+ * array of `batch` sample counts, each in (n_fft / 2, row_len]; what is stored at or past lengths[b] in row b is not read.  Clip b has
+ * W_b = (1 + lengths[b] / hop) / patch_t latent frames and gets what the plain call on its own lengths[b] samples computes (same codes under the near-tie
+ * rule of the parity tests, audio within fp32 summation order): the STFT reflects about its last sample, the shifted windows roll over its own padded width,
+ * the de-embedding zero-pads at its own end and the overlap-add normalises its own tail.  A clip's results are a function of its samples, lengths[b],
+ * Wmax = max W_b, num_streams and the precision mode - bit for bit the same in any batch, at any position, next to any other clips of the same Wmax.
+ * A W_b that is no multiple of `overlap` is ESCX_ERR_ASSERT (the message names the clip); a null table, batch < 1 or a length out of range is
+ * ESCX_ERR_INVALID_ARG; rvq+swinT handles and other window sizes are ESCX_ERR_UNSUPPORTED - all before any launch.  The tables are uploaded with every call
+ * and the batch runs as one part on the caller's stream: not meant for graph capture.
+ * ESC.encode (codecs.py:68-81): codes (B, num_streams, G, Wmax / overlap) int64, -1 at the frames at or past W_b / overlap; feat_shape (H_bottom, Wmax). */
+int escx_encode_lengths(escx_handle h, const float* wave_dev, int batch, int row_len, const int32_t* lengths, int num_streams,
+                        int64_t* codes_dev, int* feat_h, int* feat_w, void* stream);
+/* ESC.decode (codecs.py:83-94): `widths` is a HOST array of `batch` latent widths W_b, each a positive multiple of `overlap` and at most feat_w.
+ * wave_out (B, hop * (patch_t * feat_w - 1)) is 0 at and past hop * (patch_t * W_b - 1); recon_feat_dev (optional) has zero frames past patch_t * W_b.
+ * The code frames at or past W_b / overlap are never read. */
+int escx_decode_lengths(escx_handle h, const int64_t* codes_dev, int batch, int num_streams, const int32_t* widths, int feat_h, int feat_w,
+                        float* wave_out_dev, float* recon_feat_dev, void* stream);
+/* ESC.forward in eval mode (codecs.py:30-66, csrvq.py:97-129): outputs as escx_forward at Tmax = 1 + max(lengths) / hop and Wmax; raw_feat_dev (optional) is
+ * (B, Tmax, 2, in_freq) with zero frames past 1 + lengths[b] / hop, codes / wave_out / recon_feat as the two calls above, cm_loss[b] (== cb_loss) the mean
+ * over clip b's own W_b / overlap code frames. */
+int escx_forward_lengths(escx_handle h, const float* wave_dev, int batch, int row_len, const int32_t* lengths, int num_streams,
+                         int64_t* codes_dev, float* wave_out_dev, float* raw_feat_dev, float* recon_feat_dev, float* cm_loss_dev, void* stream);
 int escx_num_frames(escx_handle h, int n_samples);      /* T = 1 + n_samples / hop                      */
 int escx_output_samples(escx_handle h, int feat_w);     /* hop * (patch_t * W - 1)                      */
 
