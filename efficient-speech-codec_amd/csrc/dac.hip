@@ -15,6 +15,8 @@
 // to d_audio, for fine-tuning the whole baseline (dac_param_grad_kernels.h).
 // escx_dac_encode_lengths / escx_dac_from_codes_lengths / escx_dac_decode_lengths are encode, from_codes and decode for a batch with one length per
 // clip (padding on): per-clip length tables in the loader and the epilogue, every clip bitwise its own call.
+// escx_dac_quantize / escx_dac_quantize_backward / escx_dac_quantize_backward_params are the quantiser on a latent the caller brings (quantize.py:127-198)
+// with its gradients, and escx_dac_from_latents is the independent per-codebook search (quantize.py:222-255); DESIGN.md section 13.8.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -1560,6 +1562,37 @@ int enc_layer_rows(const escx_dac_s* d, const EncTapePlan& p, int layer) {
     return k == 6 ? p.Ts[i + 1] : p.Ts[i];
 }
 
+// The quantiser's parameter backward for B x T latent rows and n stages (quantize.py:58-70, 173-198 differentiated; escx.h has the formulas), shared
+// by escx_dac_encode_backward_params and escx_dac_quantize_backward_params: per stage in reverse the row launch, then the two projections'
+// contractions, column sums and weight-norm backward; then the codebooks; then zeros for the stages no clip ran.  zmap is the quantiser's input
+// channels-last - the encoder's last convolution run again, or the staged z of the stand-alone call; gr, U, R are (M, Dp) maps and E, Q (M, dp)
+// maps the launches work in.  lat / codes / counts are the forward's latents, codes and per-clip stage counts on the device.
+struct QParamMaps { const float* zmap; float* gr; float* U; float* R; float* E; float* Q; };
+int quantizer_param_grads(escx_dac_s* d, const ParamWs& w, hipStream_t st, const QParamMaps& m, const float* lat, const long long* codes, const int* counts,
+                          const float* d_z, const float* d_latents, const float* d_commitment, const float* d_codebook, int B, int T, int n, const float* flat,
+                          float* grad) {
+    const int D = d->latent, Dp = cpad(D), dd = d->cfg.codebook_dim, dp = cpad(dd), S = d->cfg.n_codebooks, K = d->cfg.codebook_size;
+    const size_t M = (size_t)B * T;
+    ESCX_HIP(hipMemsetAsync(m.gr, 0, M * Dp * sizeof(float), st));
+    DacQParamArgs qp{};
+    qp.win = d->qt.win; qp.wout = d->qt.wout; qp.bout = d->qt.bout; qp.cbraw = d->qt.cbraw; qp.g_z = d_z; qp.g_lat = d_latents; qp.g_cm = d_commitment;
+    qp.latents = lat; qp.codes = codes; qp.clip_n = counts; qp.zmap = m.zmap; qp.gr = m.gr; qp.U = m.U; qp.R = m.R; qp.E = m.E; qp.Q = m.Q;
+    qp.M = (int)M; qp.T = T; qp.D = D; qp.Dp = Dp; qp.d = dd; qp.dp = dp; qp.K = K; qp.n = n; qp.B = B;
+    for (int i = n - 1; i >= 0; --i) {
+        qp.stage = i;
+        launch_rvq_param_rows(D, (long long)M, qp, st);
+        param_layer(d, w, st, q_layer(d, i, true), m.U, T, m.Q, T, B, flat, grad, false);
+        param_layer(d, w, st, q_layer(d, i, false), m.E, T, m.R, T, B, flat, grad, false);
+    }
+    hipLaunchKernelGGL(dac_codebook_grad_kernel, dim3(nblk((long long)n * K, 4)), dim3(256), 0, st, (const float*)d->qt.cbraw, lat, codes, counts, d_codebook,
+                       (const long long*)(d->qoffs_dev + 6 * (size_t)S), (int)M, T, dd, K, n, B, grad);
+    if (n < S) {                                                // the stages no clip ran: a stage's seven tensors are consecutive, and so are the stages
+        const size_t lo = (size_t)d->qoffs[6 * (size_t)n], hi = (size_t)d->qoffs[6 * (size_t)S + S - 1] + (size_t)K * dd;
+        ESCX_HIP(hipMemsetAsync(grad + lo, 0, (hi - lo) * sizeof(float), st));
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" int escx_dac_encode_param_grad_slices(escx_dac d, int B, int L, int layer) {
@@ -1597,7 +1630,7 @@ extern "C" int escx_dac_encode_backward_params(escx_dac d, const float* flat, in
     const bool enc = parts & 1, qnt = parts & 2;
     const bool walk = enc || d_audio;                           // the encoder's layers are walked for their parameters or for the audio gradient
     const size_t mf = p.mf, M = (size_t)B * p.Tz;
-    const int D = d->latent, Dp = cpad(D), dd = d->cfg.codebook_dim, dp = cpad(dd), S = d->cfg.n_codebooks, K = d->cfg.codebook_size, n = p.n;
+    const int D = d->latent, Dp = cpad(D), dd = d->cfg.codebook_dim, dp = cpad(dd), K = d->cfg.codebook_size, n = p.n;
     const size_t qrow = pad64(M * dp);
     ParamWs w = enc_param_ws_plan(d);
     if ((rc = ensure_scratch(d, (5 * mf + 2 * qrow) * sizeof(float)))) return rc;
@@ -1622,27 +1655,11 @@ extern "C" int escx_dac_encode_backward_params(escx_dac d, const float* flat, in
     }
     if (qnt) {
         // z_enc: the encoder's last convolution again from the last taped map, the forward's launch (the tape does not hold the quantiser's input)
-        float* zmap = d->scratch + 4 * mf; float* Em = d->scratch + 5 * mf; float* Qm = Em + qrow;
-        float* gr = G; float* U = G2; float* R = Sm;
+        float* zmap = d->scratch + 4 * mf; float* Em = d->scratch + 5 * mf;
         const Run frun{d->snake_maps, Sm, st, d->wbuf, d->precision == ESCX_PRECISION_BF16X3 ? d->w16 : nullptr, d->conv_floats, true};
         run_layer(frun, ESCX_DAC_SNAKE_LAST, E[d->enc.size() - 1], SN + d->enc_sn.size() - 1, Mp(7 * nE), B, p.Ts[nE], zmap, p.Tz, nullptr, 0);
-        ESCX_HIP(hipMemsetAsync(gr, 0, M * Dp * sizeof(float), st));
-        DacQParamArgs qp{};
-        qp.win = d->qt.win; qp.wout = d->qt.wout; qp.bout = d->qt.bout; qp.cbraw = d->qt.cbraw; qp.g_z = d_z; qp.g_lat = d_latents; qp.g_cm = d_commitment;
-        qp.latents = lat; qp.codes = codes; qp.clip_n = counts; qp.zmap = zmap; qp.gr = gr; qp.U = U; qp.R = R; qp.E = Em; qp.Q = Qm;
-        qp.M = (int)M; qp.T = p.Tz; qp.D = D; qp.Dp = Dp; qp.d = dd; qp.dp = dp; qp.K = K; qp.n = n; qp.B = B;
-        for (int i = n - 1; i >= 0; --i) {
-            qp.stage = i;
-            launch_rvq_param_rows(D, (long long)M, qp, st);
-            param_layer(d, w, st, q_layer(d, i, true), U, p.Tz, Qm, p.Tz, B, flat, grad, false);
-            param_layer(d, w, st, q_layer(d, i, false), Em, p.Tz, R, p.Tz, B, flat, grad, false);
-        }
-        hipLaunchKernelGGL(dac_codebook_grad_kernel, dim3(nblk((long long)n * K, 4)), dim3(256), 0, st, (const float*)d->qt.cbraw, lat, codes, counts, d_codebook,
-                           (const long long*)(d->qoffs_dev + 6 * (size_t)S), (int)M, p.Tz, dd, K, n, B, grad);
-        if (n < S) {                                            // the stages no clip ran: a stage's seven tensors are consecutive, and so are the stages
-            const size_t lo = (size_t)d->qoffs[6 * (size_t)n], hi = (size_t)d->qoffs[6 * (size_t)S + S - 1] + (size_t)K * dd;
-            ESCX_HIP(hipMemsetAsync(grad + lo, 0, (hi - lo) * sizeof(float), st));
-        }
+        const QParamMaps qm{zmap, G, G2, Sm, Em, Em + qrow};
+        if ((rc = quantizer_param_grads(d, w, st, qm, lat, codes, counts, d_z, d_latents, d_commitment, d_codebook, B, p.Tz, n, flat, grad))) return rc;
     }
     if (!walk) return launch_ok("escx_dac_encode_backward_params");
     // one layer behind a Snake.  With the encoder chosen: its parameter gradients from (dY, snake(xs)), its input gradient with v kept, the Snake's
@@ -1677,6 +1694,189 @@ extern "C" int escx_dac_encode_backward_params(escx_dac d, const float* flat, in
     }
     if (d_audio) bwd_layer(run, E[0], nullptr, G, B, p.Ts[0], L, nullptr, nullptr, d_audio, 1);
     return launch_ok("escx_dac_encode_backward_params");
+}
+
+// ---- the stand-alone quantiser: ResidualVectorQuantize.forward on a latent z (nn/quantize.py:127-198) with its gradients (quantize.py:58-70 under
+// autograd), and ResidualVectorQuantize.from_latents (quantize.py:222-255 over decode_latents, quantize.py:78-94); DESIGN.md section 13.8 ----------
+namespace {
+
+// per-clip frame counts of a quantiser call: each in [1, T].  The quantiser has no convolution, so the padding mode plays no part.
+int check_frame_lengths(const int32_t* fl, int B, int T) {
+    for (int b = 0; b < B; ++b)
+        if (fl[b] < 1 || fl[b] > T) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "frame_lengths[%d]=%d outside [1, %d]", b, fl[b], T);
+    return 0;
+}
+
+// the rows of a quantiser call as the kernels index them: an int row number, a (B, T, Dp) map below 2^31 elements
+int check_rows(const escx_dac_s* d, int B, int T) {
+    if ((unsigned long long)B * T * cpad(d->latent) >= (1ull << 31)) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "batch of %d x %d frames: a latent map above 2^31 elements", B, T);
+    return 0;
+}
+
+// [frame_lengths][clip_n], each optional, in one upload (upload_counts); *fl / *cn point into the device copy or stay nullptr
+int upload_tables(escx_dac_s* d, const int32_t* frame_lengths, const int32_t* clip_n, int B, const int** fl, const int** cn, hipStream_t st) {
+    *fl = *cn = nullptr;
+    if (!frame_lengths && !clip_n) return 0;
+    std::vector<int32_t>& host = d->len_host;
+    host.clear();
+    if (frame_lengths) host.insert(host.end(), frame_lengths, frame_lengths + B);
+    if (clip_n) host.insert(host.end(), clip_n, clip_n + B);
+    const int* dev; int rc = upload_counts(d, host.data(), (int)host.size(), &dev, st); if (rc) return rc;
+    if (frame_lengths) { *fl = dev; dev += B; }
+    if (clip_n) *cn = dev;
+    return 0;
+}
+
+// escx_dac_quantize / _ex / _lengths: the staged z, then the quantiser and loss launches of escx_dac_encode_ex / escx_dac_encode_lengths on it
+int quantize_impl(escx_dac d, const float* flat, int64_t version, const float* z, int B, int T, int n_q, const int32_t* frame_lengths, const int32_t* clip_n,
+                  float* zq, int64_t* codes, float* latents, float* losses, void* stream) {
+    int rc = check_args(d, flat, B); if (rc) return rc;
+    if (!z || !zq || !codes || !latents || !losses || T < 1 || n_q < 1) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "bad argument");
+    if (frame_lengths && (rc = check_frame_lengths(frame_lengths, B, T))) return rc;
+    if (clip_n && n_q > d->cfg.n_codebooks) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "%d code slots above the %d codebooks", n_q, d->cfg.n_codebooks);
+    const int n = std::min(n_q, d->cfg.n_codebooks);
+    if (clip_n && (rc = check_clip_counts(d, clip_n, B, n))) return rc;
+    if ((rc = check_rows(d, B, T))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const int D = d->latent, Dp = cpad(D);
+    const size_t M = (size_t)B * T, zf = pad64(M * Dp);
+    if ((rc = ensure_scratch(d, (zf + pad64((size_t)n * M) + pad64((size_t)n * B)) * sizeof(float)))) return rc;
+    const int* fl; const int* cn; if ((rc = upload_tables(d, frame_lengths, clip_n, B, &fl, &cn, st))) return rc;
+    if ((rc = pack(d, flat, (long long)version, st))) return rc;
+    float* zmap = d->scratch; float* lossb = zmap + zf;
+    if (fl) hipLaunchKernelGGL(dac_z_in_len_kernel, dim3(nblk((long long)M * Dp)), dim3(256), 0, st, z, zmap, B, D, Dp, T, fl);
+    else hipLaunchKernelGGL(dac_z_in_kernel, dim3(nblk((long long)M * Dp)), dim3(256), 0, st, z, zmap, B, D, Dp, T);
+    DacQArgs qa{};
+    qa.t = d->qt; qa.zmap = zmap; qa.z = zq; qa.codes = (long long*)codes; qa.latents = latents; qa.loss = lossb;
+    qa.M = (int)M; qa.T = T; qa.D = D; qa.Dp = Dp; qa.d = d->cfg.codebook_dim; qa.K = d->cfg.codebook_size; qa.n = n;
+    qa.clip_n = cn; qa.frame_len = fl;
+    if (fl && cn) launch_rvq<false, DAC_Q_LEN | DAC_Q_CLIPS>(D, (long long)M, qa, st);
+    else if (fl) launch_rvq<false, DAC_Q_LEN | DAC_Q_PLAIN>(D, (long long)M, qa, st);
+    else if (cn) launch_rvq<false, DAC_Q_CLIPS>(D, (long long)M, qa, st);
+    else launch_rvq<false, DAC_Q_PLAIN>(D, (long long)M, qa, st);
+    if (fl) hipLaunchKernelGGL(dac_loss_len_kernel, dim3(1), dim3(256), 0, st, lossb, lossb + pad64((size_t)n * M), losses, B, T, n, d->cfg.codebook_dim, fl);
+    else hipLaunchKernelGGL(dac_loss_kernel, dim3(1), dim3(256), 0, st, lossb, lossb + pad64((size_t)n * M), losses, B, T, n, d->cfg.codebook_dim);
+    return launch_ok("escx_dac_quantize");
+}
+
+// what both backwards check of the forward's shapes; the per-clip stage counts go to the device as [B] ints (clip_n == NULL: n everywhere)
+int quantize_backward_args(escx_dac d, const float* flat, const float* latents, const int64_t* codes, int B, int T, int n, const int32_t* clip_n) {
+    int rc = check_args(d, flat, B); if (rc) return rc;
+    if (!latents || !codes || T < 1) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "bad argument");
+    if (n < 1 || n > d->cfg.n_codebooks) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "%d code slots outside [1, %d]", n, d->cfg.n_codebooks);
+    if (clip_n && (rc = check_clip_counts(d, clip_n, B, n))) return rc;
+    return check_rows(d, B, T);
+}
+int upload_stage_counts(escx_dac_s* d, const int32_t* clip_n, int B, int n, const int** dev, hipStream_t st) {
+    std::vector<int32_t>& host = d->len_host;
+    if (clip_n) host.assign(clip_n, clip_n + B); else host.assign((size_t)B, n);
+    return upload_counts(d, host.data(), B, dev, st);
+}
+
+void launch_rvq_grad_out(escx_dac_s* d, const float* latents, const int64_t* codes, const int* counts, const float* d_zq, const float* d_latents,
+                         const float* d_commitment, int B, int T, int n, float* A, float* d_z, hipStream_t st) {
+    const int D = d->latent, Dp = cpad(D);
+    DacQGradArgs qa{};
+    qa.win = d->qt.win; qa.wout = d->qt.wout; qa.cbraw = d->qt.cbraw; qa.g_z = d_zq; qa.g_lat = d_latents; qa.g_cm = d_commitment;
+    qa.latents = latents; qa.codes = (const long long*)codes; qa.clip_n = counts; qa.out = A;
+    qa.M = B * T; qa.T = T; qa.D = D; qa.Dp = Dp; qa.d = d->cfg.codebook_dim; qa.K = d->cfg.codebook_size; qa.n = n; qa.B = B;
+    launch_rvq_grad(D, (long long)B * T, qa, st);
+    hipLaunchKernelGGL(dac_z_out_kernel, dim3(nblk((long long)B * D * T)), dim3(256), 0, st, (const float*)A, d_z, B, D, Dp, T);
+}
+
+// escx_dac_from_latents / _ex / _lengths: the independent search, then from_codes' launch on its codes
+int from_latents_impl(escx_dac d, const float* flat, int64_t version, const float* latents, int B, int C, int T, const int32_t* frame_lengths, const int32_t* clip_n,
+                      float* z, float* zp, int64_t* codes, void* stream) {
+    int rc = check_args(d, flat, B); if (rc) return rc;
+    if (!latents || !z || !zp || !codes || T < 1) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "bad argument");
+    const int dd = d->cfg.codebook_dim;
+    if (C < dd) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "latents of %d channels hold no codebook of %d dimensions", C, dd);
+    const int n = std::min(C / dd, d->cfg.n_codebooks);
+    if (frame_lengths && (rc = check_frame_lengths(frame_lengths, B, T))) return rc;
+    if (clip_n && (rc = check_clip_counts(d, clip_n, B, n))) return rc;
+    if ((rc = check_rows(d, B, T))) return rc;
+    if ((unsigned long long)B * C * T >= (1ull << 31)) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "latents of %d x %d x %d: above 2^31 elements", B, C, T);
+    hipStream_t st = (hipStream_t)stream;
+    const int* fl; const int* cn; if ((rc = upload_tables(d, frame_lengths, clip_n, B, &fl, &cn, st))) return rc;
+    if ((rc = pack(d, flat, (long long)version, st))) return rc;
+    const long long M = (long long)B * T;
+    DacSearchArgs sa{};
+    sa.cbn = d->qt.cbn; sa.c2 = d->qt.c2; sa.latents = latents; sa.codes = (long long*)codes; sa.clip_n = cn; sa.frame_len = fl;
+    sa.M = (int)M; sa.T = T; sa.C = C; sa.d = dd; sa.K = d->cfg.codebook_size; sa.n = n;
+    hipLaunchKernelGGL(dac_latent_search_kernel, dim3(nblk(M * n, 4)), dim3(256), 0, st, sa);
+    DacQArgs qa{};
+    qa.t = d->qt; qa.codes_in = (const long long*)codes; qa.z = z; qa.latents = zp;
+    qa.M = (int)M; qa.T = T; qa.D = d->latent; qa.Dp = cpad(d->latent); qa.d = dd; qa.K = d->cfg.codebook_size; qa.n = n;
+    qa.clip_n = cn; qa.frame_len = fl;
+    if (fl && cn) launch_rvq<true, DAC_Q_LEN | DAC_Q_CLIPS>(d->latent, M, qa, st);
+    else if (fl) launch_rvq<true, DAC_Q_LEN | DAC_Q_PLAIN>(d->latent, M, qa, st);
+    else if (cn) launch_rvq<true, DAC_Q_CLIPS>(d->latent, M, qa, st);
+    else launch_rvq<true, DAC_Q_PLAIN>(d->latent, M, qa, st);
+    return launch_ok("escx_dac_from_latents");
+}
+
+}  // namespace
+
+extern "C" int escx_dac_quantize(escx_dac d, const float* flat, int64_t version, const float* z, int B, int T, int n_q, float* zq, int64_t* codes, float* latents,
+                                 float* losses, void* stream) {
+    return quantize_impl(d, flat, version, z, B, T, n_q, nullptr, nullptr, zq, codes, latents, losses, stream);
+}
+extern "C" int escx_dac_quantize_ex(escx_dac d, const float* flat, int64_t version, const float* z, int B, int T, int n_q, const int32_t* clip_n, float* zq,
+                                    int64_t* codes, float* latents, float* losses, void* stream) {
+    return quantize_impl(d, flat, version, z, B, T, n_q, nullptr, clip_n, zq, codes, latents, losses, stream);
+}
+extern "C" int escx_dac_quantize_lengths(escx_dac d, const float* flat, int64_t version, const float* z, int B, int Tmax, const int32_t* frame_lengths, int n_q,
+                                         const int32_t* clip_n, float* zq, int64_t* codes, float* latents, float* losses, void* stream) {
+    if (!frame_lengths) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null frame_lengths");
+    return quantize_impl(d, flat, version, z, B, Tmax, n_q, frame_lengths, clip_n, zq, codes, latents, losses, stream);
+}
+
+extern "C" int escx_dac_quantize_backward(escx_dac d, const float* flat, int64_t version, const float* latents, const int64_t* codes, int B, int T, int n,
+                                          const int32_t* clip_n, const float* d_zq, const float* d_latents, const float* d_commitment, float* d_z, void* stream) {
+    int rc = quantize_backward_args(d, flat, latents, codes, B, T, n, clip_n); if (rc) return rc;
+    if (!d_z) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "bad argument");
+    hipStream_t st = (hipStream_t)stream;
+    if ((rc = ensure_scratch(d, pad64((size_t)B * T * cpad(d->latent)) * sizeof(float)))) return rc;
+    const int* counts; if ((rc = upload_stage_counts(d, clip_n, B, n, &counts, st))) return rc;
+    if ((rc = pack(d, flat, (long long)version, st))) return rc;
+    launch_rvq_grad_out(d, latents, codes, counts, d_zq, d_latents, d_commitment, B, T, n, d->scratch, d_z, st);
+    return launch_ok("escx_dac_quantize_backward");
+}
+
+extern "C" int escx_dac_quantize_backward_params(escx_dac d, const float* flat, int64_t version, const float* z, const float* latents, const int64_t* codes, int B,
+                                                 int T, int n, const int32_t* clip_n, const float* d_zq, const float* d_latents, const float* d_commitment,
+                                                 const float* d_codebook, float* d_z, float* grad, void* stream) {
+    int rc = quantize_backward_args(d, flat, latents, codes, B, T, n, clip_n); if (rc) return rc;
+    if (!z || !grad) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "bad argument");
+    hipStream_t st = (hipStream_t)stream;
+    const int D = d->latent, Dp = cpad(D), dp = cpad(d->cfg.codebook_dim);
+    const size_t M = (size_t)B * T, zf = pad64(M * Dp), qrow = pad64(M * dp);
+    ParamWs w = enc_param_ws_plan(d);
+    if ((rc = ensure_scratch(d, (5 * zf + 2 * qrow) * sizeof(float)))) return rc;
+    if (!d->pwe) ESCX_HIP(hipMalloc((void**)&d->pwe, w.total() * sizeof(float)));
+    w.pw = d->pwe; w.pw16 = d->pwe16;                           // the projections' contractions stay on the fp32 MFMA (param_layer, split_ok false)
+    const int* counts; if ((rc = upload_stage_counts(d, clip_n, B, n, &counts, st))) return rc;
+    if ((rc = pack(d, flat, (long long)version, st))) return rc;
+    float* A = d->scratch; float* zmap = A + zf; float* Em = A + 5 * zf;
+    if (d_z) launch_rvq_grad_out(d, latents, codes, counts, d_zq, d_latents, d_commitment, B, T, n, A, d_z, st);   // escx_dac_quantize_backward's launches
+    hipLaunchKernelGGL(dac_z_in_kernel, dim3(nblk((long long)M * Dp)), dim3(256), 0, st, z, zmap, B, D, Dp, T);
+    const QParamMaps qm{zmap, A + 2 * zf, A + 3 * zf, A + 4 * zf, Em, Em + qrow};
+    if ((rc = quantizer_param_grads(d, w, st, qm, latents, (const long long*)codes, counts, d_zq, d_latents, d_commitment, d_codebook, B, T, n, flat, grad))) return rc;
+    return launch_ok("escx_dac_quantize_backward_params");
+}
+
+extern "C" int escx_dac_from_latents(escx_dac d, const float* flat, int64_t version, const float* latents, int B, int C, int T, float* z, float* zp, int64_t* codes,
+                                     void* stream) {
+    return from_latents_impl(d, flat, version, latents, B, C, T, nullptr, nullptr, z, zp, codes, stream);
+}
+extern "C" int escx_dac_from_latents_ex(escx_dac d, const float* flat, int64_t version, const float* latents, int B, int C, int T, const int32_t* clip_n, float* z,
+                                        float* zp, int64_t* codes, void* stream) {
+    return from_latents_impl(d, flat, version, latents, B, C, T, nullptr, clip_n, z, zp, codes, stream);
+}
+extern "C" int escx_dac_from_latents_lengths(escx_dac d, const float* flat, int64_t version, const float* latents, int B, int C, int Tmax,
+                                             const int32_t* frame_lengths, const int32_t* clip_n, float* z, float* zp, int64_t* codes, void* stream) {
+    if (!frame_lengths) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null frame_lengths");
+    return from_latents_impl(d, flat, version, latents, B, C, Tmax, frame_lengths, clip_n, z, zp, codes, stream);
 }
 
 extern "C" int escx_dac_test_grad_math(const float* x, const float* alpha, float* out, int64_t n, int mode, void* stream) {

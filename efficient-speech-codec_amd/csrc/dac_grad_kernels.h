@@ -206,4 +206,14 @@ __global__ void dac_test_grad_math_kernel(const float* __restrict__ x, const flo
     else out[i] = dac_tanh_grad(x[i]);
 }
 
+// The stand-alone quantiser's d_z (quantize.py:127-198 under autograd, differentiated in its input): dac_rvq_grad_kernel's channels-last
+// (B, T, Dp) gradient map stored in the caller's (B, D, T) layout.  The mirror of dac_z_in_kernel: one thread per output element, the stores
+// coalesced along t; a copy, so no arithmetic and no order to fix.
+__global__ void dac_z_out_kernel(const float* __restrict__ g, float* __restrict__ out, int B, int D, int Dp, int T) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long long)B * D * T) return;
+    const int t = (int)(i % T); const long long bc = i / T; const int c = (int)(bc % D), b = (int)(bc / D);
+    out[i] = g[((size_t)b * T + t) * Dp + c];
+}
+
 }  // namespace escx

@@ -511,4 +511,63 @@ __global__ void dac_z_in_len_kernel(const float* __restrict__ z, float* __restri
     out[i] = (c < D && t < tl[b]) ? z[((size_t)b * D + c) * T + t] : 0.f;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Independent codebook search of ResidualVectorQuantize.from_latents (quantize.py:222-255 over VectorQuantize.decode_latents, quantize.py:78-94):
+// stage i looks up its own d channels of per-codebook latents (B, C, T) that something else predicted; there is no residual chain, so the n stages
+// of a row are n independent searches.  One wave per (stage, latent row) pair, stage-major (wave w: stage w / M, row w % M), so the four waves of
+// a workgroup and its neighbours scan the same codebook.  Every lane reads the row's d channels straight from the (B, C, T) layout (one address
+// per channel across the wave: a broadcast), then repeats dac_rvq_kernel's search on them operation for operation: the normalisation
+// e = z_e / max(||z_e||, 1e-12), dist_k = (sum e^2 - 2 e.c_k) + sum c_k^2 with the dot product as one fma chain over d, the lane-strided scan
+// in which the first minimum stays, the butterfly that prefers the lower index, code 0 when every distance is NaN.  No contraction into fma
+// outside the explicit chain, so the codes are bitwise the ones dac_rvq_kernel emits for the same latents.  No LDS, no atomics.
+// clip_n / frame_len ([B] or nullptr): a slot at or past its clip's stage count, and every slot of a row at or past its clip's frame count, is a
+// wave-uniform early exit that writes -1 and reads nothing.  Only the codes are written: z_p and z_q come from dac_rvq_kernel<.., FROM_CODES>.
+// ------------------------------------------------------------------------------------------------
+struct DacSearchArgs {
+    const float* cbn; const float* c2;      // DacQTables: [S][K][d] normalised rows, [S][K] their squared norms
+    const float* latents;                   // (B, C, T), stage i in the channels [i d, (i + 1) d)
+    long long* codes;                       // (B, n, T)
+    const int* clip_n;                      // [B] stage counts, each in [1, n], or nullptr
+    const int* frame_len;                   // [B] frames per clip, each in [1, T], or nullptr
+    int M, T, C, d, K, n;
+};
+
+__global__ __launch_bounds__(256) void dac_latent_search_kernel(DacSearchArgs a) {
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x & 63;
+    const long long w = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (w >= (long long)a.M * a.n) return;                      // wave-uniform
+    const int i = (int)(w / a.M), row = (int)(w - (long long)i * a.M);
+    const int b = row / a.T, t = row - b * a.T;
+    const int d = a.d, K = a.K;
+    int nb = a.n;                                               // stages of this row (wave-uniform)
+    if (a.clip_n) nb = max(0, min(a.clip_n[b], a.n));
+    if (a.frame_len && t >= a.frame_len[b]) nb = 0;
+    long long* out = a.codes + ((size_t)b * a.n + i) * a.T + t;
+    if (i >= nb) { if (lane == 0) *out = -1; return; }
+    float ze[DAC_DMAX];
+    _Pragma("unroll") for (int jd = 0; jd < DAC_DMAX; ++jd) if (jd < d) ze[jd] = a.latents[((size_t)b * a.C + (size_t)i * d + jd) * a.T + t];
+    float nn = 0.f;
+    _Pragma("unroll") for (int jd = 0; jd < DAC_DMAX; ++jd) if (jd < d) nn += ze[jd] * ze[jd];
+    const float den = fmaxf(sqrtf(nn), 1e-12f);
+    float e[DAC_DMAX], e2 = 0.f;
+    _Pragma("unroll") for (int jd = 0; jd < DAC_DMAX; ++jd) if (jd < d) { e[jd] = ze[jd] / den; e2 += e[jd] * e[jd]; }
+    float bd = INFINITY; int best = 0x7fffffff;
+    const float* cbn = a.cbn + (size_t)i * K * d;
+    const float* c2 = a.c2 + (size_t)i * K;
+    for (int k = lane; k < K; k += 64) {
+        float dot = 0.f;
+        _Pragma("unroll") for (int jd = 0; jd < DAC_DMAX; ++jd) if (jd < d) dot = fmaf(e[jd], cbn[(size_t)k * d + jd], dot);
+        const float dist = (e2 - 2.f * dot) + c2[k];
+        if (dist < bd) { bd = dist; best = k; }                              // k rises per lane: the first minimum stays
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float od = __shfl_xor(bd, o, 64); const int ok = __shfl_xor(best, o, 64);
+        if (od < bd || (od == bd && ok < best)) { bd = od; best = ok; }
+    }
+    if (best == 0x7fffffff) best = 0;                                       // every distance NaN
+    if (lane == 0) *out = best;
+}
+
 }  // namespace escx

@@ -181,7 +181,19 @@ SIGNATURES = {
     "escx_dac_encode_backward_params": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                                 c_void_p, c_void_p, c_void_p]),
     "escx_dac_encode_param_grad_slices": (c_int, [c_void_p, c_int, c_int, c_int]),
-    "escx_spec_loss_create": (c_int, [POINTER(EscxSpecLossConfig), c_int, POINTER(c_void_p)]),
+    "escx_dac_quantize": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "escx_dac_quantize_ex": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, POINTER(c_int32), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "escx_dac_quantize_lengths": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, POINTER(c_int32), c_int, POINTER(c_int32), c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_void_p]),
+    "escx_dac_quantize_backward": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_int32), c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p]),
+    "escx_dac_quantize_backward_params": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_int32), c_void_p, c_void_p,
+                                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "escx_dac_from_latents": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "escx_dac_from_latents_ex": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, POINTER(c_int32), c_void_p, c_void_p, c_void_p, c_void_p]),
+    "escx_dac_from_latents_lengths": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, POINTER(c_int32), POINTER(c_int32), c_void_p, c_void_p,
+                                              c_void_p, c_void_p]),
+    "escx_spec_loss_create":(c_int, [POINTER(EscxSpecLossConfig), c_int, POINTER(c_void_p)]),
     "escx_spec_loss_destroy": (None, [c_void_p]),
     "escx_spec_loss_workspace_floats": (c_int64, [c_void_p, c_int, c_int, c_int, c_int]),
     "escx_spec_loss_eval": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -10,6 +10,11 @@ Fine-tuning (still eval mode): `set_trainable("decoder")` gives `decode` the dec
 `set_encode_trainable("encoder" | "quantizer" | "both")` gives `encode` the encoder's and the quantiser's (`_EncodeParamGrad`), and with both
 `forward(x)` delivers the gradient of every parameter of the model.
 
+The quantiser is callable on its own, as the reference's public `model.quantizer` is: `quantizer(z, n_quantizers)` (quantize.py:127-198)
+snaps a latent the caller brings to the codebooks, with the straight-through gradient in `z` (`_QuantizeGrad`) and, after
+set_encode_trainable("quantizer" | "both"), the quantiser's parameter gradients (`_QuantizeParamGrad`); `quantizer.from_latents(latents)`
+(quantize.py:222-255) searches every codebook independently on per-codebook latents and has no gradient.
+
 Mixed-length batches (not part of the reference's surface): `encode` / `forward` take `lengths`, `decode` / `quantizer.from_codes` take
 `frame_lengths`, one entry per clip; every clip's results are bitwise those of the call on that clip alone.
 
@@ -173,6 +178,7 @@ class DAC(nn.Module):
                     p.copy_(v.flatten(1).norm(dim=1).view(p.shape))
         q = self.quantizer                                           # the reference's `quantizer` holds the parameters and from_codes (quantize.py:200-220)
         q.from_codes, q.n_codebooks, q.codebook_size, q.codebook_dim = self._from_codes, n_codebooks, codebook_size, [codebook_dim] * n_codebooks
+        q.forward, q.from_latents = self._quantize, self._from_latents       # quantizer(z, n_quantizers) and from_latents (quantize.py:127-198, 222-255)
         self._handles, self._flat = {}, {}
         self._precision = "fp32"
         self._grad_precision = "fp32"
@@ -865,6 +871,113 @@ class DAC(nn.Module):
                                                          (ctypes.c_int32 * B)(*counts), ctypes.c_void_p(z.data_ptr()), ctypes.c_void_p(zp.data_ptr()), stream))
         return z, zp, codes
 
+    # ---- the stand-alone quantiser (include/escx.h escx_dac_quantize and its neighbours) ----------------------------------
+    def _quantizer_named(self):
+        return [(k, p) for k, p in self.named_parameters() if k.startswith("quantizer.")]
+
+    def _quantizer_trains(self) -> bool:
+        return (self._encode_trainable in ("quantizer", "both") and torch.is_grad_enabled()
+                and any(p.requires_grad for _, p in self._quantizer_named()))
+
+    def _quantize_call(self, z: torch.Tensor, n: int, counts: Optional[List[int]], fl: Optional[List[int]]):
+        """One escx_dac_quantize / _ex / _lengths call on a checked z: (z_q, codes, latents, losses (2,))."""
+        lib, hd, flat, dev, stream = self._ctx(z, "z")
+        B, _, T = z.shape
+        zc = z.to(torch.float32).contiguous()
+        zq = torch.empty(B, self.latent_dim, T, device=dev)
+        codes = torch.empty(B, n, T, dtype=torch.int64, device=dev)
+        latents = torch.empty(B, n * self.codebook_dim, T, device=dev)
+        losses = torch.empty(2, device=dev)
+        cn = (ctypes.c_int32 * B)(*counts) if counts is not None else None
+        head = (hd, ctypes.c_void_p(flat.data_ptr()), self._version(), ctypes.c_void_p(zc.data_ptr()), B, T)
+        outs = (ctypes.c_void_p(zq.data_ptr()), ctypes.c_void_p(codes.data_ptr()), ctypes.c_void_p(latents.data_ptr()), ctypes.c_void_p(losses.data_ptr()), stream)
+        with torch.cuda.device(dev):
+            if fl is not None:
+                _native.check(lib.escx_dac_quantize_lengths(*head, (ctypes.c_int32 * B)(*fl), n, cn, *outs))
+            elif counts is not None:
+                _native.check(lib.escx_dac_quantize_ex(*head, n, cn, *outs))
+            else:
+                _native.check(lib.escx_dac_quantize(*head, n, *outs))
+        return zq, codes, latents, losses
+
+    def _quantize(self, z: torch.Tensor, n_quantizers: Union[int, Sequence[int], torch.Tensor] = None, frame_lengths=None):
+        """ResidualVectorQuantize.forward in eval mode (quantize.py:127-198) on a latent the caller brings; `model.quantizer(z, n_quantizers)` is this
+        method: (z_q (B, D, T), codes (B, n, T) int64, latents (B, n d, T), commitment_loss, codebook_loss).  z is (B, latent_dim, T); the values
+        are the ones the quantiser inside encode computes from the same map, in every precision mode and whatever `padding` says.  n_quantizers
+        is None, an int (above n_codebooks means n_codebooks) or one count per clip, with encode's semantics and fillers (codes -1, latents 0).
+        frame_lengths (one frame count in [1, T] per clip; not part of the reference's surface) has decode's semantics: nothing at or past a clip's
+        length is read, z_q and latents are 0 and codes -1 there, clip b is bitwise the call on z[b:b+1, :, :frame_lengths[b]] alone and the
+        losses are the mean of the single-clip calls' losses; no gradients with it.
+
+        When gradients are enabled and z requires one, z_q, latents and commitment_loss carry the gradient of the reference's eval-mode autograd:
+        the straight-through estimator per stage and the commitment term against the detached codebook vector (quantize.py:58-70;
+        `_QuantizeGrad`); codes and codebook_loss carry none.  After set_encode_trainable("quantizer" | "both") every quantiser parameter that
+        requires a gradient gets one too - in_proj / out_proj bias, weight_g, weight_v and, through codebook_loss, the codebooks - and a stage
+        no clip runs gets None (`_QuantizeParamGrad`); z.grad is bitwise the frozen path's."""
+        if self.training:
+            raise NotImplementedError("esc.baselines.DAC is inference only: call .eval() (DAC training is not implemented)")
+        if not isinstance(z, torch.Tensor) or z.dim() != 3 or z.shape[1] != self.latent_dim or z.shape[0] < 1 or z.shape[2] < 1:
+            raise ValueError(f"z must be (B, {self.latent_dim}, T) with B, T >= 1, got {tuple(getattr(z, 'shape', ()))}")
+        B, _, T = z.shape
+        counts = self._clip_counts(n_quantizers, B) if self._is_per_clip(n_quantizers) else None
+        n = self._n_quantizers(n_quantizers) if counts is None else max(counts)
+        fl = None if frame_lengths is None else self._clip_lengths(frame_lengths, B, T, "frame_lengths")
+        _check_device(z, "z")
+        wants, trains = torch.is_grad_enabled() and z.requires_grad, self._quantizer_trains()
+        if fl is not None and (wants or trains):
+            raise NotImplementedError("quantizer with frame_lengths is not implemented on the gradient paths (a z that requires grad, or "
+                                      "set_encode_trainable with a quantiser parameter that requires grad): call it under torch.no_grad() or "
+                                      "differentiate clip by clip")
+        if trains:
+            named = self._quantizer_named()
+            return _QuantizeParamGrad.apply(z, self, n, counts, tuple(k for k, _ in named), *[p for _, p in named])
+        if wants:
+            return _QuantizeGrad.apply(z, self, n, counts)
+        with torch.no_grad():
+            zq, codes, latents, losses = self._quantize_call(z, n, counts, fl)
+        return zq, codes, latents, losses[0], losses[1]
+
+    @torch.no_grad()
+    def _from_latents(self, latents: torch.Tensor, n_quantizers: Union[int, Sequence[int], torch.Tensor] = None, frame_lengths=None):
+        """ResidualVectorQuantize.from_latents (quantize.py:222-255): per-codebook latents (B, C, T) that something else predicted ->
+        (z_q (B, D, T), z_p (B, n d, T), codes (B, n, T) int64); `model.quantizer.from_latents` is this method.  n = min(C // codebook_dim,
+        n_codebooks); trailing channels that fill no codebook are ignored and C < codebook_dim raises ValueError.  Every stage searches its own d
+        channels independently (VectorQuantize.decode_latents, quantize.py:78-94), so the codes are bitwise the ones quantizer(z) emits for the
+        same latents, and (z_q, z_p) are bitwise from_codes(codes)[:2].  n_quantizers (an int or one count per clip, each at most n) and
+        frame_lengths are this port's extensions, as on from_codes: a stage slot past a clip's count holds code -1 and z_p 0, and the rows at or
+        past a clip's frames hold 0 / -1 and are not read.  The search has no gradient in the reference and none here: the outputs never carry a
+        grad_fn, and parameter gradients through from_latents are not built (train the quantiser through quantizer(z) or encode)."""
+        if self.training:
+            raise NotImplementedError("esc.baselines.DAC is inference only: call .eval() (DAC training is not implemented)")
+        if not isinstance(latents, torch.Tensor) or latents.dim() != 3 or latents.shape[0] < 1 or latents.shape[2] < 1:
+            raise ValueError(f"latents must be (B, C, T) with B, T >= 1, got {tuple(getattr(latents, 'shape', ()))}")
+        B, C, T = latents.shape
+        if C < self.codebook_dim:
+            raise ValueError(f"latents of {C} channels hold no codebook of {self.codebook_dim} dimensions")
+        n = min(C // self.codebook_dim, self.n_codebooks)
+        counts = None
+        if n_quantizers is not None:
+            counts = self._clip_counts(n_quantizers if self._is_per_clip(n_quantizers) else [n_quantizers] * B, B)
+            if max(counts) > n:
+                raise ValueError(f"per-clip n_quantizers up to {max(counts)} for latents of {n} codebooks")
+        fl = None if frame_lengths is None else self._clip_lengths(frame_lengths, B, T, "frame_lengths")
+        lib, hd, flat, dev, stream = self._ctx(latents, "latents")
+        lc = latents.to(torch.float32).contiguous()
+        z = torch.empty(B, self.latent_dim, T, device=dev)
+        zp = torch.empty(B, n * self.codebook_dim, T, device=dev)
+        codes = torch.empty(B, n, T, dtype=torch.int64, device=dev)
+        cn = (ctypes.c_int32 * B)(*counts) if counts is not None else None
+        head = (hd, ctypes.c_void_p(flat.data_ptr()), self._version(), ctypes.c_void_p(lc.data_ptr()), B, C, T)
+        outs = (ctypes.c_void_p(z.data_ptr()), ctypes.c_void_p(zp.data_ptr()), ctypes.c_void_p(codes.data_ptr()), stream)
+        with torch.cuda.device(dev):
+            if fl is not None:
+                _native.check(lib.escx_dac_from_latents_lengths(*head, (ctypes.c_int32 * B)(*fl), cn, *outs))
+            elif counts is not None:
+                _native.check(lib.escx_dac_from_latents_ex(*head, cn, *outs))
+            else:
+                _native.check(lib.escx_dac_from_latents(*head, *outs))
+        return z, zp, codes
+
     def forward(self, audio_data: torch.Tensor, sample_rate: int = None, n_quantizers: Union[int, Sequence[int], torch.Tensor] = None, lengths=None):
         """dac.py:268-323 in eval mode: right-pad to a multiple of the hop, encode, decode, trim the audio to the input length.  n_quantizers
         may be one count per clip, as in encode.  lengths (one sample count in [1, L] per clip): every clip goes through the reference's
@@ -1295,3 +1408,90 @@ class _EncodeParamGrad(torch.autograd.Function):
             # views of the one buffer: the slots are disjoint, so the p.grad that autograd makes of them never alias each other
             grads.append(grad[off:off + cnt].view(named[key].shape) if need and not unused else None)
         return (None if d_audio is None else d_audio.to(ctx.x_dtype), None, None, None, None, *grads)
+
+
+def _quantize_forward(ctx, z, model, n, counts):
+    """The forward both quantiser Functions share: escx_dac_quantize / _ex, with what the backward reads kept on ctx.  There is no tape: the
+    backward's operands are the forward's own latents and codes, saved as they are."""
+    zq, codes, latents, losses = model._quantize_call(z.detach(), n, counts, None)
+    cm, cb = losses[0].clone(), losses[1].clone()
+    ctx.model, ctx.version, ctx.counts, ctx.z_dtype = model, model._version(), counts, z.dtype
+    ctx.set_materialize_grads(False)                         # an output the loss does not use hands None to backward: a NULL cotangent, not a map of zeros
+    return zq, codes, latents, cm, cb
+
+
+def _quantize_backward_args(ctx, latents, codes, cotangents):
+    """(lib, hd, flat, dev, stream, B, T, n, clip_n, pointers of the cotangents) of a quantiser backward, after the parameter-version check."""
+    model = ctx.model
+    if model._version() != ctx.version:
+        raise RuntimeError("a parameter of the DAC module was changed in place between quantizer(z) and its backward: the latents and codes were "
+                           "made with the earlier weights (quantise again after changing parameters)")
+    lib, hd, flat, dev, stream = model._ctx(latents, "the latents")
+    B, n, T = codes.shape
+    gs = [None if g is None else g.to(device=dev, dtype=torch.float32).contiguous() for g in cotangents]
+    cn = (ctypes.c_int32 * B)(*ctx.counts) if ctx.counts is not None else None
+    return lib, hd, flat, dev, stream, B, T, n, cn, gs, [None if g is None else ctypes.c_void_p(g.data_ptr()) for g in gs]
+
+
+class _QuantizeGrad(torch.autograd.Function):
+    """model.quantizer(z) with the latent gradient (include/escx.h escx_dac_quantize / escx_dac_quantize_backward): the reference's eval-mode
+    autograd through the residual quantiser (quantize.py:58-70, 173-198).  z_q, latents and the commitment loss are differentiable; the codes are
+    integers and the codebook loss detaches z_e.  backward is one launch of the encoder path's quantiser backward on the forward's own latents
+    and codes, then the store into z's layout; first order only, fp32 VALU, no atomics.  counts: one stage count per clip, or None."""
+
+    @staticmethod
+    def forward(ctx, z, model, n, counts):
+        zq, codes, latents, cm, cb = _quantize_forward(ctx, z, model, n, counts)
+        ctx.save_for_backward(latents, codes)
+        ctx.mark_non_differentiable(codes, cb)
+        return zq, codes, latents, cm, cb
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_zq, _d_codes, d_latents, d_cm, _d_cb):
+        latents, codes = ctx.saved_tensors
+        lib, hd, flat, dev, stream, B, T, n, cn, _gs, ptr = _quantize_backward_args(ctx, latents, codes, (d_zq, d_latents, d_cm))
+        d_z = torch.empty(B, ctx.model.latent_dim, T, device=dev)
+        with torch.cuda.device(dev):
+            _native.check(lib.escx_dac_quantize_backward(hd, ctypes.c_void_p(flat.data_ptr()), ctx.version, ctypes.c_void_p(latents.data_ptr()),
+                                                         ctypes.c_void_p(codes.data_ptr()), B, T, n, cn, ptr[0], ptr[1], ptr[2],
+                                                         ctypes.c_void_p(d_z.data_ptr()), stream))
+        return d_z.to(ctx.z_dtype), None, None, None
+
+
+class _QuantizeParamGrad(torch.autograd.Function):
+    """model.quantizer(z) with the gradients of the quantiser's parameters (include/escx.h escx_dac_quantize_backward_params), after
+    set_encode_trainable("quantizer" | "both"): `_EncodeParamGrad`'s quantiser block on the staged z.  backward returns the gradient of every
+    quantiser parameter that requires one and whose stage the call ran, and of z if it requires one (bitwise `_QuantizeGrad`'s); the codebook
+    loss carries the codebooks' gradient.  First order only; no atomics.  keys: the names of `params`, in state_dict order."""
+
+    @staticmethod
+    def forward(ctx, z, model, n, counts, keys, *params):
+        zq, codes, latents, cm, cb = _quantize_forward(ctx, z, model, n, counts)
+        ctx.save_for_backward(latents, codes, z.detach().to(torch.float32).contiguous())
+        ctx.keys, ctx.stages = keys, n
+        ctx.mark_non_differentiable(codes)                   # the codebook loss is differentiable in the codebooks
+        return zq, codes, latents, cm, cb
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_zq, _d_codes, d_latents, d_cm, d_cb):
+        latents, codes, zc = ctx.saved_tensors
+        model = ctx.model
+        lib, hd, flat, dev, stream, B, T, n, cn, _gs, ptr = _quantize_backward_args(ctx, latents, codes, (d_zq, d_latents, d_cm, d_cb))
+        d_z = torch.empty(B, model.latent_dim, T, device=dev) if ctx.needs_input_grad[0] else None
+        grad = torch.empty_like(flat)                        # only the quantiser's slots are written, and only they are read below
+        with torch.cuda.device(dev):
+            _native.check(lib.escx_dac_quantize_backward_params(hd, ctypes.c_void_p(flat.data_ptr()), ctx.version, ctypes.c_void_p(zc.data_ptr()),
+                                                                ctypes.c_void_p(latents.data_ptr()), ctypes.c_void_p(codes.data_ptr()), B, T, n, cn,
+                                                                ptr[0], ptr[1], ptr[2], ptr[3], None if d_z is None else ctypes.c_void_p(d_z.data_ptr()),
+                                                                ctypes.c_void_p(grad.data_ptr()), stream))
+        idx = dev.index if dev.index is not None else torch.cuda.current_device()
+        slots = {key: (off, cnt) for key, off, cnt in model._flat[idx]["layout"]}
+        named = dict(model.named_parameters())
+        grads = []
+        for key, need in zip(ctx.keys, ctx.needs_input_grad[5:]):
+            # a stage the call did not run is not on the reference's graph: None, not the zeros the library wrote
+            off, cnt = slots[key]
+            grads.append(grad[off:off + cnt].view(named[key].shape) if need and int(key.split(".")[2]) < ctx.stages else None)
+        return (None if d_z is None else d_z.to(ctx.z_dtype), None, None, None, None, *grads)

@@ -697,6 +697,63 @@ int escx_dac_encode_backward_params(escx_dac d, const float* flat_params_dev, in
  * layers and the two projections from the configuration alone) from the first escx_dac_encode_backward_params of the handle on, and its
  * split-operand partial region from the first such call in that mode on. */
 int escx_dac_encode_param_grad_slices(escx_dac d, int batch, int n_samples, int layer);
+/* ---- The stand-alone quantiser: latent in, codes out (eval mode) -----------------------------------------------------------
+ * ResidualVectorQuantize.forward on a latent the caller brings (nn/quantize.py:127-198 over VectorQuantize.forward, quantize.py:58-70), the public
+ * `model.quantizer(z, n_quantizers)` of the reference: z (B, D, T) device -> z_q (B, D, T), codes (B, n, T), latents (B, n * codebook_dim, T),
+ * losses[2] = (commitment_loss, codebook_loss) on the device; n = min(n_quantizers, n_codebooks).  z is staged channels-last as escx_dac_decode stages
+ * it and the quantiser and loss launches are escx_dac_encode's, so every value is the one the quantiser inside escx_dac_encode computes from the same
+ * map.  The quantiser is fp32 in every precision mode and has no convolution: the result depends on neither escx_dac_set_precision nor
+ * escx_dac_set_padding.  ESCX_ERR_INVALID_ARG (null pointer, batch < 1, n_frames < 1, n_quantizers < 1) leaves the handle usable. */
+int escx_dac_quantize(escx_dac d, const float* flat_params_dev, int64_t params_version, const float* z_dev, int batch, int n_frames, int n_quantizers,
+                      float* zq_dev, int64_t* codes_dev, float* latents_dev, float* losses_dev, void* stream);
+/* escx_dac_quantize with per-clip stage counts clip_n[batch] (HOST array or NULL), the per-item mask of quantize.py:181-190 with the semantics, the
+ * fillers (codes -1, latents 0) and the errors of escx_dac_encode_ex's clip_n: n_quantizers is the number of code slots, in [max(clip_n), n_codebooks]. */
+int escx_dac_quantize_ex(escx_dac d, const float* flat_params_dev, int64_t params_version, const float* z_dev, int batch, int n_frames, int n_quantizers,
+                         const int32_t* clip_n, float* zq_dev, int64_t* codes_dev, float* latents_dev, float* losses_dev, void* stream);
+/* escx_dac_quantize (quantize.py:127-198) of z (B, D, n_frames) with frame_lengths[b] in [1, n_frames] frames of clip b (HOST array), the semantics of
+ * escx_dac_decode_lengths on the input and of escx_dac_encode_lengths on the outputs: nothing at or past a clip's length is read, z_q and latents
+ * are 0 and codes -1 there, clip b is bitwise escx_dac_quantize of its own frames, and the losses are the mean over the clips of the single-clip
+ * calls' losses.  clip_n (HOST array or NULL) is escx_dac_quantize_ex's.  An entry outside its range is ESCX_ERR_INVALID_ARG before any launch. */
+int escx_dac_quantize_lengths(escx_dac d, const float* flat_params_dev, int64_t params_version, const float* z_dev, int batch, int n_frames,
+                              const int32_t* frame_lengths, int n_quantizers, const int32_t* clip_n, float* zq_dev, int64_t* codes_dev, float* latents_dev,
+                              float* losses_dev, void* stream);
+/* d_z (B, D, T) = the cotangents d_zq (B, D, T), d_latents (B, n_codes * codebook_dim, T) and the DEVICE scalar d_commitment pulled back through
+ * escx_dac_quantize / _ex (quantize.py:58-70, 173-198 under autograd: the straight-through estimator per stage, quantize.py:64-66, and the commitment
+ * term against the detached codebook vector, quantize.py:61); each may be NULL (zero).  The operands are the forward's own outputs latents_dev
+ * (B, n_codes * codebook_dim, T) and codes_dev (B, n_codes, T) and its stage counts (clip_n HOST array, or NULL for n_codes everywhere): there is no
+ * tape.  One launch of escx_dac_encode_backward's quantiser kernel, then the (B, T, Dp) -> (B, D, T) store.  fp32 VALU, no atomics: bitwise
+ * deterministic, and without d_commitment a clip's d_z does not depend on its batch.  The caller answers for params_version being the forward's
+ * (esc.baselines.DAC records it and raises).  ESCX_ERR_INVALID_ARG: null latents / codes / d_z, n_codes outside [1, n_codebooks], a bad count. */
+int escx_dac_quantize_backward(escx_dac d, const float* flat_params_dev, int64_t params_version, const float* latents_dev, const int64_t* codes_dev, int batch,
+                               int n_frames, int n_codes, const int32_t* clip_n, const float* d_zq_dev, const float* d_latents_dev,
+                               const float* d_commitment_dev, float* d_z_dev, void* stream);
+/* The gradient of every quantiser parameter of escx_dac_quantize / _ex (quantize.py:58-70, 173-198 differentiated with respect to in_proj / out_proj
+ * bias, weight_g, weight_v, nn/layers.py:5-10, and the codebooks): the quantiser block of escx_dac_encode_backward_params, the same launches with the
+ * same formulas, whose z_enc operand is the staged z_dev (B, D, T) the forward was given.  d_codebook is the DEVICE scalar on the codebook loss (or
+ * NULL).  grad_flat_dev has flat_params_dev's layout: the slots of every `quantizer.*` parameter are OVERWRITTEN, the stages at or past n_codes with
+ * zeros, and no other float is touched.  d_z_dev may be NULL; when given it is bitwise escx_dac_quantize_backward's.  The workspace is
+ * escx_dac_encode_backward_params' (escx_dac_param_grad_workspace_floats counts it from the first call on).  No atomics: two calls are bitwise equal.
+ * Errors are escx_dac_quantize_backward's plus ESCX_ERR_INVALID_ARG for a NULL z_dev or grad_flat_dev, found before the handle changes. */
+int escx_dac_quantize_backward_params(escx_dac d, const float* flat_params_dev, int64_t params_version, const float* z_dev, const float* latents_dev,
+                                      const int64_t* codes_dev, int batch, int n_frames, int n_codes, const int32_t* clip_n, const float* d_zq_dev,
+                                      const float* d_latents_dev, const float* d_commitment_dev, const float* d_codebook_dev, float* d_z_dev,
+                                      float* grad_flat_dev, void* stream);
+/* ResidualVectorQuantize.from_latents (quantize.py:222-255) over VectorQuantize.decode_latents (quantize.py:78-94): per-codebook latents
+ * (B, n_channels, T) -> z_q (B, D, T), z_p (B, n * codebook_dim, T) and codes (B, n, T) with n = min(n_channels / codebook_dim, n_codebooks); trailing
+ * channels that fill no codebook are ignored and n_channels < codebook_dim is ESCX_ERR_INVALID_ARG.  Every stage searches its own channels
+ * independently - one wave per (stage, row) - with the operations of the fused quantiser's search, so the codes are bitwise those escx_dac_quantize
+ * emits for the same latents; z_q and z_p are escx_dac_from_codes' launch on those codes.  A latent whose every distance is NaN gets code 0. */
+int escx_dac_from_latents(escx_dac d, const float* flat_params_dev, int64_t params_version, const float* latents_dev, int batch, int n_channels, int n_frames,
+                          float* z_dev, float* zp_dev, int64_t* codes_dev, void* stream);
+/* escx_dac_from_latents (quantize.py:222-255) with per-clip stage counts clip_n[batch] (HOST array or NULL, each in [1, n]): the slots at or past a
+ * clip's count are not searched, hold code -1 and z_p 0 and add nothing to z_q, as in escx_dac_from_codes_ex. */
+int escx_dac_from_latents_ex(escx_dac d, const float* flat_params_dev, int64_t params_version, const float* latents_dev, int batch, int n_channels, int n_frames,
+                             const int32_t* clip_n, float* z_dev, float* zp_dev, int64_t* codes_dev, void* stream);
+/* escx_dac_from_latents (quantize.py:222-255) with frame_lengths[b] in [1, n_frames] frames of clip b (HOST array): the rows at or past a clip's
+ * length are not read and hold z_q 0, z_p 0 and codes -1, as in escx_dac_from_codes_lengths.  clip_n (HOST array or NULL) is escx_dac_from_latents_ex's. */
+int escx_dac_from_latents_lengths(escx_dac d, const float* flat_params_dev, int64_t params_version, const float* latents_dev, int batch, int n_channels,
+                                  int n_frames, const int32_t* frame_lengths, const int32_t* clip_n, float* z_dev, float* zp_dev, int64_t* codes_dev,
+                                  void* stream);
 /* Test hook: the kernels' Snake (mode 0: x + sin(alpha x)^2 / (alpha + 1e-9), nn/layers.py:19-24) or tanh (mode 1) over n device values. */
 int escx_dac_test_math(const float* x_dev, const float* alpha_dev, float* out_dev, int64_t n, int mode, void* stream);
 /* Test hook of the backward of DAC.decode (dac.py:249-266): the kernels' Snake derivative (mode 0: 1 + alpha sin(2 alpha x) / (alpha + 1e-9), the
