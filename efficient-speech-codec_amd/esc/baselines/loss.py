@@ -1,4 +1,5 @@
-"""Training losses of the DAC baseline (`dac/nn/loss.py:11-327`) on the MI355X: L1Loss, SISDRLoss, MultiScaleSTFTLoss, MelSpectrogramLoss.
+"""Training losses of the DAC baseline (`dac/nn/loss.py:11-368`) on the MI355X: L1Loss, SISDRLoss, MultiScaleSTFTLoss, MelSpectrogramLoss, and GANLoss
+over esc.models.Discriminator (at the end of this file; escx_gan_term through esc.modules.loss._GanTermFn).
 
 Same classes, constructor keywords, defaults and call order as the reference: `loss(x, y)` with x the estimate and y the reference signal (SISDRLoss
 names its first argument `references`, as the reference does).  The arithmetic and the gradients run in libescx.so (include/escx.h escx_spec_loss_eval,
@@ -19,8 +20,10 @@ import torch
 from torch import nn
 
 from .. import _native
+from ..models.discriminator import _buffer_plan
+from ..modules.loss import _GanTermFn, _by_buffer
 
-__all__ = ["L1Loss", "SISDRLoss", "MultiScaleSTFTLoss", "MelSpectrogramLoss", "slaney_filterbank"]
+__all__ = ["L1Loss", "SISDRLoss", "MultiScaleSTFTLoss", "MelSpectrogramLoss", "GANLoss", "slaney_filterbank"]
 
 
 def _ptr(t):
@@ -307,3 +310,105 @@ class MelSpectrogramLoss(_SpectralLoss):
     def _scales(self):
         return [(int(w), int(m), float(fmin), None if fmax is None else float(fmax))
                 for m, fmin, fmax, w in zip(self.n_mels, self.mel_fmin, self.mel_fmax, self.window_lengths)]
+
+
+# ---- GAN ----------------------------------------------------------------------------------------------------------------------------------
+class _DiscLossFn(torch.autograd.Function):
+    """mean_b(sum over sub-discriminators of mean (0 - D(fake_b))^2 + mean (1 - D(real_b))^2) from ONE discriminator forward over [fake | real], differentiable
+    in the discriminator's parameters.  The backward runs per half of that pass - clips [0, B), then [B, 2B): every buffer is batch-major, so a clip range of
+    the pass is a pass - and adds the two parameter gradients.  That is the arithmetic of esc.modules.GANLoss.discriminator_loss, whose two halves are two
+    passes: each half's weight gradients are reduced and rounded on their own.  One backward over all 2B clips sums the four clips before rounding and lands a
+    few float32 ulps elsewhere on the norm gradients where the halves nearly cancel (1.3e-6 on one of 324 tensors of the yml's discriminator)."""
+
+    @staticmethod
+    def forward(ctx, disc, f, r, *params):
+        B = f.shape[0]
+        both = disc(torch.cat([f, r], dim=0).unsqueeze(1))
+        loss = 0
+        for sub in both:                        # the clip-range form: the pass's own buffer, clips [0, B) against 0 and [B, 2B) against 1
+            buf, *meta = sub.entries[-1]
+            loss = loss + _GanTermFn.apply(buf, None, (tuple(meta),), 0, 0.0, 0, B) + _GanTermFn.apply(buf, None, (tuple(meta),), 0, 1.0, B, B)
+        ctx.disc, ctx.both, ctx.B = disc, both, B
+        return loss.mean()
+
+    @staticmethod
+    def backward(ctx, g):
+        disc, both, B = ctx.disc, ctx.both, ctx.B
+        dev = both.wave.device
+        lib, hd = disc._handle(dev)
+        flat = disc._ensure_flat(dev, lib, hd)
+        st = disc._flat[dev.index if dev.index is not None else torch.cuda.current_device()]
+        scale = (g.to(torch.float32) / B).expand(B).contiguous()                 # d mean_b(term_b)
+        total = None
+        for lo, target in ((0, 0.0), (B, 1.0)):
+            half = both.clips(lo, lo + B)
+            dbufs = [None] * len(half.bufs)
+            for sub in half:
+                buf, C, Cp, D0, D1, P1, off1 = sub.entries[-1]             # the last map of a sub-discriminator is a buffer of its own
+                grad = torch.empty_like(buf)
+                with torch.cuda.device(dev):
+                    _native.check(lib.escx_gan_term_grad(_ptr(buf), None, _ptr(scale), _ptr(grad), B, C, Cp, D0, D1, P1, 0, float(target), _stream(dev)))
+                dbufs[next(i for i, b in enumerate(half.bufs) if b.data_ptr() == buf.data_ptr())] = grad
+            gflat = torch.empty_like(flat)
+            n = len(half.layout)
+            _, where = _buffer_plan(half.layout)
+            at = lambda bufs: (ctypes.c_void_p * n)(*[(None if bufs[bi] is None else bufs[bi].data_ptr() + 4 * off1 * half.layout[i][2])     # noqa: E731
+                                                      for i, (bi, off1) in enumerate(where)])
+            with torch.cuda.device(dev):
+                _native.check(lib.escx_disc_backward(hd, _ptr(flat), disc._version(), _ptr(half.wave), B, half.wave.shape[1], at(half.bufs), at(dbufs), _ptr(gflat), None,
+                                                     _stream(dev)))
+            total = gflat if total is None else total + gflat
+        if disc._flat_grad_mode and "gflat" in st:              # esc.optim.FlatAdamW: the parameters' .grad are views of one buffer, written in place
+            st["gflat"].copy_(total) if st["gfresh"] else st["gflat"].add_(total)
+            st["gfresh"] = False
+            return (None,) * (3 + len(st["layout"]))
+        params = dict(disc.named_parameters())
+        by_id = {id(params[k]): total[off:off + n_].view(params[k].shape) for k, off, n_ in st["layout"]}
+        return (None, None, None) + tuple(by_id.get(id(p)) for p in disc.parameters())
+
+
+class GANLoss(nn.Module):
+    """Least-squares GAN and feature-matching losses of the adversarial recipe (loss.py:330-368) over esc.models.Discriminator, the reference's
+    `dac.model.Discriminator`.  `discriminator_loss(fake, real)` -> 0-dim; `generator_loss(fake, real)` -> (loss_g, loss_feature), both 0-dim.
+
+    The reference takes `torch.mean` over whole maps; the terms here are evaluated per clip on the discriminator's channels-last buffers (escx_gan_term, no
+    NCHW map is materialised) and averaged over the batch, which is the same number for clips of one length.  Each loss call runs the discriminator ONCE,
+    over [fake | real]: a clip's maps do not depend on the batch it is in, so the values are those of the reference's two passes (the discriminator's
+    parameter gradients too: _DiscLossFn runs the backward of that one forward per half).  Signals of unequal shape take
+    two passes in `discriminator_loss`; `generator_loss` refuses them (the feature-matching term compares maps of equal size, in the reference as well).
+
+    What is differentiable: `discriminator_loss` in the discriminator's parameters only (fake is detached as in the reference, and real is data);
+    `generator_loss` in `fake` only.  One departure from the reference: its `generator_loss(...)` backward also deposits gradients in the discriminator's
+    parameters, which its trainer then discards (`optimizer_d.zero_grad()` precedes every discriminator backward, train_customize.py:286); here the
+    discriminator's `p.grad` are left untouched by `generator_loss` and its backward."""
+
+    def __init__(self, discriminator):
+        super().__init__()
+        self.discriminator = discriminator
+
+    def forward(self, fake, real):
+        """(d_fake, d_real): the discriminator's feature maps of both signals, as the reference returns them (two passes, fully differentiable)."""
+        return self.discriminator(_signal(fake).unsqueeze(1)), self.discriminator(_signal(real).unsqueeze(1))
+
+    def discriminator_loss(self, fake, real):
+        f, r = _signal(fake).detach(), _signal(real).detach()
+        if f.shape != r.shape:
+            d_fake, d_real = self.discriminator(f.unsqueeze(1)), self.discriminator(r.unsqueeze(1))
+            loss = 0
+            for xf, xr in zip(d_fake, d_real):
+                (bf, *mf), (br, *mr) = xf.entries[-1], xr.entries[-1]
+                loss = loss + _GanTermFn.apply(bf, None, (tuple(mf),), 0, 0.0).mean() + _GanTermFn.apply(br, None, (tuple(mr),), 0, 1.0).mean()
+            return loss
+        return _DiscLossFn.apply(self.discriminator, f, r, *self.discriminator.parameters())
+
+    def generator_loss(self, fake, real):
+        f, r = _pair(fake, real)
+        B = f.shape[0]
+        both = self.discriminator(torch.cat([f, r.detach()], dim=0).unsqueeze(1), detach_params=True, grad_clips=B)
+        loss_g, loss_f = 0, 0
+        for sub in both:
+            buf, *meta = sub.entries[-1]
+            loss_g = loss_g + _GanTermFn.apply(buf, None, (tuple(meta),), 0, 1.0, 0, B)
+            for buf, metas in _by_buffer(sub.entries[:-1]):
+                loss_f = loss_f + _GanTermFn.apply(buf, buf.detach()[B:], tuple(metas), 1, 0.0, 0, B)
+        return loss_g.mean(), loss_f.mean()

@@ -1,8 +1,11 @@
 #!/usr/bin/env python
-"""The DAC baseline's non-adversarial trainer (reference: baselines/descript/scripts/train_customize_no_adv.py:238-278) on the native path.
+"""The DAC baseline's trainers on the native path: the non-adversarial one (reference: baselines/descript/scripts/train_customize_no_adv.py:238-278) and,
+with --adv, the adversarial one (train_customize.py:263-319).
 
     python -m scripts.train_dac --config conf/16khz_dns_9k.yml --data ./train_wavs --steps 1000 --save_path ./dac_out
     python -m scripts.train_dac --synthetic dac_tiny --steps 2 --batch_size 2            # synthetic weights and clips: a smoke run
+    python -m scripts.train_dac --adv --config conf/16khz_dns_9k.yml --data ./train_wavs --steps 1000 --save_path ./dac_out
+    python -m scripts.train_dac --adv --config ... --resume ./dac_out/latest --steps 2000   # continue: --steps is the step to stop at
 
 One step is the reference's train_loop: forward with the quantiser dropout, MultiScaleSTFTLoss + MelSpectrogramLoss + L1Loss on the waveform plus the two
 VQ losses weighted by `lambdas`, backward, clip_grad_norm_(1e3), AdamW, ExponentialLR.  The model stays in eval mode - esc.baselines.DAC has no training
@@ -12,6 +15,16 @@ in the layout DAC.load reads: <save_path>/<tag>/dac/weights.pth with "state_dict
 
 One departure: with the yml's decoder rates (8, 5, 4, 2) the model returns 8 samples fewer than it takes (the stride-5 block), and the losses need equal
 lengths, so the signal is cut to the reconstruction's length before the losses.
+
+--adv is the reference's order, which is not the order of ESC's adversarial trainer (scripts/train.py AdvStepper): generator forward; the discriminator's
+update on GANLoss.discriminator_loss(recons, signal) (zero_grad, backward, clip_grad_norm_(10), AdamW, ExponentialLR: discriminator_update); then the
+waveform / spectral losses and GANLoss.generator_loss(recons, signal) with the UPDATED discriminator, the VQ losses, and the generator's update.  The
+discriminator therefore runs twice per step, each time once over [reconstructions | signals]; the pass cannot be shared between the two updates, because its
+weights change in between.  The discriminator is the yml's `Discriminator:` block and is saved to <save_path>/<tag>/discriminator/ (weights.pth with
+"state_dict" and "metadata": {"kwargs"}, optimizer.pth, scheduler.pth) next to <tag>/dac/, as train_customize.py:346-377 does through audiotools'
+save_to_folder; both layouts are assumed from the reference's code, not read from a checkpoint it wrote.  --resume <save_path>/<tag> restores the model, its
+optimiser and scheduler (with --adv the discriminator's three files as well) and continues the step count and the learning rate from the scheduler's; the
+clip generators restart from seed + step.
 
 Not here: wandb, the audiotools dataset and transforms, PESQ.  --data takes a directory of wav files at the model's rate (scipy), cut into random clips;
 without it the clips are synthetic.  Validation reports the three losses only.
@@ -28,13 +41,15 @@ import numpy as np
 import torch
 
 from esc import synth
-from esc.baselines import DAC, L1Loss, MelSpectrogramLoss, MultiScaleSTFTLoss
+from esc.baselines import DAC, Discriminator, GANLoss, L1Loss, MelSpectrogramLoss, MultiScaleSTFTLoss
 
 # conf/16khz_dns_9k.yml
 LAMBDAS = {"mel/loss": 15.0, "adv/feat_loss": 2.0, "adv/gen_loss": 1.0, "vq/commitment_loss": 0.25, "vq/codebook_loss": 1.0}
 YML_LOSSES = {"MultiScaleSTFTLoss": dict(window_lengths=[2048, 512]),
               "MelSpectrogramLoss": dict(n_mels=[5, 10, 20, 40, 80, 160, 320], window_lengths=[32, 64, 128, 256, 512, 1024, 2048], mel_fmin=[0, 0, 0, 0, 0, 0, 0],
                                          mel_fmax=[None] * 7, pow=1.0, clamp_eps=1e-5, mag_weight=0.0)}
+YML_DISCRIMINATOR = dict(sample_rate=16000, rates=[], periods=[2, 3, 5, 7, 11], fft_sizes=[2048, 1024, 512],
+                         bands=[[0.0, 0.1], [0.1, 0.25], [0.25, 0.5], [0.5, 0.75], [0.75, 1.0]])
 OPTIM = {"AdamW": dict(betas=[0.8, 0.99], lr=1e-4), "ExponentialLR": dict(gamma=0.999996)}
 
 
@@ -44,9 +59,21 @@ def make_losses(cfg, sample_rate):
             "mel": MelSpectrogramLoss(sample_rate=sample_rate, **cfg["MelSpectrogramLoss"])}
 
 
-def train_step_losses(model, losses, signal, n_quantizers, lambdas, audio_hook=None):
+def discriminator_update(gan, optimizer_d, scheduler_d, recons, signal):
+    """train_customize.py:283-293: the discriminator's whole update on the detached reconstruction.  Returns adv/disc_loss and other/grad_norm_d."""
+    loss = gan.discriminator_loss(recons, signal)
+    optimizer_d.zero_grad()
+    loss.backward()
+    grad_norm = torch.nn.utils.clip_grad_norm_(gan.discriminator.parameters(), 10.0)
+    optimizer_d.step()
+    scheduler_d.step()
+    return {"adv/disc_loss": loss.detach(), "other/grad_norm_d": grad_norm}
+
+
+def train_step_losses(model, losses, signal, n_quantizers, lambdas, audio_hook=None, adv=None):
     """train_loop (:251-263) up to the backward: the dict of loss values with the weighted total under "loss".  audio_hook(audio) sees the reconstruction
-    (with its gradient retained) before the losses."""
+    (with its gradient retained) before the losses.  adv = (GANLoss, optimizer_d, scheduler_d) makes it train_customize.py's train_loop (:263-305): the
+    discriminator is updated right after the generator's forward, and adv/gen_loss, adv/feat_loss come from the updated discriminator."""
     out = model(signal, model.sample_rate, n_quantizers=n_quantizers)
     recons = out["audio"]
     signal = signal[..., :recons.shape[-1]]            # decoder rates with an odd stride (the yml's 5) return a few samples fewer than they take: compare what there is
@@ -55,9 +82,13 @@ def train_step_losses(model, losses, signal, n_quantizers, lambdas, audio_hook=N
         audio_hook(recons)
     # a loss without a weight is reported only (the yml weighs the mel loss alone): on the detached audio its forward computes no unit gradient
     arg = lambda k: recons if lambdas.get(k) else recons.detach()           # noqa: E731
-    output = {"stft/loss": losses["stft"](arg("stft/loss"), signal), "mel/loss": losses["mel"](arg("mel/loss"), signal),
+    output = discriminator_update(*adv, recons, signal) if adv is not None else {}
+    output.update({"stft/loss": losses["stft"](arg("stft/loss"), signal), "mel/loss": losses["mel"](arg("mel/loss"), signal),
               "waveform/loss": losses["waveform"](arg("waveform/loss"), signal),
-              "vq/commitment_loss": out["vq/commitment_loss"], "vq/codebook_loss": out["vq/codebook_loss"]}
+              "vq/commitment_loss": out["vq/commitment_loss"], "vq/codebook_loss": out["vq/codebook_loss"]})
+    if adv is not None:
+        weighed = lambdas.get("adv/gen_loss") or lambdas.get("adv/feat_loss")
+        output["adv/gen_loss"], output["adv/feat_loss"] = adv[0].generator_loss(recons if weighed else recons.detach(), signal)
     output["loss"] = sum(v * output[k] for k, v in lambdas.items() if k in output)
     return output
 
@@ -80,6 +111,26 @@ def save_checkpoint(model, optimizer, scheduler, save_path, tag):
     torch.save(optimizer.state_dict(), os.path.join(folder, "optimizer.pth"))
     torch.save(scheduler.state_dict(), os.path.join(folder, "scheduler.pth"))
     return os.path.join(folder, "weights.pth")
+
+
+def save_discriminator(disc, optimizer_d, scheduler_d, save_path, tag):
+    """train_customize.py:369-375: <save_path>/<tag>/discriminator/, the same three files as the generator's folder."""
+    folder = os.path.join(save_path, tag, "discriminator")
+    os.makedirs(folder, exist_ok=True)
+    kwargs = dict(disc.cfg, bands=[list(b) for b in disc.cfg["bands"]])
+    torch.save({"state_dict": {k: v.detach().cpu() for k, v in disc.state_dict().items()}, "metadata": {"kwargs": kwargs}}, os.path.join(folder, "weights.pth"))
+    torch.save(optimizer_d.state_dict(), os.path.join(folder, "optimizer.pth"))
+    torch.save(scheduler_d.state_dict(), os.path.join(folder, "scheduler.pth"))
+    return os.path.join(folder, "weights.pth")
+
+
+def resume_from(folder, module, optimizer, scheduler):
+    """Restore what save_checkpoint / save_discriminator wrote into `folder`; returns the number of steps the scheduler has taken."""
+    ck = torch.load(os.path.join(folder, "weights.pth"), map_location="cpu", weights_only=True)
+    module.load_state_dict(ck["state_dict"], strict=True)
+    optimizer.load_state_dict(torch.load(os.path.join(folder, "optimizer.pth"), map_location="cuda", weights_only=True))
+    scheduler.load_state_dict(torch.load(os.path.join(folder, "scheduler.pth"), map_location="cpu", weights_only=True))
+    return scheduler.last_epoch
 
 
 class Clips:
@@ -125,10 +176,12 @@ def main():
     ap.add_argument("--duration", type=float, default=None, help="seconds per clip (default 3.0; 0.16 with --synthetic)")
     ap.add_argument("--save_path", default="./dac_output")
     ap.add_argument("--valid_freq", type=int, default=0, help="validate every this many steps (0: at the end only)")
+    ap.add_argument("--adv", action="store_true", help="the adversarial recipe (train_customize.py): GANLoss over the yml's Discriminator, updated before the generator")
+    ap.add_argument("--resume", default=None, help="<save_path>/<tag> of an earlier run: restore weights, optimisers and schedulers and continue the step count")
     a = ap.parse_args()
     if bool(a.config) == bool(a.synthetic):
         ap.error("give exactly one of --config and --synthetic")
-    cfg = dict(OPTIM, lambdas=dict(LAMBDAS), batch_size=16, seed=53, **YML_LOSSES)
+    cfg = dict(OPTIM, lambdas=dict(LAMBDAS), batch_size=16, seed=53, Discriminator=dict(YML_DISCRIMINATOR), **YML_LOSSES)
     if a.config:
         import yaml
         cfg.update(yaml.safe_load(open(a.config)))
@@ -150,13 +203,25 @@ def main():
     losses = make_losses(cfg, model.sample_rate)
     optimizer = torch.optim.AdamW(model.parameters(), lr=cfg["AdamW"]["lr"], betas=tuple(cfg["AdamW"]["betas"]))
     scheduler = torch.optim.lr_scheduler.ExponentialLR(optimizer, cfg["ExponentialLR"]["gamma"])
-    clips = Clips(a.data, model.sample_rate, int(round(duration * model.sample_rate)), seed)
+    adv, start = None, 0
+    if a.adv:
+        disc = Discriminator(**cfg["Discriminator"]).to("cuda")
+        optimizer_d = torch.optim.AdamW(disc.parameters(), lr=cfg["AdamW"]["lr"], betas=tuple(cfg["AdamW"]["betas"]))
+        scheduler_d = torch.optim.lr_scheduler.ExponentialLR(optimizer_d, cfg["ExponentialLR"]["gamma"])
+        adv = (GANLoss(disc), optimizer_d, scheduler_d)
+    if a.resume:
+        start = resume_from(os.path.join(a.resume, "dac"), model, optimizer, scheduler)
+        if a.adv:
+            resume_from(os.path.join(a.resume, "discriminator"), disc, optimizer_d, scheduler_d)
+        print(f"resumed {a.resume} at step {start}", flush=True)
+    clips = Clips(a.data, model.sample_rate, int(round(duration * model.sample_rate)), seed + start)
+    clips.count = start * B
     print(f"clips of {clips.n} samples from " + (f"{len(clips.waves)} wav files" if clips.waves else "the synthetic generator"), flush=True)
-    gen = torch.Generator().manual_seed(seed)
+    gen = torch.Generator().manual_seed(seed + start)
     lambdas = cfg["lambdas"]
-    for step in range(1, a.steps + 1):
+    for step in range(start + 1, a.steps + 1):
         signal = clips.batch(B).to("cuda")
-        output = train_step_losses(model, losses, signal, model.sample_n_quantizers(B, gen), lambdas)
+        output = train_step_losses(model, losses, signal, model.sample_n_quantizers(B, gen), lambdas, adv=adv)
         optimizer.zero_grad()
         output["loss"].backward()
         grad_norm = torch.nn.utils.clip_grad_norm_(model.parameters(), 1e3)
@@ -169,6 +234,8 @@ def main():
             print(f"step {step}  " + "  ".join(f"test/{k} {v:.6g}" for k, v in sorted(val.items())), flush=True)
     path = save_checkpoint(model, optimizer, scheduler, a.save_path, "latest")
     print(f"saved {path}")
+    if a.adv:
+        print(f"saved {save_discriminator(disc, optimizer_d, scheduler_d, a.save_path, 'latest')}")
 
 
 if __name__ == "__main__":
