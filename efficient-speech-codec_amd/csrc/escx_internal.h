@@ -120,6 +120,11 @@ int check_ready(escx_handle_s* h);
 // ordered, so consecutive calls may reuse the buffer; growing synchronises the device once.
 float* stream_scratch(hipStream_t st, int slot, size_t floats);
 int launch_ok(const char* what);
+// train.hip: windowed-DFT (D [2 Fq][w], DT its transpose) and HTK filterbank (fb [Mp][Fq], fbT) matrices of the seven mel resolutions, one table per
+// device, built on first use and rebuilt when the sample rate changes.  Shared by the mel loss (escx_mel_loss_ex) and the mel distance (metrics.hip).
+struct MelScale { int w, hop, F, Fq, n_mels, Mp; float *D, *DT, *fb, *fbT; };
+struct MelState { MelScale sc[7]; float* base = nullptr; int sr = 0; };
+int build_mel(int dev, int sr, MelState** out);
 int build_gather_map(escx_handle_s* h);
 // escx_params.cpp, used by the launch sequences of escx_api.cpp
 void use_set(escx_handle_s* h, int i);          // makes workspace set i the current one (the inherited WsFields)

@@ -1393,11 +1393,10 @@ extern "C" int escx_stft_loss(const float* raw_feat, const float* recon_feat, in
 namespace {
 const int MEL_WINDOWS[7] = {32, 64, 128, 256, 512, 1024, 2048};
 const int MEL_BINS[7] = {5, 10, 20, 40, 80, 160, 320};
-struct MelScale { int w, hop, F, Fq, n_mels, Mp; float *D, *DT, *fb, *fbT; };
-struct MelState { MelScale sc[7]; float* base = nullptr; int sr = 0; };
 MelState* g_mel[64] = {nullptr};            // per device: DFT / mel filterbank matrices of the 7 resolutions (constants, built once)
+}  // namespace
 
-int build_mel(int dev, int sr, MelState** out) {
+int escx::build_mel(int dev, int sr, MelState** out) {
     if (dev < 0 || dev >= 64) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "device index out of range");
     if (g_mel[dev] && g_mel[dev]->sr == sr) { *out = g_mel[dev]; return 0; }
     if (g_mel[dev]) { (void)hipDeviceSynchronize(); (void)hipFree(g_mel[dev]->base); delete g_mel[dev]; g_mel[dev] = nullptr; }
@@ -1440,7 +1439,6 @@ int build_mel(int dev, int sr, MelState** out) {
     *out = ms;
     return 0;
 }
-}  // namespace
 
 // MelSpectrogramLoss (generator_loss.py:37-74): 7 resolutions, L1 on mel magnitudes + L1 on log10(mel^2); d_recon (B, L) optional.
 // STFTs are windowed-DFT GEMMs (FrameA loader with reflect padding), the mel projection another GEMM; nothing leaves the device.

@@ -199,6 +199,9 @@ SIGNATURES = {
     "escx_spec_loss_eval": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "escx_wave_l1": (c_int, [c_void_p, c_void_p, c_int64, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     "escx_sisdr": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "escx_mel_distance": (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(c_int32), c_int, c_void_p, c_void_p]),
+    "escx_sisdr_metric": (c_int, [c_void_p, c_void_p, c_int, c_int64, POINTER(c_int32), c_int, c_int, c_void_p, c_void_p]),
+    "escx_code_histogram": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "escx_set_rccl_library": (c_int, [c_char_p]),
     "escx_allgather_codes": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p]),
 }

@@ -7,7 +7,14 @@ clip, codebook utilisation, `perf_stats.json` with the same layout.
 
 `--one_pass` encodes every batch once and decodes it at each bitrate (both codecs emit prefix codes): the same table, bit for bit, as the
 default sweep that runs the whole forward once per bitrate.
+
+    python -m scripts.test --eval_folder_path ./utterances --ragged --batch_size 8 --model_path ./esc9kbps      # whole utterances of different lengths
+
+`--ragged` evaluates a folder whose files differ in length in batches: every file is trimmed to the longest length the model reconstructs in full
+(snap_length), batches are formed longest first and run through the codecs' `lengths` calls and the length-aware HIP metrics of esc.metrics, and every
+file gets the numbers of the reference's batch-size-1 loop.  `--native_metrics` alone swaps the metric classes on the uniform path.
 """
+import inspect
 import math
 import argparse
 import json
@@ -20,7 +27,7 @@ from torch.utils.data import DataLoader, default_collate
 
 from esc.models import make_model
 from .metrics import EntropyCounter, MelSpectrogramDistance, SISDR
-from .utils import EvalSet, read_yaml
+from .utils import EvalSet, RaggedEvalSet, in_file_order, ragged_collate, read_yaml
 
 
 def parse_args():
@@ -33,6 +40,8 @@ def parse_args():
     p.add_argument("--dac_path", type=str, default=None, help="DAC baseline checkpoint (weights.pth, esc.baselines.DAC.load)")
     p.add_argument("--n_quantizers", type=str, default=None, help="DAC: codebook counts of the evaluated bitrates, e.g. 3,6,9,12,15,18")
     p.add_argument("--one_pass", action="store_true", help="encode each batch once for the whole sweep (eval_epoch_one_pass)")
+    p.add_argument("--ragged", action="store_true", help="files of different lengths in one batch: RaggedEvalSet, esc.metrics, eval_epoch_ragged")
+    p.add_argument("--native_metrics", action="store_true", help="MelDistance / SISDR / utilisation from esc.metrics (HIP) instead of scripts.metrics")
     p.add_argument("--save_path", type=str, default=None)
     p.add_argument("--device", type=str, default="cuda")
     return p.parse_args()
@@ -91,8 +100,8 @@ class DacEvalModel(torch.nn.Module):
         EvalSet's clips (a whole number of hops minus 80 samples) are not affected."""
         return torch.nn.functional.pad(audio[:, 0], (0, length - audio.shape[-1]))
 
-    def forward(self, x, x_feat, num_streams):
-        out = self.dac(x[:, None], None, self.code_slots(num_streams))
+    def forward(self, x, x_feat, num_streams, lengths=None):
+        out = self.dac(x[:, None], None, self.code_slots(num_streams)) if lengths is None else self.dac(x[:, None], None, self.code_slots(num_streams), lengths=lengths)
         return {"recon_audio": self._fit(out["audio"], x.shape[-1]), "codes": out["codes"][:, :, None]}
 
     def sweep(self, x, streams):
@@ -187,6 +196,52 @@ def eval_epoch_one_pass(model, eval_loader, metric_funcs, e_counter, device, bps
     return table
 
 
+def _takes_lengths(fn):
+    return "lengths" in inspect.signature(fn.forward if isinstance(fn, torch.nn.Module) else fn).parameters
+
+
+def _ragged_metric(fn, x, recon, lengths):
+    """Per-clip values of one metric on a zero-padded batch: the length-aware metrics of esc.metrics take the batch; anything else (PESQ, on the
+    host) is applied clip by clip to x[b, :L_b] and recon[b, :L_b]."""
+    if _takes_lengths(fn):
+        return fn(x, recon, lengths=lengths).tolist()
+    return [float(fn(x[b:b + 1, :n], recon[b:b + 1, :n])[0]) for b, n in enumerate(lengths)]
+
+
+@torch.no_grad()
+def eval_epoch_ragged(model, eval_loader, metric_funcs, e_counter, device, bps_per_stream, num_streams=None, verbose=True):
+    """eval_epoch over batches of clips of different lengths: `eval_loader` yields (x zero-padded, lengths, file indices) (ragged_collate), the model is
+    called with `lengths`, the metrics get them too, and the counter skips the -1 filler of the codes.  Per-file values are stored by file index and
+    averaged in file order, so the table does not depend on how the batches were formed; its layout is eval_epoch's.  A model without mixed-length
+    batches raises its own NotImplementedError."""
+    was_training = model.training
+    model.eval()
+    streams = [num_streams] if num_streams is not None else list(range(1, model.max_streams + 1))
+    table = {name: [] for name in metric_funcs}
+    table["utilization"] = []
+    try:
+        for s in streams:
+            scores = {name: {} for name in metric_funcs}
+            e_counter.reset_stats(num_streams=_code_slots(model, s))
+            for x, lengths, indices in eval_loader:
+                x = x.to(device)
+                out = model(x=x, x_feat=None, num_streams=s, lengths=lengths)
+                for name, fn in metric_funcs.items():
+                    scores[name].update(zip(indices, _ragged_metric(fn, x, out["recon_audio"], lengths)))
+                e_counter.update(out["codes"])
+            rate = e_counter.compute_utilization()[0]
+            means = {name: float(np.mean(in_file_order(vals))) for name, vals in scores.items()}
+            for name, v in means.items():
+                table[name].append(round(v, 4))
+            table["utilization"].append(rate)
+            if verbose:
+                line = " | ".join(f"{name}: {v:.4f}" for name, v in means.items())
+                print(f"Test Metrics at {s * bps_per_stream:.2f}kbps: {line} | utilization: {rate:.4f}")
+    finally:
+        model.train(was_training)
+    return table
+
+
 def _golden_root():
     return os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))), "tests", "golden")
 
@@ -229,18 +284,32 @@ def load_model(args):
     return model, cfg
 
 
+def _loader(args, model, ragged):
+    if ragged:
+        return DataLoader(RaggedEvalSet(args.eval_folder_path, model), batch_size=args.batch_size, shuffle=False, collate_fn=ragged_collate)
+    return DataLoader(EvalSet(args.eval_folder_path), batch_size=args.batch_size, shuffle=False, collate_fn=default_collate)
+
+
 def run(args):
-    eval_loader = DataLoader(EvalSet(args.eval_folder_path), batch_size=args.batch_size, shuffle=False, collate_fn=default_collate)
-    metric_funcs = {"MelDistance": MelSpectrogramDistance().to(args.device), "SISDR": SISDR().to(args.device)}
+    ragged = getattr(args, "ragged", False)
+    native = ragged or getattr(args, "native_metrics", False)
+    if ragged and getattr(args, "one_pass", False):
+        sys.exit("--ragged --one_pass is not implemented: the one-pass sweep takes no per-clip lengths (drop one of the two)")
+    if native:
+        from esc import metrics as native_metrics
+    Mel, Sdr, Counter = (native_metrics.MelSpectrogramDistance, native_metrics.SISDR, native_metrics.EntropyCounter) if native else \
+        (MelSpectrogramDistance, SISDR, EntropyCounter)
+    metric_funcs = {"MelDistance": Mel().to(args.device), "SISDR": Sdr().to(args.device)}
     try:
         from .metrics import PESQ
         metric_funcs = {"PESQ": PESQ(), **metric_funcs}
     except ImportError:
         print("pesq is not installed: PESQ is skipped", file=sys.stderr)
-    epoch = eval_epoch_one_pass if getattr(args, "one_pass", False) else eval_epoch
+    epoch = eval_epoch_ragged if ragged else (eval_epoch_one_pass if getattr(args, "one_pass", False) else eval_epoch)
     if _is_dac(args):
         model = load_dac(args).to(args.device)
-        e_counter = EntropyCounter(model.dac.codebook_size, num_streams=model.code_slots(model.max_streams), num_groups=1, device=args.device)
+        eval_loader = _loader(args, model, ragged)
+        e_counter = Counter(model.dac.codebook_size, num_streams=model.code_slots(model.max_streams), num_groups=1, device=args.device)
         bps = model.bps_per_stream                  # None: the counts are not k, 2k, ...: the sweep's own lines would carry the wrong kbps
         performances = epoch(model, eval_loader, metric_funcs, e_counter, args.device, num_streams=None, verbose=bps is not None, bps_per_stream=bps or 0.0)
         if bps is None:
@@ -250,7 +319,8 @@ def run(args):
     else:
         model, mcfg = load_model(args)
         model = model.to(args.device)
-        e_counter = EntropyCounter(mcfg["codebook_size"], num_streams=mcfg["max_streams"], num_groups=mcfg["group_size"], device=args.device)
+        eval_loader = _loader(args, model, ragged)
+        e_counter = Counter(mcfg["codebook_size"], num_streams=mcfg["max_streams"], num_groups=mcfg["group_size"], device=args.device)
         performances = epoch(model, eval_loader, metric_funcs, e_counter, args.device, num_streams=None, verbose=True, bps_per_stream=1.5)
     save_path = args.save_path or getattr(args, "dac_path", None) and os.path.dirname(args.dac_path) or args.model_path or "."
     os.makedirs(save_path, exist_ok=True)

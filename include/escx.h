@@ -804,6 +804,25 @@ int escx_wave_l1(const float* est_dev, const float* ref_dev, int64_t n, float sc
 int escx_sisdr(const float* references_dev, const float* estimates_dev, int batch, int64_t n_samples, int scaling, int zero_mean, int has_clip_min,
                float clip_min, float* loss_dev, float* d_references_dev, float* d_estimates_dev, void* stream);
 
+/* ---- evaluation metrics with per-clip lengths (reference: scripts/metrics.py:12-171, driven by eval_epoch, scripts/test.py:23-55) -------------------
+ * A batch of clips of different lengths is zero-padded to n_samples; clip b is its first lengths_host[b] samples and gets the value of the reference's
+ * call on that clip alone.  lengths_host follows the convention of the mixed-length codec calls: a HOST array of `batch` sample counts, copied by the
+ * entry point; NULL = every clip has n_samples.  Nothing at or past a clip's length is read in either signal.  Every argument is checked before the
+ * first launch (ESCX_ERR_INVALID_ARG; a length outside its range is named with its clip).  No floating-point atomics: two calls are bitwise equal,
+ * and at equal (batch, n_samples) a clip's value does not depend on the other clips or their lengths.  Run on the current device, asynchronous on `stream`. */
+/* MelSpectrogramDistance (scripts/metrics.py:96-121): out_dev[b] = sum over the 7 resolutions of
+ * mean |log10(clamp(mel_raw)^2) - log10(clamp(mel_recon)^2)| over n_mels x the clip's OWN frames (1 + len[b] / hop of them, torch.stft center=True
+ * reflecting about the clip's own end).  1024 < len[b] <= n_samples; the matrices are those of the mel loss above (same sample_rate rebuild rule). */
+int escx_mel_distance(const float* raw_dev, const float* recon_dev, int batch, int n_samples, const int32_t* lengths_host, int sample_rate,
+                      float* out_dev, void* stream);
+/* SISDR (scripts/metrics.py:123-171), dB per clip over the clip's own samples (1 <= len[b] <= n_samples), fp64 accumulation in a fixed order; eps = 1e-8
+ * on the projection, on the cross term and inside the log10 as in the reference; the mean of zero_mean is over len[b].  Identical signals give +inf. */
+int escx_sisdr_metric(const float* ref_dev, const float* est_dev, int batch, int64_t n_samples, const int32_t* lengths_host, int scaling, int zero_mean,
+                      float* out_dev, void* stream);
+/* EntropyCounter.update (scripts/metrics.py:37-51): counts_dev[(s*G+g)*K + k] += number of codes == k in codes (B,S,G,T) int64; negative codes (the -1
+ * filler of mixed-length / mixed-bitrate batches) are skipped, codes >= K are counted in overflow_dev[0] and nothing else.  counts and overflow int64. */
+int escx_code_histogram(const int64_t* codes_dev, int B, int S, int G, int T, int K, int64_t* counts_dev, int64_t* overflow_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
