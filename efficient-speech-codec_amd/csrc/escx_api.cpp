@@ -575,32 +575,130 @@ static int rvq_decode(escx_handle_s* h, const int64_t* codes, int B, int S, cons
 static int rvq_forward(escx_handle_s* h, const float* wave, const float* feat, int B, int LT, const int32_t* streams, int S, int64_t* codes, float* wave_out,
                        float* raw_feat, float* recon_feat, float* cm_loss, void* stream);
 
-// csrvq.py:131-158
-static int run_csvq_encode(escx_handle_s* h, const Shapes& s, int S, long long* codes, hipStream_t st) {
+// Argument checks that several entry points share: each issues its message in one place.
+static int check_count(const char* what, int S, int max, const char* suffix = "") {
+    if (S < 1 || S > max) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "%s=%d outside [1, %d]%s", what, S, max, suffix);
+    return 0;
+}
+static int check_samples(escx_handle_s* h, int L) {
+    if (L <= h->n_fft / 2) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "n_samples=%d too short for reflect padding of %d", L, h->n_fft / 2);
+    return 0;
+}
+static int fail_overlap() { ESCX_FAIL(ESCX_ERR_ASSERT, "Time dimension must be multiple of overlap"); }
+static int check_feat_shape(escx_handle_s* h, const Shapes& s, int fh, int fw) {
+    if (s.W != fw || s.encH[h->n - 1] != fh) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "feat_shape (%d,%d) does not match the model (%d,%d)", fh, fw, s.encH[h->n - 1], s.W);
+    return 0;
+}
+// frames of a forward call's input: LT samples (long enough for the reflect padding) or LT frames (at least one patch)
+static int input_frames(escx_handle_s* h, bool wave, int LT, int* T) {
+    if (wave) { const int rc = check_samples(h, LT); *T = frames_of(h, LT); return rc; }
+    if (LT < h->cfg.patch_t) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "n_frames=%d shorter than one patch", LT);
+    *T = LT;
+    return 0;
+}
+
+// Input of the pass [b0, b0 + nb): waveforms (B, L) through the STFT, or frame-major spectra `feat` (B, T, in_dim, F) padded, into h->spec; `raw_feat`
+// (optional) receives the spectrum in the reference's order.
+static int stage_input(escx_handle_s* h, const float* wave, const float* feat, int b0, int nb, int L, int T, float* raw_feat, hipStream_t st) {
+    const size_t row = (size_t)T * h->cfg.in_dim * h->F;
+    int rc;
+    if (wave) { if ((rc = run_stft(h, wave + (size_t)b0 * L, nb, L, T, h->spec, st))) return rc; }
+    else spec_pad(h, feat + b0 * row, h->spec, (long long)nb * T, st);
+    if (raw_feat) spec_unpad(h, h->spec, raw_feat + b0 * row, (long long)nb * T, st);
+    return 0;
+}
+// Output of the pass [b0, b0 + nb): h->rspec (T2 frames per clip) through the inverse STFT into wave_out; `recon_feat` (optional) receives the spectrum.
+static int finish_output(escx_handle_s* h, int b0, int nb, int T2, float* wave_out, float* recon_feat, hipStream_t st) {
     const escx_config& c = h->cfg;
-    const int n = h->n, G = c.group_size;
-    const long long bstride = (long long)S * G * s.Tq, sstride = (long long)G * s.Tq;
+    int rc;
+    if ((rc = run_istft(h, h->rspec, nb, T2, wave_out + (size_t)b0 * c.hop_length * (T2 - 1), st))) return rc;
+    if (recon_feat) spec_unpad(h, h->rspec, recon_feat + (size_t)b0 * T2 * c.in_dim * h->F, (long long)nb * T2, st);
+    return 0;
+}
+
+static int clips_over(const int* S, int B, int j) { int c = 0; while (c < B && S[c] > j) ++c; return c; }     // S non-increasing
+
+// Stream counts of one pass of a whole-path call: the pass's clips in workspace order with S[0] >= S[1] >= ... (mixed-stream calls: MixPlan::S_ws), or
+// S == nullptr and every clip carries `uniform` streams.  Stream j then runs on a PREFIX of the pass - the same kernels on a smaller batch.
+namespace {
+struct PassStreams {
+    const int* S; int uniform;
+    int over(int nb, int j) const { return S ? clips_over(S, nb, j) : (j < uniform ? nb : 0); }      // of the pass's first nb clips, those that carry stream j
+};
+}  // namespace
+
+// csrvq.py:131-158: stream j runs on the clips that carry it; the refinement after it and the decoder block that feeds stream j + 1 only on those that
+// carry stream j + 1 as well (csrvq.py:151: a clip's last stream only emits codes).
+static int run_csvq_encode(escx_handle_s* h, const Shapes& s, PassStreams ps, long long* codes, long long bstride, hipStream_t st) {
+    const int n = h->n;
+    const long long sstride = (long long)h->cfg.group_size * s.Tq;
     int rc, H = s.encH[n - 1], Hn;
     float* dec = h->decA; float* other = h->decB;
-    if ((rc = run_pvq_quantize(h, h->quants[0], h->enc_hs[n - 1], nullptr, s.B, s.W, codes, bstride, nullptr, S == 1 ? nullptr : dec, st))) return rc;
-    if (S == 1) return 0;
-    for (int i = 0; i < S - 1; ++i) {
-        const Quant& q = h->quants[i + 1];
-        const bool last = (i + 2 == S);                                      // csrvq.py:151: the last requested stream only emits codes
-        if ((rc = run_pvq_quantize(h, q, h->enc_hs[n - 1 - i], dec, s.B, s.W, codes + (i + 1) * sstride, bstride, nullptr, last ? nullptr : dec, st))) return rc;
-        if (last) break;
-        if ((rc = run_layer(h, h->layers[n + i], dec, other, s.B, H, s.W, &Hn, st))) return rc;
+    int nref = ps.over(s.B, 1);                                           // clips that go on to stream 1
+    if ((rc = run_pvq_quantize(h, h->quants[0], h->enc_hs[n - 1], nullptr, s.B, s.W, codes, bstride, nullptr, nref ? dec : nullptr, st))) return rc;
+    for (int i = 0; nref > 0; ++i) {
+        const int nq = nref;                                              // clips that carry stream i + 1
+        nref = ps.over(nq, i + 2);                                        // ... and stream i + 2: they need the refinement and block i
+        if ((rc = run_pvq_quantize(h, h->quants[i + 1], h->enc_hs[n - 1 - i], dec, nq, s.W, codes + (i + 1) * sstride, bstride, nullptr, nref ? dec : nullptr, st))) return rc;
+        if (!nref) break;
+        if ((rc = run_layer(h, h->layers[n + i], dec, other, nref, H, s.W, &Hn, st))) return rc;
         std::swap(dec, other); H = Hn;
     }
     return 0;
 }
 
+// csrvq.py:160-183 + codecs.py:83-94: stream i + 1 is de-quantised and added in place on the clips that carry it; the others keep `dec` (the reference's
+// pass-through).  Every decoder block runs on the whole pass.  codes == nullptr with no refinement streams ({nullptr, 1}): the bottleneck map is in
+// h->decA already and the walk is Decoder.forward (base.py:195-203: blocks, post_nn, PatchDeEmbed), the rvq codec's decoder.
+static int run_csvq_decode(escx_handle_s* h, const long long* codes, long long bstride, int B, PassStreams ps, int Hb, int W, float* rspec, hipStream_t st) {
+    const int n = h->n;
+    const long long sstride = (long long)h->cfg.group_size * (W / h->cfg.overlap);
+    int rc, H = Hb, Hn;
+    float* dec = h->decA; float* other = h->decB;
+    if (codes && (rc = run_pvq_decode(h, h->quants[0], codes, bstride, nullptr, B, W, dec, st))) return rc;
+    for (int i = 0; i + 1 < n; ++i) {
+        const int nq = ps.over(B, i + 1);
+        if (nq && (rc = run_pvq_decode(h, h->quants[i + 1], codes + (i + 1) * sstride, bstride, dec, nq, W, dec, st))) return rc;
+        if ((rc = run_layer(h, h->layers[n + i], dec, other, B, H, W, &Hn, st))) return rc;
+        std::swap(dec, other); H = Hn;
+    }
+    if ((rc = run_layer(h, h->layers[2 * n - 1], dec, other, B, H, W, &Hn, st))) return rc;
+    return run_deembed(h, other, B, W, rspec, st);
+}
+
+// csrvq.py:97-129 in eval mode + codecs.py:83-94: stream 0, then (stream i + 1, block i) pairs; stream i + 1 quantises the clips that carry it, the
+// others pass through.  slot_clips[j] = the clips that ran stream slot j; its per-vector commitment terms go to loss + j * G * s.B * Tq as
+// [G][slot_clips[j] * Tq] (loss may be null) and are reduced per clip by the caller (no atomics).
+static int run_csvq_forward(escx_handle_s* h, const Shapes& s, PassStreams ps, long long* codes, long long bstride, float* loss, int slot_clips[8],
+                            float* rspec, hipStream_t st) {
+    const int n = h->n;
+    const long long sstride = (long long)h->cfg.group_size * s.Tq;
+    const size_t lslot = (size_t)sstride * s.B;
+    int rc, H = s.encH[n - 1], Hn;
+    float* dec = h->decA; float* other = h->decB;
+    std::fill(slot_clips, slot_clips + 8, 0);
+    slot_clips[0] = s.B;
+    if ((rc = run_pvq_quantize(h, h->quants[0], h->enc_hs[n - 1], nullptr, s.B, s.W, codes, bstride, loss, dec, st))) return rc;
+    for (int i = 0; i + 1 < n; ++i) {
+        const int nq = ps.over(s.B, i + 1);
+        if (nq) {
+            if ((rc = run_pvq_quantize(h, h->quants[i + 1], h->enc_hs[n - 1 - i], dec, nq, s.W, codes + (i + 1) * sstride, bstride, loss ? loss + (size_t)(i + 1) * lslot : nullptr, dec, st))) return rc;
+            slot_clips[i + 1] = nq;
+        }
+        if ((rc = run_layer(h, h->layers[n + i], dec, other, s.B, H, s.W, &Hn, st))) return rc;
+        std::swap(dec, other); H = Hn;
+    }
+    if ((rc = run_layer(h, h->layers[2 * n - 1], dec, other, s.B, H, s.W, &Hn, st))) return rc;
+    return run_deembed(h, other, s.B, s.W, rspec, st);
+}
+static int slots_used(const int* slot_clips) { int k = 0; while (k < 8 && slot_clips[k]) ++k; return k; }     // a uniform pass: slots 0 .. min(S, n) - 1
+
 extern "C" int escx_encode(escx_handle h, const float* wave, int B, int L, int S, int64_t* codes, int* fh, int* fw, void* stream) {
     if (h && h->kind == 1) return rvq_encode(h, wave, B, L, nullptr, S, codes, fh, fw, stream);
     int rc = check_ready(h); if (rc) return rc;
     if (!wave || !codes) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null pointer");
-    if (S < 1 || S > h->cfg.max_streams) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "num_streams=%d outside [1, %d]", S, h->cfg.max_streams);
-    if (L <= h->n_fft / 2) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "n_samples=%d too short for reflect padding of %d", L, h->n_fft / 2);
+    if ((rc = check_count("num_streams", S, h->cfg.max_streams))) return rc;
+    if ((rc = check_samples(h, L))) return rc;
     Shapes s; if ((rc = ensure_ws(h, B, frames_of(h, L), &s))) return rc;
     const long long cstride = (long long)S * h->cfg.group_size * s.Tq;
     if ((rc = ensure_pvq_tables(h, (hipStream_t)stream))) return rc;
@@ -608,29 +706,12 @@ extern "C" int escx_encode(escx_handle h, const float* wave, int B, int L, int S
         Shapes sp = s; sp.B = nb; int r;
         if ((r = run_stft(h, wave + (size_t)b0 * L, nb, L, sp.T, h->spec, st))) return r;
         if ((r = run_encoder(h, sp, st))) return r;
-        return run_csvq_encode(h, sp, S, (long long*)codes + b0 * cstride, st);
+        return run_csvq_encode(h, sp, {nullptr, S}, (long long*)codes + b0 * cstride, cstride, st);
     });
     if (rc) return rc;
     if (fh) *fh = s.encH[h->n - 1];
     if (fw) *fw = s.W;
     return ESCX_OK;
-}
-
-// csrvq.py:160-183 + codecs.py:83-94
-static int run_csvq_decode(escx_handle_s* h, const long long* codes, int B, int S, int Hb, int W, float* rspec, hipStream_t st) {
-    const escx_config& c = h->cfg;
-    const int n = h->n, G = c.group_size, Tq = W / c.overlap;
-    const long long bstride = (long long)S * G * Tq, sstride = (long long)G * Tq;
-    int rc, H = Hb, Hn;
-    float* dec = h->decA; float* other = h->decB;
-    if ((rc = run_pvq_decode(h, h->quants[0], codes, bstride, nullptr, B, W, dec, st))) return rc;
-    for (int i = 0; i + 1 < n; ++i) {
-        if (i < S - 1 && (rc = run_pvq_decode(h, h->quants[i + 1], codes + (i + 1) * sstride, bstride, dec, B, W, dec, st))) return rc;
-        if ((rc = run_layer(h, h->layers[n + i], dec, other, B, H, W, &Hn, st))) return rc;
-        std::swap(dec, other); H = Hn;
-    }
-    if ((rc = run_layer(h, h->layers[2 * n - 1], dec, other, B, H, W, &Hn, st))) return rc;
-    return run_deembed(h, other, B, W, rspec, st);
 }
 
 extern "C" int escx_decode(escx_handle h, const int64_t* codes, int B, int S, int fh, int fw, float* wave_out, float* recon_feat,
@@ -639,18 +720,17 @@ extern "C" int escx_decode(escx_handle h, const int64_t* codes, int B, int S, in
     int rc = check_infer_ready(h); if (rc) return rc;
     if (!codes || !wave_out) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null pointer");
     const escx_config& c = h->cfg;
-    if (S < 1 || S > c.max_streams) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "codes.size(1)=%d outside [1, %d]", S, c.max_streams);
-    if (fw < 1 || fw % c.overlap) ESCX_FAIL(ESCX_ERR_ASSERT, "Time dimension must be multiple of overlap");
+    if ((rc = check_count("codes.size(1)", S, c.max_streams))) return rc;
+    if (fw < 1 || fw % c.overlap) return fail_overlap();
     Shapes s; if ((rc = ensure_ws(h, B, frames_for_width(h, fw), &s))) return rc;
-    if (s.W != fw || s.encH[h->n - 1] != fh) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "feat_shape (%d,%d) does not match the model (%d,%d)", fh, fw, s.encH[h->n - 1], s.W);
-    const int T2 = c.patch_t * fw, out_len = c.hop_length * (T2 - 1);
+    if ((rc = check_feat_shape(h, s, fh, fw))) return rc;
+    const int T2 = c.patch_t * fw;
     const long long cstride = (long long)S * c.group_size * (fw / c.overlap);
     if ((rc = ensure_pvq_tables(h, (hipStream_t)stream))) return rc;
     rc = run_halves(h, B, s.T, (hipStream_t)stream, [&](int b0, int nb, hipStream_t st) -> int {
         int r;
-        if ((r = run_csvq_decode(h, (const long long*)codes + b0 * cstride, nb, S, fh, fw, h->rspec, st))) return r;
-        if ((r = run_istft(h, h->rspec, nb, T2, wave_out + (size_t)b0 * out_len, st))) return r;
-        if (recon_feat) spec_unpad(h, h->rspec, recon_feat + (size_t)b0 * T2 * c.in_dim * h->F, (long long)nb * T2, st);
+        if ((r = run_csvq_decode(h, (const long long*)codes + b0 * cstride, cstride, nb, {nullptr, S}, fh, fw, h->rspec, st))) return r;
+        if ((r = finish_output(h, b0, nb, T2, wave_out, recon_feat, st))) return r;
         return launch_ok("decode");
     });
     return rc;
@@ -658,51 +738,28 @@ extern "C" int escx_decode(escx_handle h, const int64_t* codes, int B, int S, in
 
 // codecs.py:30-66 in eval mode.  Exactly one of `wave` (B, L) and `feat` (B, T, in_dim, F: the reference's x_feat (B,F,T,2)
 // permuted to frame-major) is given; with `feat` the STFT is skipped (codecs.py:33-34).
-static int forward_impl(escx_handle h, const float* wave, const float* feat, int B, int L, int T, int S, int64_t* codes, float* wave_out,
+static int forward_impl(escx_handle h, const float* wave, const float* feat, int B, int LT, int S, int64_t* codes, float* wave_out,
                         float* raw_feat, float* recon_feat, float* cm_loss, void* stream) {
-    if (h && h->kind == 1) return rvq_forward(h, wave, feat, B, wave ? L : T, nullptr, S, codes, wave_out, raw_feat, recon_feat, cm_loss, stream);
+    if (h && h->kind == 1) return rvq_forward(h, wave, feat, B, LT, nullptr, S, codes, wave_out, raw_feat, recon_feat, cm_loss, stream);
     int rc = check_infer_ready(h); if (rc) return rc;
     if ((!wave && !feat) || !codes || !wave_out) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null pointer");
     const escx_config& c = h->cfg;
-    if (S < 1 || S > c.max_streams) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "num_streams=%d outside [1, %d]", S, c.max_streams);
-    if (wave && L <= h->n_fft / 2) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "n_samples=%d too short for reflect padding of %d", L, h->n_fft / 2);
-    if (!wave && T < c.patch_t) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "n_frames=%d shorter than one patch", T);
-    if (wave) T = frames_of(h, L);
+    if ((rc = check_count("num_streams", S, c.max_streams))) return rc;
+    int T; if ((rc = input_frames(h, wave != nullptr, LT, &T))) return rc;
     Shapes s; if ((rc = ensure_ws(h, B, T, &s))) return rc;
-    if (s.W % c.overlap) ESCX_FAIL(ESCX_ERR_ASSERT, "Time dimension must be multiple of overlap");
-    const int n = h->n, G = c.group_size;
-    const long long bstride = (long long)S * G * s.Tq, sstride = (long long)G * s.Tq;
-    const int T2 = c.patch_t * s.W, out_len = c.hop_length * (T2 - 1);
+    if (s.W % c.overlap) return fail_overlap();
+    const int G = c.group_size, T2 = c.patch_t * s.W;
+    const long long bstride = (long long)S * G * s.Tq;
     if ((rc = ensure_pvq_tables(h, (hipStream_t)stream))) return rc;
     return run_halves(h, B, s.T, (hipStream_t)stream, [&](int b0, int nb, hipStream_t st) -> int {
         Shapes sp = s; sp.B = nb; int r;
-        long long* cd = (long long*)codes + b0 * bstride;
-        if (wave) { if ((r = run_stft(h, wave + (size_t)b0 * L, nb, L, sp.T, h->spec, st))) return r; }
-        else spec_pad(h, feat + (size_t)b0 * sp.T * c.in_dim * h->F, h->spec, (long long)nb * sp.T, st);
-        if (raw_feat) spec_unpad(h, h->spec, raw_feat + (size_t)b0 * sp.T * c.in_dim * h->F, (long long)nb * sp.T, st);
+        if ((r = stage_input(h, wave, feat, b0, nb, LT, sp.T, raw_feat, st))) return r;
         if ((r = run_encoder(h, sp, st))) return r;
-        // per-vector commitment terms of stream slot i go to loss_terms[i][G][nb*Tq]; reduced per clip at the end (no atomics)
-        const size_t lslot = (size_t)G * nb * sp.Tq;
         float* loss = cm_loss ? h->loss_terms : nullptr;
-        int n_slots = 1;
-        // csrvq.py:97-129 in eval mode: stream 0, then (stream i+1, block i) pairs; untransmitted streams pass through
-        int H = sp.encH[n - 1], Hn;
-        float* dec = h->decA; float* other = h->decB;
-        if ((r = run_pvq_quantize(h, h->quants[0], h->enc_hs[n - 1], nullptr, nb, sp.W, cd, bstride, loss, dec, st))) return r;
-        for (int i = 0; i + 1 < n; ++i) {
-            if (i < S - 1) {
-                const Quant& q = h->quants[i + 1];
-                if ((r = run_pvq_quantize(h, q, h->enc_hs[n - 1 - i], dec, nb, sp.W, cd + (i + 1) * sstride, bstride, loss ? loss + (size_t)(i + 1) * lslot : nullptr, dec, st))) return r;
-                n_slots = i + 2;
-            }
-            if ((r = run_layer(h, h->layers[n + i], dec, other, nb, H, sp.W, &Hn, st))) return r;
-            std::swap(dec, other); H = Hn;
-        }
-        if ((r = run_layer(h, h->layers[2 * n - 1], dec, other, nb, H, sp.W, &Hn, st))) return r;
-        if ((r = run_deembed(h, other, nb, sp.W, h->rspec, st))) return r;
-        if ((r = run_istft(h, h->rspec, nb, T2, wave_out + (size_t)b0 * out_len, st))) return r;
-        if (recon_feat) spec_unpad(h, h->rspec, recon_feat + (size_t)b0 * T2 * c.in_dim * h->F, (long long)nb * T2, st);
-        if (cm_loss) loss_reduce(loss, n_slots, G, nb * sp.Tq, sp.Tq, cm_loss + b0, st);
+        int slot_clips[8];
+        if ((r = run_csvq_forward(h, sp, {nullptr, S}, (long long*)codes + b0 * bstride, bstride, loss, slot_clips, h->rspec, st))) return r;
+        if ((r = finish_output(h, b0, nb, T2, wave_out, recon_feat, st))) return r;
+        if (cm_loss) loss_reduce(loss, slots_used(slot_clips), G, nb * sp.Tq, sp.Tq, cm_loss + b0, st);
         return launch_ok("forward");
     });
 }
@@ -710,13 +767,13 @@ static int forward_impl(escx_handle h, const float* wave, const float* feat, int
 extern "C" int escx_forward(escx_handle h, const float* wave, int B, int L, int S, int64_t* codes, float* wave_out, float* raw_feat,
                             float* recon_feat, float* cm_loss, void* stream) {
     if (!wave) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null pointer");
-    return forward_impl(h, wave, nullptr, B, L, 0, S, codes, wave_out, raw_feat, recon_feat, cm_loss, stream);
+    return forward_impl(h, wave, nullptr, B, L, S, codes, wave_out, raw_feat, recon_feat, cm_loss, stream);
 }
 
 extern "C" int escx_forward_feat(escx_handle h, const float* feat, int B, int T, int S, int64_t* codes, float* wave_out, float* recon_feat,
                                  float* cm_loss, void* stream) {
     if (!feat) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null pointer");
-    return forward_impl(h, nullptr, feat, B, 0, T, S, codes, wave_out, nullptr, recon_feat, cm_loss, stream);
+    return forward_impl(h, nullptr, feat, B, T, S, codes, wave_out, nullptr, recon_feat, cm_loss, stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -734,13 +791,13 @@ struct MixPlan {
 };
 }  // namespace
 
-static int check_streams(escx_handle_s* h, int B, const int32_t* streams, int* Smax) {
+// HOST per-clip counts, each in [1, max] (`suffix` names the bound in the message: "" = max_streams, " (num_rvqs)"); *Smax = the largest
+static int check_streams(int B, const int32_t* streams, int max, const char* suffix, int* Smax) {
     if (!streams) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null streams pointer");
     if (B < 1) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "batch=%d: the per-clip stream counts need at least one clip", B);
     int m = 0;
     for (int b = 0; b < B; ++b) {
-        if (streams[b] < 1 || streams[b] > h->cfg.max_streams)
-            ESCX_FAIL(ESCX_ERR_INVALID_ARG, "streams[%d]=%d outside [1, %d]", b, streams[b], h->cfg.max_streams);
+        if (streams[b] < 1 || streams[b] > max) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "streams[%d]=%d outside [1, %d]%s", b, streams[b], max, suffix);
         m = std::max(m, (int)streams[b]);
     }
     *Smax = m;
@@ -800,53 +857,13 @@ static int upload_plan(escx_handle_s* h, const MixPlan& p, int32_t* dev, hipStre
     return 0;
 }
 
-static int clips_over(const int* S, int B, int j) { int c = 0; while (c < B && S[c] > j) ++c; return c; }     // S non-increasing
-
-// csrvq.py:131-158 on a pass whose clips carry S[0] >= S[1] >= ... streams: stream j runs on the clips with S > j; the refinement after it
-// and the decoder block that feeds stream j + 1 only on those with S > j + 1 (run_csvq_encode is the uniform form).
-static int run_csvq_encode_streams(escx_handle_s* h, const Shapes& s, const int* S, long long* codes, long long bstride, hipStream_t st) {
-    const int n = h->n;
-    const long long sstride = (long long)h->cfg.group_size * s.Tq;
-    int rc, H = s.encH[n - 1], Hn;
-    float* dec = h->decA; float* other = h->decB;
-    int nref = clips_over(S, s.B, 1);                                     // clips that go on to stream 1
-    if ((rc = run_pvq_quantize(h, h->quants[0], h->enc_hs[n - 1], nullptr, s.B, s.W, codes, bstride, nullptr, nref ? dec : nullptr, st))) return rc;
-    for (int i = 0; nref > 0; ++i) {
-        const int nq = nref;                                              // clips that carry stream i + 1
-        nref = clips_over(S, nq, i + 2);                                  // ... and stream i + 2: they need the refinement and block i
-        if ((rc = run_pvq_quantize(h, h->quants[i + 1], h->enc_hs[n - 1 - i], dec, nq, s.W, codes + (i + 1) * sstride, bstride, nullptr, nref ? dec : nullptr, st))) return rc;
-        if (!nref) break;
-        if ((rc = run_layer(h, h->layers[n + i], dec, other, nref, H, s.W, &Hn, st))) return rc;
-        std::swap(dec, other); H = Hn;
-    }
-    return 0;
-}
-
-// csrvq.py:160-183 + codecs.py:83-94 on a pass sorted by descending S: stream i + 1 is de-quantised and added in place on the clips that carry
-// it; the others keep `dec` (the reference's pass-through).  Every decoder block runs on the whole pass.
-static int run_csvq_decode_streams(escx_handle_s* h, const long long* codes, long long bstride, int B, const int* S, int Hb, int W, float* rspec, hipStream_t st) {
-    const int n = h->n;
-    const long long sstride = (long long)h->cfg.group_size * (W / h->cfg.overlap);
-    int rc, H = Hb, Hn;
-    float* dec = h->decA; float* other = h->decB;
-    if ((rc = run_pvq_decode(h, h->quants[0], codes, bstride, nullptr, B, W, dec, st))) return rc;
-    for (int i = 0; i + 1 < n; ++i) {
-        const int nq = clips_over(S, B, i + 1);
-        if (nq && (rc = run_pvq_decode(h, h->quants[i + 1], codes + (i + 1) * sstride, bstride, dec, nq, W, dec, st))) return rc;
-        if ((rc = run_layer(h, h->layers[n + i], dec, other, B, H, W, &Hn, st))) return rc;
-        std::swap(dec, other); H = Hn;
-    }
-    if ((rc = run_layer(h, h->layers[2 * n - 1], dec, other, B, H, W, &Hn, st))) return rc;
-    return run_deembed(h, other, B, W, rspec, st);
-}
-
 extern "C" int escx_encode_streams(escx_handle h, const float* wave, int B, int L, const int32_t* streams, int64_t* codes, int* fh, int* fw,
                                    void* stream) {
     if (h && h->kind == 1) return rvq_encode(h, wave, B, L, streams, 0, codes, fh, fw, stream);
     int rc = check_ready(h); if (rc) return rc;
     if (!wave || !codes) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null pointer");
-    int Smax = 0; if ((rc = check_streams(h, B, streams, &Smax))) return rc;
-    if (L <= h->n_fft / 2) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "n_samples=%d too short for reflect padding of %d", L, h->n_fft / 2);
+    int Smax = 0; if ((rc = check_streams(B, streams, h->cfg.max_streams, "", &Smax))) return rc;
+    if ((rc = check_samples(h, L))) return rc;
     Shapes s; if ((rc = ensure_ws(h, B, frames_of(h, L), &s))) return rc;
     MixPlan p; plan_streams(h, B, s.T, streams, Smax, &p);
     const int GT = h->cfg.group_size * s.Tq;
@@ -862,7 +879,7 @@ extern "C" int escx_encode_streams(escx_handle h, const float* wave, int B, int 
         Shapes sp = s; sp.B = nb; int r;
         if ((r = run_stft(h, wave_ws + (size_t)b0 * L, nb, L, sp.T, h->spec, sti))) return r;
         if ((r = run_encoder(h, sp, sti))) return r;
-        return run_csvq_encode_streams(h, sp, p.S_ws() + b0, codes_ws + b0 * cstride, cstride, sti);
+        return run_csvq_encode(h, sp, {p.S_ws() + b0, 0}, codes_ws + b0 * cstride, cstride, sti);
     });
     if (rc) return rc;
     PROF("mix_scatter", 0, 2.0 * B * cstride * 8, codes_permute(codes_ws, cstride, (long long*)codes, maps + B, maps + 3 * B, B, Smax, GT, st));
@@ -878,11 +895,11 @@ extern "C" int escx_decode_streams(escx_handle h, const int64_t* codes, int B, i
     int rc = check_infer_ready(h); if (rc) return rc;
     if (!codes || !wave_out) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null pointer");
     const escx_config& c = h->cfg;
-    int Smax = 0; if ((rc = check_streams(h, B, streams, &Smax))) return rc;
+    int Smax = 0; if ((rc = check_streams(B, streams, c.max_streams, "", &Smax))) return rc;
     if (Smax_in < Smax || Smax_in > c.max_streams) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "codes.size(1)=%d: must lie in [max(streams)=%d, %d]", Smax_in, Smax, c.max_streams);
-    if (fw < 1 || fw % c.overlap) ESCX_FAIL(ESCX_ERR_ASSERT, "Time dimension must be multiple of overlap");
+    if (fw < 1 || fw % c.overlap) return fail_overlap();
     Shapes s; if ((rc = ensure_ws(h, B, frames_for_width(h, fw), &s))) return rc;
-    if (s.W != fw || s.encH[h->n - 1] != fh) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "feat_shape (%d,%d) does not match the model (%d,%d)", fh, fw, s.encH[h->n - 1], s.W);
+    if ((rc = check_feat_shape(h, s, fh, fw))) return rc;
     MixPlan p; plan_streams(h, B, s.T, streams, Smax, &p);
     const int T2 = c.patch_t * fw, out_len = c.hop_length * (T2 - 1), GT = c.group_size * (fw / c.overlap);
     const long long in_stride = (long long)Smax_in * GT, cstride = (long long)Smax * GT, frow = (long long)T2 * c.in_dim * h->F;
@@ -897,9 +914,8 @@ extern "C" int escx_decode_streams(escx_handle h, const int64_t* codes, int B, i
     PROF("mix_gather", 0, 2.0 * B * cstride * 8, codes_permute((const long long*)codes, in_stride, codes_ws, maps, maps + 2 * B, B, Smax, GT, st));
     rc = run_halves(h, B, s.T, st, [&](int b0, int nb, hipStream_t sti) -> int {
         int r;
-        if ((r = run_csvq_decode_streams(h, codes_ws + b0 * cstride, cstride, nb, p.S_ws() + b0, fh, fw, h->rspec, sti))) return r;
-        if ((r = run_istft(h, h->rspec, nb, T2, wave_ws + (size_t)b0 * out_len, sti))) return r;
-        if (recon_ws) spec_unpad(h, h->rspec, recon_ws + (size_t)b0 * frow, (long long)nb * T2, sti);
+        if ((r = run_csvq_decode(h, codes_ws + b0 * cstride, cstride, nb, {p.S_ws() + b0, 0}, fh, fw, h->rspec, sti))) return r;
+        if ((r = finish_output(h, b0, nb, T2, wave_ws, recon_ws, sti))) return r;
         return launch_ok("decode_streams");
     });
     if (rc) return rc;
@@ -915,19 +931,15 @@ extern "C" int escx_forward_streams(escx_handle h, const float* wave, const floa
     int rc = check_infer_ready(h); if (rc) return rc;
     if ((!wave == !feat) || !codes || !wave_out) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null pointer (exactly one of wave / feat, codes and wave_out are required)");
     const escx_config& c = h->cfg;
-    int Smax = 0; if ((rc = check_streams(h, B, streams, &Smax))) return rc;
-    const int L = wave ? LT : 0;
-    int T = wave ? 0 : LT;
-    if (wave && L <= h->n_fft / 2) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "n_samples=%d too short for reflect padding of %d", L, h->n_fft / 2);
-    if (!wave && T < c.patch_t) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "n_frames=%d shorter than one patch", T);
-    if (wave) T = frames_of(h, L);
+    int Smax = 0; if ((rc = check_streams(B, streams, c.max_streams, "", &Smax))) return rc;
+    int T; if ((rc = input_frames(h, wave != nullptr, LT, &T))) return rc;
     Shapes s; if ((rc = ensure_ws(h, B, T, &s))) return rc;
-    if (s.W % c.overlap) ESCX_FAIL(ESCX_ERR_ASSERT, "Time dimension must be multiple of overlap");
+    if (s.W % c.overlap) return fail_overlap();
     MixPlan p; plan_streams(h, B, s.T, streams, Smax, &p);
     const int n = h->n, G = c.group_size, GT = G * s.Tq;
-    const long long cstride = (long long)Smax * GT, sstride = GT;
+    const long long cstride = (long long)Smax * GT;
     const int T2 = c.patch_t * s.W, out_len = c.hop_length * (T2 - 1);
-    const long long in_row = wave ? (long long)L : (long long)s.T * c.in_dim * h->F, raw_row = (long long)s.T * c.in_dim * h->F, rec_row = (long long)T2 * c.in_dim * h->F;
+    const long long in_row = wave ? (long long)LT : (long long)s.T * c.in_dim * h->F, raw_row = (long long)s.T * c.in_dim * h->F, rec_row = (long long)T2 * c.in_dim * h->F;
     int32_t* maps; float *in_ws, *wave_ws, *raw_ws = nullptr, *recon_ws = nullptr, *loss_ws = nullptr; long long* codes_ws;
     MixBufs mb; mb.add(&maps, p.ints.size()); mb.add(&in_ws, (size_t)B * in_row); mb.add(&codes_ws, (size_t)B * cstride); mb.add(&wave_ws, (size_t)B * out_len);
     if (raw_feat) mb.add(&raw_ws, (size_t)B * raw_row);
@@ -941,33 +953,14 @@ extern "C" int escx_forward_streams(escx_handle h, const float* wave, const floa
     const int32_t* Sdev = maps + 2 * B;
     rc = run_halves(h, B, s.T, st, [&](int b0, int nb, hipStream_t st) -> int {
         Shapes sp = s; sp.B = nb; int r;
-        const int* S = p.S_ws() + b0;
-        long long* cd = codes_ws + b0 * cstride;
-        if (wave) { if ((r = run_stft(h, in_ws + (size_t)b0 * L, nb, L, sp.T, h->spec, st))) return r; }
-        else spec_pad(h, in_ws + (size_t)b0 * in_row, h->spec, (long long)nb * sp.T, st);
-        if (raw_ws) spec_unpad(h, h->spec, raw_ws + (size_t)b0 * raw_row, (long long)nb * sp.T, st);
+        if ((r = stage_input(h, wave ? in_ws : nullptr, in_ws, b0, nb, LT, sp.T, raw_ws, st))) return r;
         if ((r = run_encoder(h, sp, st))) return r;
-        // per-vector commitment terms of stream slot j go to loss_terms[j][G][clips of slot j * Tq]; reduced per clip over its own slots
-        const size_t lslot = (size_t)G * nb * sp.Tq;
         float* loss = cm_loss ? h->loss_terms : nullptr;
-        int slot_clips[8] = {nb};
-        int H = sp.encH[n - 1], Hn;
-        float* dec = h->decA; float* other = h->decB;
-        if ((r = run_pvq_quantize(h, h->quants[0], h->enc_hs[n - 1], nullptr, nb, sp.W, cd, cstride, loss, dec, st))) return r;
-        for (int i = 0; i + 1 < n; ++i) {
-            const int nq = clips_over(S, nb, i + 1);                  // clips that carry stream i + 1; the others pass through
-            if (nq) {
-                if ((r = run_pvq_quantize(h, h->quants[i + 1], h->enc_hs[n - 1 - i], dec, nq, sp.W, cd + (i + 1) * sstride, cstride, loss ? loss + (size_t)(i + 1) * lslot : nullptr, dec, st))) return r;
-                slot_clips[i + 1] = nq;
-            }
-            if ((r = run_layer(h, h->layers[n + i], dec, other, nb, H, sp.W, &Hn, st))) return r;
-            std::swap(dec, other); H = Hn;
-        }
-        if ((r = run_layer(h, h->layers[2 * n - 1], dec, other, nb, H, sp.W, &Hn, st))) return r;
-        if ((r = run_deembed(h, other, nb, sp.W, h->rspec, st))) return r;
-        if ((r = run_istft(h, h->rspec, nb, T2, wave_ws + (size_t)b0 * out_len, st))) return r;
-        if (recon_ws) spec_unpad(h, h->rspec, recon_ws + (size_t)b0 * rec_row, (long long)nb * T2, st);
-        if (cm_loss) PROF("loss_reduce_streams", 0, (double)nb * Smax * GT * 4, loss_reduce_streams(loss, (long long)lslot, Sdev + b0, n, slot_clips, G, sp.Tq, nb, loss_ws + b0, st));
+        int slot_clips[8];
+        if ((r = run_csvq_forward(h, sp, {p.S_ws() + b0, 0}, codes_ws + b0 * cstride, cstride, loss, slot_clips, h->rspec, st))) return r;
+        if ((r = finish_output(h, b0, nb, T2, wave_ws, recon_ws, st))) return r;
+        // every clip is reduced over its own slots
+        if (cm_loss) PROF("loss_reduce_streams", 0, (double)nb * Smax * GT * 4, loss_reduce_streams(loss, (long long)GT * nb, Sdev + b0, n, slot_clips, G, sp.Tq, nb, loss_ws + b0, st));
         return launch_ok("forward_streams");
     });
     if (rc) return rc;
@@ -1001,6 +994,11 @@ static int len_common_checks(escx_handle_s* h, int B, const int32_t* v, const ch
     if (B < 1) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "batch=%d: the per-clip %s need at least one clip", B, what);
     return 0;
 }
+static int check_one_set(escx_handle_s* h, int B, int T) {      // the batch runs as one part: workspace set 0 has to hold all of it
+    const auto& w = h->sets[0].shp;
+    if (w.B < B || w.T < T) ESCX_FAIL(ESCX_ERR_STATE, "workspace set holds %d clips of %d frames, the batch needs %d of %d", w.B, w.T, B, T);
+    return 0;
+}
 
 // samples per clip -> latent widths; every L_b in (n_fft / 2, Lx], every W_b a multiple of `overlap`
 static int plan_lengths(escx_handle_s* h, int B, int Lx, const int32_t* lengths, LenCtx* lc, int* Lmax) {
@@ -1032,11 +1030,11 @@ extern "C" int escx_encode_lengths(escx_handle h, const float* wave, int B, int 
     if ((rc = len_common_checks(h, B, lengths, "lengths"))) return rc;
     if (!wave || !codes) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null pointer");
     const escx_config& c = h->cfg;
-    if (S < 1 || S > c.max_streams) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "num_streams=%d outside [1, %d]", S, c.max_streams);
+    if ((rc = check_count("num_streams", S, c.max_streams))) return rc;
     LenCtx lc; int Lmax = 0;
     if ((rc = plan_lengths(h, B, Lx, lengths, &lc, &Lmax))) return rc;
     Shapes s; if ((rc = ensure_ws(h, B, frames_of(h, Lmax), &s, B))) return rc;
-    if (h->sets[0].shp.B < B || h->sets[0].shp.T < s.T) ESCX_FAIL(ESCX_ERR_STATE, "workspace set holds %d clips of %d frames, the batch needs %d of %d", h->sets[0].shp.B, h->sets[0].shp.T, B, s.T);
+    if ((rc = check_one_set(h, B, s.T))) return rc;
     hipStream_t st = (hipStream_t)stream;
     MixBufs mb; if ((rc = upload_lengths(h, mb, &lc, lengths, st))) return rc;
     if ((rc = ensure_pvq_tables(h, st))) return rc;
@@ -1044,7 +1042,7 @@ extern "C" int escx_encode_lengths(escx_handle h, const float* wave, int B, int 
     LenGuard guard(h, &lc);
     if ((rc = run_stft(h, wave, B, Lx, s.T, h->spec, st))) return rc;
     if ((rc = run_encoder(h, s, st))) return rc;
-    if ((rc = run_csvq_encode(h, s, S, (long long*)codes, st))) return rc;
+    if ((rc = run_csvq_encode(h, s, {nullptr, S}, (long long*)codes, (long long)S * c.group_size * s.Tq, st))) return rc;
     PROF("codes_mask_len", 0, 8.0 * B * S * c.group_size * s.Tq, codes_mask_len((const long long*)codes, (long long*)codes, lc.d_W, c.overlap, B, S * c.group_size, s.Tq, -1, st));
     if ((rc = launch_ok("encode_lengths"))) return rc;
     if (fh) *fh = s.encH[h->n - 1];
@@ -1068,13 +1066,13 @@ extern "C" int escx_decode_lengths(escx_handle h, const int64_t* codes, int B, i
     if ((rc = len_common_checks(h, B, widths, "frame_lengths"))) return rc;
     if (!codes || !wave_out) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null pointer");
     const escx_config& c = h->cfg;
-    if (S < 1 || S > c.max_streams) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "codes.size(1)=%d outside [1, %d]", S, c.max_streams);
-    if (fw < 1 || fw % c.overlap) ESCX_FAIL(ESCX_ERR_ASSERT, "Time dimension must be multiple of overlap");
+    if ((rc = check_count("codes.size(1)", S, c.max_streams))) return rc;
+    if (fw < 1 || fw % c.overlap) return fail_overlap();
     LenCtx lc;
     if ((rc = plan_widths(h, B, fw, widths, &lc))) return rc;
     Shapes s; if ((rc = ensure_ws(h, B, frames_for_width(h, fw), &s, B))) return rc;
-    if (h->sets[0].shp.B < B || h->sets[0].shp.T < s.T) ESCX_FAIL(ESCX_ERR_STATE, "workspace set holds %d clips of %d frames, the batch needs %d of %d", h->sets[0].shp.B, h->sets[0].shp.T, B, s.T);
-    if (s.W != fw || s.encH[h->n - 1] != fh) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "feat_shape (%d,%d) does not match the model (%d,%d)", fh, fw, s.encH[h->n - 1], s.W);
+    if ((rc = check_one_set(h, B, s.T))) return rc;
+    if ((rc = check_feat_shape(h, s, fh, fw))) return rc;
     const int T2 = c.patch_t * fw, Tq = fw / c.overlap;
     hipStream_t st = (hipStream_t)stream;
     long long* codes_ws = nullptr;
@@ -1085,7 +1083,7 @@ extern "C" int escx_decode_lengths(escx_handle h, const int64_t* codes, int B, i
     LenGuard guard(h, &lc);
     // the clip's own code frames are copied; the slots past them are not read (the copy holds code 0 there, which feeds dead tokens only)
     PROF("codes_mask_len", 0, 16.0 * B * S * c.group_size * Tq, codes_mask_len((const long long*)codes, codes_ws, lc.d_W, c.overlap, B, S * c.group_size, Tq, 0, st));
-    if ((rc = run_csvq_decode(h, codes_ws, B, S, fh, fw, h->rspec, st))) return rc;
+    if ((rc = run_csvq_decode(h, codes_ws, (long long)S * c.group_size * Tq, B, {nullptr, S}, fh, fw, h->rspec, st))) return rc;
     if ((rc = run_istft(h, h->rspec, B, T2, wave_out, st))) return rc;
     if (recon_feat) PROF("unpad_len", 0, 2.0 * B * T2 * c.in_dim * h->F * 4, unpad_rows_len(h->rspec, recon_feat, lc.d_W, 1, c.patch_t, c.hop_length, B, T2, c.in_dim, h->F, h->Fp, st));
     return launch_ok("decode_lengths");
@@ -1098,41 +1096,29 @@ extern "C" int escx_forward_lengths(escx_handle h, const float* wave, int B, int
     if ((rc = len_common_checks(h, B, lengths, "lengths"))) return rc;
     if (!wave || !codes || !wave_out) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null pointer");
     const escx_config& c = h->cfg;
-    if (S < 1 || S > c.max_streams) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "num_streams=%d outside [1, %d]", S, c.max_streams);
+    if ((rc = check_count("num_streams", S, c.max_streams))) return rc;
     LenCtx lc; int Lmax = 0;
     if ((rc = plan_lengths(h, B, Lx, lengths, &lc, &Lmax))) return rc;
     Shapes s; if ((rc = ensure_ws(h, B, frames_of(h, Lmax), &s, B))) return rc;
-    if (h->sets[0].shp.B < B || h->sets[0].shp.T < s.T) ESCX_FAIL(ESCX_ERR_STATE, "workspace set holds %d clips of %d frames, the batch needs %d of %d", h->sets[0].shp.B, h->sets[0].shp.T, B, s.T);
+    if ((rc = check_one_set(h, B, s.T))) return rc;
     hipStream_t st = (hipStream_t)stream;
     MixBufs mb; if ((rc = upload_lengths(h, mb, &lc, lengths, st))) return rc;
     if ((rc = ensure_pvq_tables(h, st))) return rc;
     use_set(h, 0);
     LenGuard guard(h, &lc);
-    const int n = h->n, G = c.group_size;
-    const long long bstride = (long long)S * G * s.Tq, sstride = (long long)G * s.Tq;
-    const int T2 = c.patch_t * s.W;
+    const int G = c.group_size, T2 = c.patch_t * s.W;
+    const long long bstride = (long long)S * G * s.Tq;
     long long* cd = (long long*)codes;
     if ((rc = run_stft(h, wave, B, Lx, s.T, h->spec, st))) return rc;
     if (raw_feat) PROF("unpad_len", 0, 2.0 * B * s.T * c.in_dim * h->F * 4, unpad_rows_len(h->spec, raw_feat, lc.d_L, 0, c.patch_t, c.hop_length, B, s.T, c.in_dim, h->F, h->Fp, st));
     if ((rc = run_encoder(h, s, st))) return rc;
-    const size_t lslot = (size_t)G * B * s.Tq;
     float* loss = cm_loss ? h->loss_terms : nullptr;
-    int n_slots = 1;
-    int H = s.encH[n - 1], Hn;
-    float* dec = h->decA; float* other = h->decB;
-    if ((rc = run_pvq_quantize(h, h->quants[0], h->enc_hs[n - 1], nullptr, B, s.W, cd, bstride, loss, dec, st))) return rc;
-    for (int i = 0; i + 1 < n; ++i) {
-        if (i < S - 1) {
-            if ((rc = run_pvq_quantize(h, h->quants[i + 1], h->enc_hs[n - 1 - i], dec, B, s.W, cd + (i + 1) * sstride, bstride, loss ? loss + (size_t)(i + 1) * lslot : nullptr, dec, st))) return rc;
-            n_slots = i + 2;
-        }
-        if ((rc = run_layer(h, h->layers[n + i], dec, other, B, H, s.W, &Hn, st))) return rc;
-        std::swap(dec, other); H = Hn;
-    }
-    if ((rc = run_layer(h, h->layers[2 * n - 1], dec, other, B, H, s.W, &Hn, st))) return rc;
-    if ((rc = run_deembed(h, other, B, s.W, h->rspec, st))) return rc;
+    int slot_clips[8];
+    if ((rc = run_csvq_forward(h, s, {nullptr, S}, cd, bstride, loss, slot_clips, h->rspec, st))) return rc;
     if ((rc = run_istft(h, h->rspec, B, T2, wave_out, st))) return rc;
     if (recon_feat) PROF("unpad_len", 0, 2.0 * B * T2 * c.in_dim * h->F * 4, unpad_rows_len(h->rspec, recon_feat, lc.d_W, 1, c.patch_t, c.hop_length, B, T2, c.in_dim, h->F, h->Fp, st));
+    const int n_slots = slots_used(slot_clips);
+    const size_t lslot = (size_t)G * B * s.Tq;
     if (cm_loss) PROF("loss_reduce_len", 0, (double)n_slots * lslot * 4, loss_reduce_len(loss, lc.d_W, c.overlap, n_slots, G, B, s.Tq, cm_loss, st));
     PROF("codes_mask_len", 0, 8.0 * B * bstride, codes_mask_len(cd, cd, lc.d_W, c.overlap, B, S * G, s.Tq, -1, st));
     return launch_ok("forward_lengths");
@@ -1160,34 +1146,16 @@ static int run_prvq(escx_handle_s* h, const float* enc, const long long* codes_i
     return launch_ok("prvq");
 }
 
-// Decoder.forward (base.py:195-203) on the bottleneck map h->decA: blocks, post_nn, PatchDeEmbed -> rspec
+// Decoder.forward (base.py:195-203) on the bottleneck map h->decA: blocks, post_nn, PatchDeEmbed -> rspec (the decode walk without quantiser streams)
 static int run_plain_decoder(escx_handle_s* h, int B, int Hb, int W, float* rspec, hipStream_t st) {
-    const int n = h->n;
-    int rc, H = Hb, Hn;
-    float* dec = h->decA; float* other = h->decB;
-    for (int i = 0; i + 1 < n; ++i) {
-        if ((rc = run_layer(h, h->layers[n + i], dec, other, B, H, W, &Hn, st))) return rc;
-        std::swap(dec, other); H = Hn;
-    }
-    if ((rc = run_layer(h, h->layers[2 * n - 1], dec, other, B, H, W, &Hn, st))) return rc;
-    return run_deembed(h, other, B, W, rspec, st);
+    return run_csvq_decode(h, nullptr, 0, B, {nullptr, 1}, Hb, W, rspec, st);
 }
 
 // stage counts of an rvq call: per clip (streams != nullptr) in [1, num_rvqs], or one S in [1, num_rvqs]; *Smax = the code slots per clip
 static int rvq_counts(escx_handle_s* h, int B, const int32_t* streams, int S, int* Smax) {
-    if (!streams) {
-        if (S < 1 || S > h->num_rvqs) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "num_streams=%d outside [1, %d] (num_rvqs)", S, h->num_rvqs);
-        *Smax = S;
-        return 0;
-    }
-    if (B < 1) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "batch=%d: the per-clip stream counts need at least one clip", B);
-    int m = 0;
-    for (int b = 0; b < B; ++b) {
-        if (streams[b] < 1 || streams[b] > h->num_rvqs) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "streams[%d]=%d outside [1, %d] (num_rvqs)", b, streams[b], h->num_rvqs);
-        m = std::max(m, (int)streams[b]);
-    }
-    *Smax = m;
-    return 0;
+    if (streams) return check_streams(B, streams, h->num_rvqs, " (num_rvqs)", Smax);
+    *Smax = S;
+    return check_count("num_streams", S, h->num_rvqs, " (num_rvqs)");
 }
 
 // per-clip counts on the device (the handle's grow-only staging buffer), or nullptr for a uniform call
@@ -1206,7 +1174,7 @@ static int rvq_encode(escx_handle_s* h, const float* wave, int B, int L, const i
     int rc = check_ready(h); if (rc) return rc;
     if (!wave || !codes) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null pointer");
     int Smax = 0; if ((rc = rvq_counts(h, B, streams, S, &Smax))) return rc;
-    if (L <= h->n_fft / 2) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "n_samples=%d too short for reflect padding of %d", L, h->n_fft / 2);
+    if ((rc = check_samples(h, L))) return rc;
     Shapes s; if ((rc = ensure_ws(h, B, frames_of(h, L), &s))) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int* Sdev; if ((rc = rvq_upload(h, B, streams, &Sdev, st))) return rc;
@@ -1229,23 +1197,22 @@ static int rvq_decode(escx_handle_s* h, const int64_t* codes, int B, int S, cons
     int rc = check_infer_ready(h); if (rc) return rc;
     if (!codes || !wave_out) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null pointer");
     const escx_config& c = h->cfg;
-    if (S < 1 || S > h->num_rvqs) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "codes.size(1)=%d outside [1, %d] (num_rvqs)", S, h->num_rvqs);
+    if ((rc = check_count("codes.size(1)", S, h->num_rvqs, " (num_rvqs)"))) return rc;
     int Smax = 0; if ((rc = rvq_counts(h, B, streams, S, &Smax))) return rc;
     if (Smax > S) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "codes.size(1)=%d: must be at least max(streams)=%d", S, Smax);
-    if (fw < 1 || fw % c.overlap) ESCX_FAIL(ESCX_ERR_ASSERT, "Time dimension must be multiple of overlap");
+    if (fw < 1 || fw % c.overlap) return fail_overlap();
     Shapes s; if ((rc = ensure_ws(h, B, frames_for_width(h, fw), &s))) return rc;
-    if (s.W != fw || s.encH[h->n - 1] != fh) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "feat_shape (%d,%d) does not match the model (%d,%d)", fh, fw, s.encH[h->n - 1], s.W);
+    if ((rc = check_feat_shape(h, s, fh, fw))) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int* Sdev; if ((rc = rvq_upload(h, B, streams, &Sdev, st))) return rc;
     if ((rc = ensure_pvq_tables(h, st))) return rc;
-    const int T2 = c.patch_t * fw, out_len = c.hop_length * (T2 - 1);
+    const int T2 = c.patch_t * fw;
     const long long cstride = (long long)S * c.group_size * (fw / c.overlap);
     return run_halves(h, B, s.T, st, [&](int b0, int nb, hipStream_t sti) -> int {
         int r;
         if ((r = run_prvq(h, nullptr, (const long long*)codes + b0 * cstride, nb, fw, nullptr, cstride, Sdev ? Sdev + b0 : nullptr, S, nullptr, 0, h->decA, sti))) return r;
         if ((r = run_plain_decoder(h, nb, fh, fw, h->rspec, sti))) return r;
-        if ((r = run_istft(h, h->rspec, nb, T2, wave_out + (size_t)b0 * out_len, sti))) return r;
-        if (recon_feat) spec_unpad(h, h->rspec, recon_feat + (size_t)b0 * T2 * c.in_dim * h->F, (long long)nb * T2, sti);
+        if ((r = finish_output(h, b0, nb, T2, wave_out, recon_feat, sti))) return r;
         return launch_ok("rvq_decode");
     });
 }
@@ -1257,31 +1224,24 @@ static int rvq_forward(escx_handle_s* h, const float* wave, const float* feat, i
     if ((!wave == !feat) || !codes || !wave_out) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null pointer (exactly one of wave / feat, codes and wave_out are required)");
     const escx_config& c = h->cfg;
     int Smax = 0; if ((rc = rvq_counts(h, B, streams, S, &Smax))) return rc;
-    const int L = wave ? LT : 0;
-    int T = wave ? 0 : LT;
-    if (wave && L <= h->n_fft / 2) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "n_samples=%d too short for reflect padding of %d", L, h->n_fft / 2);
-    if (!wave && T < c.patch_t) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "n_frames=%d shorter than one patch", T);
-    if (wave) T = frames_of(h, L);
+    int T; if ((rc = input_frames(h, wave != nullptr, LT, &T))) return rc;
     Shapes s; if ((rc = ensure_ws(h, B, T, &s))) return rc;
-    if (s.W % c.overlap) ESCX_FAIL(ESCX_ERR_ASSERT, "Time dimension must be multiple of overlap");
+    if (s.W % c.overlap) return fail_overlap();
     hipStream_t st = (hipStream_t)stream;
     const int* Sdev; if ((rc = rvq_upload(h, B, streams, &Sdev, st))) return rc;
     if ((rc = ensure_pvq_tables(h, st))) return rc;
-    const int G = c.group_size, T2 = c.patch_t * s.W, out_len = c.hop_length * (T2 - 1);
+    const int G = c.group_size, T2 = c.patch_t * s.W;
     const long long cstride = (long long)Smax * G * s.Tq;
     return run_halves(h, B, s.T, st, [&](int b0, int nb, hipStream_t sti) -> int {
         Shapes sp = s; sp.B = nb; int r;
-        if (wave) { if ((r = run_stft(h, wave + (size_t)b0 * L, nb, L, sp.T, h->spec, sti))) return r; }
-        else spec_pad(h, feat + (size_t)b0 * sp.T * c.in_dim * h->F, h->spec, (long long)nb * sp.T, sti);
-        if (raw_feat) spec_unpad(h, h->spec, raw_feat + (size_t)b0 * sp.T * c.in_dim * h->F, (long long)nb * sp.T, sti);
+        if ((r = stage_input(h, wave, feat, b0, nb, LT, sp.T, raw_feat, sti))) return r;
         if ((r = run_encoder(h, sp, sti))) return r;
         // per-vector commitment terms of stage s go to loss_terms[s][G][nb * Tq] (0 past a clip's own count); reduced per clip in a fixed order
         const long long lslot = (long long)G * nb * sp.Tq;
         float* loss = cm_loss ? h->loss_terms : nullptr;
         if ((r = run_prvq(h, h->enc_hs[h->n - 1], nullptr, nb, sp.W, (long long*)codes + b0 * cstride, cstride, Sdev ? Sdev + b0 : nullptr, Smax, loss, lslot, h->decA, sti))) return r;
         if ((r = run_plain_decoder(h, nb, sp.encH[h->n - 1], sp.W, h->rspec, sti))) return r;
-        if ((r = run_istft(h, h->rspec, nb, T2, wave_out + (size_t)b0 * out_len, sti))) return r;
-        if (recon_feat) spec_unpad(h, h->rspec, recon_feat + (size_t)b0 * T2 * c.in_dim * h->F, (long long)nb * T2, sti);
+        if ((r = finish_output(h, b0, nb, T2, wave_out, recon_feat, sti))) return r;
         if (cm_loss) PROF("loss_reduce", 0, (double)lslot * Smax * 4, loss_reduce(loss, Smax, G, nb * sp.Tq, sp.Tq, cm_loss + b0, sti));
         return launch_ok("rvq_forward");
     });
@@ -1293,7 +1253,7 @@ static int rvq_forward(escx_handle_s* h, const float* wave, const float* feat, i
 extern "C" int escx_spec_transform(escx_handle h, const float* wave, int B, int L, float* spec, void* stream) {
     int rc = check_ready(h); if (rc) return rc;
     if (!wave || !spec || B < 1) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "bad argument");
-    if (L <= h->n_fft / 2) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "n_samples=%d too short for reflect padding of %d", L, h->n_fft / 2);
+    if ((rc = check_samples(h, L))) return rc;
     const int T = frames_of(h, L);
     TmpBuf t; if (t.alloc((size_t)B * T * h->cfg.in_dim * h->Fp)) ESCX_FAIL(ESCX_ERR_HIP, "hipMalloc failed");
     hipStream_t st = (hipStream_t)stream;
@@ -1361,7 +1321,7 @@ extern "C" int escx_pvq_encode(escx_handle h, int sid, const float* enc, const f
     int rc = check_ready(h); if (rc) return rc;
     if (h->kind != 0) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "escx_pvq_encode: the cross-scale quantisers do not exist on an rvq handle (escx_rvq_encode / escx_rvq_decode)");
     if (sid < 0 || sid >= h->cfg.max_streams) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "stream_id out of range");
-    if (W % h->cfg.overlap) ESCX_FAIL(ESCX_ERR_ASSERT, "Time dimension must be multiple of overlap");
+    if (W % h->cfg.overlap) return fail_overlap();
     const Quant& q = h->quants[sid];
     Shapes s; if ((rc = stage_ws_for_w(h, B, W, &s))) return rc;
     hipStream_t st = (hipStream_t)stream;
@@ -1377,7 +1337,7 @@ extern "C" int escx_pvq_decode(escx_handle h, int sid, const int64_t* codes, int
     int rc = check_ready(h); if (rc) return rc;
     if (h->kind != 0) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "escx_pvq_decode: the cross-scale quantisers do not exist on an rvq handle (escx_rvq_encode / escx_rvq_decode)");
     if (sid < 0 || sid >= h->cfg.max_streams) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "stream_id out of range");
-    if (W % h->cfg.overlap) ESCX_FAIL(ESCX_ERR_ASSERT, "Time dimension must be multiple of overlap");
+    if (W % h->cfg.overlap) return fail_overlap();
     const Quant& q = h->quants[sid];
     Shapes s; if ((rc = stage_ws_for_w(h, B, W, &s))) return rc;
     hipStream_t st = (hipStream_t)stream;
@@ -1395,8 +1355,8 @@ extern "C" int escx_rvq_encode(escx_handle h, const float* tokens, int B, int W,
     if (h->kind != 1) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "escx_rvq_encode needs an rvq handle (escx_create_rvq)");
     if (!tokens || !codes) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null pointer");
     if (B < 1 || W < 1) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "batch and W must be positive");
-    if (S < 1 || S > h->num_rvqs) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "num_streams=%d outside [1, %d] (num_rvqs)", S, h->num_rvqs);
-    if (W % h->cfg.overlap) ESCX_FAIL(ESCX_ERR_ASSERT, "Time dimension must be multiple of overlap");
+    if ((rc = check_count("num_streams", S, h->num_rvqs, " (num_rvqs)"))) return rc;
+    if (W % h->cfg.overlap) return fail_overlap();
     const Quant& q = h->quants[0];
     Shapes s; if ((rc = stage_ws_for_w(h, B, W, &s))) return rc;
     hipStream_t st = (hipStream_t)stream;
@@ -1414,8 +1374,8 @@ extern "C" int escx_rvq_decode(escx_handle h, const int64_t* codes, int B, int S
     if (h->kind != 1) ESCX_FAIL(ESCX_ERR_UNSUPPORTED, "escx_rvq_decode needs an rvq handle (escx_create_rvq)");
     if (!codes || !tokens_out) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "null pointer");
     if (B < 1 || W < 1) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "batch and W must be positive");
-    if (S < 1 || S > h->num_rvqs) ESCX_FAIL(ESCX_ERR_INVALID_ARG, "codes.size(1)=%d outside [1, %d] (num_rvqs)", S, h->num_rvqs);
-    if (W % h->cfg.overlap) ESCX_FAIL(ESCX_ERR_ASSERT, "Time dimension must be multiple of overlap");
+    if ((rc = check_count("codes.size(1)", S, h->num_rvqs, " (num_rvqs)"))) return rc;
+    if (W % h->cfg.overlap) return fail_overlap();
     const Quant& q = h->quants[0];
     Shapes s; if ((rc = stage_ws_for_w(h, B, W, &s))) return rc;
     hipStream_t st = (hipStream_t)stream;
